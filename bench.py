@@ -13,9 +13,12 @@ own N per-device workers (one process per GPU through torch.distributed.run on 1
 line — no external launcher needed; launched under torchrun it is a worker.  torch.distributed (RCCL) is used
 for the barrier and the max-over-ranks clock only; there is no collective on the data path.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including `roofline` for the dominant kernel
-(HIP events on the engine's own stream) and `cpu_baseline` (a whole create_proof by the oracle's CPU port on the
-host cores; the reference Rust prover cannot be built here — no toolchain).
+Prints ONE JSON line on rank 0: `value` = proofs/s over exactly K timed steps after the warm-up (W jobs per
+pipeline), `ms_per_step` = one timed step.  A plain run does nothing else; `--full` adds, after the timed steps, four
+more timed passes, `roofline` for the dominant kernel (HIP events on the engine's own stream), lone-proof latencies,
+the k = 17 EVM leg, the comparison of every timed proof with the oracle's committed digests and `cpu_baseline` (a
+whole create_proof by the oracle's CPU port on the host cores; the reference Rust prover is not built by this
+project).  `--dump-outputs DIR` writes the last timed step's proof.
 """
 import argparse
 import json
@@ -431,6 +434,13 @@ def check_against_oracle_digests(proofs):
     return n
 
 
+def dump_outputs(path, proof):
+    """`--dump-outputs DIR`: what the timed path returned for its last step — one proof — as DIR/proof.npy, its bytes as float32
+    values 0..255 (exact).  Jobs and blinding are seeded by the job index, so two builds can be compared byte for byte."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float32))
+
+
 def digests_on_file(proofs):
     """CPU stand-in of check_against_oracle_digests (the fake workload makes no proofs): how many of this rank's jobs have a
     committed oracle digest to be compared with — `--gpus 8 --steps 32` must find all 256."""
@@ -615,6 +625,7 @@ def self_launch(args, fake):
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--inflight", str(args.inflight), "--lockstep", str(args.lockstep), "--backend", args.backend, "--k17-steps", str(args.k17_steps)]
     cmd += (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--one-device"] if args.one_device else [])
+    cmd += (["--full"] if args.full else []) + (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
     if n > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
                "--master-port", str(free_port())] + cmd[1:]
@@ -627,6 +638,85 @@ def self_launch(args, fake):
     if out.returncode != 0 or len(lines) != 1:
         raise SystemExit("bench.py: worker launch failed (rc %d)" % out.returncode)
     print(lines[0])
+
+
+def full_figures(out, wl, args, world, local_rank, nfl, median):
+    """`--full`: every figure of the line beyond the headline, measured after the timed steps (rank 0).  `median`: proofs/s of
+    the median timed pass.  Returns the workload, or None once the k = 17 leg has closed it."""
+    n = 1 << K
+    eng = wl.engs[0]
+    acc_total = acc_n = msm_total = msm_n = cols = 0
+    for e in wl.engs:
+        a, b = e.timer_stats(4)  # ZK_T_MSM_ACCUM
+        acc_total, acc_n = acc_total + a, acc_n + b
+        a, b = e.timer_stats(0)
+        msm_total, msm_n = msm_total + a, msm_n + b
+        cols += e.timer_stats(5)[1]  # ZK_T_MSM_COLUMNS: commitments are batched, a launch serves 1-2 columns here
+    accum_ms = acc_total / max(acc_n, 1)
+    cols_per_launch = cols / max(acc_n, 1)
+    alg_bytes = 96.0 * n * cols_per_launch  # SURVEY.md §8d: MSM(n) = 32 B scalar + 64 B base per point, per column
+    achieved = alg_bytes / (accum_ms * 1e-3) / 1e9
+    out["roofline"] = {
+        "kernel": "msm_wacc_fast_kernel",
+        "bound": "hbm",
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "traffic": pmc_traffic_bytes(),
+        "traffic_source": "NOT measured in this run: per-launch FETCH_SIZE + WRITE_SIZE of the committed rocprofv3 PMC passes of "
+                          "this same command (latest profiles/*proof_k19_pmc_hbm.csv); hardware counters cannot be read in-process. "
+                          "Calibration on the kernel's own access pattern (MI355X_MICROARCH.md, HBM): `traffic_expected` = one 64-byte "
+                          "table gather + one 4-byte entry per bucket addition (68 B x 16 x 2^19) + one 144-byte partial sum per lane and "
+                          "bucket, per column; the counters report ~88 % of it (part of the 512 MiB table stays in the 256 MiB Infinity "
+                          "Cache) — 64-byte gathers are counted at full size, the 2x correction of wide streaming reads does not apply",
+        "traffic_expected": (68.0 * 16 * n + 144.0 * (n + 32768)) * cols_per_launch,
+        "avg_launch_ms": accum_ms,
+        "launches": int(acc_n),
+        "columns_per_launch": cols_per_launch,
+        "note": "integer-ALU-bound kernel (no MFMA, SURVEY.md 8d); MSM pass, sort .. accumulate, avg %.3f ms x %d per proof as timed inside the overlapping pipelines (reduction tails: on the side stream up to two proofs in flight, on the main stream beyond); quotient kernel %.3f ms"
+        % (msm_total / max(msm_n, 1), msm_n // max(args.steps, 1), eng.last_ms(2)),
+    }
+    out["single_proof_ms"] = sorted(wl.single() for _ in range(5))[2]  # median of five (every latency figure of the line is a median)
+    out["roofline"]["alu"] = alu_roofline(eng, K, local_rank)
+    try:
+        clock = clock_under_load(wl, local_rank, wl.jobs[:args.steps])
+    except Exception as e:  # noqa: BLE001 — a library without the probe (A/B variants of older rounds)
+        clock = {"error": str(e)[:120]}
+    out["roofline"]["clock"] = clock
+    out["roofline"]["valu_issue"] = valu_issue_roofline(world / median * 1e3, clock)  # ms per proof on ONE GPU
+    # `achieved` above divides by the launches' durations INSIDE the timed region, where the accumulations of the pipelines in
+    # flight overlap (each launch shares the chip and takes longer: 0.65 ms with two pipelines on queues that serialised them,
+    # ~1.0 ms with four that run side by side — while proofs/s went UP).  The kernel's own rate is the lone launch:
+    lone_ms = out["roofline"]["alu"]["avg_launch_ms"]
+    out["roofline"]["exclusive"] = {"avg_launch_ms": lone_ms, "columns_per_launch": 1.0, "achieved": 96.0 * n / (lone_ms * 1e-3) / 1e9,
+                                    "unit": "GB/s", "frac": 96.0 * n / (lone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                    "note": "one commitment alone on the GPU after the timed region (same measurement as roofline.alu)"}
+    out["roofline"]["launches_overlap"] = ("%d pipelines in flight: their accumulate launches overlap in time, so the per-launch "
+                                           "duration of the timed region (and of the rocprofv3 summary of this command) is not the "
+                                           "kernel's own rate — see `exclusive`" % nfl)
+    # BASELINE.json configs[2]: the same proof with the EVM (Keccak) transcript and GWC, as /prove_evm makes it
+    pl = wl.pipes[0]
+    evm = []
+    for i in range(5):
+        t1 = time.perf_counter()
+        pe = pl.eng.prove(pl.pk, pl.resident[wl.jobs[0]], bytes([i + 1]) * 32, wl.E.ZK_TRANSCRIPT_EVM)
+        evm.append(time.perf_counter() - t1)
+    assert len(pe) == 1536
+    out["single_proof_evm_ms"] = sorted(evm)[2] * 1e3  # median of five, like single_proof_ms (round 5: a minimum of three)
+    out["single_proof_with_h2d_ms"] = sorted(wl.single_with_h2d() for _ in range(5))[2]  # PCIe-inclusive; never `value`
+    out["roofline"]["kernels"] = kernel_rooflines(eng, pl, wl)
+    out["single_proof_seam_ms"] = seam_single_proof_ms(eng)
+    if world == 1 and args.k17_steps > 0:
+        # BASELINE.json configs[0]'s degree and the proving server's own (main.rs:17): k = 17, here as /prove_evm makes it
+        wl.close()
+        wl = None
+        out.update(k17_leg(args))
+    if world == 1 and not args.no_cpu_baseline:
+        cb = cpu_baseline()
+        out["cpu_baseline_k17"] = cb.pop("k17", None)  # configs[0]: bench_secp256r1_ecdsa at k = 17, Blake2b, CPU only
+        out["cpu_baseline"] = cb
+    return wl
 
 
 def main():
@@ -652,6 +742,12 @@ def main():
     ap.add_argument("--k17-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--opt", action="append", default=[], metavar="ID=VALUE",
                     help="tuning experiments: zk_ctx_set_option(ID, VALUE) on every pipeline (include/zkmi355.h ZK_OPT_*)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline, after the timed steps: four more timed passes (median and spread), "
+                         "the resident-advice pass, lone-proof latencies, rooflines, the seam figure, the k = 17 EVM leg, the CPU "
+                         "baseline and the comparison of every timed proof with the oracle's committed digests")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the proof of the last timed step (rank 0) to DIR/proof.npy: its bytes as float32 values 0..255")
     args = ap.parse_args()
     options = []
     for o in args.opt:  # ID=VALUE, or ID=V0,V1,.. (one value per pipeline)
@@ -708,10 +804,7 @@ def main():
 
     for _ in range(1 if fake else max(1, (args.warmup * nfl + len(wl.warm) - 1) // len(wl.warm))):
         wl.run_with_h2d(wl.warm)  # the timed region's own path: upload from the pinned staging buffer, then prove
-    single_ms = None
     if not fake:
-        barrier()
-        single_ms = sorted(wl.single() for _ in range(5))[2]  # median of five (every latency figure of the line is a median)
         for e in wl.engs:
             e.timer_reset()
     wl.proofs.clear()
@@ -721,8 +814,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     assert len(wl.proofs) == args.steps
-    # byte parity of the timed steps themselves: every rank compares its proofs with the oracle's digests (outside the clock)
-    oracle_checked = digests_on_file(wl.proofs) if fake else check_against_oracle_digests(wl.proofs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.proofs[wl.jobs[args.steps - 1]])
     per_rank_ms = [elapsed / args.steps * 1e3]
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
@@ -731,10 +824,6 @@ def main():
         per_rank_ms = [float(x.item()) / args.steps * 1e3 for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    if dist is not None:
-        tc = torch.tensor([oracle_checked], dtype=torch.float64, device=tdev)
-        dist.all_reduce(tc, op=dist.ReduceOp.SUM)
-        oracle_checked = int(tc.item())
     host_setup = {"synthesize_s_per_job": round(wl.synth_s, 3), "keygen_s": round(wl.keygen_s, 3)}
     if dist is not None:
         # every rank's set-up time (SRS + window tables + key + workspaces, per pipeline): a SCALE record separates it from steady state
@@ -755,46 +844,53 @@ def main():
     launcher = {"launcher": "torchrun" if dist is not None else "in-process", "jobs_covered_exactly_once": jobs_exactly_once,
                 "ranks_share_device": bool(args.one_device and world > 1),
                 "numa_binding": numa,
-                "dist_backend": (dist.get_backend() if dist is not None else None), "ms_per_step_per_rank": per_rank_ms,
-                # timed proofs (all ranks) whose bytes were compared with the oracle's committed digests: all of them for the
-                # 256-job batch of configs[3]
-                "proofs_checked_against_oracle_digests": oracle_checked}
+                "dist_backend": (dist.get_backend() if dist is not None else None), "ms_per_step_per_rank": per_rank_ms}
+    value = world * args.steps / elapsed
 
-    pass_ranks = [per_rank_ms]  # every timed pass's per-rank clocks; the line carries the median pass's
-
-    def timed(fn, record=True):
-        """One more timed pass over the same K jobs (same barriers, max-over-ranks clock) -> whole-job proofs/s."""
-        barrier()
-        t1 = time.perf_counter()
-        fn(wl.jobs[:args.steps])
-        barrier()
-        dt = time.perf_counter() - t1
-        mine_ms = [dt / args.steps * 1e3]
+    if args.full:
+        # byte parity of the timed steps themselves: every rank compares its proofs with the oracle's digests (outside the clock)
+        oracle_checked = digests_on_file(wl.proofs) if fake else check_against_oracle_digests(wl.proofs)
         if dist is not None:
-            tt = torch.tensor([dt], dtype=torch.float64, device=tdev)
-            ev = [torch.zeros_like(tt) for _ in range(world)]
-            dist.all_gather(ev, tt)
-            mine_ms = [float(x.item()) / args.steps * 1e3 for x in ev]
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt = float(tt.item())
-        if record:
-            pass_ranks.append(mine_ms)
-        return world * args.steps / dt
+            tc = torch.tensor([oracle_checked], dtype=torch.float64, device=tdev)
+            dist.all_reduce(tc, op=dist.ReduceOp.SUM)
+            oracle_checked = int(tc.item())
+        # timed proofs (all ranks) whose bytes were compared with the oracle's committed digests: all of them for the 256-job batch
+        # of configs[3]
+        launcher["proofs_checked_against_oracle_digests"] = oracle_checked
 
-    # Four further timed repeats of the same region (after `value`'s): the median and the spread say how large a
-    # round-over-round delta must be before it means anything (boxes and runs differ by ~3 %).
-    # Round 6: `value` IS the median of the five (each is EXACTLY K steps between barriers, max over ranks); the first pass — the
-    # one rounds 1-5 reported, in practice the slowest: clocks and caches settle during it — stays beside it as `value_first`.
-    repeats = [world * args.steps / elapsed] + [timed(wl.run_with_h2d) for _ in range(0 if fake else 4)]
-    value = sorted(repeats)[len(repeats) // 2]
-    launcher["ms_per_step_per_rank"] = pass_ranks[repeats.index(value)]  # the median pass's (first pass: ms_per_step_per_rank_first)
-    launcher["ms_per_step_per_rank_first"] = per_rank_ms
-    launcher["value_first"] = repeats[0]
-    launcher["value_repeats"] = repeats
-    launcher["value_median"] = value
-    launcher["value_spread_pct"] = (max(repeats) - min(repeats)) / (sum(repeats) / len(repeats)) * 100.0
-    if not fake:
-        launcher["value_advice_resident"] = timed(wl.run, record=False)  # the columns already in HBM (rounds 1-4 reported this as `value`)
+        pass_ranks = [per_rank_ms]  # every timed pass's per-rank clocks
+
+        def timed(fn, record=True):
+            """One more timed pass over the same K jobs (same barriers, max-over-ranks clock) -> whole-job proofs/s."""
+            barrier()
+            t1 = time.perf_counter()
+            fn(wl.jobs[:args.steps])
+            barrier()
+            dt = time.perf_counter() - t1
+            mine_ms = [dt / args.steps * 1e3]
+            if dist is not None:
+                tt = torch.tensor([dt], dtype=torch.float64, device=tdev)
+                ev = [torch.zeros_like(tt) for _ in range(world)]
+                dist.all_gather(ev, tt)
+                mine_ms = [float(x.item()) / args.steps * 1e3 for x in ev]
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                dt = float(tt.item())
+            if record:
+                pass_ranks.append(mine_ms)
+            return world * args.steps / dt
+
+        # Four further timed repeats of the same region (after `value`'s): the median and the spread say how large a
+        # round-over-round delta must be before it means anything (boxes and runs differ by ~3 %).  `value_median` is what
+        # round 6 reported as `value`.
+        repeats = [value] + [timed(wl.run_with_h2d) for _ in range(0 if fake else 4)]
+        median = sorted(repeats)[len(repeats) // 2]
+        launcher["ms_per_step_per_rank_median"] = pass_ranks[repeats.index(median)]
+        launcher["value_first"] = repeats[0]
+        launcher["value_repeats"] = repeats
+        launcher["value_median"] = median
+        launcher["value_spread_pct"] = (max(repeats) - min(repeats)) / (sum(repeats) / len(repeats)) * 100.0
+        if not fake:
+            launcher["value_advice_resident"] = timed(wl.run, record=False)  # the columns already in HBM (rounds 1-4 reported this as `value`)
 
     if rank == 0 and fake:
         print(json.dumps({"metric": "webauthn_es256_proofs_per_sec_k19", "value": value,
@@ -802,21 +898,8 @@ def main():
                           "ms_per_step": world / value * 1e3, "scaling": "weak", "data": "fake",
                           "jobs_total": world * args.steps, "host_setup": host_setup, **launcher}))
     elif rank == 0:
-        n = 1 << K
-        eng = wl.engs[0]
-        acc_total = acc_n = msm_total = msm_n = cols = 0
-        for e in wl.engs:
-            a, b = e.timer_stats(4)  # ZK_T_MSM_ACCUM
-            acc_total, acc_n = acc_total + a, acc_n + b
-            a, b = e.timer_stats(0)
-            msm_total, msm_n = msm_total + a, msm_n + b
-            cols += e.timer_stats(5)[1]  # ZK_T_MSM_COLUMNS: commitments are batched, a launch serves 1-2 columns here
-        accum_ms = acc_total / max(acc_n, 1)
-        cols_per_launch = cols / max(acc_n, 1)
         assert all(len(p) == 960 for p in wl.proofs.values())  # halo2-circuits/src/results/ecdsa_bench.csv:2
         assert len(set(wl.proofs.values())) == len(wl.proofs)  # distinct jobs -> distinct proofs: nothing cached
-        alg_bytes = 96.0 * n * cols_per_launch  # MSM(n) = 32 B scalar + 64 B base per point, per column
-        achieved = alg_bytes / (accum_ms * 1e-3) / 1e9
         out = {
             "metric": "webauthn_es256_proofs_per_sec_k19",
             "value": value,
@@ -824,8 +907,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": world / value * 1e3,  # of the median pass (the first pass: world / value_first)
-            "single_proof_ms": single_ms,
+            "ms_per_step": world / value * 1e3,  # of the K timed steps
             **launcher,
             "inflight_per_gpu": nfl,
             "lockstep": args.lockstep,
@@ -838,66 +920,9 @@ def main():
             "data": "synthetic",
             "config": {"workload": WORKLOAD, "k": K, "transcript": "blake2b", "multiopen": "shplonk", "proof_bytes": 960,
                        "parallelism": "replicas:%d (one independent proof stream per GPU, no collective)" % world},
-            "roofline": {
-                "kernel": "msm_wacc_fast_kernel",
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": pmc_traffic_bytes(),
-                "traffic_source": "NOT measured in this run: per-launch FETCH_SIZE + WRITE_SIZE of the committed rocprofv3 PMC passes of "
-                                  "this same command (latest profiles/*proof_k19_pmc_hbm.csv); hardware counters cannot be read in-process. "
-                                  "Calibration on the kernel's own access pattern (MI355X_MICROARCH.md, HBM): `traffic_expected` = one 64-byte "
-                                  "table gather + one 4-byte entry per bucket addition (68 B x 16 x 2^19) + one 144-byte partial sum per lane and "
-                                  "bucket, per column; the counters report ~88 % of it (part of the 512 MiB table stays in the 256 MiB Infinity "
-                                  "Cache) — 64-byte gathers are counted at full size, the 2x correction of wide streaming reads does not apply",
-                "traffic_expected": (68.0 * 16 * n + 144.0 * (n + 32768)) * cols_per_launch,
-                "avg_launch_ms": accum_ms,
-                "launches": int(acc_n),
-                "columns_per_launch": cols_per_launch,
-                "note": "integer-ALU-bound kernel (no MFMA, SURVEY.md 8d); MSM pass, sort .. accumulate, avg %.3f ms x %d per proof as timed inside the overlapping pipelines (reduction tails: on the side stream up to two proofs in flight, on the main stream beyond); quotient kernel %.3f ms"
-                % (msm_total / max(msm_n, 1), msm_n // max(args.steps, 1), eng.last_ms(2)),
-            },
         }
-        out["roofline"]["alu"] = alu_roofline(eng, K, local_rank)
-        try:
-            clock = clock_under_load(wl, local_rank, wl.jobs[:args.steps])
-        except Exception as e:  # noqa: BLE001 — a library without the probe (A/B variants of older rounds)
-            clock = {"error": str(e)[:120]}
-        out["roofline"]["clock"] = clock
-        out["roofline"]["valu_issue"] = valu_issue_roofline(world / value * 1e3, clock)  # ms per proof on ONE GPU
-        # `achieved` above divides by the launches' durations INSIDE the timed region, where the accumulations of the pipelines in
-        # flight overlap (each launch shares the chip and takes longer: 0.65 ms with two pipelines on queues that serialised them,
-        # ~1.0 ms with four that run side by side — while proofs/s went UP).  The kernel's own rate is the lone launch:
-        lone_ms = out["roofline"]["alu"]["avg_launch_ms"]
-        out["roofline"]["exclusive"] = {"avg_launch_ms": lone_ms, "columns_per_launch": 1.0, "achieved": 96.0 * n / (lone_ms * 1e-3) / 1e9,
-                                        "unit": "GB/s", "frac": 96.0 * n / (lone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                        "note": "one commitment alone on the GPU after the timed region (same measurement as roofline.alu)"}
-        out["roofline"]["launches_overlap"] = ("%d pipelines in flight: their accumulate launches overlap in time, so the per-launch "
-                                               "duration of the timed region (and of the rocprofv3 summary of this command) is not the "
-                                               "kernel's own rate — see `exclusive`" % nfl)
-        # BASELINE.json configs[2]: the same proof with the EVM (Keccak) transcript and GWC, as /prove_evm makes it
-        pl = wl.pipes[0]
-        evm = []
-        for i in range(5):
-            t1 = time.perf_counter()
-            pe = pl.eng.prove(pl.pk, pl.resident[wl.jobs[0]], bytes([i + 1]) * 32, wl.E.ZK_TRANSCRIPT_EVM)
-            evm.append(time.perf_counter() - t1)
-        assert len(pe) == 1536
-        out["single_proof_evm_ms"] = sorted(evm)[2] * 1e3  # median of five, like single_proof_ms (round 5: a minimum of three)
-        out["single_proof_with_h2d_ms"] = sorted(wl.single_with_h2d() for _ in range(5))[2]  # PCIe-inclusive; never `value`
-        out["roofline"]["kernels"] = kernel_rooflines(eng, pl, wl)
-        out["single_proof_seam_ms"] = seam_single_proof_ms(eng)
-        if world == 1 and args.k17_steps > 0:
-            # BASELINE.json configs[0]'s degree and the proving server's own (main.rs:17): k = 17, here as /prove_evm makes it
-            wl.close()
-            wl = None
-            out.update(k17_leg(args))
-        if world == 1 and not args.no_cpu_baseline:
-            cb = cpu_baseline()
-            out["cpu_baseline_k17"] = cb.pop("k17", None)  # configs[0]: bench_secp256r1_ecdsa at k = 17, Blake2b, CPU only
-            out["cpu_baseline"] = cb
+        if args.full:
+            wl = full_figures(out, wl, args, world, local_rank, nfl, launcher["value_median"])
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -3,8 +3,8 @@ used to run the REFERENCE's verifier where it lies
 (/root/reference/proving-server/P256Verifier.yul) on a proof.
 
 Oracle tooling (test infrastructure): it exists only in the build container —
-nothing here is a copy of the reference; the Yul file is read at run time and
-tests that use it skip when /root/reference is absent (e.g. on the GPU box).
+nothing here is a copy of the reference; the Yul file is read at run time.  The
+suite holds the verdicts it reached (tests/golden/make_yul_verdicts.py).
 
 EVM precompiles 0x5 (modexp), 0x6 (ecAdd), 0x7 (ecMul) are implemented with the
 oracle's BN254 code; 0x8 (pairing) is replaced by the equivalent check with the

@@ -1,7 +1,7 @@
 """NS-1 closed on the GPU box: the bytes the reference's generated verifier accepts are the bytes THIS build emits.
 
-tests/test_oracle_verifier.py::test_reference_yul_verifier_accepts_engine_proof runs the reference's own
-`proving-server/P256Verifier.yul` (in place, CPU container only) on tests/golden/engine_proof_k17_evm.json.  That fixture was
+tests/test_oracle_verifier.py::test_reference_yul_verifier_accepts_engine_proof holds the verdicts of the reference's own
+`proving-server/P256Verifier.yul` on tests/golden/engine_proof_k17_evm.json (tests/golden/yul_verdicts.json).  That fixture was
 made on a GPU by tests/golden/make_engine_fixture.py; here the same inputs (k = 17 bench shape, witness seed 0x5eed0019,
 rng seed bytes(range(32)), EVM transcript + GWC — what `/prove_evm` does, halo2-circuits/src/ecc/ecdsa_p256.rs:366-373) go
 through the current engine and must give the fixture's proof bytes and verifying key, so that the chain

@@ -54,6 +54,25 @@ def test_bench_launches_its_own_workers():
     assert out.returncode == 0 and json.loads(out.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain run (fake workload) times exactly --steps steps, prints the headline line without any `--full` figure, and
+    `--dump-outputs DIR` writes the proof of the last timed step as float32 (the fake workload's proofs are 960 zero bytes)."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ZKMI355_BENCH_WORKER")}
+    env["ZKMI355_BENCH_FAKE"] = "1"
+    d = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads(out.stdout.strip().splitlines()[-1])
+    assert j["steps"] == 3 and j["jobs_total"] == 3 and j["ms_per_step"] >= 10.0  # rank 0 sleeps 10 ms per job
+    assert abs(j["value"] - 1e3 / j["ms_per_step"]) < 1e-6
+    assert "value_repeats" not in j and "proofs_checked_against_oracle_digests" not in j
+    a = np.load(d / "proof.npy")
+    assert a.dtype == np.float32 and a.shape == (960,) and not a.any()
+
+
 def test_job_seeds_are_disjoint_across_ranks():
     # BASELINE config 4: job i uses witness seed 0x5eed0019 + i; rank r of N takes i = r, r + N, ...
     import webauthn_halo2_amd as zk
@@ -78,7 +97,8 @@ def test_eight_ranks_cover_the_256_job_batch_exactly_once():
     travel in the line, and the slowest rank sets `value`."""
     env = dict(os.environ, ZKMI355_BENCH_FAKE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "32", "--warmup", "1"]
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "32", "--warmup", "1",
+           "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -2,10 +2,9 @@
 verifying key constants baked into the reference's generated verifier, accepts
 the reference's golden EVM proof and reproduces its Fiat-Shamir challenges.
 CPU only."""
+import hashlib
 import json
 import os
-
-import pytest
 
 from zkoracle import plonk
 
@@ -56,19 +55,27 @@ def test_tampered_golden_proof_rejected():
     assert not plonk.verify(vk, b"", "evm")  # contracts/test/P256Account.t.sol:106-118: empty proof must fail
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proving-server/P256Verifier.yul"),
-                    reason="reference tree not present (GPU box)")
-def test_reference_yul_verifier_agrees():
-    """Runs the reference's generated verifier where it lies through oracle/tools/yul_exec.py."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle", "tools"))
-    import yul_exec
-    _, vk, proof = load_k17()
-    ok, vm = yul_exec.run_verifier("/root/reference/proving-server/P256Verifier.yul", proof)
-    assert ok and vm.precompile_calls == {5: 1, 6: 38, 7: 39, 8: 1}
+def yul_verdicts():
+    """What the reference's generated verifier (P256Verifier.yul, run by oracle/tools/yul_exec.py) decided on the suite's two EVM
+    proofs: recorded by tests/golden/make_yul_verdicts.py where the reference tree is."""
+    return json.load(open(os.path.join(GOLD, "yul_verdicts.json")))
+
+
+def flipped(proof, pos_mask):
     bad = bytearray(proof)
-    bad[777] ^= 0x10
-    assert yul_exec.run_verifier("/root/reference/proving-server/P256Verifier.yul", bytes(bad))[0] == plonk.verify(vk, bytes(bad), "evm") == False  # noqa: E712
+    bad[pos_mask[0]] ^= pos_mask[1]
+    return bytes(bad)
+
+
+def test_reference_yul_verifier_agrees():
+    """The oracle verifier reaches the reference's generated verifier's verdicts on the same bytes: the golden proof, and the
+    golden proof with one bit flipped."""
+    rec = yul_verdicts()["golden"]
+    _, vk, proof = load_k17()
+    assert hashlib.sha256(proof).hexdigest() == rec["proof_sha256"]
+    assert rec["accepted"] and rec["precompile_calls"] == {"5": 1, "6": 38, "7": 39, "8": 1}
+    assert plonk.verify(vk, proof, "evm") == rec["accepted"]
+    assert plonk.verify(vk, flipped(proof, rec["flip"]), "evm") == rec["flipped_accepted"] == False  # noqa: E712
 
 
 def load_engine_fixture():
@@ -92,23 +99,21 @@ def test_engine_proof_fixture_verifies():
     assert vk.transcript_repr == vkrepr.transcript_repr(vk.shape, vk.fixed_commitments, vk.permutation_commitments)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proving-server/P256Verifier.yul"),
-                    reason="reference tree not present (GPU box)")
 def test_reference_yul_verifier_accepts_engine_proof():
-    """BASELINE config 3: the reference's GENERATED verifier program (proving-server/P256Verifier.yul,
-    executed where it lies) accepts the device prover's EVM proof bytes unchanged.  The program is
-    vk-specific, so the synthetic circuit's 12 vk commitments and transcript_repr replace the ECDSA
-    circuit's literals in memory; every instruction of the verification logic is the reference's."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle", "tools"))
-    import yul_exec
+    """BASELINE config 3: the reference's GENERATED verifier program (proving-server/P256Verifier.yul) accepted the device
+    prover's EVM proof bytes unchanged (tests/golden/yul_verdicts.json).  The program is vk-specific, so the synthetic circuit's 12
+    vk commitments and transcript_repr replaced the ECDSA circuit's literals in memory; every instruction of the verification
+    logic was the reference's.  The oracle verifier reaches the same verdicts on the same bytes and squeezes the same
+    Fiat-Shamir challenges; the unmodified program (ECDSA circuit's key) rejected the proof, and so does the oracle under that key."""
+    rec = yul_verdicts()["engine"]
     vk, proof = load_engine_fixture()
-    key = (vk.transcript_repr, list(vk.fixed_commitments) + list(vk.permutation_commitments))
-    yul = "/root/reference/proving-server/P256Verifier.yul"
-    ok, vm = yul_exec.run_verifier(yul, proof, vk=key)
-    assert ok and vm.precompile_calls == {5: 1, 6: 38, 7: 39, 8: 1}
-    # the unmodified program (ECDSA circuit's key) must reject it, and a flipped bit must be rejected with our key
-    assert not yul_exec.run_verifier(yul, proof)[0]
-    bad = bytearray(proof)
-    bad[1500] ^= 1
-    assert not yul_exec.run_verifier(yul, bytes(bad), vk=key)[0]
+    assert hashlib.sha256(proof).hexdigest() == rec["proof_sha256"]
+    assert rec["accepted_with_its_key"] and rec["precompile_calls"] == {"5": 1, "6": 38, "7": 39, "8": 1}
+    ok, pf = plonk.verify(vk, proof, "evm", return_detail=True)
+    assert ok == rec["accepted_with_its_key"]
+    for name, val in rec["challenges"].items():
+        assert pf.challenges[name] == int(val, 16), name
+    _, ecdsa_vk, _ = load_k17()
+    assert ecdsa_vk.shape == vk.shape
+    assert plonk.verify(ecdsa_vk, proof, "evm") == rec["accepted_with_the_programs_key"] == False  # noqa: E712
+    assert plonk.verify(vk, flipped(proof, rec["flip"]), "evm") == rec["flipped_accepted_with_its_key"] == False  # noqa: E712

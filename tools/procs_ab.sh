@@ -6,7 +6,7 @@ val() { python -c "
 import json,sys
 v=[json.loads(open(f).read().strip().splitlines()[-1])['value_advice_resident'] for f in sys.argv[1:]]
 print(' + '.join('%.1f'%x for x in v), '= %.1f proofs/s'%sum(v))" "$@"; }
-B="python bench.py --no-cpu-baseline --steps 80"
+B="python bench.py --full --no-cpu-baseline --steps 80"
 echo "== k=19, 1 process x 4 pipelines"; $B --inflight 4 2>/dev/null > gpurun_out/pa_1.log; val gpurun_out/pa_1.log
 echo "== k=19, 2 processes x 2 pipelines, tails auto (side streams: each process sees two active contexts)"
 $B --inflight 2 2>/dev/null > gpurun_out/pa_2.log & $B --inflight 2 2>/dev/null > gpurun_out/pa_3.log & wait; val gpurun_out/pa_2.log gpurun_out/pa_3.log

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 one() {  # label, extra args
   local label="$1"; shift
-  python bench.py --no-cpu-baseline --k17-steps 0 "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --k17-steps 0 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-28s value %.2f  repeats %s  single %.2f ms' % ('$label', d['value'], ' '.join('%.1f'%x for x in d.get('value_repeats',[])), d.get('single_proof_ms',0)))

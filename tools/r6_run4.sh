@@ -12,7 +12,7 @@ done > $O/t1_parts.txt 2>&1
 cat $O/t1_parts.txt
 for r in 1 2; do
   for o in 10=2 10=1; do
-    python bench.py --no-cpu-baseline --k17-steps 0 --steps 40 --opt $o 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$o', 'value %.2f first %.2f repeats %s single %.2f'%(d['value'], d['value_first'], ['%.1f'%x for x in d['value_repeats']], d['single_proof_ms']))"
+    python bench.py --full --no-cpu-baseline --k17-steps 0 --steps 40 --opt $o 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$o', 'value %.2f first %.2f repeats %s single %.2f'%(d['value'], d['value_first'], ['%.1f'%x for x in d['value_repeats']], d['single_proof_ms']))"
   done
 done > $O/t1_bench.txt 2>&1
 cat $O/t1_bench.txt

@@ -363,6 +363,31 @@ int zk_prove_batch(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /*
 /* upload canonical (non-Montgomery) integers and convert on the device */
 int zk_poly_upload_canonical(zk_ctx* ctx, zk_poly p, const uint64_t* host_canonical, size_t n);
 
+/* ---- verify_proof ---------------------------------------------------------------------------------------------------
+ * plonk::verify_proof with the KZG pairing check (ecdsa_p256.rs:429-469: `verify` = Blake2b + SHPLONK, `verify_evm` = EVM +
+ * GWC; no instances).  The check is e(A, [s]G2) = e(B, G2) with g[0], g2 and s_g2 of the context's resident SRS: a proof
+ * made under another SRS is rejected.  A bad proof is a verdict (ZK_OK, *ok = 0 / verdicts[j] = 0), never an error; the
+ * error codes mean bad arguments (ZK_EINVAL), a full key whose SRS was replaced, or no SRS / no G2 half in the context
+ * (ZK_ESTATE: zk_srs_load needs zk_srs_set_g2 first). */
+/* replaces VerifyingKey::read::<_, ECDSACircuit<Fr>> (ecdsa_p256.rs:431-435): the zk_vk_write image of `params`' shape
+ * gives a VERIFYING-ONLY key — commitments and transcript_repr, no SRS-sized memory, no prover workspace (zk_prove,
+ * zk_prove_batch, zk_pk_write, zk_vk_write and the phase-level entry points return ZK_ESTATE for it; zk_pk_shape,
+ * zk_vk_export, zk_verify and zk_pk_free work).  transcript_repr NULL: computed as zk_keygen does. */
+int zk_vk_read(zk_ctx* ctx, const zk_circuit_params* params, const uint8_t* bytes, size_t len, int format,
+               const uint64_t transcript_repr_mont[4], zk_pk* out);
+/* the inverse of zk_vk_export: a verifying-only key from affine Montgomery commitments (n_fixed and n_perm of the shape,
+ * fixed columns in zk_vk_export's order); a point off the curve is ZK_EINVAL */
+int zk_vk_from_parts(zk_ctx* ctx, const zk_circuit_params* params, const uint64_t* fixed_commitments, const uint64_t* perm_commitments,
+                     const uint64_t transcript_repr_mont[4], zk_pk* out);
+/* one proof of `pk` (full or verifying-only): *ok = 1 if it verifies.  The batch of one below. */
+int zk_verify(zk_ctx* ctx, zk_pk pk, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok);
+/* `batch` proofs of one key: verdicts[j] = what zk_verify says of proof j.  Points are decoded and the per-proof sums
+ * are made on the device, the proofs are folded with random 128-bit weights into one pairing, and a failing set is halved
+ * until every verdict is exact.  ZK_EINVAL: batch == 0 or > ZK_VERIFY_BATCH_MAX. */
+#define ZK_VERIFY_BATCH_MAX 1024
+int zk_verify_batch(zk_ctx* ctx, zk_pk pk, size_t batch, int transcript, int scheme, const uint8_t* const* proofs, const size_t* lens,
+                    uint8_t* verdicts);
+
 /* ---- timing of the last call of each kind, measured with HIP events on the
  *      context stream (ms); used by bench.py for the roofline figures ---------- */
 #define ZK_T_MSM 0

@@ -127,6 +127,7 @@ struct zk_ctx {
     void* seam_buf[2] = {nullptr, nullptr};
     size_t seam_bytes[2] = {0, 0};
     Fr* small = nullptr;  // 2048 + 8 elements for reductions
+    struct VerifyWs* vws = nullptr;  // zk_verify_batch's device buffers (verify.hip), grow-only
     Fr* host_small = nullptr;  // pinned, 8 elements
     // polys
     std::unordered_map<uint64_t, PolyRec> polys;
@@ -245,3 +246,4 @@ int srs_alloc(zk_ctx* c, uint32_t k);
 void srs_adopt(zk_ctx* c, uint32_t k, G1Affine* g, G1Affine* g_lagrange);
 int srs_build_tables(zk_ctx* c, uint32_t k);
 void srs_set_g2_from_secret(zk_ctx* c, const Fr& s_mont);
+void verify_ws_destroy(struct VerifyWs* w);

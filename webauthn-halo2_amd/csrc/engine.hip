@@ -664,6 +664,7 @@ void zk_ctx_destroy(zk_ctx* c) {
     for (int i = 0; i < 2; i++)
         if (c->seam_buf[i]) hipFree(c->seam_buf[i]);
     if (c->small) hipFree(c->small);
+    verify_ws_destroy(c->vws);
     for (int i = 0; i < ZK_T_COUNT; i++)
         for (int j = 0; j < 2; j++)
             if (c->ev[i][j]) hipEventDestroy(c->ev[i][j]);

@@ -113,6 +113,8 @@ struct zk_pk_rec {
     Fr *l0_c3 = nullptr, *l_last_c3 = nullptr, *l_active_c3 = nullptr;
     std::vector<G1Affine> fixed_commit, perm_commit;
     Fr transcript_repr;
+    bool verify_only = false;          // zk_vk_read / zk_vk_from_parts: the verifying key alone (no key polynomials, no workspace)
+    G1Affine* d_vk_bases = nullptr;    // the commitments on the device, fixed then permutation (verify.hip; listed in `dev`)
     // prover workspace
     std::vector<Fr*> adv_val, adv_poly, adv_coset;
     std::vector<Fr*> z_val, z_poly, z_coset;
@@ -202,3 +204,6 @@ int pk_ensure_batch(zk_ctx* c, zk_pk_rec* pk, uint32_t batch);
 // transcript_repr of a key made or read here: halo2.s own hash of the pinned verifying key (vkrepr.h); a stand-in for the shapes
 // that rendering does not cover; a host-supplied value replaces either
 Fr pk_standin_transcript_repr(const zk_pk_rec* pk);
+// a verifying-only key record registered in the context (verify.hip); transcript_repr NULL: computed as zk_keygen does
+int pk_make_verify_only(zk_ctx* c, const Layout& lay, const std::vector<G1Affine>& fixed, const std::vector<G1Affine>& perm,
+                        const uint64_t transcript_repr[4], zk_pk* out);

@@ -726,7 +726,7 @@ ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_adv
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;
+    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
     if (n_advice != lay.n_adv || n_chunks != lay.n_chunks || n_lookups != lay.n_lookups) return ZK_EINVAL;
     const size_t N = (size_t)4 * lay.n;
     auto ext = [&](zk_poly p) -> Fr* {
@@ -1899,6 +1899,7 @@ ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, co
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
+    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
@@ -1944,7 +1945,7 @@ int phase_open(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, Phase
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;
+    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != pk->lay.n_adv) return ZK_EINVAL;
     out.c = c;
     out.pk = pk;
@@ -2167,7 +2168,7 @@ ZK_API(zk_pk_export_poly, (zk_ctx* c, zk_pk h, int which, size_t index, zk_poly 
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;
+    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
     const std::vector<Fr*>* v = which == ZK_PK_FIXED_POLY ? &pk->fixed_poly : which == ZK_PK_SIGMA_POLY ? &pk->sigma_poly : nullptr;
     if (!v || index >= v->size()) return ZK_EINVAL;
     Fr* d = phase_vec(c, dst, pk->lay.n);
@@ -2250,6 +2251,7 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
+    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;

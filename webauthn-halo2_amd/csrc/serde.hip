@@ -30,6 +30,7 @@
 // they carry: s_g2 of the SRS (yul:1131-1134) and the k=17 vk commitments (yul:880-980), see tests/.
 #include <string.h>
 
+#include "pairing.h"
 #include "pk.h"
 #include "vkrepr.h"
 
@@ -158,12 +159,6 @@ bool host_lt_p(const uint32_t* v, const uint32_t* p) {
     return false;
 }
 
-Fq fq_small(uint32_t x) {
-    Fq t = Fq::zero();
-    t.v[0] = x;
-    return fe_to_mont(t);
-}
-
 bool host_g1_on_curve(const G1Affine& p) {
     return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
 }
@@ -214,66 +209,6 @@ void host_g1_write(const G1Affine& p, int format, uint8_t* b) {
     memcpy(b, &p, 64);
 }
 
-// ---- Fq2 = Fq[u] / (u^2 + 1) and the twist y^2 = x^3 + 3 / (9 + u): only for g2 / s_g2 of the SRS file
-struct Fq2 {
-    Fq c0, c1;
-};
-Fq2 f2_add(const Fq2& a, const Fq2& b) { return {fe_add(a.c0, b.c0), fe_add(a.c1, b.c1)}; }
-Fq2 f2_sub(const Fq2& a, const Fq2& b) { return {fe_sub(a.c0, b.c0), fe_sub(a.c1, b.c1)}; }
-Fq2 f2_mul(const Fq2& a, const Fq2& b) {
-    return {fe_sub(fe_mul(a.c0, b.c0), fe_mul(a.c1, b.c1)), fe_add(fe_mul(a.c0, b.c1), fe_mul(a.c1, b.c0))};
-}
-Fq2 f2_inv(const Fq2& a) {
-    const Fq d = fe_inv(fe_add(fe_sqr(a.c0), fe_sqr(a.c1)));
-    return {fe_mul(a.c0, d), fe_neg(fe_mul(a.c1, d))};
-}
-bool f2_is_zero(const Fq2& a) { return a.c0.is_zero() && a.c1.is_zero(); }
-bool f2_eq(const Fq2& a, const Fq2& b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-Fq2 f2_small(uint32_t a, uint32_t b) { return {fq_small(a), fq_small(b)}; }
-Fq2 f2_twist_b() { return f2_mul(f2_small(3, 0), f2_inv(f2_small(9, 1))); }
-
-struct G2A {
-    Fq2 x, y;
-    bool inf;
-};
-G2A g2_add(const G2A& a, const G2A& b) {
-    if (a.inf) return b;
-    if (b.inf) return a;
-    Fq2 lam;
-    if (f2_eq(a.x, b.x)) {
-        if (!f2_eq(a.y, b.y)) return G2A{a.x, a.y, true};
-        lam = f2_mul(f2_mul(f2_small(3, 0), f2_mul(a.x, a.x)), f2_inv(f2_add(a.y, a.y)));
-    } else {
-        lam = f2_mul(f2_sub(b.y, a.y), f2_inv(f2_sub(b.x, a.x)));
-    }
-    G2A r;
-    r.inf = false;
-    r.x = f2_sub(f2_sub(f2_mul(lam, lam), a.x), b.x);
-    r.y = f2_sub(f2_mul(lam, f2_sub(a.x, r.x)), a.y);
-    return r;
-}
-G2A g2_mul(G2A p, const Fr& k_mont) {
-    const Fr k = fe_from_mont(k_mont);
-    G2A acc{p.x, p.y, true};
-    for (int i = 0; i < 256; i++) {
-        if ((k.v[i >> 5] >> (i & 31)) & 1) acc = g2_add(acc, p);
-        p = g2_add(p, p);
-    }
-    return acc;
-}
-Fq fq_from_hex_words(const uint32_t be[8]) {  // big-endian word order, canonical -> Montgomery
-    Fq t;
-    for (int i = 0; i < 8; i++) t.v[i] = be[7 - i];
-    return fe_to_mont(t);
-}
-G2A g2_generator() {  // the BN254 G2 generator (reference proving-server/P256Verifier.yul:1125-1128 holds it as x.c1, x.c0, y.c1, y.c0)
-    static const uint32_t X0[8] = {0x1800DEEF, 0x121F1E76, 0x426A0066, 0x5E5C4479, 0x674322D4, 0xF75EDADD, 0x46DEBD5C, 0xD992F6ED};
-    static const uint32_t X1[8] = {0x198E9393, 0x920D483A, 0x7260BFB7, 0x31FB5D25, 0xF1AA4933, 0x35A9E712, 0x97E485B7, 0xAEF312C2};
-    static const uint32_t Y0[8] = {0x12C85EA5, 0xDB8C6DEB, 0x4AAB7180, 0x8DCB408F, 0xE3D1E769, 0x0C43D37B, 0x4CE6CC01, 0x66FA7DAA};
-    static const uint32_t Y1[8] = {0x090689D0, 0x585FF075, 0xEC9E99AD, 0x690C3395, 0xBC4B3133, 0x70B38EF3, 0x55ACDADC, 0xD122975B};
-    return G2A{{fq_from_hex_words(X0), fq_from_hex_words(X1)}, {fq_from_hex_words(Y0), fq_from_hex_words(Y1)}, false};
-}
-bool g2_on_curve(const G2A& p) { return f2_eq(f2_mul(p.y, p.y), f2_add(f2_mul(f2_mul(p.x, p.x), p.x), f2_twist_b())); }
 
 // sqrt in Fq2 (complex method); false if `a` is not a square
 bool f2_sqrt(const Fq2& a, Fq2* out) {
@@ -301,26 +236,6 @@ bool f2_sqrt(const Fq2& a, Fq2* out) {
 }
 
 size_t g2_size(int format) { return format == ZK_SERDE_PROCESSED ? 64 : 128; }
-// raw image: x.c0 || x.c1 || y.c0 || y.c1 Montgomery
-void g2_to_raw(const G2A& p, uint8_t raw[128]) {
-    if (p.inf) {
-        memset(raw, 0, 128);
-        return;
-    }
-    memcpy(raw, p.x.c0.v, 32);
-    memcpy(raw + 32, p.x.c1.v, 32);
-    memcpy(raw + 64, p.y.c0.v, 32);
-    memcpy(raw + 96, p.y.c1.v, 32);
-}
-G2A g2_from_raw(const uint8_t raw[128]) {
-    G2A p;
-    memcpy(p.x.c0.v, raw, 32);
-    memcpy(p.x.c1.v, raw + 32, 32);
-    memcpy(p.y.c0.v, raw + 64, 32);
-    memcpy(p.y.c1.v, raw + 96, 32);
-    p.inf = f2_is_zero(p.x) && f2_is_zero(p.y);
-    return p;
-}
 void host_g2_write(const uint8_t raw[128], int format, uint8_t* b) {
     if (format != ZK_SERDE_PROCESSED) {
         memcpy(b, raw, 128);
@@ -662,7 +577,7 @@ ZK_API(zk_vk_write, (zk_ctx* c, zk_pk h, int format, uint8_t* out, size_t cap, s
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
-    if (it->second->srs_gen != c->srs_gen) return ZK_ESTATE;
+    if (it->second->srs_gen != c->srs_gen || it->second->verify_only) return ZK_ESTATE;  // (no selector columns to write)
     *len = vk_size(it->second->lay, format);
     if (!out) return ZK_OK;
     if (cap < *len) return ZK_EINVAL;
@@ -681,7 +596,7 @@ ZK_API(zk_vk_load, (zk_ctx* c, zk_pk h, const uint8_t* bytes, size_t len, int fo
         auto it = c->pks.find(h);
         if (it == c->pks.end()) return ZK_EINVAL;
         zk_pk_rec* pk = it->second;
-        if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;
+        if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
         if (len != vk_size(pk->lay, format)) return ZK_EINVAL;
         In in{bytes, len};
         ParsedVk vk;
@@ -699,13 +614,30 @@ ZK_API(zk_vk_load, (zk_ctx* c, zk_pk h, const uint8_t* bytes, size_t len, int fo
     return transcript_repr ? zk_pk_set_transcript_repr(c, h, transcript_repr) : ZK_OK;
 }
 
+// VerifyingKey::read: a verifying-only key from the zk_vk_write image of `params`' shape (its selector bits must be the
+// layout's, as zk_pk_read demands); no SRS is needed
+ZK_API(zk_vk_read, (zk_ctx* c, const zk_circuit_params* params, const uint8_t* bytes, size_t len, int format, const uint64_t transcript_repr[4], zk_pk* out), (c, params, bytes, len, format, transcript_repr, out)) {
+    if (!c || !params || !bytes || !out || !format_ok(format)) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    Layout lay;
+    if (params->num_advice > 1 && 2 * (uint64_t)params->num_idle_gate_columns > params->num_advice) return ZK_ELAYOUT;
+    if (!lay.init(*params)) return ZK_EINVAL;
+    if (len != vk_size(lay, format)) return ZK_EINVAL;
+    In in{bytes, len};
+    ParsedVk vk;
+    int rc = parse_vk(lay, in, format, &vk);
+    if (rc) return rc;
+    if (!layout_selectors_fit(lay, vk.selectors)) return ZK_ELAYOUT;
+    return pk_make_verify_only(c, lay, vk.fixed, vk.perm, transcript_repr, out);
+}
+
 ZK_API(zk_pk_write, (zk_ctx* c, zk_pk h, int format, uint8_t* out, size_t cap, size_t* len), (c, h, format, out, cap, len)) {
     if (!c || !len || !format_ok(format)) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;
+    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
     const Layout& lay = pk->lay;
     *len = pk_size(lay, format);
     if (!out) return ZK_OK;

@@ -171,6 +171,7 @@ struct Transcript {
     virtual void common_scalar(const Fr& s_mont) = 0;
     virtual void write_scalar(const Fr& s_mont) = 0;
     virtual bool write_point(const G1Affine& p_mont) = 0;  // false for the identity
+    virtual void common_point(const G1Affine& p_mont) = 0;  // the read side: absorbs a point the proof holds (not the identity)
     virtual Fr squeeze() = 0;                             // Montgomery
     std::vector<uint8_t> out;
 };
@@ -196,6 +197,12 @@ struct EvmTranscript : Transcript {
         buf.insert(buf.end(), b, b + 64);
         out.insert(out.end(), b, b + 64);
         return true;
+    }
+    void common_point(const G1Affine& p) override {
+        uint8_t b[64];
+        fe_to_be32(fe_from_mont(p.x).v, b);
+        fe_to_be32(fe_from_mont(p.y).v, b + 32);
+        buf.insert(buf.end(), b, b + 64);
     }
     Fr squeeze() override {
         if (buf.size() == 32) buf.push_back(0x01);
@@ -241,6 +248,13 @@ struct Blake2bTranscript : Transcript {
         c[31] |= (uint8_t)((y.v[0] & 1) << 7);
         out.insert(out.end(), c, c + 32);
         return true;
+    }
+    void common_point(const G1Affine& p) override {
+        const Fq x = fe_from_mont(p.x), y = fe_from_mont(p.y);
+        const uint8_t pre = 1;
+        st.update(&pre, 1);
+        st.update((const uint8_t*)x.v, 32);
+        st.update((const uint8_t*)y.v, 32);
     }
     Fr squeeze() override {
         const uint8_t pre = 0;

@@ -1,0 +1,427 @@
+// verifier.h — the host half of plonk::verify_proof for the circuit family of this engine (zk_verify / zk_verify_batch).
+//
+// Restates halo2_proofs' verifier (plonk/verifier.rs, the permutation / lookup / vanishing verifiers, KZG multi-open
+// `poly/kzg/multiopen/{gwc,shplonk}/verifier.rs`) the way the repository's pinned verifier does: the proof is read in the
+// prover's order, the challenges are squeezed from the same transcripts (transcript.h), the expected quotient value is the
+// y-Horner of the gate, permutation and lookup expressions at x divided by x^n - 1, and the multi-open reduces everything
+// to one KZG check e(A, [s]G2) = e(B, G2).  What leaves this file is that check as two lists of (scalar, base) terms — the
+// bases are the proof's points, the key's commitments and g[0] — which the device sums (verify.hip).  A proof that fails
+// before that point (non-canonical scalar, a zero where the verifier divides) is rejected here.
+//
+// Proof points are decoded before this runs (they depend on the bytes only): `pts` holds them in transcript order, affine
+// Montgomery, already checked (canonical, on the curve, not the identity).  Host code only: it compiles without a device.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "pk.h"
+#include "transcript.h"
+
+namespace zk {
+namespace verifier {
+
+struct Term {
+    Fr s;           // Montgomery
+    uint32_t base;  // [0, n_points): the proof's points; then fixed commitments, permutation commitments, g[0] (ProofLayout)
+};
+
+// where everything sits in a proof of one key / transcript / scheme
+struct ProofLayout {
+    bool evm = false, shplonk = false;
+    size_t point_size = 0, len = 0;
+    std::vector<uint32_t> point_off;   // byte offset of each point, transcript order
+    uint32_t n_points = 0;             // = point_off.size()
+    uint32_t n_fix = 0, n_perm = 0;
+    uint32_t base_fix() const { return n_points; }
+    uint32_t base_perm() const { return n_points + n_fix; }
+    uint32_t base_g0() const { return n_points + n_fix + n_perm; }
+    uint32_t n_bases() const { return base_g0() + 1; }
+};
+
+// one opened value: commitment (a base index, or H for the quotient pieces combined with powers of x^n), rotation, eval index
+static constexpr uint32_t KEY_H = 0xffffffffu;
+struct Query {
+    uint32_t key;
+    int rot;
+    uint32_t eval;
+};
+
+// point indices in transcript order
+struct PointIdx {
+    uint32_t adv, lk_perm, perm_z, lk_z, random, h, opening;
+};
+inline PointIdx point_idx(const Layout& lay) {
+    PointIdx p;
+    p.adv = 0;
+    p.lk_perm = lay.n_adv;                        // (a', s') per lookup
+    p.perm_z = p.lk_perm + 2 * lay.n_lookups;
+    p.lk_z = p.perm_z + lay.n_chunks;
+    p.random = p.lk_z + lay.n_lookups;
+    p.h = p.random + 1;
+    p.opening = p.h + lay.n_h;
+    return p;
+}
+// scalar indices (evaluations) in transcript order
+struct EvalIdx {
+    uint32_t adv, fix, random, sigma, perm, lookup, count;
+};
+inline EvalIdx eval_idx(const Layout& lay) {
+    EvalIdx e;
+    e.adv = 0;
+    e.fix = (uint32_t)lay.advice_queries.size();
+    e.random = e.fix + lay.n_fix;
+    e.sigma = e.random + 1;
+    e.perm = e.sigma + (uint32_t)lay.perm_cols.size();
+    e.lookup = e.perm + 3 * lay.n_chunks - 1;  // (z, z_next, z_last) per chunk, the last chunk without z_last
+    e.count = e.lookup + 5 * lay.n_lookups;
+    return e;
+}
+inline uint32_t perm_eval(const Layout& lay, uint32_t chunk, uint32_t which) {  // which: 0 z, 1 z_next, 2 z_last
+    (void)lay;
+    return eval_idx(lay).perm + 3 * chunk + which;
+}
+
+// the verifier's queries in halo2's order (the pinned verifier's build_queries, then h and the random polynomial)
+inline std::vector<Query> build_queries(const Layout& lay, const ProofLayout& pl) {
+    const PointIdx P = point_idx(lay);
+    const EvalIdx E = eval_idx(lay);
+    std::vector<Query> q;
+    for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
+        q.push_back({P.adv + lay.advice_queries[i].first, lay.advice_queries[i].second, E.adv + i});
+    for (uint32_t i = 0; i < lay.n_chunks; i++) {
+        q.push_back({P.perm_z + i, 0, perm_eval(lay, i, 0)});
+        q.push_back({P.perm_z + i, 1, perm_eval(lay, i, 1)});
+    }
+    for (int i = (int)lay.n_chunks - 2; i >= 0; i--) q.push_back({P.perm_z + i, lay.last_rot, perm_eval(lay, i, 2)});
+    for (uint32_t l = 0; l < lay.n_lookups; l++) {
+        const uint32_t e = E.lookup + 5 * l;  // z, z_next, a', a'(w^-1 x), s'
+        q.push_back({P.lk_z + l, 0, e});
+        q.push_back({P.lk_perm + 2 * l, 0, e + 2});
+        q.push_back({P.lk_perm + 2 * l + 1, 0, e + 4});
+        q.push_back({P.lk_perm + 2 * l, -1, e + 3});
+        q.push_back({P.lk_z + l, 1, e + 1});
+    }
+    for (uint32_t f = 0; f < lay.n_fix; f++) q.push_back({pl.base_fix() + f, 0, E.fix + f});
+    for (uint32_t i = 0; i < lay.perm_cols.size(); i++) q.push_back({pl.base_perm() + i, 0, E.sigma + i});
+    q.push_back({KEY_H, 0, E.count});  // the expected h(x): an extra value, appended to the evaluations
+    q.push_back({P.random, 0, E.random});
+    return q;
+}
+
+// GWC: the distinct rotations in order of first appearance
+inline std::vector<int> gwc_rotations(const std::vector<Query>& qs) {
+    std::vector<int> rots;
+    for (const Query& q : qs)
+        if (std::find(rots.begin(), rots.end(), q.rot) == rots.end()) rots.push_back(q.rot);
+    return rots;
+}
+
+inline ProofLayout proof_layout(const Layout& lay, bool evm, bool shplonk) {
+    ProofLayout pl;
+    pl.evm = evm;
+    pl.shplonk = shplonk;
+    pl.point_size = evm ? 64 : 32;
+    pl.n_fix = lay.n_fix;
+    pl.n_perm = (uint32_t)lay.perm_cols.size();
+    const PointIdx P = point_idx(lay);
+    const EvalIdx E = eval_idx(lay);
+    size_t off = 0;
+    auto pts = [&](uint32_t n) {
+        for (uint32_t i = 0; i < n; i++) {
+            pl.point_off.push_back((uint32_t)off);
+            off += pl.point_size;
+        }
+    };
+    pts(P.opening);  // every commitment before the evaluations
+    off += 32 * (size_t)E.count;
+    pl.n_points = P.opening;  // (provisional: the opening points follow)
+    if (shplonk) {
+        pts(2);
+    } else {
+        ProofLayout tmp = pl;
+        pts((uint32_t)gwc_rotations(build_queries(lay, tmp)).size());
+    }
+    pl.n_points = (uint32_t)pl.point_off.size();
+    pl.len = off;
+    return pl;
+}
+
+inline bool fr_read(const uint8_t* b, bool big_endian, Fr* out_mont) {
+    Fr c;
+    for (int i = 0; i < 32; i++) ((uint8_t*)c.v)[i] = big_endian ? b[31 - i] : b[i];
+    for (int i = 7; i >= 0; i--) {
+        if (c.v[i] != FrParams::P[i]) {
+            if (c.v[i] > FrParams::P[i]) return false;
+            break;
+        }
+        if (i == 0) return false;  // == r
+    }
+    *out_mont = fe_to_mont(c);
+    return true;
+}
+
+inline Fr fr_delta_host() { return fe_pow_u64(fr_from_u64(7), 1ull << 28); }  // 7^(2^28), the permutation coset generator
+
+struct Challenges {
+    Fr theta, beta, gamma, y, x, v, u, shplonk_y;
+};
+
+struct Prepared {
+    std::vector<Term> a, b;
+    Challenges ch;
+};
+
+// a product of terms that shares bases: one term per base (zero scalars kept out)
+inline void merge_terms(std::vector<Term>& t) {
+    std::stable_sort(t.begin(), t.end(), [](const Term& x, const Term& y) { return x.base < y.base; });
+    std::vector<Term> out;
+    for (const Term& x : t) {
+        if (!out.empty() && out.back().base == x.base) out.back().s = fe_add(out.back().s, x.s);
+        else out.push_back(x);
+    }
+    t.clear();
+    for (const Term& x : out)
+        if (!x.s.is_zero()) t.push_back(x);
+}
+
+// false: the proof is rejected before the pairing (non-canonical scalar, an inverse of zero).  Otherwise `out` holds the two
+// term lists of the KZG check.  proof.len == pl.len is the caller's check.
+inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLayout& pl, const uint8_t* proof, const G1Affine* pts,
+                    Prepared* out) {
+    EvmTranscript evm;
+    Blake2bTranscript b2;
+    Transcript* tr = pl.evm ? (Transcript*)&evm : (Transcript*)&b2;
+    const PointIdx P = point_idx(lay);
+    const EvalIdx E = eval_idx(lay);
+    Challenges& ch = out->ch;
+    tr->common_scalar(transcript_repr);
+    uint32_t np = 0;
+    auto absorb_points = [&](uint32_t n) {
+        for (uint32_t i = 0; i < n; i++) tr->common_point(pts[np++]);
+    };
+    absorb_points(lay.n_adv);
+    ch.theta = tr->squeeze();
+    absorb_points(2 * lay.n_lookups);
+    ch.beta = tr->squeeze();
+    ch.gamma = tr->squeeze();
+    absorb_points(lay.n_chunks + lay.n_lookups + 1);
+    ch.y = tr->squeeze();
+    absorb_points(lay.n_h);
+    ch.x = tr->squeeze();
+    std::vector<Fr> ev(E.count + 1);
+    const size_t ev_off = (size_t)P.opening * pl.point_size;
+    for (uint32_t i = 0; i < E.count; i++) {
+        if (!fr_read(proof + ev_off + 32 * (size_t)i, pl.evm, &ev[i])) return false;
+        tr->common_scalar(ev[i]);
+    }
+
+    // ---- expected h(x) (the pinned verifier's expected_h_eval) ----
+    const Fr one = Fr::one(), x = ch.x, y = ch.y, beta = ch.beta, gamma = ch.gamma;
+    const Fr w = fr_omega(lay.k);
+    Fr xn = x;
+    for (uint32_t i = 0; i < lay.k; i++) xn = fe_sqr(xn);
+    const Fr xn1 = fe_sub(xn, one);
+    if (xn1.is_zero()) return false;
+    const Fr c = fe_mul(xn1, fe_inv_fast(fr_from_u64(lay.n)));
+    const Fr w_inv = fe_inv_fast(w);
+    bool zero_div = false;
+    auto L = [&](int i) {  // l_i(x) = w^i (x^n - 1) / (n (x - w^i)), i may be negative
+        Fr wi = one;
+        const Fr step = i >= 0 ? w : w_inv;
+        for (int t = 0; t < (i >= 0 ? i : -i); t++) wi = fe_mul(wi, step);
+        const Fr d = fe_sub(x, wi);
+        if (d.is_zero()) zero_div = true;
+        return fe_mul(fe_mul(wi, c), fe_inv_fast(d));
+    };
+    const Fr l0 = L(0), l_last = L(-(int)(BLINDING_FACTORS + 1));
+    Fr l_blind = Fr::zero();
+    for (int i = 1; i <= (int)BLINDING_FACTORS; i++) l_blind = fe_add(l_blind, L(-i));
+    if (zero_div) return false;
+    const Fr active = fe_sub(fe_sub(one, l_last), l_blind);
+    auto adv = [&](uint32_t col, int rot) {
+        for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
+            if (lay.advice_queries[i].first == col && lay.advice_queries[i].second == rot) return ev[E.adv + i];
+        return Fr::zero();
+    };
+    auto fix = [&](uint32_t f) { return ev[E.fix + f]; };
+    std::vector<Fr> exprs;
+    for (uint32_t j = 0; j < lay.n_gate; j++) {
+        const Fr a = adv(j, 0), b = adv(j, 1), cc = adv(j, 2), d = adv(j, 3);
+        const uint32_t col = lay.gate_sel[j] & 0xffffffu, form = lay.gate_sel[j] >> 24;
+        const Fr q = fix(col);
+        Fr sel = q;
+        if (form) sel = fe_mul(q, fe_sub(fr_from_u64(form == 1 ? 2 : 1), q));
+        exprs.push_back(fe_mul(sel, fe_sub(fe_add(a, fe_mul(b, cc)), d)));
+    }
+    auto col_eval = [&](const Col& col) { return col.fixed ? fix(col.idx) : adv(col.idx, 0); };
+    auto pe = [&](uint32_t i, uint32_t which) { return ev[perm_eval(lay, i, which)]; };
+    exprs.push_back(fe_mul(l0, fe_sub(one, pe(0, 0))));
+    const Fr zl = pe(lay.n_chunks - 1, 0);
+    exprs.push_back(fe_mul(l_last, fe_sub(fe_sqr(zl), zl)));
+    for (uint32_t i = 1; i < lay.n_chunks; i++) exprs.push_back(fe_mul(l0, fe_sub(pe(i, 0), pe(i - 1, 2))));
+    const Fr delta = fr_delta_host();
+    Fr cur_base = fe_mul(beta, x);  // beta x delta^(i chunk_len)
+    for (uint32_t i = 0; i < lay.n_chunks; i++) {
+        const uint32_t lo = i * lay.chunk_len, hi = std::min<uint32_t>(lo + lay.chunk_len, (uint32_t)lay.perm_cols.size());
+        Fr left = pe(i, 1), right = pe(i, 0), cur = cur_base;
+        for (uint32_t t = lo; t < hi; t++) {
+            const Fr ce = col_eval(lay.perm_cols[t]);
+            left = fe_mul(left, fe_add(fe_add(ce, fe_mul(beta, ev[E.sigma + t])), gamma));
+            right = fe_mul(right, fe_add(fe_add(ce, cur), gamma));
+            cur = fe_mul(cur, delta);
+        }
+        cur_base = cur;
+        exprs.push_back(fe_mul(active, fe_sub(left, right)));
+    }
+    for (uint32_t l = 0; l < lay.n_lookups; l++) {
+        const Fr* le = &ev[E.lookup + 5 * l];
+        const Fr z = le[0], zn = le[1], ap = le[2], ap_inv = le[3], sp = le[4];
+        const Fr inp = lay.single ? fe_mul(fix(lay.fx_qlookup), adv(0, 0)) : adv(lay.n_gate + l, 0);
+        const Fr tab = fix(lay.fx_table);
+        exprs.push_back(fe_mul(l0, fe_sub(one, z)));
+        exprs.push_back(fe_mul(l_last, fe_sub(fe_sqr(z), z)));
+        const Fr left = fe_mul(fe_mul(zn, fe_add(ap, beta)), fe_add(sp, gamma));
+        const Fr right = fe_mul(fe_mul(z, fe_add(inp, beta)), fe_add(tab, gamma));
+        exprs.push_back(fe_mul(active, fe_sub(left, right)));
+        exprs.push_back(fe_mul(l0, fe_sub(ap, sp)));
+        exprs.push_back(fe_mul(fe_mul(active, fe_sub(ap, sp)), fe_sub(ap, ap_inv)));
+    }
+    Fr acc = Fr::zero();
+    for (const Fr& e : exprs) acc = fe_add(fe_mul(acc, y), e);
+    ev[E.count] = fe_mul(acc, fe_inv_fast(xn1));  // expected h(x)
+
+    // ---- multi-open ----
+    const std::vector<Query> qs = build_queries(lay, pl);
+    std::vector<Fr> xn_pow(lay.n_h);
+    xn_pow[0] = one;
+    for (uint32_t i = 1; i < lay.n_h; i++) xn_pow[i] = fe_mul(xn_pow[i - 1], xn);
+    auto point_of = [&](int rot) {  // x w^rot
+        Fr r = x;
+        const Fr step = rot >= 0 ? w : w_inv;
+        for (int t = 0; t < (rot >= 0 ? rot : -rot); t++) r = fe_mul(r, step);
+        return r;
+    };
+    auto commit = [&](std::vector<Term>& dst, uint32_t key, const Fr& s) {  // s * commitment(key)
+        if (key == KEY_H) {
+            for (uint32_t i = 0; i < lay.n_h; i++) dst.push_back({fe_mul(s, xn_pow[i]), P.h + i});
+        } else {
+            dst.push_back({s, key});
+        }
+    };
+    std::vector<Term>& A = out->a;
+    std::vector<Term>& B = out->b;
+    A.clear();
+    B.clear();
+    if (!pl.shplonk) {
+        ch.v = tr->squeeze();
+        const std::vector<int> rots = gwc_rotations(qs);
+        for (uint32_t i = 0; i < rots.size(); i++) tr->common_point(pts[np + i]);
+        ch.u = tr->squeeze();
+        Fr pu = one, eval_multi = Fr::zero();
+        for (uint32_t si = 0; si < rots.size(); si++) {
+            const Fr z = point_of(rots[si]);
+            Fr pv = one, eb = Fr::zero();
+            for (const Query& q : qs) {
+                if (q.rot != rots[si]) continue;
+                commit(B, q.key, fe_mul(pu, pv));
+                eb = fe_add(eb, fe_mul(pv, ev[q.eval]));
+                pv = fe_mul(pv, ch.v);
+            }
+            eval_multi = fe_add(eval_multi, fe_mul(pu, eb));
+            B.push_back({fe_mul(pu, z), np + si});
+            A.push_back({pu, np + si});
+            pu = fe_mul(pu, ch.u);
+        }
+        B.push_back({fe_neg(eval_multi), pl.base_g0()});
+    } else {
+        // commitments with their rotation sets, by first appearance; rotation sets keyed by the set, by first appearance
+        struct ComRots {
+            uint32_t key;
+            std::vector<int> rots;
+        };
+        std::vector<ComRots> cr;
+        std::vector<int> all_rots;
+        for (const Query& q : qs) {
+            if (std::find(all_rots.begin(), all_rots.end(), q.rot) == all_rots.end()) all_rots.push_back(q.rot);
+            auto it = std::find_if(cr.begin(), cr.end(), [&](const ComRots& c2) { return c2.key == q.key; });
+            if (it == cr.end()) cr.push_back({q.key, {q.rot}});
+            else if (std::find(it->rots.begin(), it->rots.end(), q.rot) == it->rots.end()) it->rots.push_back(q.rot);
+        }
+        struct RSet {
+            std::vector<int> rots;  // sorted
+            std::vector<uint32_t> keys;
+        };
+        std::vector<RSet> rs;
+        for (ComRots& c2 : cr) {
+            std::sort(c2.rots.begin(), c2.rots.end());
+            auto it = std::find_if(rs.begin(), rs.end(), [&](const RSet& r) { return r.rots == c2.rots; });
+            if (it == rs.end()) rs.push_back({c2.rots, {c2.key}});
+            else it->keys.push_back(c2.key);
+        }
+        auto eval_of = [&](uint32_t key, int rot) {
+            Fr e = Fr::zero();
+            for (const Query& q : qs)
+                if (q.key == key && q.rot == rot) e = ev[q.eval];
+            return e;
+        };
+        ch.shplonk_y = tr->squeeze();
+        ch.v = tr->squeeze();
+        tr->common_point(pts[np]);
+        ch.u = tr->squeeze();
+        tr->common_point(pts[np + 1]);
+        const Fr u = ch.u;
+        Fr r_outer = Fr::zero(), z0 = one, z0_diff_inv = one, pv = one;
+        for (uint32_t i = 0; i < rs.size(); i++) {
+            std::vector<Fr> pts_i;
+            for (int r : rs[i].rots) pts_i.push_back(point_of(r));
+            Fr zd = one;
+            for (int r : all_rots)
+                if (std::find(rs[i].rots.begin(), rs[i].rots.end(), r) == rs[i].rots.end()) zd = fe_mul(zd, fe_sub(u, point_of(r)));
+            if (i == 0) {
+                z0 = one;
+                for (const Fr& p : pts_i) z0 = fe_mul(z0, fe_sub(u, p));
+                if (zd.is_zero()) return false;
+                z0_diff_inv = fe_inv_fast(zd);
+                zd = one;
+            } else {
+                zd = fe_mul(zd, z0_diff_inv);
+            }
+            // Lagrange interpolation through (pts_i, evals) evaluated at u
+            const size_t m = pts_i.size();
+            std::vector<Fr> basis(m);
+            for (size_t j = 0; j < m; j++) {
+                Fr num = one, den = one;
+                for (size_t t = 0; t < m; t++) {
+                    if (t == j) continue;
+                    num = fe_mul(num, fe_sub(u, pts_i[t]));
+                    den = fe_mul(den, fe_sub(pts_i[j], pts_i[t]));
+                }
+                if (den.is_zero()) return false;
+                basis[j] = fe_mul(num, fe_inv_fast(den));
+            }
+            Fr py = one, r_inner = Fr::zero();
+            for (uint32_t key : rs[i].keys) {
+                Fr rx = Fr::zero();
+                for (size_t j = 0; j < m; j++) rx = fe_add(rx, fe_mul(eval_of(key, rs[i].rots[j]), basis[j]));
+                r_inner = fe_add(r_inner, fe_mul(py, rx));
+                commit(B, key, fe_mul(fe_mul(py, pv), zd));
+                py = fe_mul(py, ch.shplonk_y);
+            }
+            r_outer = fe_add(r_outer, fe_mul(fe_mul(pv, r_inner), zd));
+            pv = fe_mul(pv, ch.v);
+        }
+        B.push_back({fe_neg(r_outer), pl.base_g0()});
+        B.push_back({fe_neg(z0), np});
+        B.push_back({u, np + 1});
+        A.push_back({one, np + 1});
+    }
+    merge_terms(A);
+    merge_terms(B);
+    return true;
+}
+
+}  // namespace verifier
+}  // namespace zk

@@ -1,0 +1,530 @@
+// verify.hip — plonk::verify_proof on the resident engine: zk_verify / zk_verify_batch, and the verifying-only keys of
+// zk_vk_read / zk_vk_from_parts.
+//
+// One batch of proofs of one key goes through four steps:
+//   1. device: every proof point of the batch is decoded in one launch (verify_decode_kernel: 32-byte compressed points of
+//      the Blake2b transcript, 64-byte big-endian x || y of the EVM one), with a flag per point — canonical, on the curve,
+//      not the identity, the rules of the repository's pinned verifier;
+//   2. host: one transcript per proof (verifier.h) — challenges, expected h(x), the GWC or SHPLONK opening — giving the
+//      two term lists of the proof's KZG check e(A_j, [s]G2) = e(B_j, G2); a proof that fails here (length, a point, a
+//      non-canonical scalar) has its verdict and leaves the batch.  Spread over at most 16 host threads;
+//   3. device: all A_j, B_j in one launch (verify_msm_kernel: one wave per accumulator, lanes own terms and share one
+//      doubling chain over the scalars' bits, then a tree sum through LDS);
+//   4. fold: A = sum rho_j A_j, B = sum rho_j B_j with 128-bit rho_j drawn from a hash of the key's transcript_repr and
+//      every proof's bytes (the same kernel over the accumulators), ONE host pairing (pairing.h); if it fails, the set is
+//      halved and each half folded and paired again, down to single proofs, so every verdict is the proof's own.
+// zk_verify is the batch of one: the same path, without a fold.
+#include <string.h>
+
+#include <algorithm>
+#include <thread>
+
+#include "pairing.h"
+#include "pk.h"
+#include "verifier.h"
+#include "vkrepr.h"
+
+using zk::verifier::Term;
+
+namespace {
+
+struct Words8 {
+    uint32_t w[8];
+};
+
+__device__ __forceinline__ bool v_lt_p(const uint32_t* v) {
+    for (int i = 7; i >= 0; i--)
+        if (v[i] != FqParams::P[i]) return v[i] < FqParams::P[i];
+    return false;
+}
+__device__ __forceinline__ Fq v_three_mont() {
+    Fq t = Fq::zero();
+    t.v[0] = 3;
+    return fe_to_mont(t);
+}
+// 32 bytes at b as a 256-bit integer, little- or big-endian
+__device__ __forceinline__ Fq v_load_bytes(const uint8_t* b, bool big_endian) {
+    Fq r;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const uint32_t byte = big_endian ? b[31 - (4 * k + t)] : b[4 * k + t];
+            w |= byte << (8 * t);
+        }
+        r.v[k] = w;
+    }
+    return r;
+}
+
+// point i of the batch: bytes at off[i]; out = affine Montgomery, flag[i] = 1 if the point is one the verifier accepts
+__global__ void verify_decode_kernel(const uint8_t* __restrict__ bytes, const uint32_t* __restrict__ off, uint32_t n, int evm, Words8 sqrt_exp,
+                                     G1Affine* __restrict__ out, uint8_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* b = bytes + off[i];
+    G1Affine r;
+    r.x = Fq::zero();
+    r.y = Fq::zero();
+    uint8_t ok = 0;
+    if (evm) {
+        const Fq x = v_load_bytes(b, true), y = v_load_bytes(b + 32, true);
+        if (v_lt_p(x.v) && v_lt_p(y.v) && !(x.is_zero() && y.is_zero())) {
+            const Fq xm = fe_to_mont(x), ym = fe_to_mont(y);
+            if (fe_sqr(ym) == fe_add(fe_mul(fe_sqr(xm), xm), v_three_mont())) {
+                r.x = xm;
+                r.y = ym;
+                ok = 1;
+            }
+        }
+    } else {
+        Fq x = v_load_bytes(b, false);
+        const uint32_t sign = x.v[7] >> 31;
+        x.v[7] &= 0x7fffffffu;
+        if (v_lt_p(x.v)) {  // (x = 0 has no point: 3 is not a square mod p)
+            const Fq xm = fe_to_mont(x);
+            const Fq rhs = fe_add(fe_mul(fe_sqr(xm), xm), v_three_mont());
+            Fq y = fe_pow(rhs, sqrt_exp.w);  // p = 3 (mod 4)
+            if (fe_sqr(y) == rhs) {
+                if ((fe_from_mont(y).v[0] & 1u) != sign) y = fe_neg(y);
+                r.x = xm;
+                r.y = y;
+                ok = 1;
+            }
+        }
+    }
+    fe_store(&out[i].x, r.x);
+    fe_store(&out[i].y, r.y);
+    flag[i] = ok;
+}
+
+struct VSeg {
+    uint32_t first, count;
+};
+
+// out[s] = sum over the segment's terms of scalar * base.  One 64-lane wave per segment; lane l owns terms l, l + 64, ...
+// and all lanes walk the scalars' top `nbits` bits together (acc = 2 acc + the lane's bases whose bit is set), then the 64
+// partial sums are added pairwise through LDS.  Scalars are canonical integers; a base index below n0 reads t0, below n0 + n1
+// t1, anything else t2[0] (g[0] of the SRS).  Zero scalars and identity bases (0, 0) contribute nothing.
+__global__ __launch_bounds__(64) void verify_msm_kernel(const Fr* __restrict__ scal, const uint32_t* __restrict__ idx, const VSeg* __restrict__ segs,
+                                                        const G1Affine* __restrict__ t0, uint32_t n0, const G1Affine* __restrict__ t1, uint32_t n1,
+                                                        const G1Affine* __restrict__ t2, uint32_t nbits, G1X* __restrict__ out) {
+    __shared__ G1X sh[64];
+    const VSeg sg = segs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    G1X acc = G1X::identity();
+    for (int bit = (int)nbits - 1; bit >= 0; bit--) {
+        acc = g1x_dbl(acc);
+        for (uint32_t t = lane; t < sg.count; t += 64) {
+            const uint32_t j = sg.first + t;
+            const uint32_t w = reinterpret_cast<const uint32_t*>(scal + j)[bit >> 5];
+            if (!((w >> (bit & 31)) & 1)) continue;
+            const uint32_t bi = idx[j];
+            const G1Affine* bp = bi < n0 ? t0 + bi : bi < n0 + n1 ? t1 + (bi - n0) : t2;
+            const G1Affine p = affine_load(bp);
+            if (!affine_is_identity(p)) g1x_add_affine(acc, p.x, p.y);
+        }
+    }
+    sh[lane] = acc;
+    __syncthreads();
+    for (uint32_t s = 32; s > 0; s >>= 1) {
+        if (lane < s) {
+            G1X a = sh[lane];
+            g1x_add(a, sh[lane + s]);
+            sh[lane] = a;
+        }
+        __syncthreads();
+    }
+    if (lane == 0) g1x_store(out + blockIdx.x, sh[0]);
+}
+
+Words8 fq_sqrt_exp_words() {  // (p + 1) / 4
+    Words8 e;
+    uint64_t carry = 1;
+    uint32_t t[8];
+    for (int i = 0; i < 8; i++) {
+        const uint64_t s = (uint64_t)FqParams::P[i] + carry;
+        t[i] = (uint32_t)s;
+        carry = s >> 32;
+    }
+    for (int i = 0; i < 8; i++) e.w[i] = (t[i] >> 2) | (i + 1 < 8 ? t[i + 1] << 30 : 0);
+    return e;
+}
+
+// grow-only device buffer
+int ws_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
+    if (*cap >= bytes) return ZK_OK;
+    if (*p) {
+        hipStreamSynchronize(c->stream);
+        hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+    }
+    const size_t want = std::max<size_t>(bytes, 4096);
+    if (hipMalloc(p, want) != hipSuccess) return ZK_ENOMEM;
+    *cap = want;
+    return ZK_OK;
+}
+
+// affine forms of XYZZ sums (one inversion for all of them)
+std::vector<G1Affine> to_affine_batch(const std::vector<G1X>& v) {
+    std::vector<Fq> den, pre;
+    for (const G1X& p : v)
+        if (!p.is_identity()) {
+            den.push_back(p.zz);
+            den.push_back(p.zzz);
+        }
+    pre.resize(den.size());
+    Fq acc = Fq::one();
+    for (size_t i = 0; i < den.size(); i++) {
+        pre[i] = acc;
+        acc = fe_mul(acc, den[i]);
+    }
+    Fq inv = fe_inv_fast(acc);
+    std::vector<Fq> dinv(den.size());
+    for (size_t i = den.size(); i-- > 0;) {
+        dinv[i] = fe_mul(inv, pre[i]);
+        inv = fe_mul(inv, den[i]);
+    }
+    std::vector<G1Affine> out(v.size());
+    size_t k = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (v[i].is_identity()) {
+            out[i].x = Fq::zero();
+            out[i].y = Fq::zero();
+            continue;
+        }
+        out[i].x = fe_mul(v[i].x, dinv[k++]);
+        out[i].y = fe_mul(v[i].y, dinv[k++]);
+    }
+    return out;
+}
+
+template <class Fn>
+void parallel_for(size_t n, Fn fn) {
+    const size_t T = std::min<size_t>(16, n / 4);  // at most 16 host threads, never the machine's core count
+    if (T <= 1) {
+        for (size_t i = 0; i < n; i++) fn(i);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < T; t++)
+        th.emplace_back([&, t]() {
+            for (size_t i = t; i < n; i += T) fn(i);
+        });
+    for (size_t i = 0; i < n; i += T) fn(i);
+    for (auto& x : th) x.join();
+}
+
+}  // namespace
+
+// the context's verify workspace (grow-only, sized by the largest batch seen)
+struct VerifyWs {
+    void *bytes = nullptr, *off = nullptr, *pts = nullptr, *flag = nullptr, *scal = nullptr, *idx = nullptr, *seg = nullptr, *out = nullptr,
+         *fold = nullptr;
+    size_t c_bytes = 0, c_off = 0, c_pts = 0, c_flag = 0, c_scal = 0, c_idx = 0, c_seg = 0, c_out = 0, c_fold = 0;
+};
+
+void verify_ws_destroy(VerifyWs* w) {
+    if (!w) return;
+    for (void* p : {w->bytes, w->off, w->pts, w->flag, w->scal, w->idx, w->seg, w->out, w->fold})
+        if (p) hipFree(p);
+    delete w;
+}
+
+// a key record holding the verifying key only: commitments (host and device), transcript_repr; no SRS-sized memory
+int pk_make_verify_only(zk_ctx* c, const Layout& lay, const std::vector<G1Affine>& fixed, const std::vector<G1Affine>& perm,
+                        const uint64_t transcript_repr[4], zk_pk* out) {
+    if (fixed.size() != lay.n_fix || perm.size() != lay.perm_cols.size()) return ZK_EINVAL;
+    Fr repr;
+    if (transcript_repr) {
+        memcpy(&repr, transcript_repr, 32);
+        bool lt = false;
+        for (int i = 7; i >= 0; i--)
+            if (repr.v[i] != FrParams::P[i]) {
+                lt = repr.v[i] < FrParams::P[i];
+                break;
+            }
+        if (!lt) return ZK_EINVAL;
+    } else {
+        repr = vkrepr::transcript_repr(lay, fixed, perm);
+    }
+    zk_pk_rec* pk = new (std::nothrow) zk_pk_rec();
+    if (!pk) return ZK_ENOMEM;
+    pk->lay = lay;
+    pk->verify_only = true;
+    pk->srs_gen = c->srs_gen;
+    pk->fixed_commit = fixed;
+    pk->perm_commit = perm;
+    pk->transcript_repr = repr;
+    const uint64_t h = c->next_handle++;
+    c->pks[h] = pk;
+    *out = h;
+    return ZK_OK;
+}
+
+// the key's commitments on the device (fixed, then permutation), made on the first verify and kept with the key
+static int pk_vk_bases(zk_ctx* c, zk_pk_rec* pk) {
+    if (pk->d_vk_bases) return ZK_OK;
+    const size_t n = pk->fixed_commit.size() + pk->perm_commit.size();
+    G1Affine* d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(G1Affine)) != hipSuccess) return ZK_ENOMEM;
+    pk->dev.push_back(reinterpret_cast<Fr*>(d));  // freed with the key's other allocations (pk_destroy)
+    std::vector<G1Affine> h(pk->fixed_commit);
+    h.insert(h.end(), pk->perm_commit.begin(), pk->perm_commit.end());
+    if (c->audit.on) c->audit.op(c->stream, {}, {d}, "verify: key commitments upload");
+    HIPCHK(c, hipMemcpyAsync(d, h.data(), n * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, aud_sync(c, c->stream));  // (h is pageable and goes out of scope)
+    pk->d_vk_bases = d;
+    return ZK_OK;
+}
+
+ZK_API(zk_vk_from_parts, (zk_ctx* c, const zk_circuit_params* params, const uint64_t* fixed_commitments, const uint64_t* perm_commitments, const uint64_t transcript_repr[4], zk_pk* out), (c, params, fixed_commitments, perm_commitments, transcript_repr, out)) {
+    if (!c || !params || !fixed_commitments || !perm_commitments || !out) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    Layout lay;
+    if (params->num_advice > 1 && 2 * (uint64_t)params->num_idle_gate_columns > params->num_advice) return ZK_ELAYOUT;
+    if (!lay.init(*params)) return ZK_EINVAL;
+    std::vector<G1Affine> fixed(lay.n_fix), perm(lay.perm_cols.size());
+    memcpy(fixed.data(), fixed_commitments, fixed.size() * sizeof(G1Affine));
+    memcpy(perm.data(), perm_commitments, perm.size() * sizeof(G1Affine));
+    for (const std::vector<G1Affine>* v : {&fixed, &perm})
+        for (const G1Affine& p : *v) {
+            const Fq x = fe_from_mont(p.x), y = fe_from_mont(p.y);  // (a Montgomery image >= p would not round-trip)
+            if (fe_to_mont(x) != p.x || fe_to_mont(y) != p.y) return ZK_EINVAL;
+            if (!affine_is_identity(p) && fe_sqr(p.y) != fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3))) return ZK_EINVAL;
+        }
+    return pk_make_verify_only(c, lay, fixed, perm, transcript_repr, out);
+}
+
+namespace {
+
+struct Job {
+    zk_ctx* c;
+    zk_pk_rec* pk;
+    VerifyWs* w;
+    G2A g2, s_g2;
+    // per proof of the batch that reached the device sums: A_j (index 2 j), B_j (2 j + 1) of the accumulators
+    std::vector<uint32_t> live;
+    std::vector<G1Affine> acc;
+    std::vector<Fr> rho;
+};
+
+// sum_{j in S} rho_j A_j and rho_j B_j on the device (64 terms per segment; the segments' sums are added here)
+int fold(Job& J, const std::vector<uint32_t>& S, G1Affine* A, G1Affine* B) {
+    zk_ctx* c = J.c;
+    VerifyWs* w = J.w;
+    std::vector<Fr> sc;
+    std::vector<uint32_t> ix;
+    std::vector<VSeg> sg;
+    for (int side = 0; side < 2; side++)
+        for (size_t lo = 0; lo < S.size(); lo += 64) {
+            const size_t hi = std::min(S.size(), lo + 64);
+            sg.push_back({(uint32_t)sc.size(), (uint32_t)(hi - lo)});
+            for (size_t t = lo; t < hi; t++) {
+                sc.push_back(fe_from_mont(J.rho[S[t]]));
+                ix.push_back(2 * S[t] + side);
+            }
+        }
+    int rc;
+    if ((rc = ws_grow(c, &w->scal, &w->c_scal, sc.size() * sizeof(Fr))) || (rc = ws_grow(c, &w->idx, &w->c_idx, ix.size() * 4)) ||
+        (rc = ws_grow(c, &w->seg, &w->c_seg, sg.size() * sizeof(VSeg))) || (rc = ws_grow(c, &w->out, &w->c_out, sg.size() * sizeof(G1X))))
+        return rc;
+    if (c->audit.on) c->audit.op(c->stream, {}, {w->scal, w->idx, w->seg}, "verify: fold arguments upload");
+    HIPCHK(c, hipMemcpyAsync(w->scal, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->idx, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->seg, sg.data(), sg.size() * sizeof(VSeg), hipMemcpyHostToDevice, c->stream));
+    if (c->audit.on) c->audit.op(c->stream, {w->scal, w->idx, w->seg, w->fold}, {w->out}, "verify: fold (verify_msm_kernel)");
+    hipLaunchKernelGGL(verify_msm_kernel, dim3((uint32_t)sg.size()), dim3(64), 0, c->stream, (const Fr*)w->scal, (const uint32_t*)w->idx,
+                       (const VSeg*)w->seg, (const G1Affine*)w->fold, (uint32_t)J.acc.size(), (const G1Affine*)nullptr, 0u,
+                       (const G1Affine*)w->fold, 128u, (G1X*)w->out);
+    HIPCHK(c, hipGetLastError());
+    std::vector<G1X> res(sg.size());
+    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "verify: fold results download");
+    HIPCHK(c, hipMemcpyAsync(res.data(), w->out, res.size() * sizeof(G1X), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, aud_sync(c, c->stream));
+    G1X sum[2] = {G1X::identity(), G1X::identity()};
+    const size_t per_side = sg.size() / 2;
+    for (size_t i = 0; i < sg.size(); i++) g1x_add(sum[i / per_side], res[i]);
+    const std::vector<G1Affine> af = to_affine_batch({sum[0], sum[1]});
+    *A = af[0];
+    *B = af[1];
+    return ZK_OK;
+}
+
+// exact verdicts for the proofs S (positions into J.live): one fold + pairing, halves on failure
+int settle(Job& J, const std::vector<uint32_t>& S, uint8_t* verdicts) {
+    if (S.empty()) return ZK_OK;
+    bool ok;
+    if (S.size() == 1) {
+        ok = pairing_check(J.acc[2 * S[0]], J.acc[2 * S[0] + 1], J.g2, J.s_g2);
+    } else {
+        G1Affine A, B;
+        if (int rc = fold(J, S, &A, &B)) return rc;
+        ok = pairing_check(A, B, J.g2, J.s_g2);
+    }
+    if (ok) {
+        for (uint32_t s : S) verdicts[J.live[s]] = 1;
+        return ZK_OK;
+    }
+    if (S.size() == 1) return ZK_OK;
+    const size_t h = S.size() / 2;
+    if (int rc = settle(J, std::vector<uint32_t>(S.begin(), S.begin() + h), verdicts)) return rc;
+    return settle(J, std::vector<uint32_t>(S.begin() + h, S.end()), verdicts);
+}
+
+}  // namespace
+
+ZK_API(zk_verify_batch, (zk_ctx* c, zk_pk h, size_t batch, int transcript, int scheme, const uint8_t* const* proofs, const size_t* lens, uint8_t* verdicts), (c, h, batch, transcript, scheme, proofs, lens, verdicts)) {
+    if (!c || !proofs || !lens || !verdicts || batch == 0 || batch > ZK_VERIFY_BATCH_MAX) return ZK_EINVAL;
+    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
+    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
+    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    for (size_t j = 0; j < batch; j++)
+        if (!proofs[j] && lens[j]) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->pks.find(h);
+    if (it == c->pks.end()) return ZK_EINVAL;
+    zk_pk_rec* pk = it->second;
+    if (!pk->verify_only && pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // a full key under a replaced SRS: its vk is stale
+    if (c->srs_k < 0 || !c->g2_valid) return ZK_ESTATE;  // g[0], g2 and s_g2 come from the resident SRS
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    const uint64_t aud0 = c->audit.violations;
+    c->audit.base_of.clear();
+    if (!c->vws && !(c->vws = new (std::nothrow) VerifyWs())) return ZK_ENOMEM;
+    VerifyWs* w = c->vws;
+    if ((rc = pk_vk_bases(c, pk))) return rc;
+    const Layout& lay = pk->lay;
+    const verifier::ProofLayout pl = verifier::proof_layout(lay, transcript == ZK_TRANSCRIPT_EVM, scheme == ZK_SCHEME_SHPLONK);
+    std::vector<uint8_t> v(batch, 0);
+    Job J{c, pk, w, g2_from_raw(c->g2_raw), g2_from_raw(c->s_g2_raw), {}, {}, {}};
+
+    // 1. decode every point of every proof of the right length
+    std::vector<uint32_t> cand;
+    for (size_t j = 0; j < batch; j++)
+        if (lens[j] == pl.len) cand.push_back((uint32_t)j);
+    if (!cand.empty()) {
+        const size_t np = pl.n_points, nb = cand.size() * pl.len, npts = cand.size() * np;
+        std::vector<uint8_t> bytes(nb);
+        std::vector<uint32_t> off(npts);
+        for (size_t t = 0; t < cand.size(); t++) {
+            memcpy(bytes.data() + t * pl.len, proofs[cand[t]], pl.len);
+            for (size_t i = 0; i < np; i++) off[t * np + i] = (uint32_t)(t * pl.len + pl.point_off[i]);
+        }
+        if ((rc = ws_grow(c, &w->bytes, &w->c_bytes, nb)) || (rc = ws_grow(c, &w->off, &w->c_off, npts * 4)) ||
+            (rc = ws_grow(c, &w->pts, &w->c_pts, npts * sizeof(G1Affine))) || (rc = ws_grow(c, &w->flag, &w->c_flag, npts)))
+            return rc;
+        if (c->audit.on) c->audit.op(c->stream, {}, {w->bytes, w->off}, "verify: proof bytes upload");
+        HIPCHK(c, hipMemcpyAsync(w->bytes, bytes.data(), nb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(w->off, off.data(), npts * 4, hipMemcpyHostToDevice, c->stream));
+        if (c->audit.on) c->audit.op(c->stream, {w->bytes, w->off}, {w->pts, w->flag}, "verify: point decoding (verify_decode_kernel)");
+        hipLaunchKernelGGL(verify_decode_kernel, dim3((uint32_t)((npts + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)w->bytes,
+                           (const uint32_t*)w->off, (uint32_t)npts, transcript == ZK_TRANSCRIPT_EVM ? 1 : 0, fq_sqrt_exp_words(),
+                           (G1Affine*)w->pts, (uint8_t*)w->flag);
+        HIPCHK(c, hipGetLastError());
+        std::vector<G1Affine> pts(npts);
+        std::vector<uint8_t> flag(npts);
+        if (c->audit.on) c->audit.op(c->stream, {w->pts, w->flag}, {}, "verify: decoded points download");
+        HIPCHK(c, hipMemcpyAsync(pts.data(), w->pts, npts * sizeof(G1Affine), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(flag.data(), w->flag, npts, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, aud_sync(c, c->stream));
+
+        // 2. transcripts and term lists, per proof on the host
+        std::vector<verifier::Prepared> prep(cand.size());
+        std::vector<uint8_t> good(cand.size(), 0);
+        parallel_for(cand.size(), [&](size_t t) {
+            try {
+                for (size_t i = 0; i < np; i++)
+                    if (!flag[t * np + i]) return;
+                good[t] = verifier::prepare(lay, pk->transcript_repr, pl, proofs[cand[t]], pts.data() + t * np, &prep[t]) ? 1 : 0;
+            } catch (...) {
+                good[t] = 2;  // (allocation failure)
+            }
+        });
+        for (uint8_t g : good)
+            if (g == 2) return ZK_ENOMEM;
+
+        // 3. every A_j, B_j in one launch.  Bases: the batch's decoded points, then the key's commitments, then g[0]
+        std::vector<Fr> sc;
+        std::vector<uint32_t> ix;
+        std::vector<VSeg> sg;
+        const uint32_t n_key = pl.n_fix + pl.n_perm;
+        for (size_t t = 0; t < cand.size(); t++) {
+            if (!good[t]) continue;
+            J.live.push_back(cand[t]);
+            for (const std::vector<Term>* terms : {&prep[t].a, &prep[t].b}) {
+                sg.push_back({(uint32_t)sc.size(), (uint32_t)terms->size()});
+                for (const Term& x : *terms) {
+                    sc.push_back(fe_from_mont(x.s));
+                    const uint32_t b = x.base;
+                    ix.push_back(b < pl.n_points ? (uint32_t)(t * np + b) : b < pl.base_g0() ? (uint32_t)(npts + b - pl.n_points) : (uint32_t)(npts + n_key));
+                }
+            }
+        }
+        if (!J.live.empty()) {
+            if ((rc = ws_grow(c, &w->scal, &w->c_scal, sc.size() * sizeof(Fr))) || (rc = ws_grow(c, &w->idx, &w->c_idx, ix.size() * 4)) ||
+                (rc = ws_grow(c, &w->seg, &w->c_seg, sg.size() * sizeof(VSeg))) || (rc = ws_grow(c, &w->out, &w->c_out, sg.size() * sizeof(G1X))))
+                return rc;
+            if (c->audit.on) c->audit.op(c->stream, {}, {w->scal, w->idx, w->seg}, "verify: term lists upload");
+            HIPCHK(c, hipMemcpyAsync(w->scal, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(w->idx, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(w->seg, sg.data(), sg.size() * sizeof(VSeg), hipMemcpyHostToDevice, c->stream));
+            if (c->audit.on)
+                c->audit.op(c->stream, {w->scal, w->idx, w->seg, w->pts, pk->d_vk_bases, c->g}, {w->out}, "verify: accumulators (verify_msm_kernel)");
+            hipLaunchKernelGGL(verify_msm_kernel, dim3((uint32_t)sg.size()), dim3(64), 0, c->stream, (const Fr*)w->scal, (const uint32_t*)w->idx,
+                               (const VSeg*)w->seg, (const G1Affine*)w->pts, (uint32_t)npts, (const G1Affine*)pk->d_vk_bases, n_key,
+                               (const G1Affine*)c->g, 256u, (G1X*)w->out);
+            HIPCHK(c, hipGetLastError());
+            std::vector<G1X> res(sg.size());
+            if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "verify: accumulators download");
+            HIPCHK(c, hipMemcpyAsync(res.data(), w->out, res.size() * sizeof(G1X), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, aud_sync(c, c->stream));
+            J.acc = to_affine_batch(res);
+
+            // 4. fold with rho_j from a hash of the key and every proof, one pairing, bisection on failure
+            if (J.live.size() > 1) {
+                Blake2b hs("zkmi355-vbatch-r");
+                const Fr repr = fe_from_mont(pk->transcript_repr);
+                hs.update((const uint8_t*)repr.v, 32);
+                for (size_t j = 0; j < batch; j++) {
+                    const uint64_t ln = lens[j];
+                    hs.update((const uint8_t*)&ln, 8);
+                    if (ln) hs.update(proofs[j], ln);
+                }
+                uint8_t seed[64];
+                hs.finalize_copy(seed);
+                J.rho.resize(J.live.size());
+                for (size_t s = 0; s < J.live.size(); s++) {
+                    Blake2b hr("zkmi355-vbatch-j");
+                    hr.update(seed, 64);
+                    const uint64_t sj = s;
+                    hr.update((const uint8_t*)&sj, 8);
+                    uint8_t d[64];
+                    hr.finalize_copy(d);
+                    Fr r = Fr::zero();
+                    memcpy(r.v, d, 16);  // 128 bits
+                    if (r.is_zero()) r.v[0] = 1;
+                    J.rho[s] = fe_to_mont(r);
+                }
+                if ((rc = ws_grow(c, &w->fold, &w->c_fold, J.acc.size() * sizeof(G1Affine)))) return rc;
+                if (c->audit.on) c->audit.op(c->stream, {}, {w->fold}, "verify: accumulators upload for the fold");
+                HIPCHK(c, hipMemcpyAsync(w->fold, J.acc.data(), J.acc.size() * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
+            }
+            std::vector<uint32_t> S(J.live.size());
+            for (uint32_t s = 0; s < S.size(); s++) S[s] = s;
+            if ((rc = settle(J, S, v.data()))) return rc;
+        }
+    }
+    memcpy(verdicts, v.data(), batch);
+    return aud_verdict(c, aud0, ZK_OK);
+}
+
+ZK_API(zk_verify, (zk_ctx* c, zk_pk h, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok), (c, h, transcript, scheme, proof, len, ok)) {
+    if (!ok) return ZK_EINVAL;
+    uint8_t v = 0;
+    const int rc = zk_verify_batch(c, h, 1, transcript, scheme, &proof, &len, &v);
+    if (rc == ZK_OK) *ok = v;
+    return rc;
+}

@@ -22,8 +22,10 @@ What the scope of this repository imposes, stated where a caller
     host first (plain secp256r1 ECDSA verification of (r, s) over msg_hash under the public key) and refuse
     an invalid request, so that, unlike a bare seed-hash, an invalid signature or arbitrary bytes never
     yields a verifying proof.  The reference's `generate_proof*` names are deliberately NOT exported.
-  * `verify` / `verify_evm` (ecdsa_p256.rs:429-469) are ms-scale host work outside the hot path and
-    are not reimplemented in the product; tests verify proofs with the oracle's verifier.
+  * `verify` / `verify_evm` (ecdsa_p256.rs:429-469) check a proof against the resident `gen_srs(degree)` with a real
+    pairing (zk_verify): the verifying key file is read once into a cached verifying-only key (re-read when the file
+    changes), the proof points are decoded and the check's multi-scalar sums made on the device, the pairing on the host.
+    `verify_batch` sends many proofs of one key through one zk_verify_batch call.
 """
 import hashlib
 import os
@@ -33,7 +35,7 @@ import threading
 import numpy as np
 
 from . import circuit
-from .engine import ZK_TRANSCRIPT_BLAKE2B, ZK_TRANSCRIPT_EVM, Engine
+from .engine import ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_TRANSCRIPT_BLAKE2B, ZK_TRANSCRIPT_EVM, Engine
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -129,6 +131,9 @@ def _gen_srs_locked(degree, device):
         for _, pk in st["keys"].values():
             st["eng"].pk_free(pk)
         st["keys"].clear()
+        for vk in st.get("vks", {}).values():  # verifying keys of the old degree's shape
+            st["eng"].pk_free(vk)
+        st["vks"] = {}
         with _SLOTS_LOCK:
             for sets in st["slots"].values():
                 for polys in sets:
@@ -354,5 +359,45 @@ def generate_proof_evm_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key
     return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_EVM, device, rng_seed)
 
 
-# `verify` / `verify_evm` (ecdsa_p256.rs:429-469) are not mirrored: verification is host-side pairing work outside the engine's
-# path — the reference's verify_proof, its generated verifier, or (in tests) the oracle verifier check the proofs.
+# ---- verify / verify_evm (ecdsa_p256.rs:429-469) -----------------------------------------------------------------------------
+
+def _resident_vk(degree, verifying_key_path, device):
+    """(engine, verifying-only key) for the file: VerifyingKey::read::<_, ECDSACircuit<Fr>> (ecdsa_p256.rs:431-435) once per file
+    version, cached with the device's resident state (the key is a few kB: commitments and transcript_repr)."""
+    with _STATE_LOCK:
+        eng = _gen_srs_locked(degree, device)
+        st = _STATE[device]
+        vks = st.setdefault("vks", {})
+        try:
+            stt = os.stat(verifying_key_path)
+        except OSError as e:  # the reference panics with "Unable to open verifying key file" (ecdsa_p256.rs:432)
+            raise FileNotFoundError(f"Unable to open verifying key file: {verifying_key_path}") from e
+        tag = (os.path.abspath(verifying_key_path), stt.st_mtime_ns, stt.st_size)
+        if tag not in vks:
+            for old in [t for t in vks if t[0] == tag[0]]:
+                eng.pk_free(vks.pop(old))
+            with open(verifying_key_path, "rb") as f:
+                data = f.read()
+            vks[tag] = eng.vk_read(_config_for(degree), data)
+        return eng, vks[tag]
+
+
+def verify(degree: int, proof: bytes, verifying_key_path: str, device: int = 0) -> bool:
+    """`verify` (ecdsa_p256.rs:429-447): Blake2b transcript + SHPLONK, no instances, against gen_srs(degree)."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device)
+    return eng.verify(vk, bytes(proof), ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+
+
+def verify_evm(degree: int, proof: bytes, verifying_key_path: str, device: int = 0) -> bool:
+    """`verify_evm` (ecdsa_p256.rs:449-469): Keccak EvmTranscript + GWC, no instances, against gen_srs(degree)."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device)
+    return eng.verify(vk, bytes(proof), ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
+
+
+def verify_batch(degree: int, proofs, verifying_key_path: str, evm: bool, device: int = 0):
+    """Many proofs of one verifying key in one zk_verify_batch call: one verdict per proof, each what verify / verify_evm
+    says of it."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device)
+    if evm:
+        return eng.verify_batch(vk, [bytes(p) for p in proofs], ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
+    return eng.verify_batch(vk, [bytes(p) for p in proofs], ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)

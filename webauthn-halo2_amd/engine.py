@@ -24,6 +24,7 @@ ZK_OPT_MSM_WINDOW, ZK_OPT_MSM_BATCH, ZK_OPT_NTT_MAX_RADIX_LOG2, ZK_OPT_GP_BATCH_
 ZK_OPT_MSM_TAIL_MAIN_ABOVE, ZK_OPT_BATCH_PASS_COLUMNS, ZK_OPT_XFORM_STREAM, ZK_OPT_MSM_STREAM, ZK_OPT_MSM_T1, ZK_OPT_STREAM_AUDIT = 6, 7, 8, 9, 10, 11
 ZK_OPT_STREAM_PRIORITY, ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_ACTIVITY_HOLD = 12, 13, 14
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
+ZK_VERIFY_BATCH_MAX = 1024
 
 
 def device_pci_bus_id(device=0):
@@ -164,6 +165,11 @@ def load_library():
         "zk_quotient": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_uint64), sz,
                          ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p, u64p, ctypes.c_int, ctypes.c_uint64], ctypes.c_int),
         "zk_poly_upload_canonical": ([vp, ctypes.c_uint64, u64p, sz], ctypes.c_int),
+        "zk_vk_read": ([vp, ctypes.POINTER(CircuitParamsC), vp, sz, ctypes.c_int, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+        "zk_vk_from_parts": ([vp, ctypes.POINTER(CircuitParamsC), u64p, u64p, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+        "zk_verify": ([vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        "zk_verify_batch": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz),
+                             ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -472,6 +478,55 @@ class Engine:
         self._chk(self.L.zk_prove_batch(self.ctx, pk, B, hs, na, b"".join(bytes(sd) for sd in seeds), transcript, scheme, buf, stride,
                                         ctypes.byref(ln)), "zk_prove_batch")
         return [buf.raw[j * stride:j * stride + ln.value] for j in range(B)]
+
+    # ---- verify_proof ----------------------------------------------------------------------------------
+    @staticmethod
+    def _params_c(params):
+        return CircuitParamsC(params.degree, params.num_advice, params.num_lookup_advice, params.num_fixed, params.lookup_bits,
+                              getattr(params, "idle_gate_columns", 0))
+
+    def vk_read(self, params, data, fmt=ZK_SERDE_RAW_BYTES, transcript_repr=None):
+        """VerifyingKey::read: a verifying-only key (commitments + transcript_repr, no prover state) from a zk_vk_write image."""
+        cp = self._params_c(params)
+        keep, ptr, n = self._bytes_arg(data)
+        t = None if transcript_repr is None else _p(np.ascontiguousarray(transcript_repr, dtype=np.uint64).reshape(4))
+        h = ctypes.c_uint64()
+        self._chk(self.L.zk_vk_read(self.ctx, ctypes.byref(cp), ptr, n, fmt, t, ctypes.byref(h)), "zk_vk_read")
+        return h.value
+
+    def vk_from_parts(self, params, fixed_commitments, perm_commitments, transcript_repr=None):
+        """The inverse of vk_export: a verifying-only key from affine Montgomery commitments ((n, 8) uint64 each)."""
+        from .circuit import Layout
+
+        cp = self._params_c(params)
+        fc, pc = _arr(fixed_commitments, 8), _arr(perm_commitments, 8)
+        lay = Layout(params)  # (the C entry point reads exactly the shape's counts)
+        if fc.shape[0] != lay.n_fix or pc.shape[0] != len(lay.perm_cols):
+            raise ZkError(-1, f"zk_vk_from_parts: the shape has {lay.n_fix} fixed and {len(lay.perm_cols)} permutation commitments")
+        t = None if transcript_repr is None else _p(np.ascontiguousarray(transcript_repr, dtype=np.uint64).reshape(4))
+        h = ctypes.c_uint64()
+        self._chk(self.L.zk_vk_from_parts(self.ctx, ctypes.byref(cp), _p(fc), _p(pc), t, ctypes.byref(h)), "zk_vk_from_parts")
+        return h.value
+
+    def verify(self, pk, proof, transcript, scheme=ZK_SCHEME_DEFAULT) -> bool:
+        """plonk::verify_proof with the KZG pairing check against the resident SRS (zk_verify)."""
+        proof = bytes(proof)
+        ok = ctypes.c_int(0)
+        self._chk(self.L.zk_verify(self.ctx, pk, transcript, scheme, proof, len(proof), ctypes.byref(ok)), "zk_verify")
+        return bool(ok.value)
+
+    def verify_batch(self, pk, proofs, transcript, scheme=ZK_SCHEME_DEFAULT):
+        """zk_verify_batch: one verdict per proof, each what verify() says of it (batches above ZK_VERIFY_BATCH_MAX are split)."""
+        proofs = [bytes(p) for p in proofs]
+        out = []
+        for lo in range(0, len(proofs), ZK_VERIFY_BATCH_MAX):
+            part = proofs[lo:lo + ZK_VERIFY_BATCH_MAX]
+            ptrs = (ctypes.c_char_p * len(part))(*part)
+            lens = (ctypes.c_size_t * len(part))(*[len(p) for p in part])
+            v = (ctypes.c_uint8 * len(part))()
+            self._chk(self.L.zk_verify_batch(self.ctx, pk, len(part), transcript, scheme, ptrs, lens, v), "zk_verify_batch")
+            out.extend(bool(x) for x in v)
+        return out
 
     def proof_size(self, pk, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
         ln = ctypes.c_size_t()

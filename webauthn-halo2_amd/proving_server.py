@@ -1,6 +1,6 @@
 """JSON-in / hex-out request contract of the reference's proving server, on the resident engine.
 
-Mirrors the two proving endpoints of proving-server/src/main.rs (the Rocket server itself is out of scope —
+Mirrors the proving and verifying endpoints of proving-server/src/main.rs (the Rocket server itself is out of scope —
 SURVEY.md §2 #9 — only its request/response contract is reproduced so that a batch of recorded requests can
 be replayed against the engine):
 
@@ -9,6 +9,9 @@ be replayed against the engine):
     POST /prove_evm  -> hex::encode(generate_proof_evm(..., DEGREE))   main.rs:49-63
     POST /prove      -> hex::encode(generate_proof(..., DEGREE))       main.rs:65-79
     POST /setup      -> download_keys(DEGREE, "./keys/proving_key.pk", "./keys/verifying_key.vk")   main.rs:29-37
+    struct VerifyRequestBody { verifying_key_path: String, proof: String }      main.rs:409-413
+    POST /verify     -> verify(DEGREE, hex::decode(proof)?, path) ? "verified" : "rejected"      main.rs:415-425
+    POST /verify_evm -> verify_evm(DEGREE, hex::decode(proof)?, path) ? "verified" : "rejected"  main.rs:427-439
     const DEGREE: u32 = 17                                             main.rs:17
 
 The five byte arrays are LITTLE-endian, as the web client builds them (web-demo/src/pages/index.tsx:285-293:
@@ -19,6 +22,7 @@ The proofs are those of `ecdsa_p256.generate_proof*_synthetic` (the same-shape s
 signature checked on the host — see that module's docstring for what that does and does not mean).
 """
 import json
+import re
 import threading
 
 from . import ecdsa_p256
@@ -93,4 +97,63 @@ def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE):
         t.start()
     for t in ths:
         t.join()
+    return out
+
+
+_HEX = re.compile(r"[0-9a-fA-F]*")
+
+
+def parse_verify_request(body):
+    """VerifyRequestBody from a JSON string / dict -> (verifying_key_path, proof bytes).  The proof hex is decoded as strictly as
+    `hex::decode`: even length, hex digits only (either case), no 0x prefix, no whitespace — otherwise ValueError, where the
+    reference answers with its FromHexError."""
+    if isinstance(body, (str, bytes, bytearray)):
+        body = json.loads(body)
+    if not isinstance(body, dict):
+        raise ValueError("request body must be a JSON object")
+    path, proof = body.get("verifying_key_path"), body.get("proof")
+    if not isinstance(path, str):
+        raise ValueError("verifying_key_path: expected a string")
+    if not isinstance(proof, str):
+        raise ValueError("proof: expected a string")
+    if len(proof) % 2:
+        raise ValueError("proof: odd number of hex digits")  # FromHexError::OddLength
+    if not _HEX.fullmatch(proof):
+        raise ValueError("proof: invalid hex character")  # FromHexError::InvalidHexCharacter
+    return path, bytes.fromhex(proof)
+
+
+def verify(body, device=0, degree=DEGREE) -> str:
+    """POST /verify: Blake2b + SHPLONK; "verified" or "rejected"."""
+    path, proof = parse_verify_request(body)
+    return "verified" if ecdsa_p256.verify(degree, proof, path, device) else "rejected"
+
+
+def verify_evm(body, device=0, degree=DEGREE) -> str:
+    """POST /verify_evm: Keccak EvmTranscript + GWC; "verified" or "rejected"."""
+    path, proof = parse_verify_request(body)
+    return "verified" if ecdsa_p256.verify_evm(degree, proof, path, device) else "rejected"
+
+
+def verify_batch(bodies, evm=True, device=0, degree=DEGREE):
+    """A recorded batch of verify requests: the proofs of each verifying key go through ONE zk_verify_batch call.  Returns
+    "verified" / "rejected" per request, in request order; a malformed request yields its exception."""
+    out = [None] * len(bodies)
+    by_key = {}
+    for i, b in enumerate(bodies):
+        try:
+            path, proof = parse_verify_request(b)
+        except ValueError as e:
+            out[i] = e
+            continue
+        by_key.setdefault(path, []).append((i, proof))
+    for path, items in by_key.items():
+        try:
+            verdicts = ecdsa_p256.verify_batch(degree, [p for _, p in items], path, evm, device)
+        except Exception as e:  # (an unreadable key file: every request of that key fails)
+            for i, _ in items:
+                out[i] = e
+            continue
+        for (i, _), ok in zip(items, verdicts):
+            out[i] = "verified" if ok else "rejected"
     return out

@@ -15,6 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))  # this directory: the suite's helpers
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import test_gpu_prover as t  # noqa: E402
+from prover_shapes import random_shapes  # noqa: E402
 from zkoracle import fastprover as fp  # noqa: E402
 
 
@@ -109,7 +110,7 @@ def main():
                     print("FAIL", shape, i, repr(e)[:300], flush=True)
         print("failures", bad)
         return 1 if bad else 0
-    shapes = mid_shapes(count, seed) if mid else t._random_shapes(count, seed)
+    shapes = mid_shapes(count, seed) if mid else random_shapes(count, seed)
     for shape in shapes:
         t0 = time.time()
         try:

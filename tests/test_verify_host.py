@@ -10,7 +10,9 @@ import subprocess
 
 import pytest
 
-from zkoracle import plonk, srs
+from zkoracle import plonk, prover, srs
+from zkoracle.hashes import ChaCha20Rng
+from prover_shapes import DRAW_SEED, SHAPES, random_shapes
 import verify_cases as vc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +44,8 @@ def run_job(exe, shape, kind, scheme, repr_, fixed, perm, proofs):
         assert t[0] == "verdict"
         d = {"ok": t[1] == "1"}
         d.update({t[i]: t[i + 1] for i in range(2, len(t) - 1, 2)})
+        if "terms" in t:  # |A| |B|: the sizes of the two KZG term lists
+            d["terms"] = (int(t[t.index("terms") + 1]), int(t[t.index("terms") + 2]))
         res.append(d)
     assert len(res) == len(proofs)
     return res
@@ -102,3 +106,44 @@ def test_idle_gate_columns_shape(exe):
         res = run_job(exe, vk.shape, kind, scheme, vk.transcript_repr, vk.fixed_commitments, vk.permutation_commitments,
                       [proof, proof[:-1] + bytes([proof[-1] ^ 4])])
         assert [r["ok"] for r in res] == [True, plonk.verify(vk, proof[:-1] + bytes([proof[-1] ^ 4]), kind, scheme)]
+
+
+def oracle_case(name):
+    """(oracle proving key, advice) of a CPU-tier case: the head of the shared random draw, manycols, an adversarial layout, the
+    identity-commitment key."""
+    if name.startswith("rand"):
+        return vc.oracle_key(random_shapes(6, DRAW_SEED)[int(name[4:])])
+    if name == "manycols":
+        return vc.oracle_key(SHAPES["manycols"])
+    if name == "adversarial":
+        import adversarial_layout as adv
+        sh = plonk.Shape(8, 3, 2, 2, 5)
+        fixed, copies, advice = adv.build(sh, 1234)
+        return prover.keygen(prover.Circuit(sh, fixed, copies, advice)), advice
+    p, asg = vc.identity_assignment()
+    return prover.keygen(prover.Circuit(vc.oracle_shape(p), asg.fixed, asg.copies, asg.advice)), asg
+
+
+@pytest.mark.parametrize("name", ["rand%d" % i for i in range(6)] + ["manycols", "adversarial", "identity"])
+def test_shape_sweep_same_verdicts(exe, name):
+    """Oracle proofs of more column shapes, intact and tampered, all four combinations: verdicts and challenges equal to the oracle
+    verifier's.  The wide shapes put more than 128 terms in a KZG term list — three or more per lane of the device's
+    one-wave-per-sum kernel (csrc/verify.hip), which tests/test_gpu_verify_shapes.py runs on the same shapes."""
+    pk, asg = oracle_case(name)
+    advice = asg if isinstance(asg, list) else asg.advice
+    vk = pk.vk
+    if name == "identity":
+        assert vk.fixed_commitments[1] is None and all(c is not None for i, c in enumerate(vk.fixed_commitments) if i != 1)
+    fixed = [c if c is not None else (0, 0) for c in vk.fixed_commitments]  # the identity, as the engine writes it
+    for kind, scheme in vc.COMBOS:
+        proof = prover.create_proof(pk, advice, ChaCha20Rng(b"\x17" * 32), kind, scheme)
+        cases = [("intact", proof)] + vc.variants(proof, vk.shape, kind, scheme, seed=sum(map(ord, name + kind + scheme)))
+        res = run_job(exe, vk.shape, kind, scheme, vk.transcript_repr, fixed, vk.permutation_commitments, [c[1] for c in cases])
+        want = [plonk.verify(vk, c[1], kind, scheme) for c in cases]
+        assert want[0]
+        assert [r["ok"] for r in res] == want, (kind, scheme, [c[0] for c, r, w in zip(cases, res, want) if r["ok"] != w])
+        ok, pf = plonk.verify(vk, proof, kind, scheme, return_detail=True)
+        for ch in ("theta", "beta", "gamma", "y", "x", "v", "u") + (("shplonk_y",) if scheme == "shplonk" else ()):
+            assert int(res[0][ch], 16) == pf.challenges[ch], (kind, scheme, ch)
+        if name in ("rand0", "manycols"):  # A = 45 / 36 gate columns
+            assert res[0]["terms"][1] > 128, res[0]["terms"]

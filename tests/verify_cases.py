@@ -13,16 +13,39 @@ COMBOS = [("evm", "gwc"), ("evm", "shplonk"), ("blake2b", "gwc"), ("blake2b", "s
 SMALL_SHAPES = {"k19like": (1, 1, 1, 7, 6), "k17like": (4, 1, 1, 7, 5), "idle": (4, 1, 1, 6, 4, 1)}
 
 
+# F = 2: the identity-commitment key (identity_assignment)
+IDENTITY_SHAPE = (3, 1, 2, 7, 5)
+
+
 def params_of(name):
-    A, L, F, k, lb, idle = (SMALL_SHAPES[name] + (0,))[:6]
+    return params_of_shape(SMALL_SHAPES[name])
+
+
+def params_of_shape(shape):
+    A, L, F, k, lb, idle = (tuple(shape) + (0,))[:6]
     return zk.circuit.CircuitParams(degree=k, num_advice=A, num_lookup_advice=L, num_fixed=F, lookup_bits=lb, idle_gate_columns=idle)
 
 
-def oracle_key(name, seed=0x5EED0019):
-    p = params_of(name)
+def oracle_shape(p):
+    return plonk.Shape(p.degree, p.num_advice, p.num_lookup_advice, p.num_fixed, p.lookup_bits, p.idle_gate_columns)
+
+
+def identity_assignment(seed=0x5EED0019):
+    """A circuit of IDENTITY_SHAPE whose second constants column holds no constants: the column is all zero and every copy into
+    it is dropped, so its fixed commitment is the identity — None in the oracle's key, (0, 0) in the engine's."""
+    p = params_of_shape(IDENTITY_SHAPE)
     asg = zk.circuit.synthesize(p, seed)
-    sh = plonk.Shape(p.degree, p.num_advice, p.num_lookup_advice, p.num_fixed, p.lookup_bits, p.idle_gate_columns)
-    return prover.keygen(prover.Circuit(sh, asg.fixed, asg.copies, asg.advice)), asg
+    col = asg.layout.perm_index("fixed", 1)
+    assert any(asg.fixed[1]) and any(col in (a[0], b[0]) for a, b in asg.copies)  # (there was something to drop)
+    asg.fixed[1] = [0] * len(asg.fixed[1])
+    asg.copies = [(a, b) for a, b in asg.copies if col not in (a[0], b[0])]
+    return p, asg
+
+
+def oracle_key(name, seed=0x5EED0019):
+    p = params_of(name) if isinstance(name, str) else params_of_shape(name)
+    asg = zk.circuit.synthesize(p, seed)
+    return prover.keygen(prover.Circuit(oracle_shape(p), asg.fixed, asg.copies, asg.advice)), asg
 
 
 def oracle_proof(pk, asg, kind, scheme, seed=b"\x07" * 32):

@@ -192,6 +192,30 @@ int zk_srs_read(zk_ctx* ctx, const uint8_t* bytes, size_t len, int format);
 /* G2 half of a ParamsKZG adopted with zk_srs_load (G2Affine memory images: x.c0 || x.c1 || y.c0 || y.c1, Montgomery) */
 int zk_srs_set_g2(zk_ctx* ctx, const uint64_t g2[16], const uint64_t s_g2[16]);
 
+/* ---- an SRS without its secret: downsize and check ------------------------------------------------------------------
+ * replaces halo2's g_to_lagrange (arithmetic.rs [RECALLED]) on the caller's points: out[i] = [1/n] sum_j [w^-ij] g[j], n = 2^k,
+ * 1 <= k <= 24, w the domain generator of k; affine Montgomery in and out, identity (0, 0).  Exact for any points (identity,
+ * repeated and opposite points included); a coordinate not below p or a point off the curve is ZK_EINVAL. */
+int zk_g_to_lagrange(zk_ctx* ctx, const uint64_t* g /* n x 8 */, uint32_t k, uint64_t* out /* n x 8 */);
+/* replaces ParamsKZG::downsize(k): keeps the first 2^k points of g, rebuilds g_lagrange from them on the device (also for
+ * k == zk_srs_k), keeps g2 / s_g2, builds the window tables.  The result is a NEW shared block: contexts made with
+ * zk_ctx_create_shared before the call keep the old SRS and their keys; keys made here under the old SRS get ZK_ESTATE.
+ * ZK_EINVAL: k < 1 or k > zk_srs_k; ZK_ESTATE: no SRS.  On any failure the resident SRS, its tables and its keys stay. */
+int zk_srs_downsize(zk_ctx* ctx, uint32_t k);
+/* ParamsKZG::read_custom + downsize(k) in one pass over the image, without building anything of the file's degree K: the
+ * image is checked exactly as zk_srs_read checks it (an image zk_srs_read refuses is refused here too), streamed through a
+ * fixed staging buffer, and only the degree-k SRS stays.  ZK_EINVAL also for k < 1 or k > K; otherwise zk_srs_read's rules. */
+int zk_srs_read_downsize(zk_ctx* ctx, const uint8_t* bytes, size_t len, int format, uint32_t k);
+/* randomized structure check of the resident SRS, weights drawn from ChaCha20(seed).  *flags gets one bit per check passed:
+ *   ZK_SRS_CHECK_POWERS      g[i+1] = [tau] g[i] with s_g2 = [tau] g2 (two MSMs and one pairing equation)
+ *   ZK_SRS_CHECK_LAGRANGE    g_lagrange is the Lagrange basis of g (an NTT and two MSMs)
+ *   ZK_SRS_CHECK_GENERATORS  g[0] is the G1 generator (1, 2) and g2 the G2 generator
+ * A failed check is a verdict (ZK_OK), not an error.  ZK_ESTATE: no SRS, or no G2 half (zk_srs_load without zk_srs_set_g2). */
+#define ZK_SRS_CHECK_POWERS 1u
+#define ZK_SRS_CHECK_LAGRANGE 2u
+#define ZK_SRS_CHECK_GENERATORS 4u
+int zk_srs_check(zk_ctx* ctx, const uint8_t seed[32], uint32_t* flags);
+
 /* ---- resident polynomials -------------------------------------------------- */
 int zk_poly_alloc(zk_ctx* ctx, size_t n, zk_poly* out);
 /* the handle dies; the memory is parked in the context (a few vectors, at most 2 GiB) for the next zk_poly_alloc of the same

@@ -245,5 +245,9 @@ int srs_alloc(zk_ctx* c, uint32_t k);
 // the previous SRS, its window tables and every key made under it are dropped only now
 void srs_adopt(zk_ctx* c, uint32_t k, G1Affine* g, G1Affine* g_lagrange);
 int srs_build_tables(zk_ctx* c, uint32_t k);
+// the same for bases of 2^k points made from a resident or streamed SRS (downsize): the old SRS stays resident on failure
+int srs_install(zk_ctx* c, uint32_t k, G1Affine* g, G1Affine* g_lagrange);
+// halo2's g_to_lagrange between device buffers of 2^k affine points (g1_ntt.hip; in == out allowed)
+int ctx_g1_to_lagrange(zk_ctx* c, const G1Affine* d_in, uint32_t k, G1Affine* d_out);
 void srs_set_g2_from_secret(zk_ctx* c, const Fr& s_mont);
 void verify_ws_destroy(struct VerifyWs* w);

@@ -1034,6 +1034,36 @@ void srs_adopt(zk_ctx* c, uint32_t k, G1Affine* g, G1Affine* g_lagrange) {
     c->g_lagrange = c->srs->g_lagrange = g_lagrange;
 }
 
+// zk_srs_downsize / zk_srs_read_downsize: the two bases become the resident SRS in a NEW block (contexts sharing the old one
+// keep it, and their keys), with their window tables; g2 / s_g2 stay as they are.  Until the tables are built the previous SRS
+// is kept aside: on failure it is put back, with its tables and its keys, and the two buffers are freed.
+int srs_install(zk_ctx* c, uint32_t k, G1Affine* g, G1Affine* g_lagrange) {
+    std::shared_ptr<SrsBlock> old = c->srs;
+    const int old_k = c->srs_k;
+    G1Affine *og = c->g, *ogl = c->g_lagrange, *ogt = c->g_table, *oglt = c->g_lagrange_table;
+    const uint32_t old_c = c->table_c;
+    const bool old_gi = c->g_has_identity, old_gli = c->g_lagrange_has_identity, g2v = c->g2_valid;
+    const uint64_t old_gen = c->srs_gen;
+    srs_adopt(c, k, g, g_lagrange);
+    c->g2_valid = g2v;
+    const int rc = srs_build_tables(c, k);
+    if (rc != ZK_OK) {
+        c->srs = old;  // (the new block goes: it frees both bases and any table built)
+        c->srs_k = old_k;
+        c->g = og;
+        c->g_lagrange = ogl;
+        c->g_table = ogt;
+        c->g_lagrange_table = oglt;
+        c->table_c = old_c;
+        c->g_has_identity = old_gi;
+        c->g_lagrange_has_identity = old_gli;
+        c->srs_gen = old_gen;
+        return rc;
+    }
+    c->srs_k = (int)k;
+    return ZK_OK;
+}
+
 int srs_alloc(zk_ctx* c, uint32_t k) {
     if (k < 1 || k > 24) return ZK_EINVAL;
     const size_t n = (size_t)1 << k;

@@ -322,9 +322,13 @@ struct In {
 
 }  // namespace
 
-// engine.hip
-int srs_alloc(zk_ctx* c, uint32_t k);
-int srs_build_tables(zk_ctx* c, uint32_t k);
+namespace zk {
+// RawBytes validation of n device points (zk_g_to_lagrange): *d_err |= 1 for a coordinate not below p or a point off the curve
+hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hipStream_t st) {
+    hipLaunchKernelGGL(g1_validate_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, st, d, n, d_err);
+    return hipGetLastError();
+}
+}  // namespace zk
 
 // s_g2 = [s]G2 after zk_srs_setup (called from engine.hip with the secret)
 void srs_set_g2_from_secret(zk_ctx* c, const Fr& s_mont) {
@@ -454,6 +458,94 @@ ZK_API(zk_srs_read, (zk_ctx* c, const uint8_t* bytes, size_t len, int format), (
     srs_adopt(c, k, fresh[0], fresh[1]);
     if ((rc = srs_build_tables(c, k)) != ZK_OK) return rc;
     c->srs_k = (int)k;
+    memcpy(c->g2_raw, g2, 128);
+    memcpy(c->s_g2_raw, s_g2, 128);
+    c->g2_valid = true;
+    return ZK_OK;
+}
+
+// ParamsKZG::read_custom + downsize(k) without anything of the file's degree K on the device: the image is checked as
+// zk_srs_read checks it (length, both G2 points, every point of both G1 sections unless the format is unchecked), streamed
+// through a staging buffer of SRS_STAGE points; the first 2^k points of g are kept, g_lagrange is rebuilt from them.
+ZK_API(zk_srs_read_downsize, (zk_ctx* c, const uint8_t* bytes, size_t len, int format, uint32_t k), (c, bytes, len, format, k)) {
+    if (!c || !bytes || len < 4 || !format_ok(format)) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const uint32_t K = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);
+    if (K < 1 || K > 24) return ZK_EINVAL;
+    const size_t N = (size_t)1 << K;
+    const size_t gs = g1_size(format);
+    if (len != 4 + 2 * N * gs + 2 * g2_size(format)) return ZK_EINVAL;
+    uint8_t g2[128], s_g2[128];
+    if (!host_g2_read(bytes + 4 + 2 * N * gs, format, g2) || !host_g2_read(bytes + 4 + 2 * N * gs + g2_size(format), format, s_g2)) return ZK_EINVAL;
+    if (k < 1 || k > K) return ZK_EINVAL;  // halo2's downsize asserts k <= self.k
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    ctx_release_spares(c);
+    const size_t n = (size_t)1 << k;
+    const size_t SRS_STAGE = (size_t)1 << 18;
+    const size_t chunk = N < SRS_STAGE ? N : SRS_STAGE;
+    G1Affine *g = nullptr, *gl = nullptr, *stage = nullptr;
+    uint8_t* packed = nullptr;  // compressed points (Processed)
+    uint32_t* d_err = (uint32_t*)c->small;
+    auto drop = [&]() {
+        hipFree(g);
+        hipFree(gl);
+        hipFree(stage);
+        hipFree(packed);
+    };
+    if (hipMalloc(&g, n * sizeof(G1Affine)) != hipSuccess || hipMalloc(&gl, n * sizeof(G1Affine)) != hipSuccess ||
+        hipMalloc(&stage, chunk * sizeof(G1Affine)) != hipSuccess ||
+        (format == ZK_SERDE_PROCESSED && hipMalloc(&packed, chunk * 32) != hipSuccess)) {
+        (void)hipGetLastError();
+        drop();
+        return ZK_ENOMEM;
+    }
+    hipError_t e = hipMemsetAsync(d_err, 0, 4, c->stream);
+    // section 0 = g, 1 = g_lagrange; an unchecked image needs nothing beyond g[0 .. n)
+    for (int b = 0; b < 2 && e == hipSuccess; b++) {
+        const size_t end = format == ZK_SERDE_RAW_BYTES_UNCHECKED ? (b ? 0 : n) : N;
+        for (size_t off = 0; off < end && e == hipSuccess; off += chunk) {
+            const size_t cnt = end - off < chunk ? end - off : chunk;
+            const uint8_t* src = bytes + 4 + (size_t)b * N * gs + off * gs;
+            if (format == ZK_SERDE_PROCESSED) {
+                e = hipMemcpyAsync(packed, src, cnt * 32, hipMemcpyHostToDevice, c->stream);
+                if (e == hipSuccess)
+                    hipLaunchKernelGGL(g1_decompress_kernel, dim3(blocks_for(cnt, 64)), dim3(64), 0, c->stream, packed, stage, (uint32_t)cnt,
+                                       fq_sqrt_exp(), d_err);
+            } else {
+                e = hipMemcpyAsync(stage, src, cnt * 64, hipMemcpyHostToDevice, c->stream);
+                if (e == hipSuccess && format == ZK_SERDE_RAW_BYTES)
+                    hipLaunchKernelGGL(g1_validate_kernel, dim3(blocks_for(cnt, 64)), dim3(64), 0, c->stream, stage, (uint32_t)cnt, d_err);
+            }
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess && b == 0 && off < n) {
+                const size_t keep = n - off < cnt ? n - off : cnt;
+                e = hipMemcpyAsync(g + off, stage, keep * sizeof(G1Affine), hipMemcpyDeviceToDevice, c->stream);
+            }
+        }
+    }
+    uint32_t herr = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(stage);
+    hipFree(packed);
+    stage = nullptr;
+    packed = nullptr;
+    if (e != hipSuccess) {
+        drop();
+        c->last_hip = (int)e;
+        return ZK_EHIP;
+    }
+    if (herr) {  // as zk_srs_read: a point off the curve / a non-canonical coordinate anywhere in the file
+        drop();
+        return ZK_EINVAL;
+    }
+    if ((rc = ctx_g1_to_lagrange(c, g, (uint32_t)k, gl)) != ZK_OK) {
+        drop();
+        return rc;
+    }
+    // the new SRS goes in whole or not at all: until srs_install succeeds the resident one, its G2 half and its keys stay
+    if ((rc = srs_install(c, (uint32_t)k, g, gl)) != ZK_OK) return rc;
     memcpy(c->g2_raw, g2, 128);
     memcpy(c->s_g2_raw, s_g2, 128);
     c->g2_valid = true;

@@ -116,17 +116,64 @@ class _Hold:
         return False
 
 
+# (device) -> absolute path of the ParamsKZG file (RawBytes, as Params::write writes it) whose SRS gen_srs downsizes; a device
+# without an entry uses the seed-0 setup.  The source is explicit: no $PARAMS_DIR lookup.
+_PARAMS_FILES = {}
+
+
+def set_params_file(path, device: int = 0):
+    """The SRS source of `device`: a trusted-setup ParamsKZG file of any degree K (the caller ships the ceremony's largest), or
+    None for halo2-base's seed-0 setup (the default).  From now on gen_srs(degree) on the device reads the file and downsizes
+    it to `degree` (ParamsKZG::read + downsize) — ValueError when degree > K.  A new source takes effect like a new degree: at
+    the next gen_srs the device's keys and verifying keys are freed and its pipelines rebuilt on the new SRS."""
+    with _STATE_LOCK:
+        if path is None:
+            _PARAMS_FILES.pop(device, None)
+            return
+        path = os.path.abspath(path)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"Unable to open params file: {path}")
+        _PARAMS_FILES[device] = path
+
+
+def _source_tag(device):
+    """The identity of the device's SRS source: None (seed-0 setup) or (path, mtime, size) of its params file, as _resident_vk
+    keys its files."""
+    path = _PARAMS_FILES.get(device)
+    if path is None:
+        return None
+    try:
+        stt = os.stat(path)
+    except OSError as e:
+        raise FileNotFoundError(f"Unable to open params file: {path}") from e
+    return (path, stt.st_mtime_ns, stt.st_size)
+
+
+def params_file_degree(path) -> int:
+    """K of a ParamsKZG file: its first four bytes, u32 little-endian."""
+    with open(path, "rb") as f:
+        head = f.read(4)
+    if len(head) != 4:
+        raise ValueError(f"{path}: not a ParamsKZG file")
+    return int.from_bytes(head, "little")
+
+
 def gen_srs(degree: int, device: int = 0) -> Engine:
-    """halo2-base `gen_srs(k)`: ParamsKZG::setup(k, ChaCha20Rng::from_seed([0; 32])), kept resident."""
+    """halo2-base `gen_srs(k)`, kept resident: ParamsKZG::setup(k, ChaCha20Rng::from_seed([0; 32])), or — after
+    set_params_file(path) — ParamsKZG::read(path) + downsize(k)."""
     with _STATE_LOCK:
         return _gen_srs_locked(degree, device)
 
 
 def _gen_srs_locked(degree, device):
-    st = _STATE.setdefault(device, {"eng": None, "k": None, "keys": {}, "slots": {}, "extra": [], "free": None})
+    st = _STATE.setdefault(device, {"eng": None, "k": None, "src": None, "keys": {}, "slots": {}, "extra": [], "free": None})
+    src = _source_tag(device)
+    if src is not None and degree > params_file_degree(src[0]):
+        # halo2's downsize asserts k <= self.k; nothing resident changes
+        raise ValueError(f"degree {degree} is larger than the params file's ({params_file_degree(src[0])}): {src[0]}")
     if st["eng"] is None:
         st["eng"] = Engine(device)
-    if st["k"] != degree:
+    if st["k"] != degree or st.get("src") != src:
         _drain(st)  # requests still proving under the old SRS hold a pipeline: wait for them before anything is closed
         for _, pk in st["keys"].values():
             st["eng"].pk_free(pk)
@@ -143,8 +190,14 @@ def _gen_srs_locked(degree, device):
         for m in st["extra"]:  # the further pipelines saw the old SRS: they go with it
             m["eng"].close()
         st["extra"] = []
-        st["eng"].srs_setup(degree, bytes(32))
-        st["k"] = degree
+        st["k"] = None  # (until the new SRS is resident: a failed read leaves the device to be set up again by the next call)
+        if src is None:
+            st["eng"].srs_setup(degree, bytes(32))
+        else:
+            with open(src[0], "rb") as f:
+                data = f.read()
+            st["eng"].srs_read_downsize(data, degree)
+        st["k"], st["src"] = degree, src
         st["extra"] = [{"eng": Engine(device, share_with=st["eng"]), "keys": {}, "slots": {}} for _ in range(pipelines_for(degree, device) - 1)]
         st["free"] = queue.LifoQueue()
         for i in range(len(st["extra"]), -1, -1):  # pipeline 0 (the first context) on top: a lone request takes it

@@ -25,6 +25,7 @@ ZK_OPT_MSM_TAIL_MAIN_ABOVE, ZK_OPT_BATCH_PASS_COLUMNS, ZK_OPT_XFORM_STREAM, ZK_O
 ZK_OPT_STREAM_PRIORITY, ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_ACTIVITY_HOLD = 12, 13, 14
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
+ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 
 
 def device_pci_bus_id(device=0):
@@ -157,6 +158,10 @@ def load_library():
         "zk_srs_write": ([vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_srs_read": ([vp, vp, sz, ctypes.c_int], ctypes.c_int),
         "zk_srs_set_g2": ([vp, u64p, u64p], ctypes.c_int),
+        "zk_g_to_lagrange": ([vp, u64p, u32, u64p], ctypes.c_int),
+        "zk_srs_downsize": ([vp, u32], ctypes.c_int),
+        "zk_srs_read_downsize": ([vp, vp, sz, ctypes.c_int, u32], ctypes.c_int),
+        "zk_srs_check": ([vp, ctypes.c_char_p, ctypes.POINTER(u32)], ctypes.c_int),
         "zk_vk_write": ([vp, ctypes.c_uint64, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_vk_load": ([vp, ctypes.c_uint64, vp, sz, ctypes.c_int, u64p], ctypes.c_int),
         "zk_pk_write": ([vp, ctypes.c_uint64, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
@@ -306,6 +311,33 @@ class Engine:
     def srs_set_g2(self, g2, s_g2):
         a, b = (np.ascontiguousarray(v, dtype=np.uint64).reshape(16) for v in (g2, s_g2))
         self._chk(self.L.zk_srs_set_g2(self.ctx, _p(a), _p(b)), "zk_srs_set_g2")
+
+    # ---- an SRS without its secret: ParamsKZG::downsize and the structure check ----------------
+    def g_to_lagrange(self, g, k):
+        """halo2's g_to_lagrange on 2^k affine Montgomery points ((n, 8) uint64, identity (0, 0)): [1/n] iNTT over G1."""
+        a = _arr(g, 8)
+        if a.shape[0] != (1 << k):
+            raise ValueError("g must hold 2^k points")
+        out = np.zeros_like(a)
+        self._chk(self.L.zk_g_to_lagrange(self.ctx, _p(a), k, _p(out)), "zk_g_to_lagrange")
+        return out
+
+    def srs_downsize(self, k):
+        """ParamsKZG::downsize(k) of the resident SRS: the first 2^k points of g, g_lagrange rebuilt on the device."""
+        self._chk(self.L.zk_srs_downsize(self.ctx, k), "zk_srs_downsize")
+
+    def srs_read_downsize(self, data, k, fmt=ZK_SERDE_RAW_BYTES):
+        """ParamsKZG::read_custom + downsize(k) of a params image of any degree K >= k."""
+        keep, ptr, n = self._bytes_arg(data)
+        self._chk(self.L.zk_srs_read_downsize(self.ctx, ptr, n, fmt, k), "zk_srs_read_downsize")
+
+    def srs_check(self, seed=bytes(32)):
+        """Randomized structure check of the resident SRS: the ZK_SRS_CHECK_* bits of the checks passed (7 = all)."""
+        if len(seed) != 32:
+            raise ValueError("check seed must be 32 bytes")
+        f = ctypes.c_uint32()
+        self._chk(self.L.zk_srs_check(self.ctx, bytes(seed), ctypes.byref(f)), "zk_srs_check")
+        return f.value
 
     def vk_write(self, pk, fmt=ZK_SERDE_RAW_BYTES):
         return self._write(self.L.zk_vk_write, "zk_vk_write", pk, fmt)

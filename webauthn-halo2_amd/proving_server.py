@@ -50,10 +50,14 @@ def parse_request(body):
     return out
 
 
-def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None):
+def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None, params_path=None):
     """POST /setup (and the server's start-up keygen, main.rs:451-456).  The proving key stays resident on
     `device`, registered under `proving_key_path` (the name later requests carry); the verifying key is
-    written only when a path is given (the reference writes ./keys/verifying_key.vk)."""
+    written only when a path is given (the reference writes ./keys/verifying_key.vk).  `params_path`: a trusted-setup
+    ParamsKZG file of degree >= `degree`, made the device's SRS source (ecdsa_p256.set_params_file) before keygen; None keeps
+    the device's current source (the seed-0 setup unless one was set)."""
+    if params_path is not None:
+        ecdsa_p256.set_params_file(params_path, device)
     ecdsa_p256.download_keys(degree, proving_key_path, verifying_key_path, device)
     return "Done"
 

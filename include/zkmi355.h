@@ -387,6 +387,34 @@ int zk_prove_batch(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /*
 /* upload canonical (non-Montgomery) integers and convert on the device */
 int zk_poly_upload_canonical(zk_ctx* ctx, zk_poly p, const uint64_t* host_canonical, size_t n);
 
+/* ---- MockProver::verify ------------------------------------------------------------------------------------------------
+ * What a witness can violate, and where.  `usable` = n - 7 rows (n - blinding factors - 1) carry the circuit; the prover blinds
+ * the rest. */
+#define ZK_FAIL_GATE 1          /* index = gate column j, row = the row its selector is non-zero on */
+#define ZK_FAIL_GATE_BLINDED 2  /* the same, but the gate reads a row the prover blinds (row + 3 >= usable rows):
+                                   a failure whatever the values - MockProver's ConstraintPoisoned */
+#define ZK_FAIL_LOOKUP 3        /* index = lookup, row = the row whose input is not in the table */
+#define ZK_FAIL_COPY 4          /* index = permutation column (zk_keygen's order), row; other_* = the cell sigma maps it to */
+typedef struct { uint32_t kind, index, row, other_index, other_row, reserved; } zk_witness_failure;
+/* replaces MockProver::run(k, &circuit, vec![]).verify() (ecdsa_p256.rs:209-248) for a resident key and resident advice
+ * columns (what zk_prove takes).  counts[kind] = number of failures of each kind (counts[0] = their sum); the first
+ * min(cap, counts[0]) failures in ascending (kind, index, row) order are written to `out` (may be NULL with cap 0).
+ * A violated circuit is a verdict (ZK_OK, counts[0] != 0), never an error.  Deterministic: same inputs, same output.
+ *   gates    every gate column j, every row r whose selector AFTER compress_selectors (q, q (2 - q) or q (1 - q) over the key's
+ *            fixed values) is non-zero: a[r] + a[r+1] a[r+2] - a[r+3] != 0 is a ZK_FAIL_GATE; r + 3 >= usable a ZK_FAIL_GATE_BLINDED
+ *   lookups  every lookup, every row r < usable: the input (one-column shapes: q_lookup[r] a_0[r]) must be below 2^lookup_bits -
+ *            the rule zk_prove returns ZK_EWITNESS by: counts[ZK_FAIL_LOOKUP] != 0 iff zk_prove refuses the witness
+ *   copies   every permutation column c, row r < usable with sigma(c, r) = (c', r') != (c, r): different values are one
+ *            ZK_FAIL_COPY at (c, r) - one per cell that differs from its sigma-image, so a corrupted cell of a pair is reported
+ *            from both sides
+ * Advice rows >= usable are never read; the inputs are not modified; nothing a proof is made of changes.  The first check of a
+ * key decodes its sigma values into cell indices on the device (4 bytes per cell, kept with the key).
+ * ZK_EINVAL: bad handle, n_advice != the shape's, a vector of another length, cap > 0 with out == NULL, or a key whose sigma
+ * values are not labels of its own usable cells (a damaged file read with ZK_SERDE_RAW_BYTES_UNCHECKED); ZK_ESTATE: a
+ * verifying-only key, or a key whose SRS was replaced. */
+int zk_witness_check(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap,
+                     uint64_t counts[5]);
+
 /* ---- verify_proof ---------------------------------------------------------------------------------------------------
  * plonk::verify_proof with the KZG pairing check (ecdsa_p256.rs:429-469: `verify` = Blake2b + SHPLONK, `verify_evm` = EVM +
  * GWC; no instances).  The check is e(A, [s]G2) = e(B, G2) with g[0], g2 and s_g2 of the context's resident SRS: a proof

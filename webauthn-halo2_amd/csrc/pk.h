@@ -152,7 +152,11 @@ struct zk_pk_rec {
     bool is_member = false;
     std::vector<zk_pk_rec*> members;
     struct BatchBufs* bb = nullptr;
+    // zk_witness_check (witness_check.hip): sigma decoded into cell indices, the verdict bitmap and its staging — made by the
+    // key's first check, never by a key that is not checked; a lock-step member has none (the check takes the key itself)
+    struct WitnessCheckState* wc = nullptr;
 };
+void wc_destroy(struct WitnessCheckState* s);
 
 // buffers of the launches a lock-step batch shares between its proofs, sized for `cap` proofs
 struct BatchBufs {

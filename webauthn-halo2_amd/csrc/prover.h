@@ -51,6 +51,15 @@ struct LookupScratch {
     uint32_t* err;     // one flag for all lookups
     uint32_t stride;   // words between the arrays of consecutive lookups
 };
+// the table rule of every lookup of this engine's keys — the range table 0 .. T - 1 (zk_keygen refuses any other table column):
+// `canonical` (out of Montgomery form) is a table element iff it is below T.  ONE predicate for the prover's histogram
+// (lk_hist_kernel: ZK_EWITNESS) and for zk_witness_check (ZK_FAIL_LOOKUP), so that the two cannot come apart
+__device__ __forceinline__ bool lk_in_table(const Fr& canonical, uint32_t T) {
+    uint32_t hi = 0;
+#pragma unroll
+    for (int k = 1; k < 8; k++) hi |= canonical.v[k];
+    return !hi && canonical.v[0] < T;
+}
 struct LkPtrs {
     const Fr* inp[MAX_LOOKUPS];
     Fr* ap[MAX_LOOKUPS];

@@ -238,10 +238,7 @@ __global__ __launch_bounds__(256) void lk_hist_kernel(LkPtrs ptrs, uint32_t usab
     uint32_t val = 0xffffffffu;  // not a table element / out of range
     if (i < usable) {
         const Fr v = fe_from_mont(fe_load(inp + i));
-        uint32_t hi = 0;
-#pragma unroll
-        for (int k = 1; k < 8; k++) hi |= v.v[k];
-        if (hi || v.v[0] >= T) atomicOr(err, 1u);
+        if (!lk_in_table(v, T)) atomicOr(err, 1u);
         else val = v.v[0];
     }
     // unselected rows contribute q_lookup * a = 0: most of the column hits hist[0].

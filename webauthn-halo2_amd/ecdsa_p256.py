@@ -5,6 +5,8 @@ the resident engine.
     create_proof_from_advice(advice_columns, ..., transcript)          the engine's real input: the advice
                                                                        columns `ECDSACircuit::synthesize`
                                                                        (ecdsa_p256.rs:117-206) leaves behind
+    mock_verify_advice(advice_columns, proving_key_path, degree)       MockProver::run(..).verify() of such columns
+                                                                       (test_secp256r1_ecdsa, ecdsa_p256.rs:209-248)
     generate_proof_synthetic / generate_proof_evm_synthetic            request-shaped stand-ins for
                                                                        generate_proof (:379-427) / _evm (:329-377)
 
@@ -269,11 +271,37 @@ def _resident_key(proving_key_path, degree, device):
     return (eng,) + keys[key]
 
 
+class WitnessError(ValueError):
+    """The advice columns do not satisfy the circuit (create_proof_from_advice(check=True)): `counts` and `failures` are what
+    Engine.witness_check returned — which gate row, lookup row or copied cell is wrong."""
+
+    def __init__(self, counts, failures):
+        self.counts, self.failures = counts, failures
+        super().__init__(f"witness violates the circuit: {counts[0]} failure(s), first {failures[:4]}")
+
+
 def create_proof_from_advice(advice_columns, proving_key_path, degree, transcript=ZK_TRANSCRIPT_BLAKE2B, device=0,
-                             rng_seed=None) -> bytes:
+                             rng_seed=None, check=False) -> bytes:
     """create_proof over host-synthesized advice columns — what an unchanged Rust host hands the engine
     after `ECDSACircuit::synthesize`.  `advice_columns`: sequence of (n, 4) uint64 arrays of canonical
-    little-endian limbs, one per advice column of the key's shape."""
+    little-endian limbs, one per advice column of the key's shape.  check=True: the columns go through
+    Engine.witness_check first and a violated circuit raises WitnessError instead of being proved."""
+    return _with_pipeline(advice_columns, proving_key_path, degree, device,
+                          lambda st, eng, pk, slots, cols, n: _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check))
+
+
+def mock_verify_advice(advice_columns, proving_key_path, degree, device=0, cap=64):
+    """`MockProver::run(degree, &circuit, vec![]).verify()` — the body of the reference's test_secp256r1_ecdsa
+    (ecdsa_p256.rs:209-248) — for a host that brings its own advice columns: the resident key and a pipeline's request slots
+    exactly as create_proof_from_advice takes them.  Returns the first `cap` failures as (kind, index, row, other_index,
+    other_row) tuples of engine.ZK_FAIL_*; the empty list is MockProver's Ok(())."""
+    return _with_pipeline(advice_columns, proving_key_path, degree, device,
+                          lambda st, eng, pk, slots, cols, n: _on_slots(st, eng, slots, cols, n, degree,
+                                                                        lambda polys: eng.witness_check(pk, polys, cap)[1]))
+
+
+def _with_pipeline(advice_columns, proving_key_path, degree, device, fn):
+    """fn(st, eng, pk, slots, cols, n) on a free pipeline of the device, with the advice columns validated."""
     _resident_key(proving_key_path, degree, device)  # (raises for an unknown key)
     n = 1 << degree
     cols = []
@@ -299,12 +327,25 @@ def create_proof_from_advice(advice_columns, proving_key_path, degree, transcrip
         name = proving_key_path or "<default>"
         if st["k"] != degree or name not in pks:  # gen_srs(another degree) ran between the key lookup above and here
             raise FileNotFoundError(f"Unable to open proving key file: {proving_key_path} (the resident key was replaced)")
-        return _prove_on(st, eng, pks[name], slots, cols, n, degree, transcript, rng_seed)
+        return fn(st, eng, pks[name], slots, cols, n)
     finally:
         q.put(which)
 
 
-def _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed):
+def _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check=False):
+    def run(polys):
+        if check:
+            counts, failures = eng.witness_check(pk, polys)
+            if counts[0]:
+                raise WitnessError(counts, failures)
+        seed = rng_seed if rng_seed is not None else os.urandom(32)  # the reference draws from OsRng (ecdsa_p256.rs:362)
+        return eng.prove(pk, polys, seed, transcript)
+
+    return _on_slots(st, eng, slots, cols, n, degree, run)
+
+
+def _on_slots(st, eng, slots, cols, n, degree, fn):
+    """fn(polys) with the columns uploaded into a set of the pipeline's request slots."""
     # request slots: the columns' device buffers are kept between requests (a hipFree per request would wait for the whole
     # device, i.e. for every other request in flight on it); concurrent requests each take a set of their own
     with _SLOTS_LOCK:
@@ -322,8 +363,7 @@ def _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed):
     try:
         for h, col in zip(polys, cols):
             eng.upload_canonical(h, col)
-        seed = rng_seed if rng_seed is not None else os.urandom(32)  # the reference draws from OsRng (ecdsa_p256.rs:362)
-        return eng.prove(pk, polys, seed, transcript)
+        return fn(polys)
     finally:
         with _SLOTS_LOCK:
             keep = slots.setdefault(len(cols), [])
@@ -388,7 +428,7 @@ def _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash) -> int:
     return int.from_bytes(hashlib.sha256(bytes(pubkey_x) + bytes(pubkey_y) + bytes(r) + bytes(s) + bytes(msg_hash)).digest()[:8], "little")
 
 
-def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, transcript, device, rng_seed):
+def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, transcript, device, rng_seed, check=False):
     for name, v in (("pubkey_x", pubkey_x), ("pubkey_y", pubkey_y), ("r", r), ("s", s), ("msg_hash", msg_hash)):
         if len(v) != 32:
             raise ValueError(f"{name} must be 32 little-endian bytes")  # the reference takes &[u8; 32]
@@ -397,19 +437,21 @@ def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degre
         raise ValueError("invalid ES256 signature (or non-canonical field encoding): request refused")
     _, p, _ = _resident_key(proving_key_path, degree, device)
     asg = circuit.synthesize(p, _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash))
-    return create_proof_from_advice([asg.to_limbs(col) for col in asg.advice], proving_key_path, degree, transcript, device, rng_seed)
+    return create_proof_from_advice([asg.to_limbs(col) for col in asg.advice], proving_key_path, degree, transcript, device, rng_seed,
+                                    check)
 
 
-def generate_proof_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None) -> bytes:
+def generate_proof_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None, check=False) -> bytes:
     """Request shape of `generate_proof` (Blake2b + SHPLONK, the /prove endpoint, proving-server/src/main.rs:65-79)
-    over the SYNTHETIC same-shape circuit — see the module docstring."""
-    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_BLAKE2B, device, rng_seed)
+    over the SYNTHETIC same-shape circuit — see the module docstring.  check: create_proof_from_advice's."""
+    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_BLAKE2B, device, rng_seed, check)
 
 
-def generate_proof_evm_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None) -> bytes:
+def generate_proof_evm_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None, check=False) -> bytes:
     """Request shape of `generate_proof_evm` (Keccak EvmTranscript + GWC, the /prove_evm endpoint,
-    proving-server/src/main.rs:49-63) over the SYNTHETIC same-shape circuit — see the module docstring."""
-    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_EVM, device, rng_seed)
+    proving-server/src/main.rs:49-63) over the SYNTHETIC same-shape circuit — see the module docstring.  check:
+    create_proof_from_advice's."""
+    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_EVM, device, rng_seed, check)
 
 
 # ---- verify / verify_evm (ecdsa_p256.rs:429-469) -----------------------------------------------------------------------------

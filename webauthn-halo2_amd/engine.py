@@ -26,6 +26,7 @@ ZK_OPT_STREAM_PRIORITY, ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_ACTIVITY_HOLD = 12, 13, 1
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
+ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
 
 
 def device_pci_bus_id(device=0):
@@ -75,6 +76,11 @@ class CircuitParamsC(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint32), ("num_advice", ctypes.c_uint32), ("num_lookup_advice", ctypes.c_uint32),
                 ("num_fixed", ctypes.c_uint32), ("lookup_bits", ctypes.c_uint32),
                 ("num_idle_gate_columns", ctypes.c_uint32)]
+
+
+class WitnessFailureC(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("index", ctypes.c_uint32), ("row", ctypes.c_uint32), ("other_index", ctypes.c_uint32),
+                ("other_row", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class ZkError(RuntimeError):
@@ -175,9 +181,15 @@ def load_library():
         "zk_verify": ([vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "zk_verify_batch": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz),
                              ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_witness_check": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(WitnessFailureC), sz,
+                              ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None:
+            if name == "zk_witness_check" and os.environ.get("ZKMI355_LIB"):
+                continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
+            raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
         fn.restype = res
     _LIB = L
@@ -510,6 +522,18 @@ class Engine:
         self._chk(self.L.zk_prove_batch(self.ctx, pk, B, hs, na, b"".join(bytes(sd) for sd in seeds), transcript, scheme, buf, stride,
                                         ctypes.byref(ln)), "zk_prove_batch")
         return [buf.raw[j * stride:j * stride + ln.value] for j in range(B)]
+
+    def witness_check(self, pk, advice_polys, cap=64):
+        """MockProver::verify of resident advice columns against a resident key (zk_witness_check) -> (counts, failures):
+        counts[kind] = failures of each ZK_FAIL_* kind (counts[0] their sum); failures = the first min(cap, counts[0]) of them
+        in ascending (kind, index, row) order as (kind, index, row, other_index, other_row) tuples.  A violated circuit is a
+        verdict, not an error; nothing is proved and nothing a proof is made of changes."""
+        hs = (ctypes.c_uint64 * max(len(advice_polys), 1))(*[p.h for p in advice_polys])
+        out = (WitnessFailureC * cap)() if cap else None
+        counts = (ctypes.c_uint64 * 5)()
+        self._chk(self.L.zk_witness_check(self.ctx, pk, hs, len(advice_polys), out, cap, counts), "zk_witness_check")
+        m = min(cap, int(counts[0]))
+        return [int(v) for v in counts], [(f.kind, f.index, f.row, f.other_index, f.other_row) for f in out[:m]] if m else []
 
     # ---- verify_proof ----------------------------------------------------------------------------------
     @staticmethod

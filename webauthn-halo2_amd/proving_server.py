@@ -62,21 +62,23 @@ def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", ver
     return "Done"
 
 
-def _prove(body, evm, device, degree, rng_seed):
+def _prove(body, evm, device, degree, rng_seed, check=False):
+    """check=True: the request's advice columns go through the witness check first (ecdsa_p256.WitnessError instead of a proof
+    no verifier accepts)."""
     q = parse_request(body)
     fn = ecdsa_p256.generate_proof_evm_synthetic if evm else ecdsa_p256.generate_proof_synthetic
-    proof = fn(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, device, rng_seed)
+    proof = fn(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, device, rng_seed, check)
     return proof.hex()  # hex::encode: lowercase, no prefix
 
 
-def prove_evm(body, device=0, degree=DEGREE, rng_seed=None) -> str:
+def prove_evm(body, device=0, degree=DEGREE, rng_seed=None, check=False) -> str:
     """POST /prove_evm: Keccak EvmTranscript + GWC; the hex string the web client puts into userOp.signature."""
-    return _prove(body, True, device, degree, rng_seed)
+    return _prove(body, True, device, degree, rng_seed, check)
 
 
-def prove(body, device=0, degree=DEGREE, rng_seed=None) -> str:
+def prove(body, device=0, degree=DEGREE, rng_seed=None, check=False) -> str:
     """POST /prove: Blake2b + SHPLONK."""
-    return _prove(body, False, device, degree, rng_seed)
+    return _prove(body, False, device, degree, rng_seed, check)
 
 
 def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE):

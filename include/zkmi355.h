@@ -236,12 +236,16 @@ int zk_poly_upload(zk_ctx* ctx, zk_poly p, const uint64_t* host_mont, size_t n);
 int zk_poly_download(zk_ctx* ctx, zk_poly p, uint64_t* host_mont, size_t n);
 int zk_poly_copy(zk_ctx* ctx, zk_poly dst, zk_poly src);
 /* rows [first, first + count) from the host: the blinding rows a host appends to a column the device made (halo2's provers push
- * `blinding_factors` random rows onto a', s' and every z before committing), without shipping the column */
+ * `blinding_factors` random rows onto a', s' and every z before committing), without shipping the column.  count == 0 is
+ * allowed (nothing is written; first <= n still holds); first + count > n is ZK_EINVAL and the vector is unchanged */
 int zk_poly_upload_range(zk_ctx* ctx, zk_poly p, size_t first, const uint64_t* host_mont, size_t count);
-/* dst[dst_first ..] = src[src_first .. src_first + count) (the h pieces: n-coefficient slices of the quotient) */
+/* dst[dst_first ..] = src[src_first .. src_first + count) (the h pieces: n-coefficient slices of the quotient).  count == 0 is
+ * allowed; a range that leaves either vector is ZK_EINVAL.  dst may be src when the two ranges are disjoint; overlapping ranges of
+ * one vector (count > 0) are ZK_EINVAL — there is no memmove form.  On ZK_EINVAL nothing is written */
 int zk_poly_copy_range(zk_ctx* ctx, zk_poly dst, size_t dst_first, zk_poly src, size_t src_first, size_t count);
 /* out = sum_j coeffs[j] * in[j] - (sub_low[0] + sub_low[1] X + .. + sub_low[n_low - 1] X^(n_low - 1)), n_low <= 8 (0: nothing
- * subtracted); all vectors of one length, out none of the inputs: the linear combinations of the multi-open provers — GWC's
+ * subtracted; vectors shorter than n_low: only the coefficients they have, the first n, are subtracted); count >= 1 inputs, which
+ * may repeat; all vectors of one length, out none of the inputs (ZK_EINVAL): the linear combinations of the multi-open provers — GWC's
  * sum_i v^i (p_i(X) - e_i) (n_low = 1), SHPLONK's sum_j y^j (P_j(X) - R_j(X)) with the remainders R_j of degree < |rotation set| —
  * and h(X) = sum_i x^(n i) h_i(X) */
 int zk_poly_lincomb(zk_ctx* ctx, zk_poly out, const zk_poly* in, const uint64_t* coeffs_mont /* count x 4 */, size_t count,

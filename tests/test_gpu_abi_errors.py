@@ -295,14 +295,7 @@ def test_phase_calls_refuse_repeated_output_handles():
 
     advh = arr(adv)
     one = (u64 * 4)(1, 0, 0, 0)
-    vp = ctypes.c_void_p
-    sz = ctypes.c_size_t
-    L.zk_lookup_permute.argtypes = [vp, u64, ctypes.POINTER(u64), sz, ctypes.POINTER(u64), ctypes.POINTER(u64), sz]
-    L.zk_lookup_product.argtypes = [vp, u64, ctypes.POINTER(u64), sz, ctypes.POINTER(u64), ctypes.POINTER(u64), sz, ctypes.POINTER(u64),
-                                    ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    L.zk_permutation_product.argtypes = [vp, u64, ctypes.POINTER(u64), sz, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), sz]
-    for f in (L.zk_lookup_permute, L.zk_lookup_product, L.zk_permutation_product):
-        f.restype = ctypes.c_int
+    # (the signatures are declared in engine.load_library; the raw calls stay: the outputs are the caller's handles here)
     EINVAL = -1
     # a'[0] == s'[1]; a'[0] == a'[1]; an advice column among the outputs
     assert L.zk_lookup_permute(eng.ctx, pk, advh, len(adv), arr([outs[0], outs[1]]), arr([outs[2], outs[0]]), 2) == EINVAL

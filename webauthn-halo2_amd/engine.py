@@ -27,6 +27,7 @@ ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
+ZK_PK_FIXED_POLY, ZK_PK_SIGMA_POLY = 0, 1
 
 
 def device_pci_bus_id(device=0):
@@ -176,6 +177,17 @@ def load_library():
         "zk_quotient": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_uint64), sz,
                          ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p, u64p, ctypes.c_int, ctypes.c_uint64], ctypes.c_int),
         "zk_poly_upload_canonical": ([vp, ctypes.c_uint64, u64p, sz], ctypes.c_int),
+        "zk_poly_upload_range": ([vp, ctypes.c_uint64, sz, u64p, sz], ctypes.c_int),
+        "zk_poly_copy_range": ([vp, ctypes.c_uint64, sz, ctypes.c_uint64, sz, sz], ctypes.c_int),
+        "zk_poly_lincomb": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), u64p, sz, u64p, sz], ctypes.c_int),
+        "zk_lookup_permute": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_uint64),
+                               ctypes.POINTER(ctypes.c_uint64), sz], ctypes.c_int),
+        "zk_lookup_product": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_uint64),
+                               ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+        "zk_permutation_product": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p,
+                                    ctypes.POINTER(ctypes.c_uint64), sz], ctypes.c_int),
+        "zk_pk_export_poly": ([vp, ctypes.c_uint64, ctypes.c_int, sz, ctypes.c_uint64], ctypes.c_int),
+        "zk_random_poly": ([vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
         "zk_vk_read": ([vp, ctypes.POINTER(CircuitParamsC), vp, sz, ctypes.c_int, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
         "zk_vk_from_parts": ([vp, ctypes.POINTER(CircuitParamsC), u64p, u64p, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
         "zk_verify": ([vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
@@ -448,6 +460,100 @@ class Engine:
     def upload_canonical(self, p, data):
         d = _arr(data, 4)
         self._chk(self.L.zk_poly_upload_canonical(self.ctx, p.h, _p(d), d.shape[0]), "zk_poly_upload_canonical")
+
+    # ---- the provers between the commitments (phase-level ABI: the host keeps transcript, RNG and blinding) --------------
+    @staticmethod
+    def _handles(polys):
+        return (ctypes.c_uint64 * max(len(polys), 1))(*[p.h for p in polys])
+
+    @staticmethod
+    def _fr(v):
+        return _p(np.ascontiguousarray(v, dtype=np.uint64).reshape(4))
+
+    def _outputs(self, count, n):
+        out = []
+        try:
+            for _ in range(count):
+                out.append(self.poly(n))
+        except ZkError:
+            self._drop(out)
+            raise
+        return out
+
+    @staticmethod
+    def _drop(polys):
+        for p in polys:
+            p.free()
+
+    def lookup_permute(self, pk, advice):
+        """zk_lookup_permute: (a', s') of every lookup of the key -> two lists of new Polys the caller frees; rows 0 .. n - 8 are
+        written, the 7 rows behind them are the host's blinding (upload_range).  ZkError -6: an input is not in the table."""
+        sh = self.pk_shape(pk)
+        n, nl = 1 << sh["k"], sh["n_lookups"]
+        out = self._outputs(2 * nl, n)
+        a, s = out[:nl], out[nl:]
+        rc = self.L.zk_lookup_permute(self.ctx, pk, self._handles(advice), len(advice), self._handles(a), self._handles(s), nl)
+        if rc:
+            self._drop(out)
+        self._chk(rc, "zk_lookup_permute")
+        return a, s
+
+    def lookup_product(self, pk, advice, permuted_input, permuted_table, beta, gamma):
+        """zk_lookup_product: the grand product zL of every lookup (rows 0 .. n - 7) -> list of new Polys the caller frees;
+        beta, gamma: Montgomery images."""
+        if len(permuted_input) != len(permuted_table):
+            raise ValueError("one permuted table per permuted input")
+        n = 1 << self.pk_shape(pk)["k"]
+        z = self._outputs(len(permuted_input), n)
+        rc = self.L.zk_lookup_product(self.ctx, pk, self._handles(advice), len(advice), self._handles(permuted_input),
+                                      self._handles(permuted_table), len(permuted_input), self._fr(beta), self._fr(gamma), self._handles(z))
+        if rc:
+            self._drop(z)
+        self._chk(rc, "zk_lookup_product")
+        return z
+
+    def permutation_product(self, pk, advice, beta, gamma):
+        """zk_permutation_product: the permutation argument's grand products, one per chunk (rows 0 .. n - 7) -> list of new
+        Polys the caller frees."""
+        sh = self.pk_shape(pk)
+        z = self._outputs(sh["n_chunks"], 1 << sh["k"])
+        rc = self.L.zk_permutation_product(self.ctx, pk, self._handles(advice), len(advice), self._fr(beta), self._fr(gamma),
+                                           self._handles(z), len(z))
+        if rc:
+            self._drop(z)
+        self._chk(rc, "zk_permutation_product")
+        return z
+
+    def poly_lincomb(self, out, ins, coeffs, sub_low=None):
+        """zk_poly_lincomb: out = sum_j coeffs[j] * ins[j] - (sub_low[0] + sub_low[1] X + ..); coeffs (count, 4), sub_low (n_low <= 8, 4),
+        Montgomery images."""
+        c = _arr(coeffs, 4)
+        if c.shape[0] != len(ins):
+            raise ValueError("one coefficient per input")
+        low = None if sub_low is None else _arr(sub_low, 4)
+        n_low = 0 if low is None else low.shape[0]
+        self._chk(self.L.zk_poly_lincomb(self.ctx, out.h, self._handles(ins), _p(c), len(ins), _p(low) if n_low else None, n_low),
+                  "zk_poly_lincomb")
+
+    def random_poly(self, key, first_block, out):
+        """zk_random_poly: out[i] = the Fr::random of ChaCha20 block first_block + i under the 32-byte `key`."""
+        if len(key) != 32:
+            raise ValueError("ChaCha20 key must be 32 bytes")
+        self._chk(self.L.zk_random_poly(self.ctx, bytes(key), first_block, out.h), "zk_random_poly")
+
+    def pk_export_poly(self, pk, which, index, dst):
+        """zk_pk_export_poly: coefficient form of the key's fixed column (ZK_PK_FIXED_POLY, query order) or sigma (ZK_PK_SIGMA_POLY)
+        number `index` into dst."""
+        self._chk(self.L.zk_pk_export_poly(self.ctx, pk, which, index, dst.h), "zk_pk_export_poly")
+
+    def upload_range(self, p, first, data):
+        """zk_poly_upload_range: rows [first, first + len(data)) of p from the host (Montgomery images)."""
+        d = _arr(data, 4)
+        self._chk(self.L.zk_poly_upload_range(self.ctx, p.h, first, _p(d) if d.shape[0] else None, d.shape[0]), "zk_poly_upload_range")
+
+    def copy_range(self, dst, dst_first, src, src_first, count):
+        """zk_poly_copy_range: dst[dst_first ..] = src[src_first .. src_first + count)."""
+        self._chk(self.L.zk_poly_copy_range(self.ctx, dst.h, dst_first, src.h, src_first, count), "zk_poly_copy_range")
 
     # ---- keygen / create_proof -------------------------------------------------------
     def keygen(self, params, fixed_canonical, copies):

@@ -419,6 +419,48 @@ typedef struct { uint32_t kind, index, row, other_index, other_row, reserved; } 
 int zk_witness_check(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap,
                      uint64_t counts[5]);
 
+/* ---- the key itself: is a resident proving key what keygen would have made of its own values? ---------------------------
+ * A ProvingKey holds every column four times - commitment, values, coefficients, extended coset - next to l_0 / l_last /
+ * l_active and the permutation's sigma columns; zk_pk_read checks lengths, element ranges, the range table and the selector
+ * bits, and ties none of these copies to each other (halo2's ProvingKey::read validates elements only).  zk_pk_check does. */
+#define ZK_PK_PART_FIXED_COMMIT 1  /* column f: commit_lagrange(fixed values f) under the RESIDENT SRS != the vk's commitment (index 0, count 1) */
+#define ZK_PK_PART_SIGMA_COMMIT 2  /* the same for permutation column c */
+#define ZK_PK_PART_FIXED_POLY   3  /* column f, index i: coefficient i != lagrange_to_coeff(fixed values f)[i] */
+#define ZK_PK_PART_SIGMA_POLY   4
+#define ZK_PK_PART_FIXED_COSET  5  /* column f, index i < 4n: coset value i != coeff_to_extended(fixed coefficients f)[i] */
+#define ZK_PK_PART_SIGMA_COSET  6
+#define ZK_PK_PART_L_COSET      7  /* column 0 / 1 / 2 = l_0 / l_last / l_active: != the closed form zk_keygen builds */
+#define ZK_PK_PART_SIGMA_LABEL  8  /* column c, index r: the sigma value is not delta^c' w^r' of a cell with c' < #permutation columns and
+                                      r' < usable (r < usable), or not the cell's own label (r >= usable) */
+#define ZK_PK_PART_SIGMA_MAP    9  /* column c, index r: no cell's sigma value names cell (c, r) - sigma is not a bijection of the cells */
+typedef struct { uint32_t part, column, index, reserved; uint64_t count; } zk_pk_finding;
+
+#define ZK_PK_CHECK_COMMITMENTS 1u /* no finding of parts 1, 2 */
+#define ZK_PK_CHECK_POLYS       2u /* none of 3, 4 */
+#define ZK_PK_CHECK_COSETS      4u /* none of 5, 6, 7 */
+#define ZK_PK_CHECK_SIGMA       8u /* none of 8, 9 */
+#define ZK_PK_CHECK_ALL        15u
+#define ZK_PK_CHECK_REPR       16u /* informational: transcript_repr is the value zk_keygen computes for these commitments and this shape
+                                      (clear after a host override with another value - not a fault of the key) */
+/* Each part is compared with what its SOURCE PART AS IT STANDS IN THE KEY yields - values -> commitment, values -> coefficients,
+ * coefficients -> extended coset - through the routines zk_keygen itself uses, byte for byte on the Montgomery images
+ * (everything the engine makes is fully reduced, so the image is unique; a non-reduced element of an unchecked file is a
+ * mismatch).  One damaged element therefore has an exact signature: a damaged VALUE is 1 commitment finding plus count = n in
+ * the column's POLY part (every coefficient of the inverse transform moves); a damaged COEFFICIENT is count = 1 in POLY and
+ * count = 4n in COSET; a damaged COSET ELEMENT is count = 1 in COSET.  Sigma: a cell whose value has a LABEL finding names
+ * nobody, so a value replaced by a non-label is LABEL 1 + MAP 1, one replaced by another cell's label is MAP 1 alone.
+ * One finding per (part, column) that has any mismatch: its lowest `index` and its `count`, in ascending (part, column) order;
+ * the first min(cap, *n_findings) are written (`out` may be NULL with cap 0), *n_findings is the total.  Fixed columns are
+ * numbered in zk_vk_export's (query) order, permutation columns in zk_keygen's.  Same key, same output, on every run.  A
+ * broken key is a verdict (ZK_OK, bits of *flags clear), never an error.  The key, every proof byte and what
+ * zk_witness_check returns are unchanged by a check; its scratch is the key's idle quotient buffer, and what it allocates
+ * on a key's first check (one bit per permutation cell, 16 bytes per (part, column)) is kept with the key.  Out of scope: the
+ * lazily derived three-coset copies (made from the cosets checked here), the range table and the selector structure (zk_keygen
+ * and zk_pk_read refuse violations).
+ * ZK_EINVAL: bad handle, NULL flags / n_findings, cap > 0 with out == NULL; ZK_ESTATE: a verifying-only key, or a key whose
+ * SRS was replaced. */
+int zk_pk_check(zk_ctx* ctx, zk_pk pk, uint32_t* flags, zk_pk_finding* out, size_t cap, size_t* n_findings);
+
 /* ---- verify_proof ---------------------------------------------------------------------------------------------------
  * plonk::verify_proof with the KZG pairing check (ecdsa_p256.rs:429-469: `verify` = Blake2b + SHPLONK, `verify_evm` = EVM +
  * GWC; no instances).  The check is e(A, [s]G2) = e(B, G2) with g[0], g2 and s_g2 of the context's resident SRS: a proof

@@ -155,8 +155,12 @@ struct zk_pk_rec {
     // zk_witness_check (witness_check.hip): sigma decoded into cell indices, the verdict bitmap and its staging — made by the
     // key's first check, never by a key that is not checked; a lock-step member has none (the check takes the key itself)
     struct WitnessCheckState* wc = nullptr;
+    // zk_pk_check (pk_check.hip): the sigma mark bitmap, the per-(part, column) counters and their staging — made by the key's
+    // first audit, kept with it; a lock-step member has none
+    struct PkCheckState* pc = nullptr;
 };
 void wc_destroy(struct WitnessCheckState* s);
+void pc_destroy(struct PkCheckState* s);
 
 // buffers of the launches a lock-step batch shares between its proofs, sized for `cap` proofs
 struct BatchBufs {

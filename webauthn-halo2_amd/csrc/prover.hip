@@ -185,6 +185,8 @@ void pk_destroy(zk_pk_rec* pk) {
     pk->bb = nullptr;
     wc_destroy(pk->wc);
     pk->wc = nullptr;
+    pc_destroy(pk->pc);
+    pk->pc = nullptr;
     for (Fr* p : pk->dev) hipFree(p);
     if (pk->tail_host) hipHostFree(pk->tail_host);
     if (pk->rows_host) hipHostFree(pk->rows_host);
@@ -317,6 +319,7 @@ static zk_pk_rec* pk_make_member(zk_ctx* c, const zk_pk_rec* pk) {
     m->members.clear();
     m->bb = nullptr;
     m->wc = nullptr;
+    m->pc = nullptr;
     for (auto* v : {&m->adv_val, &m->adv_poly, &m->adv_coset, &m->z_val, &m->z_poly, &m->z_coset, &m->lk_in, &m->lk_ap, &m->lk_ap_poly,
                     &m->lk_ap_coset, &m->lk_sp, &m->lk_sp_poly, &m->lk_sp_coset, &m->lk_z, &m->lk_z_poly, &m->lk_z_coset, &m->lk_in_coset,
                     &m->gp_num, &m->gp_den, &m->gp_loc_p, &m->gp_loc_r})

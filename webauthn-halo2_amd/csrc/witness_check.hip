@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pk.h"
+#include "sigma_decode.hip.h"
 
 using namespace zk;
 
@@ -105,10 +106,9 @@ __global__ __launch_bounds__(256) void wc_copy_kernel(const WcArgs* __restrict__
 }
 
 // sigma values -> cell indices, once per key.  sigma(c, r) = delta^c' w^r': most cells are fixed points (one product tells);
-// otherwise v^n = delta^(c' n) names the column among the shape's, and r' is the discrete logarithm of v delta^-c' in the group of
-// order 2^k, bit by bit (Pohlig-Hellman: bit i is set iff (u_i)^(2^(k-1-i)) != 1, then u_{i+1} = u_i w^-(2^i)).  A value that is
-// no such label, or a usable cell mapped into the rows the prover blinds, raises *bad (every writer stores the same word).
-// consts: delta^c | delta^(c n) | delta^-c (n_perm each) | w^-(2^i) (k)
+// the others go through the decoder the key audit shares (sigma_decode.hip.h).  A value that is no such label, or a usable cell
+// mapped into the rows the prover blinds, raises *bad (every writer stores the same word).
+// consts: sigma_decode_consts
 __global__ __launch_bounds__(256) void wc_sigma_decode_kernel(const WcArgs* __restrict__ args, const Fr* __restrict__ tw,
                                                               const Fr* __restrict__ consts, uint32_t n_perm, uint32_t k, uint32_t usable,
                                                               uint32_t* __restrict__ map, uint32_t* __restrict__ bad) {
@@ -118,28 +118,9 @@ __global__ __launch_bounds__(256) void wc_sigma_decode_kernel(const WcArgs* __re
     const Fr v = fe_load(args->sigma[c] + r);
     uint32_t m = (c << k) | r;
     if (v != fe_mul(fe_load(consts + c), fe_load(tw + r))) {
-        Fr t = v;
-        for (uint32_t i = 0; i < k; i++) t = fe_sqr(t);
-        uint32_t cc = n_perm;
-        for (uint32_t x = 0; x < n_perm && cc == n_perm; x++)
-            if (t == fe_load(consts + n_perm + x)) cc = x;
-        if (cc == n_perm) {
-            *bad = 1u;
-        } else {
-            const Fr one = Fr::one();
-            Fr u = fe_mul(v, fe_load(consts + 2 * n_perm + cc));
-            uint32_t rr = 0;
-            for (uint32_t i = 0; i < k; i++) {
-                Fr e = u;
-                for (uint32_t s = i + 1; s < k; s++) e = fe_sqr(e);
-                if (e != one) {
-                    rr |= 1u << i;
-                    u = fe_mul(u, fe_load(consts + 3 * n_perm + i));
-                }
-            }
-            if (u != one || (r < usable && rr >= usable)) *bad = 1u;
-            else m = (cc << k) | rr;
-        }
+        uint32_t cc = 0, rr = 0;
+        if (!sigma_decode_label(v, consts, n_perm, k, &cc, &rr) || (r < usable && rr >= usable)) *bad = 1u;
+        else m = (cc << k) | rr;
     }
     map[(size_t)c * n + r] = m;
 }
@@ -207,12 +188,6 @@ __global__ __launch_bounds__(256) void wc_list_kernel(const uint64_t* __restrict
             pos++;
         }
     }
-}
-
-Fr wc_delta() {  // 7^(2^28): the generator of the permutation argument's cosets
-    Fr d = fr_from_u64(7);
-    for (int i = 0; i < 28; i++) d = fe_sqr(d);
-    return d;
 }
 
 }  // namespace
@@ -320,22 +295,7 @@ int wc_ensure_sigma(zk_ctx* c, zk_pk_rec* pk) {
     const Fr* tw = nullptr;
     int rc = ctx_get_twiddles(c, k, &tw);
     if (rc) return rc;
-    std::vector<Fr> consts((size_t)3 * n_perm + k);
-    const Fr delta = wc_delta(), delta_n = fe_pow_u64(delta, lay.n), delta_inv = fe_inv_fast(delta);
-    Fr d = Fr::one(), dn = Fr::one(), di = Fr::one();
-    for (uint32_t p = 0; p < n_perm; p++) {
-        consts[p] = d;
-        consts[n_perm + p] = dn;
-        consts[2 * n_perm + p] = di;
-        d = fe_mul(d, delta);
-        dn = fe_mul(dn, delta_n);
-        di = fe_mul(di, delta_inv);
-    }
-    Fr wi = fe_inv_fast(fr_omega(k));
-    for (uint32_t i = 0; i < k; i++) {
-        consts[3 * n_perm + i] = wi;
-        wi = fe_sqr(wi);
-    }
+    const std::vector<Fr> consts = sigma_decode_consts(k, n_perm);
     Fr* d_consts = nullptr;
     if (hipMalloc(&d_consts, consts.size() * sizeof(Fr)) != hipSuccess) {
         (void)hipGetLastError();

@@ -37,7 +37,8 @@ import threading
 import numpy as np
 
 from . import circuit
-from .engine import ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_TRANSCRIPT_BLAKE2B, ZK_TRANSCRIPT_EVM, Engine
+from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_TRANSCRIPT_BLAKE2B, ZK_TRANSCRIPT_EVM,
+                     Engine)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -231,11 +232,38 @@ def _pipeline(st, i):
     return m["eng"], m["keys"], m["slots"]
 
 
-def download_keys(degree: int, proving_key_path=None, verifying_key_path=None, device: int = 0):
+class ProvingKeyError(ValueError):
+    """A proving key failed its audit (download_keys(check=True), proving_server.setup(check_keys=True)): `flags` and `findings`
+    are what Engine.pk_check returned - which part, column and index of the key is not what keygen makes of the key's own
+    values."""
+
+    def __init__(self, flags, findings):
+        self.flags, self.findings = flags, findings
+        super().__init__(f"proving key fails its audit: flags {flags:#x}, first findings {findings[:4]}")
+
+
+def check_keys(proving_key_path, degree, device=0, cap=64):
+    """Engine.pk_check of the resident key registered under `proving_key_path` -> (flags, findings)."""
+    with _STATE_LOCK:
+        eng, _, pk = _resident_key(proving_key_path, degree, device)
+        with _Hold(_STATE[device]):  # (the audit borrows the key's idle workspace: no request proves under it meanwhile)
+            return eng.pk_check(pk, cap)
+
+
+def _audit_or_raise(eng, pk):
+    flags, findings = eng.pk_check(pk)
+    if flags & ZK_PK_CHECK_ALL != ZK_PK_CHECK_ALL:
+        raise ProvingKeyError(flags, findings)
+
+
+def download_keys(degree: int, proving_key_path=None, verifying_key_path=None, device: int = 0, check: bool = False):
     """keygen_vk + keygen_pk for the ECDSA-shape circuit.  The proving key stays on the device
     (registered under `proving_key_path`; a key already registered under that name is freed first); the
     verifying key is written to `verifying_key_path` if given, as the reference writes it
-    (`vk.to_bytes(SerdeFormat::RawBytes)`, ecdsa_p256.rs:266-270: the VerifyingKey::write image of zk_vk_write)."""
+    (`vk.to_bytes(SerdeFormat::RawBytes)`, ecdsa_p256.rs:266-270: the VerifyingKey::write image of zk_vk_write).
+    check=True: the new resident key goes through Engine.pk_check, and so does - when `proving_key_path` names an existing
+    ProvingKey file (RawBytes, what the reference reads on every request, ecdsa_p256.rs:338-343) - the key of that file, read
+    beside it and freed again; a key that fails raises ProvingKeyError (a file zk_pk_read itself refuses raises ZkError)."""
     p = _config_for(degree)
     asg = circuit.synthesize(p, 0)  # structure only: fixed columns and copy constraints
     fixed = np.stack([asg.to_limbs(c) for c in asg.fixed])
@@ -255,6 +283,16 @@ def download_keys(degree: int, proving_key_path=None, verifying_key_path=None, d
                 if name in m["keys"]:
                     m["eng"].pk_free(m["keys"].pop(name))
                 m["keys"][name] = m["eng"].keygen(p, fixed, asg.copies)
+            if check:
+                _audit_or_raise(eng, pk)
+                if proving_key_path and os.path.isfile(proving_key_path):
+                    with open(proving_key_path, "rb") as f:
+                        data = f.read()
+                    from_file = eng.pk_read(p, data, ZK_SERDE_RAW_BYTES)
+                    try:
+                        _audit_or_raise(eng, from_file)
+                    finally:
+                        eng.pk_free(from_file)
         if verifying_key_path:
             with open(verifying_key_path, "wb") as f:
                 f.write(eng.vk_write(pk).tobytes())

@@ -28,6 +28,9 @@ ZK_VERIFY_BATCH_MAX = 1024
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
 ZK_PK_FIXED_POLY, ZK_PK_SIGMA_POLY = 0, 1
+(ZK_PK_PART_FIXED_COMMIT, ZK_PK_PART_SIGMA_COMMIT, ZK_PK_PART_FIXED_POLY, ZK_PK_PART_SIGMA_POLY, ZK_PK_PART_FIXED_COSET,
+ ZK_PK_PART_SIGMA_COSET, ZK_PK_PART_L_COSET, ZK_PK_PART_SIGMA_LABEL, ZK_PK_PART_SIGMA_MAP) = range(1, 10)
+ZK_PK_CHECK_COMMITMENTS, ZK_PK_CHECK_POLYS, ZK_PK_CHECK_COSETS, ZK_PK_CHECK_SIGMA, ZK_PK_CHECK_ALL, ZK_PK_CHECK_REPR = 1, 2, 4, 8, 15, 16
 
 
 def device_pci_bus_id(device=0):
@@ -82,6 +85,11 @@ class CircuitParamsC(ctypes.Structure):
 class WitnessFailureC(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint32), ("index", ctypes.c_uint32), ("row", ctypes.c_uint32), ("other_index", ctypes.c_uint32),
                 ("other_row", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PkFindingC(ctypes.Structure):
+    _fields_ = [("part", ctypes.c_uint32), ("column", ctypes.c_uint32), ("index", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("count", ctypes.c_uint64)]
 
 
 class ZkError(RuntimeError):
@@ -195,11 +203,12 @@ def load_library():
                              ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "zk_witness_check": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(WitnessFailureC), sz,
                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+        "zk_pk_check": ([vp, ctypes.c_uint64, ctypes.POINTER(u32), ctypes.POINTER(PkFindingC), sz, ctypes.POINTER(sz)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name, None)
         if fn is None:
-            if name == "zk_witness_check" and os.environ.get("ZKMI355_LIB"):
+            if name in ("zk_witness_check", "zk_pk_check") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -640,6 +649,17 @@ class Engine:
         self._chk(self.L.zk_witness_check(self.ctx, pk, hs, len(advice_polys), out, cap, counts), "zk_witness_check")
         m = min(cap, int(counts[0]))
         return [int(v) for v in counts], [(f.kind, f.index, f.row, f.other_index, f.other_row) for f in out[:m]] if m else []
+
+    def pk_check(self, pk, cap=64):
+        """The audit of a resident proving key (zk_pk_check) -> (flags, findings): flags = ZK_PK_CHECK_* bits (flags & ZK_PK_CHECK_ALL
+        == ZK_PK_CHECK_ALL: the key is what keygen would have made of its own values); findings = the first min(cap, total) of
+        one (part, column, index, count) tuple per ZK_PK_PART_* and column with a mismatch - its lowest index and how many - in
+        ascending (part, column) order.  A broken key is a verdict, not an error; the key and every proof byte are unchanged."""
+        out = (PkFindingC * cap)() if cap else None
+        flags, total = ctypes.c_uint32(0), ctypes.c_size_t(0)
+        self._chk(self.L.zk_pk_check(self.ctx, pk, ctypes.byref(flags), out, cap, ctypes.byref(total)), "zk_pk_check")
+        m = min(cap, total.value)
+        return flags.value, [(f.part, f.column, f.index, int(f.count)) for f in out[:m]] if m else []
 
     # ---- verify_proof ----------------------------------------------------------------------------------
     @staticmethod

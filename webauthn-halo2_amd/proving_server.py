@@ -50,15 +50,16 @@ def parse_request(body):
     return out
 
 
-def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None, params_path=None):
+def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None, params_path=None, check_keys=False):
     """POST /setup (and the server's start-up keygen, main.rs:451-456).  The proving key stays resident on
     `device`, registered under `proving_key_path` (the name later requests carry); the verifying key is
     written only when a path is given (the reference writes ./keys/verifying_key.vk).  `params_path`: a trusted-setup
     ParamsKZG file of degree >= `degree`, made the device's SRS source (ecdsa_p256.set_params_file) before keygen; None keeps
-    the device's current source (the seed-0 setup unless one was set)."""
+    the device's current source (the seed-0 setup unless one was set).  check_keys=True: download_keys(check=True) - the key is
+    audited (ecdsa_p256.ProvingKeyError names the part, column and index of a key that is not what keygen makes)."""
     if params_path is not None:
         ecdsa_p256.set_params_file(params_path, device)
-    ecdsa_p256.download_keys(degree, proving_key_path, verifying_key_path, device)
+    ecdsa_p256.download_keys(degree, proving_key_path, verifying_key_path, device, check=check_keys)
     return "Done"
 
 

@@ -216,6 +216,43 @@ int zk_srs_read_downsize(zk_ctx* ctx, const uint8_t* bytes, size_t len, int form
 #define ZK_SRS_CHECK_GENERATORS 4u
 int zk_srs_check(zk_ctx* ctx, const uint8_t seed[32], uint32_t* flags);
 
+/* ---- one ceremony contribution to the resident SRS ------------------------------------------------------------------
+ * The seed setup's secret is public and a ceremony file has to be trusted; zk_srs_update is the step that makes either
+ * one's own: it multiplies a fresh secret s into the resident SRS and forgets it.  With tau the (unknown) secret so far,
+ *   g[i] -> [s^i] g[i],  g_lagrange -> g_to_lagrange(g) (halo2's rule, one G1 transform on the device),  s_g2 -> [s] s_g2,
+ * so the new secret is s tau: unknown as long as ONE contributor of the chain discarded theirs, even when the chain starts
+ * at the seed-0 setup.  g2 stays.
+ * s is the first Fr draw of ChaCha20Rng::from_seed(seed), zk_srs_setup's rule.  The engine has no entropy of its own: the
+ * caller draws the 32 bytes from the operating system for this one call and discards them (as for zk_prove's seed) — who
+ * keeps the seed keeps s.  The engine clears its own copies of s, on the host and on the device, before it returns.  The
+ * call is deterministic: the same resident SRS and seed give the same bytes.
+ * The result is a NEW shared block installed as zk_srs_downsize installs its own: window tables rebuilt, keys made under
+ * the old SRS answer ZK_ESTATE, contexts made with zk_ctx_create_shared before the call keep the old SRS and their keys.
+ * ZK_EINVAL: NULL ctx / seed, or a seed whose s is 0 or 1; ZK_ESTATE: no SRS, or no G2 half (zk_srs_load without
+ * zk_srs_set_g2).  On any failure the resident SRS, its tables, s_g2 and its keys are what they were.
+ * out (may be NULL; untouched on error) receives the receipt of the step. */
+typedef struct {
+    uint64_t before_g1[8]; /* g[1] of the SRS the step started from (affine Montgomery) */
+    uint64_t after_g1[8];  /* g[1] after it = [s] before_g1 */
+    uint64_t s_g1[8];      /* [s] G1 generator */
+    uint64_t s_g2[16];     /* [s] G2 generator, zk_srs_set_g2's image */
+} zk_srs_contribution;
+int zk_srs_update(zk_ctx* ctx, const uint8_t seed[32], zk_srs_contribution* out);
+/* checks a receipt on the host (three pairing equations); *flags gets one bit per check passed.  A bad receipt is a verdict
+ * (ZK_OK with bits clear), never an error; ZK_EINVAL only for NULL arguments.  A receipt with a coordinate not below p, a
+ * point off its curve (for s_g2: outside the order-r subgroup) or an identity point gets no bit but RESIDENT.
+ * What a receipt is: a knowledge-of-exponent style proof, not a Schnorr proof — nobody can make the pair (s_g1, s_g2) with
+ * SAME_SECRET without knowing s (the knowledge-of-exponent assumption), and LINKS ties that s to the step before_g1 ->
+ * after_g1.  It is not bound to a contributor's name or to a transcript.  What it pins: a receipt with all four bits plus
+ * zk_srs_check == 7 on the resulting SRS shows tau' = s tau — the check shows powers of ONE tau' that match s_g2 and the
+ * Lagrange basis, and LINKS fixes g[1] = [tau'] G1 = [s] before_g1.  A chain is checked receipt by receipt, each before_g1
+ * being the previous after_g1. */
+#define ZK_SRS_CONTRIB_SAME_SECRET 1u /* e(s_g1, G2) == e(G1, s_g2): one s in both groups */
+#define ZK_SRS_CONTRIB_LINKS       2u /* e(after_g1, G2) == e(before_g1, s_g2) */
+#define ZK_SRS_CONTRIB_NONTRIVIAL  4u /* all points on their curves; s_g1 neither the identity nor the generator */
+#define ZK_SRS_CONTRIB_RESIDENT    8u /* after_g1 is g[1] of the context's resident SRS (clear if it has none) */
+int zk_srs_contribution_check(zk_ctx* ctx, const zk_srs_contribution* c, uint32_t* flags);
+
 /* ---- resident polynomials -------------------------------------------------- */
 int zk_poly_alloc(zk_ctx* ctx, size_t n, zk_poly* out);
 /* the handle dies; the memory is parked in the context (a few vectors, at most 2 GiB) for the next zk_poly_alloc of the same

@@ -13,10 +13,15 @@
 //
 // zk_srs_check multiplies nothing by the secret: it draws weights from a seed and tests, with two MSMs each, that g holds
 // powers of the tau behind s_g2 (one pairing equation) and that g_lagrange is the Lagrange basis of g (an NTT of the weights).
+//
+// zk_srs_update is one ceremony contribution: g[i] -> [s^i] g[i] by one scalar multiplication per point, whose XYZZ result goes
+// straight into the transform's scratch (the Lagrange basis has no pointwise update, so it is rebuilt by the same transform)
+// and whose affine form is the new g[i].  The G2 step and the receipt are host code (srs_update.h).
 #include <string.h>
 
 #include "ctx.h"
 #include "pairing.h"
+#include "srs_update.h"
 
 namespace zk {
 void launch_twiddles(Fr* tw, const Fr& w, uint32_t n, hipStream_t st);
@@ -110,10 +115,7 @@ __global__ __launch_bounds__(64) void g1_ntt_stage_kernel(G1X* __restrict__ a, c
 }
 
 // XYZZ -> affine (x = X / ZZ, y = Y / ZZZ; the identity is (0, 0)), one inversion per point as srs_fixed_base_kernel does
-__global__ __launch_bounds__(64) void g1_ntt_affine_kernel(const G1X* __restrict__ a, G1Affine* __restrict__ out, uint32_t n) {
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const G1X p = g1x_load(a + i);
+__device__ __forceinline__ G1Affine g1x_to_affine(const G1X& p) {
     G1Affine r;
     if (p.is_identity()) {
         r.x = Fq::zero();
@@ -124,6 +126,28 @@ __global__ __launch_bounds__(64) void g1_ntt_affine_kernel(const G1X* __restrict
         r.x = fe_mul(p.x, fe_sqr(u));
         r.y = fe_mul(p.y, t);
     }
+    return r;
+}
+__global__ __launch_bounds__(64) void g1_ntt_affine_kernel(const G1X* __restrict__ a, G1Affine* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const G1Affine r = g1x_to_affine(g1x_load(a + i));
+    fe_store(&out[i].x, r.x);
+    fe_store(&out[i].y, r.y);
+}
+
+// The load of zk_srs_update: q = [s^i] g[i] (pw[i] = s^i, standard Montgomery form as launch_twiddles writes it), once per
+// point for both of its uses — XYZZ into a[bitrev_k(i)], where the stage kernels expect the transform's input, and affine
+// into out[i], the new monomial basis.  64-lane workgroups as the stage kernel, whose g1x_mul this is: the multiplication's
+// live state (p, 2p, 3p, the accumulator and an addition's temporaries) decides the register count, and the inversion that
+// follows starts from the product alone.
+__global__ __launch_bounds__(64) void g1_update_kernel(const G1Affine* __restrict__ g, const Fr* __restrict__ pw, G1X* __restrict__ a,
+                                                       G1Affine* __restrict__ out, uint32_t log_n) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= (1u << log_n)) return;
+    const G1X q = g1x_mul(g1x_of_affine(affine_load(g + i)), fe_from_mont(fe_load(pw + i)));
+    g1x_store(a + (__brev(i) >> (32 - log_n)), q);
+    const G1Affine r = g1x_to_affine(q);
     fe_store(&out[i].x, r.x);
     fe_store(&out[i].y, r.y);
 }
@@ -131,6 +155,28 @@ __global__ __launch_bounds__(64) void g1_ntt_affine_kernel(const G1X* __restrict
 bool host_affine_eq(const G1Affine& a, const G1Affine& b) { return a.x == b.x && a.y == b.y; }
 
 }  // namespace
+
+// The transform from its stage kernels on: a holds the n = 2^k inputs as XYZZ in bit-reversed order (g1_ntt_load_kernel's
+// output, or g1_update_kernel's); d_out receives the affine result.  Returns with the stream drained.
+static int g1_ntt_run(zk_ctx* c, G1X* a, uint32_t k, G1Affine* d_out) {
+    const uint32_t n = 1u << k;
+    const Fr* tw = nullptr;
+    int rc = ctx_get_twiddles(c, k, &tw);
+    if (rc) return rc;
+    const Fr ninv = fe_inv(fr_from_u64(n));
+    const Fr ninv_c = fe_from_mont(ninv);
+    for (uint32_t s = 0; s < k; s++)
+        hipLaunchKernelGGL(g1_ntt_stage_kernel, dim3((n / 2 + 63) / 64), dim3(64), 0, c->stream, a, tw, k, s, (uint32_t)(s + 1 == k),
+                           ninv, ninv_c);
+    hipLaunchKernelGGL(g1_ntt_affine_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, a, d_out, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = aud_sync(c, c->stream);
+    if (e != hipSuccess) {
+        c->last_hip = (int)e;
+        return ZK_EHIP;
+    }
+    return ZK_OK;
+}
 
 // halo2's g_to_lagrange between device buffers of 2^k affine points (in == out allowed); n XYZZ points of scratch for the call
 int ctx_g1_to_lagrange(zk_ctx* c, const G1Affine* d_in, uint32_t k, G1Affine* d_out) {
@@ -144,21 +190,10 @@ int ctx_g1_to_lagrange(zk_ctx* c, const G1Affine* d_in, uint32_t k, G1Affine* d_
         (void)hipGetLastError();
         return ZK_ENOMEM;
     }
-    const Fr ninv = fe_inv(fr_from_u64(n));
-    const Fr ninv_c = fe_from_mont(ninv);
     hipLaunchKernelGGL(g1_ntt_load_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_in, a, k);
-    for (uint32_t s = 0; s < k; s++)
-        hipLaunchKernelGGL(g1_ntt_stage_kernel, dim3((n / 2 + 63) / 64), dim3(64), 0, c->stream, a, tw, k, s, (uint32_t)(s + 1 == k),
-                           ninv, ninv_c);
-    hipLaunchKernelGGL(g1_ntt_affine_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, a, d_out, n);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = aud_sync(c, c->stream);
+    rc = g1_ntt_run(c, a, k, d_out);
     hipFree(a);
-    if (e != hipSuccess) {
-        c->last_hip = (int)e;
-        return ZK_EHIP;
-    }
-    return ZK_OK;
+    return rc;
 }
 
 ZK_API(zk_g_to_lagrange, (zk_ctx* c, const uint64_t* g, uint32_t k, uint64_t* out), (c, g, k, out)) {
@@ -274,6 +309,87 @@ ZK_API(zk_srs_check, (zk_ctx* c, const uint8_t seed[32], uint32_t* flags), (c, s
     uint8_t g2_gen[128];
     g2_to_raw(g2_generator(), g2_gen);
     if (host_affine_eq(g0, gen) && memcmp(c->g2_raw, g2_gen, 128) == 0) f |= 4u;
+    *flags = f;
+    return ZK_OK;
+}
+
+// One ceremony contribution.  Everything is built beside the resident SRS — the two new bases, the new s_g2, the receipt —
+// and goes in through srs_install, so a failure at any point leaves the context as it was.  What depends on s: the host's
+// `s` and the generator's state (cleared below on every path), the n powers on the device (zeroed on the stream before the
+// buffer is freed), and the kernel argument of launch_twiddles, which lives in the runtime's argument buffer for the
+// length of that launch, as zk_srs_setup's does.
+ZK_API(zk_srs_update, (zk_ctx* c, const uint8_t seed[32], zk_srs_contribution* out), (c, seed, out)) {
+    if (!c || !seed) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->srs_k < 0 || !c->g2_valid) return ZK_ESTATE;  // (after zk_srs_load: zk_srs_set_g2 first)
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    const uint64_t aud0 = c->audit.violations;
+    const uint32_t k = (uint32_t)c->srs_k;
+    const size_t n = (size_t)1 << k;
+    Fr s = srs_update_secret(seed);
+    if (s.is_zero() || s == Fr::one()) {
+        secure_zero(&s, sizeof(s));
+        return ZK_EINVAL;
+    }
+    ctx_release_spares(c);
+    G1Affine *g = nullptr, *gl = nullptr;
+    Fr* pw = nullptr;
+    G1X* a = nullptr;
+    if (hipMalloc(&g, n * sizeof(G1Affine)) != hipSuccess || hipMalloc(&gl, n * sizeof(G1Affine)) != hipSuccess ||
+        hipMalloc(&pw, n * sizeof(Fr)) != hipSuccess || hipMalloc(&a, n * sizeof(G1X)) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(g);
+        hipFree(gl);
+        hipFree(pw);
+        secure_zero(&s, sizeof(s));
+        return ZK_ENOMEM;
+    }
+    launch_twiddles(pw, s, (uint32_t)n, c->stream);
+    hipLaunchKernelGGL(g1_update_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, c->stream, c->g, pw, a, g, k);
+    hipError_t e = hipGetLastError();
+    const hipError_t ez = hipMemsetAsync(pw, 0, n * sizeof(Fr), c->stream);  // the powers go before anything else can fail
+    if (e == hipSuccess) e = ez;
+    rc = e == hipSuccess ? g1_ntt_run(c, a, k, gl) : ZK_EHIP;
+    if (e != hipSuccess) c->last_hip = (int)e;
+    if (rc != ZK_OK) aud_sync(c, c->stream);  // (a successful transform has drained the stream itself)
+    hipFree(a);
+    hipFree(pw);  // zeroed by now
+    G1Affine g1[2];  // g[1] before and after
+    if (rc == ZK_OK && ((e = hipMemcpy(&g1[0], c->g + 1, sizeof(G1Affine), hipMemcpyDeviceToHost)) != hipSuccess ||
+                        (e = hipMemcpy(&g1[1], g + 1, sizeof(G1Affine), hipMemcpyDeviceToHost)) != hipSuccess)) {
+        c->last_hip = (int)e;
+        rc = ZK_EHIP;
+    }
+    if (rc != ZK_OK) {
+        hipFree(g);
+        hipFree(gl);
+        secure_zero(&s, sizeof(s));
+        return rc;
+    }
+    uint8_t s_g2_new[128];
+    srs_update_s_g2(c->s_g2_raw, s, s_g2_new);
+    zk_srs_contribution rec;
+    srs_contribution_make(g1[0], g1[1], s, &rec);
+    secure_zero(&s, sizeof(s));
+    if ((rc = srs_install(c, k, g, gl)) != ZK_OK) return rc;  // (the old SRS, its s_g2 and its keys stay; g and gl went with the new block)
+    memcpy(c->s_g2_raw, s_g2_new, 128);
+    if ((rc = aud_verdict(c, aud0, ZK_OK))) return rc;
+    if (out) *out = rec;
+    return ZK_OK;
+}
+
+ZK_API(zk_srs_contribution_check, (zk_ctx* c, const zk_srs_contribution* r, uint32_t* flags), (c, r, flags)) {
+    if (!c || !r || !flags) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint32_t f = srs_contribution_flags(*r);
+    if (c->srs_k >= 1) {
+        int rc = ctx_bind(c);
+        if (rc) return rc;
+        G1Affine g1;
+        HIPCHK(c, hipMemcpy(&g1, c->g + 1, sizeof(G1Affine), hipMemcpyDeviceToHost));
+        if (host_affine_eq(g1, g1_from_words(r->after_g1))) f |= ZK_SRS_CONTRIB_RESIDENT;
+    }
     *flags = f;
     return ZK_OK;
 }

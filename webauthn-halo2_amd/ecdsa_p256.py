@@ -37,8 +37,9 @@ import threading
 import numpy as np
 
 from . import circuit
-from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_TRANSCRIPT_BLAKE2B, ZK_TRANSCRIPT_EVM,
-                     Engine)
+from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_SRS_CONTRIB_LINKS,
+                     ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT, ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
+                     ZK_TRANSCRIPT_EVM, Engine)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -206,6 +207,118 @@ def _gen_srs_locked(degree, device):
         for i in range(len(st["extra"]), -1, -1):  # pipeline 0 (the first context) on top: a lone request takes it
             st["free"].put(i)
     return st["eng"]
+
+
+_RECEIPT_POINTS = (("before_g1", 8), ("after_g1", 8), ("s_g1", 8), ("s_g2", 16))
+_CONTRIB_CHAIN = ZK_SRS_CONTRIB_SAME_SECRET | ZK_SRS_CONTRIB_LINKS | ZK_SRS_CONTRIB_NONTRIVIAL
+
+
+def _sha256_file(path):
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for chunk in iter(lambda: f.read(1 << 24), b""):
+            h.update(chunk)
+    return h.hexdigest()
+
+
+def _receipt_points(receipt):
+    """the four points of a receipt as the uint64 limb arrays Engine.srs_contribution_check takes"""
+    out = {}
+    for name, words in _RECEIPT_POINTS:
+        raw = bytes.fromhex(receipt[name])
+        if len(raw) != 8 * words:
+            raise ValueError(f"receipt field {name}: {len(raw)} bytes, not {8 * words}")
+        out[name] = np.frombuffer(raw, dtype="<u8").astype(np.uint64)
+    return out
+
+
+def contribute_params(src_path, dst_path, seed: bytes, device: int = 0, degree=None) -> dict:
+    """One ceremony contribution: reads the ParamsKZG file `src_path` (RawBytes) — or, with src_path=None, runs the seed-0 setup
+    of `degree` —, multiplies the secret drawn from `seed` into it (zk_srs_update: tau -> s tau) and writes the result to
+    `dst_path` as a RawBytes params file, which set_params_file and the Rust host's ParamsKZG::read both take.  The seed is 32
+    bytes from the operating system (os.urandom(32)) that the caller uses for this one call and discards: who keeps it keeps s.
+
+    Nothing is written unless the new SRS passes the structure check (srs_check == 7) and its receipt all four contribution
+    checks; ValueError otherwise.  Also ValueError for dst_path == src_path, a seed that is not 32 bytes, or no source at all;
+    FileNotFoundError for a missing source — all before a device is touched.  The call uses a context of its own: the
+    device's resident server state is not disturbed.
+
+    Returns the receipt, a JSON-able dict:
+        before_g1, after_g1, s_g1   hex of the 64-byte affine Montgomery images (g[1] before and after the step, [s] G1)
+        s_g2                        hex of the 128-byte image of [s] G2 (x.c0 || x.c1 || y.c0 || y.c1)
+        k                           the degree of both files
+        src_sha256, dst_sha256      sha256 of the two files (src_sha256 is None for the seed-0 setup)
+    A third party checks a chain of them with check_contributions."""
+    if not isinstance(seed, (bytes, bytearray)) or len(seed) != 32:
+        raise ValueError("contribution seed must be 32 bytes")
+    if dst_path is None:
+        raise ValueError("no destination path")
+    if src_path is None:
+        if degree is None:
+            raise ValueError("no source: give src_path or degree")
+    else:
+        if os.path.abspath(src_path) == os.path.abspath(dst_path) or (os.path.exists(dst_path) and os.path.samefile(src_path, dst_path)):
+            raise ValueError("dst_path is src_path: a contribution never overwrites its source")
+        if not os.path.isfile(src_path):
+            raise FileNotFoundError(f"Unable to open params file: {src_path}")
+        if degree is not None and degree != params_file_degree(src_path):
+            raise ValueError(f"degree {degree} is not the params file's ({params_file_degree(src_path)}): {src_path}")
+    eng = Engine(device)
+    try:
+        if src_path is None:
+            eng.srs_setup(degree, bytes(32))
+        else:
+            with open(src_path, "rb") as f:
+                eng.srs_read(f.read())
+        rec = eng.srs_update(bytes(seed))
+        if eng.srs_check(os.urandom(32)) != 7:
+            raise ValueError("the updated SRS fails the structure check")
+        if eng.srs_contribution_check(rec) != _CONTRIB_CHAIN | ZK_SRS_CONTRIB_RESIDENT:
+            raise ValueError("the contribution's receipt fails its check")
+        k = eng.L.zk_srs_k(eng.ctx)
+        image = eng.srs_write(ZK_SERDE_RAW_BYTES)
+    finally:
+        eng.close()
+    tmp = dst_path + ".partial"
+    with open(tmp, "wb") as f:
+        f.write(memoryview(image))
+    os.replace(tmp, dst_path)
+    receipt = {name: rec[name].astype("<u8").tobytes().hex() for name, _ in _RECEIPT_POINTS}
+    receipt.update(k=k, src_sha256=None if src_path is None else _sha256_file(src_path), dst_sha256=_sha256_file(dst_path))
+    return receipt
+
+
+def check_contributions(params_path, receipts, device: int = 0) -> bool:
+    """Checks a params file against the chain of receipts that led to it (oldest first): every receipt shows
+    SAME_SECRET | LINKS | NONTRIVIAL, each before_g1 is the previous receipt's after_g1, the last after_g1 is g[1] of the file
+    (RESIDENT), and the file passes the structure check (srs_check == 7).  Then the file's secret is the chain's starting one
+    times every contributor's.  False for an empty chain or a file that cannot be read as RawBytes params."""
+    from .engine import ZkError
+
+    receipts = list(receipts)
+    if not receipts or not os.path.isfile(params_path):
+        return False
+    try:
+        points = [_receipt_points(r) for r in receipts]
+    except (KeyError, TypeError, ValueError):
+        return False
+    for prev, cur in zip(points, points[1:]):
+        if prev["after_g1"].tobytes() != cur["before_g1"].tobytes():
+            return False
+    eng = Engine(device)
+    try:
+        with open(params_path, "rb") as f:
+            try:
+                eng.srs_read(f.read())
+            except ZkError:
+                return False
+        for i, pts in enumerate(points):
+            want = _CONTRIB_CHAIN | (ZK_SRS_CONTRIB_RESIDENT if i == len(points) - 1 else 0)
+            if eng.srs_contribution_check(pts) & want != want:
+                return False
+        return eng.srs_check(os.urandom(32)) == 7  # fresh weights: a file cannot be made to fit a known check
+    finally:
+        eng.close()
 
 
 def shutdown(device=None):

@@ -26,6 +26,7 @@ ZK_OPT_STREAM_PRIORITY, ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_ACTIVITY_HOLD = 12, 13, 1
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
+ZK_SRS_CONTRIB_SAME_SECRET, ZK_SRS_CONTRIB_LINKS, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT = 1, 2, 4, 8
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
 ZK_PK_FIXED_POLY, ZK_PK_SIGMA_POLY = 0, 1
 (ZK_PK_PART_FIXED_COMMIT, ZK_PK_PART_SIGMA_COMMIT, ZK_PK_PART_FIXED_POLY, ZK_PK_PART_SIGMA_POLY, ZK_PK_PART_FIXED_COSET,
@@ -90,6 +91,11 @@ class WitnessFailureC(ctypes.Structure):
 class PkFindingC(ctypes.Structure):
     _fields_ = [("part", ctypes.c_uint32), ("column", ctypes.c_uint32), ("index", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("count", ctypes.c_uint64)]
+
+
+class SrsContributionC(ctypes.Structure):
+    _fields_ = [("before_g1", ctypes.c_uint64 * 8), ("after_g1", ctypes.c_uint64 * 8), ("s_g1", ctypes.c_uint64 * 8),
+                ("s_g2", ctypes.c_uint64 * 16)]
 
 
 class ZkError(RuntimeError):
@@ -177,6 +183,8 @@ def load_library():
         "zk_srs_downsize": ([vp, u32], ctypes.c_int),
         "zk_srs_read_downsize": ([vp, vp, sz, ctypes.c_int, u32], ctypes.c_int),
         "zk_srs_check": ([vp, ctypes.c_char_p, ctypes.POINTER(u32)], ctypes.c_int),
+        "zk_srs_update": ([vp, ctypes.c_char_p, ctypes.POINTER(SrsContributionC)], ctypes.c_int),
+        "zk_srs_contribution_check": ([vp, ctypes.POINTER(SrsContributionC), ctypes.POINTER(u32)], ctypes.c_int),
         "zk_vk_write": ([vp, ctypes.c_uint64, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_vk_load": ([vp, ctypes.c_uint64, vp, sz, ctypes.c_int, u64p], ctypes.c_int),
         "zk_pk_write": ([vp, ctypes.c_uint64, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
@@ -371,6 +379,31 @@ class Engine:
         f = ctypes.c_uint32()
         self._chk(self.L.zk_srs_check(self.ctx, bytes(seed), ctypes.byref(f)), "zk_srs_check")
         return f.value
+
+    # ---- one ceremony contribution --------------------------------------------------------------
+    CONTRIBUTION_FIELDS = ("before_g1", "after_g1", "s_g1", "s_g2")
+
+    def srs_update(self, seed):
+        """Multiplies the secret s = ChaCha20Rng(seed)'s first Fr into the resident SRS (tau -> s tau) and returns the receipt:
+        a dict of uint64 limb arrays before_g1, after_g1, s_g1 (8 each) and s_g2 (16).  The caller draws the seed from the
+        operating system and discards it."""
+        if len(seed) != 32:
+            raise ValueError("contribution seed must be 32 bytes")
+        c = SrsContributionC()
+        self._chk(self.L.zk_srs_update(self.ctx, bytes(seed), ctypes.byref(c)), "zk_srs_update")
+        return {f: np.array(getattr(c, f), dtype=np.uint64) for f in self.CONTRIBUTION_FIELDS}
+
+    def srs_contribution_check(self, contribution):
+        """The ZK_SRS_CONTRIB_* bits a receipt passes (15 = all; RESIDENT: its after_g1 is this context's g[1])."""
+        c = SrsContributionC()
+        for f in self.CONTRIBUTION_FIELDS:
+            a = np.ascontiguousarray(contribution[f], dtype=np.uint64).reshape(-1)
+            if a.size != len(getattr(c, f)):
+                raise ValueError("contribution field %s has the wrong length" % f)
+            setattr(c, f, type(getattr(c, f))(*[int(x) for x in a]))
+        flags = ctypes.c_uint32()
+        self._chk(self.L.zk_srs_contribution_check(self.ctx, ctypes.byref(c), ctypes.byref(flags)), "zk_srs_contribution_check")
+        return flags.value
 
     def vk_write(self, pk, fmt=ZK_SERDE_RAW_BYTES):
         return self._write(self.L.zk_vk_write, "zk_vk_write", pk, fmt)

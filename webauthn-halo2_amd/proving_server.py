@@ -55,7 +55,9 @@ def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", ver
     `device`, registered under `proving_key_path` (the name later requests carry); the verifying key is
     written only when a path is given (the reference writes ./keys/verifying_key.vk).  `params_path`: a trusted-setup
     ParamsKZG file of degree >= `degree`, made the device's SRS source (ecdsa_p256.set_params_file) before keygen; None keeps
-    the device's current source (the seed-0 setup unless one was set).  check_keys=True: download_keys(check=True) - the key is
+    the device's current source (the seed-0 setup unless one was set).  The seed-0 setup's secret is public — anybody can forge
+    proofs under it —, so a deployment passes a ceremony file, or one with its own secret multiplied in
+    (ecdsa_p256.contribute_params writes such a file, check_contributions checks its receipts).  check_keys=True: download_keys(check=True) - the key is
     audited (ecdsa_p256.ProvingKeyError names the part, column and index of a key that is not what keygen makes)."""
     if params_path is not None:
         ecdsa_p256.set_params_file(params_path, device)

@@ -86,7 +86,17 @@ int zk_sync(zk_ctx* ctx);                 /* hipStreamSynchronize on the context
  * environment variables. */
 #define ZK_OPT_MSM_WINDOW 1          /* signed window bits of the fixed-base MSM, 9..17; takes effect at the next SRS load */
 #define ZK_OPT_MSM_BATCH 2           /* columns per fixed-base MSM pass, 1..256 */
-#define ZK_OPT_NTT_MAX_RADIX_LOG2 3  /* largest radix of one NTT pass, 1..11 (clamped to the tile) */
+#define ZK_OPT_NTT_MAX_RADIX_LOG2 3  /* largest radix of one NTT pass, as its log2: v = 1..11 (anything else is ZK_EINVAL).  Every value is
+                                        honoured at every size the transforms accept (log_n <= 26), by every entry point that transforms
+                                        (zk_ntt_bn254_fr, the zk_poly transforms, keygen, zk_prove, ...): a 2^log_n transform runs
+                                        ceil(log_n / v) passes — 26 radix-2 passes at v = 1, log_n = 26 —, their radices as even as
+                                        possible (the larger ones first: log_n = 22, v = 7 -> 2^6, 2^6, 2^5, 2^5), on the smallest LDS tile
+                                        that holds 2^v: 2^9 elements for v <= 9, 2^10 for v = 10, 2^11 for v = 11; log_n <= v is ONE
+                                        pass.  0 (default) plans by size: passes of at most 2^8 on the 2^9 tile up to log_n = 16
+                                        (8 + 8), 2^9 on the 2^10 tile up to 18 (9 + 9), 2^10 on the 2^11 tile up to 20 (10 + 10), and at
+                                        most 2^7 on the 2^9 tile above (21 = 7 + 7 + 7, 22 .. 26 four passes).  Same bytes whatever the
+                                        value (tests/test_gpu_ntt_plans.py).  (A library built with another ZK_NTT_TILE_LOG than 9 keeps
+                                        that one tile and clamps v to it.) */
 #define ZK_OPT_GP_BATCH_INVERT 4     /* 1: grand products always take halo2's batch_invert form (the fallback path) */
 #define ZK_OPT_MSM_TAIL_STREAM 5     /* where the MSM reduction tails run: 0 auto, 1 the context's side stream, 2 its main stream.
                                         Auto: the side stream while at most ZK_OPT_MSM_TAIL_MAIN_ABOVE contexts are ACTIVE on the

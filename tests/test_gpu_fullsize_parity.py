@@ -60,6 +60,28 @@ def test_fullsize_proof_bytes_equal_the_committed_oracle_proof(engine, name):
     assert proof.hex() == fx["proof"]
 
 
+@pytest.mark.parametrize("value", [7, 11])
+def test_k19_proof_bytes_under_ntt_radix_option(engine, value):
+    """The committed k = 19 EVM proof again with every transform re-planned by ZK_OPT_NTT_MAX_RADIX_LOG2: 7 = three passes of 2^7
+    where the default runs two of 2^10 (2^21: the same plan), 11 = two passes on the 2^11 tile at 2^19 and 2^21 alike."""
+    fx = FIX["k19_evm_gwc"]
+    p, pk = key_for(engine, fx)
+    asg = zk.circuit.synthesize(p, fx["witness_seed"], worst_case=fx["worst_case"])
+    polys = []
+    for col in asg.advice:
+        h = engine.poly(1 << fx["degree"])
+        engine.upload_canonical(h, asg.to_limbs(col))
+        polys.append(h)
+    engine.set_option(E.ZK_OPT_NTT_MAX_RADIX_LOG2, value)
+    try:
+        proof = engine.prove(pk, polys, bytes.fromhex(fx["rng_seed"]), KIND[fx["transcript"]])
+    finally:
+        engine.set_option(E.ZK_OPT_NTT_MAX_RADIX_LOG2, 0)
+        for h in polys:
+            h.free()
+    assert proof.hex() == fx["proof"]
+
+
 @pytest.mark.parametrize("log_n", [19, 21])
 def test_ntt_full_output_at_baseline_sizes(engine, log_n):
     """Every one of the 2^19 / 2^21 outputs of the device NTT (forward and inverse, through the fine-grained seam)

@@ -312,7 +312,8 @@ def test_eval_matches_horner(engine, n):
 
 @pytest.mark.parametrize("k", [4, 9, 12])
 def test_coset_extended_domain(engine, k):
-    """coeff_to_extended: ext[i] = f(zeta * w_ext^i); extended_to_coeff inverts it."""
+    """coeff_to_extended: ext[i] = f(zeta * w_ext^i); extended_to_coeff inverts it.  (Six points by Horner, straight from the
+    definition; every element, other source lengths, truncations and sizes: tests/test_gpu_ntt_plans.py.)"""
     rng = random.Random(k)
     n, ext = 1 << k, 1 << (k + 2)
     f = rand_fr(rng, n)

@@ -86,6 +86,33 @@ def test_batch_inversion_fallback_same_bytes(engine):
     engine.pk_free(pk)
 
 
+@pytest.mark.parametrize("name", ["k10batched", "k17like"])
+def test_ntt_radix_option_same_bytes(engine, name):
+    """ZK_OPT_NTT_MAX_RADIX_LOG2 re-plans every transform of a proof (column batches in one launch per pass, the extended-domain
+    and three-coset routes, the folded 1/N of the inverse transforms) onto 1, 3, 7 and 11-bit radices: one to twelve passes per
+    transform.  The proof bytes are the default plan's, and the oracle's."""
+    A, L, F, k, lb = SHAPES[name]
+    _, asg, pk, polys = setup(engine, A, L, F, k, lb)
+    seed = b"\x37" * 32
+    want = engine.prove(pk, polys, seed, E.ZK_TRANSCRIPT_EVM)
+    if name == "k17like":
+        sh = plonk.Shape(k, A, L, F, lb)
+        opk = prover.keygen(prover.Circuit(sh, asg.fixed, asg.copies, asg.advice))
+        assert want == prover.create_proof(opk, asg.advice, ChaCha20Rng(seed), "evm")
+    try:
+        for value in (1, 3, 7, 11):
+            engine.set_option(E.ZK_OPT_NTT_MAX_RADIX_LOG2, value)
+            for domain in (0, 2):  # the automatic route, and three cosets wherever the quotient has three pieces
+                engine.set_option(E.ZK_OPT_QUOTIENT_DOMAIN, domain)
+                assert engine.prove(pk, polys, seed, E.ZK_TRANSCRIPT_EVM) == want, (name, value, domain)
+    finally:
+        engine.set_option(E.ZK_OPT_QUOTIENT_DOMAIN, 0)
+        engine.set_option(E.ZK_OPT_NTT_MAX_RADIX_LOG2, 0)
+    for h in polys:
+        h.free()
+    engine.pk_free(pk)
+
+
 def test_worst_case_witness_and_second_seed(engine):
     A, L, F, k, lb = SHAPES["k17like"]
     p, asg, pk, polys = setup(engine, A, L, F, k, lb, seed=0x5EED0019 + 3, worst=True)

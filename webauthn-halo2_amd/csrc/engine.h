@@ -39,7 +39,6 @@ hipError_t ntt_run(const NttJob& job, hipStream_t st);
 void launch_twiddles(Fr* tw, const Fr& w, uint32_t n, hipStream_t st);           // w^i, standard Montgomery form
 void launch_twiddles_scaled(Fr* tw, const Fr& w, const Fr& scale, uint32_t n, hipStream_t st);  // scale * w^i, standard form
 void launch_twiddles_internal(Fr* tw, const Fr& w, uint32_t n, hipStream_t st);  // w^i * 2^261 (plain words): ntt.hip's own form
-int ntt_plan(uint32_t log_n, uint32_t max_log_r, uint32_t bits[8]);
 
 // ---- the three-coset route of a quotient with three pieces (poly.hip "three cosets") ----
 struct Coset3Consts {  // constants of the 3 x 3 solve, standard form

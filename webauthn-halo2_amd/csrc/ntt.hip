@@ -32,6 +32,7 @@
 
 #include "engine.h"
 #include "field29.hip.h"
+#include "ntt_plan.h"
 
 namespace zk {
 
@@ -50,8 +51,7 @@ namespace zk {
 // exist for TWO-PASS plans of the mid sizes (ntt_run): a pass costs a load / inter-pass twiddle product / reduce / store round
 // per element whatever its radix, and radix 2^9 / 2^10 passes need tiles of at least two 32-byte columns to keep the global
 // accesses 64 bytes wide.  ZK_NTT_TILE_LOG (build-time) pins one tile for every size (the round-3 tuning variants).
-static constexpr int NTT_TILE_LOG = ZK_NTT_TILE_LOG;      // the default tile
-static constexpr int NTT_TILE_LOG_MAX = 11;
+static constexpr int NTT_TILE_LOG = ZK_NTT_TILE_LOG;      // the default tile (the largest is ntt_plan.h's NTT_TILE_LOG_MAX)
 typedef Fe29<FrParams> Fr29;
 
 struct NttPassArgs {
@@ -476,18 +476,6 @@ void launch_twiddles_internal(Fr* tw, const Fr& w, uint32_t n, hipStream_t st) {
 #endif
 static constexpr bool FOLD_ON = ZK_NTT_FOLD != 0, ZQ_ON = ZK_NTT_ZQ != 0;
 
-// Plan the passes of a 2^log_n transform: radices as even as possible, each <= max_log_r.
-int ntt_plan(uint32_t log_n, uint32_t max_log_r, uint32_t bits[8]) {
-    if (log_n == 0) return 0;
-    const uint32_t np = (log_n + max_log_r - 1) / max_log_r;
-    uint32_t rem = log_n;
-    for (uint32_t p = 0; p < np; p++) {
-        bits[p] = (rem + (np - p) - 1) / (np - p);
-        rem -= bits[p];
-    }
-    return (int)np;
-}
-
 // Runs all passes.  `a` is the input (left intact unless it is also `b`/`c`);
 // ping-pongs between b and c so that the result lands in `dst`.  dst must be
 // distinct from src unless a scratch `tmp` (N elements) is supplied.
@@ -502,30 +490,12 @@ hipError_t ntt_run(const NttJob& job, hipStream_t st) {
         srcs[b] = job.batch ? job.srcs[b] : job.src;
         dsts[b] = job.batch ? job.dsts[b] : job.dst;
     }
-    uint32_t bits[8];
-    // The plan: largest radix and tile by transform size.  Measured (tools/ntt_sweep.py, one vector, ms; 3 passes of 2^7 on the 2^9
-    // tile -> the plan below): 2^15 0.044 -> 0.032, 2^16 0.047 -> 0.034 (two passes of 2^8, tile 2^9); 2^17 0.052 -> 0.043, 2^18 0.076 ->
-    // 0.051 (two passes of 2^9, tile 2^10); 2^19 0.103 -> 0.079, 2^20 0.174 -> 0.158 (two passes of 2^10, tile 2^11); 2^21 stays at
-    // three passes of 2^7 (two passes of 2^11 / 2^10 on the 2^11 tile: 0.37 against 0.30 ms — one 32-byte column per tile row).
-    // An explicit radix (ZK_OPT_NTT_MAX_RADIX_LOG2) takes the smallest tile that holds it; a build that pins ZK_NTT_TILE_LOG keeps
-    // its tile and the old default radix for every size.
-    uint32_t tl = NTT_TILE_LOG, max_r = 7;
-    if (job.max_log_r) {
-        max_r = job.max_log_r;
-        if (ZK_NTT_TILE_LOG == 9) tl = max_r < 9 ? 9 : max_r > (uint32_t)NTT_TILE_LOG_MAX ? NTT_TILE_LOG_MAX : max_r;
-    } else if (ZK_NTT_TILE_LOG == 9) {
-        if (log_n <= 16) {
-            max_r = 8;
-        } else if (log_n <= 18) {
-            max_r = 9;
-            tl = 10;
-        } else if (log_n <= 20) {
-            max_r = 10;
-            tl = 11;
-        }
-    }
-    if (max_r > tl) max_r = tl;
-    const int np = ntt_plan(log_n, max_r, bits);
+    // The plan (ntt_plan.h): tile, pass count and radices by transform size and ZK_OPT_NTT_MAX_RADIX_LOG2
+    NttPlan plan;
+    if (!ntt_make_plan(log_n, job.max_log_r, &plan, ZK_NTT_TILE_LOG)) return hipErrorInvalidValue;
+    const uint32_t tl = plan.tile_log;
+    const uint32_t* bits = plan.bits;
+    const int np = (int)plan.passes;
     if (np == 0) {  // N == 1
         for (uint32_t b = 0; b < batch; b++)
             if (dsts[b] != srcs[b]) {

@@ -16,9 +16,20 @@ for s in $SRCS; do
     pids="$pids $!"
   fi
 done
+# the device harness of the field / curve headers (tests/field_device_check.hip, run by tests/test_gpu_field_device.py): one
+# source, one binary per instruction form of the 29-bit product, plus one with the curve's squarings and fused product off
+for v in "a0:-DZK_MUL29_ASM=0" "a1:-DZK_MUL29_ASM=1" "a2:-DZK_MUL29_ASM=2" "a2m:-DZK_MUL29_ASM=2 -DZK_MUL29_MASKRUN=1" \
+         "a2p:-DZK_MUL29_ASM=2 -DZK_EC29_SQR=0 -DZK_EC29_FUSE=0"; do
+  x=../tests/field_device_check_${v%%:*}
+  if [ ! -f $x ] || [ ../tests/field_device_check.hip -nt $x ] || [ -n "$(find csrc -name '*.h' -newer $x)" ]; then
+    hipcc $FLAGS ${v#*:} -Icsrc ../tests/field_device_check.hip -o $x &
+    pids="$pids $!"
+  fi
+done
 for p in $pids; do wait $p; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs
 echo "built $(pwd)/$OUT"
+echo "built $(cd ../tests && pwd)/field_device_check_{a0,a1,a2,a2m,a2p}"
 # the C++ host example of the same ABI (examples/prove_host.cpp): plain g++, linked against the library above
 cd ..
 g++ -O2 -std=c++17 -Wall -Iinclude examples/prove_host.cpp -Lwebauthn-halo2_amd -lzkmi355 -Wl,-rpath,'$ORIGIN/../webauthn-halo2_amd' -o examples/prove_host

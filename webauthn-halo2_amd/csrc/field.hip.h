@@ -277,7 +277,9 @@ inline Fe<PRM> fe_mul_host64(const Fe<PRM>& a, const Fe<PRM>& b) {
 // (32x32 + 64 -> 64, carry-out in VCC) + v_addc_co_u32 — hipcc never uses the mad's carry-out
 // by itself (it emits mad + 64-bit add + compare + select, ~4.5 instructions per product, half of
 // them register moves), hence the two-instruction asm.  The first product of a column cannot
-// overflow (the shifted-in accumulator is < 2^37) and needs no carry instruction.
+// overflow and needs no carry instruction IF it is chosen well: the shifted-in accumulator is < 2^37, so the product
+// must stay below 2^64 - 2^37.  a[i] * b[j] does not (0xffffffff^2 = 2^64 - 2^33 + 1: with words of all ones the carry was
+// lost); m * P[1] and m * P[7] do, both moduli having P[1], P[7] < 2^31 — so every column opens with one of those.
 // 128 mads + 112 carries + 8 mul_lo per product instead of ~580 instructions.
 // zk_macN: N products accumulated in ONE asm statement (hipcc pads every asm boundary with an
 // s_nop, so the products of a column are chained in groups of up to four).
@@ -305,9 +307,13 @@ __device__ __forceinline__ void zk_mac4k(uint64_t& lo, uint32_t& hi, uint32_t x0
     asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc\n\tv_mad_u64_u32 %0, vcc, %4, %5, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc\n\tv_mad_u64_u32 %0, vcc, %6, %7, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc\n\tv_mad_u64_u32 %0, vcc, %8, %9, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc"
         : "+v"(lo), "+v"(hi) : "v"(x0), "s"(k0), "v"(x1), "s"(k1), "v"(x2), "s"(k2), "v"(x3), "s"(k3) : "vcc");
 }
-// first product of a column: the shifted-in accumulator is < 2^37, no carry possible
+// first product of a column, without a carry instruction.  zk_mac_nc: onto an accumulator that is zero (column 0).
+// zk_mac_nck: m * k with the modulus limb k < 2^31 onto the shifted-in accumulator (< 2^37): below 2^63 + 2^37, no carry
 __device__ __forceinline__ void zk_mac_nc(uint64_t& lo, uint32_t x, uint32_t y) {
     asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(lo) : "v"(x), "v"(y) : "vcc");
+}
+__device__ __forceinline__ void zk_mac_nck(uint64_t& lo, uint32_t x, uint32_t k) {
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(lo) : "v"(x), "s"(k) : "vcc");
 }
 
 // sum_{i = I0}^{I1-1} a[i] * b[K - i]
@@ -339,9 +345,14 @@ __device__ __forceinline__ void zk_col_mp(uint64_t& lo, uint32_t& hi, const uint
 
 template <int K, class PRM>
 __device__ __forceinline__ void zk_fips_low(uint64_t& lo, uint32_t& hi, uint32_t (&m)[8], const Fe<PRM>& a, const Fe<PRM>& b) {
-    zk_mac_nc(lo, a.v[0], b.v[K]);
-    zk_col_ab<1, K + 1, K>(lo, hi, a, b);
-    zk_col_mp<0, K, K, PRM>(lo, hi, m);
+    static_assert(PRM::P[1] < 0x80000000u && PRM::P[7] < 0x80000000u, "the carry-free first product needs P[1], P[7] < 2^31");
+    if constexpr (K == 0) {
+        zk_mac_nc(lo, a.v[0], b.v[0]);  // lo = hi = 0 on entry
+    } else {
+        zk_mac_nck(lo, m[K - 1], PRM::P[1]);
+        zk_col_ab<0, K + 1, K>(lo, hi, a, b);
+        zk_col_mp<0, K - 1, K, PRM>(lo, hi, m);
+    }
     m[K] = (uint32_t)lo * PRM::INV;
     zk_mac1k(lo, hi, m[K], PRM::P[0]);
     lo = (lo >> 32) | ((uint64_t)hi << 32);
@@ -350,9 +361,9 @@ __device__ __forceinline__ void zk_fips_low(uint64_t& lo, uint32_t& hi, uint32_t
 template <int K, class PRM>
 __device__ __forceinline__ void zk_fips_high(uint64_t& lo, uint32_t& hi, const uint32_t (&m)[8], Fe<PRM>& r, const Fe<PRM>& a,
                                              const Fe<PRM>& b) {
-    zk_mac_nc(lo, a.v[K - 7], b.v[7]);
-    zk_col_ab<K - 6, 8, K>(lo, hi, a, b);
-    zk_col_mp<K - 7, 8, K, PRM>(lo, hi, m);
+    zk_mac_nck(lo, m[K - 7], PRM::P[7]);
+    zk_col_ab<K - 7, 8, K>(lo, hi, a, b);
+    zk_col_mp<K - 6, 8, K, PRM>(lo, hi, m);
     r.v[K - 8] = (uint32_t)lo;
     lo = (lo >> 32) | ((uint64_t)hi << 32);
     hi = 0;

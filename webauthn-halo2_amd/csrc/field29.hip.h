@@ -11,7 +11,7 @@
 // Representation ("internal form"): x is held as X = x * 2^261 mod p, as an integer in [0, k*p) for a
 // small k that the caller tracks ("lazy"), in limbs that are at most a little above 29 bits:
 //   mul29   limbs a_i * b_j < 2^60.6 (e.g. 2^30.6 x 2^30), value bounds k_a * k_b <= 168 (2^261 / p =
-//           169.4): result limbs < 2^29, value < 2p
+//           169.28): result limbs < 2^29, value < 2p
 //   add29   limb-wise;  sub29<K, E>  a + C - b with C = K*p spread so that every limb of C is >= 2^E:
 //           needs limbs b_i < 2^E, value b < K*p (and b's top limb <= (K-1)p's); result value < a + K*p
 //   norm29  carry propagation back to 29-bit limbs (value unchanged)
@@ -242,7 +242,7 @@ __device__ __forceinline__ void col_mp(uint64_t& acc, const uint32_t (&m)[9], in
     }
 }
 
-// a * b * 2^-261 mod p, lazily: result limbs < 2^29, value < p * (1 + k_a k_b / 169.4)
+// a * b * 2^-261 mod p, lazily: result limbs < 2^29, value < p * (1 + k_a k_b / 169.28)
 template <class PRM, bool SER = MUL29_SER>
 __device__ __forceinline__ Fe29<PRM> mul29(const Fe29<PRM>& a, const Fe29<PRM>& b) {
     uint32_t m[9];

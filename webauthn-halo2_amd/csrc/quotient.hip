@@ -33,7 +33,7 @@ typedef Fe29<FrParams> Fr29;
 // internal form, k = 1); the one product that leaves the row (by 1/(X^n - 1), or by 1) takes its constant in the STANDARD form,
 // which lands the result in the standard form.  227 instead of 318 instructions per product, 9 per addition instead of 33.
 // Bounds are written as (value < k p ; limb bits); a product needs limb products < 2^60.6 and gives limbs < 2^29 and
-// value < p (1 + k_a k_b / 169.4); sub29<K, 29>(a, b) needs b normalised and b < (K - 1) p.
+// value < p (1 + k_a k_b / 169.28); sub29<K, 29>(a, b) needs b normalised and b < (K - 1) p.
 __device__ __forceinline__ Fr29 q_load(const Fr* p) { return to29_x32(fe_load(p)); }  // (32 ; 29)
 
 // sum += term with term < 2p: the sum is kept normalised and is folded back below 2p every 32 terms (one product by "one")

@@ -558,6 +558,51 @@ int zk_timer_reset(zk_ctx* ctx);
 int zk_clock_probe(zk_ctx* ctx, uint32_t millis, uint64_t out[4]);
 int zk_timer_stats(zk_ctx* ctx, int which, double* total_ms, uint64_t* count);
 
+/* ---- stream placement ------------------------------------------------------
+ * The engine keeps, per device, a pool of 8 main and 32 side streams and hands a context its streams from it.  Which streams
+ * share a hardware queue decides whether four pipelines (and the streams of a lone proof) run side by side or queue behind
+ * each other (ZK_OPT_MSM_TAIL_STREAM above: 228 -> 190 proofs/s at k = 17 when main streams share queues).  The pool is made in
+ * an order that gives the wanted placement under the HIP runtime's rule for a process that made no stream before - a host
+ * that did (another GPU library, a tensor framework), another GPU_MAX_HW_QUEUES or another runtime release breaks the
+ * assumption silently.  zk_stream_placement MEASURES the placement: a stamp-and-spin kernel per stream finds the classes of
+ * streams that wait for each other (csrc/placement.h), about 30 ms on an idle device.  mode 0 reports; mode 1 also re-deals the
+ * pool from what it measured when the report is not ZK_PLACEMENT_OK and exactly four classes were seen (further streams are
+ * made when a class is short, 64 per device at most; no stream is ever destroyed).  With any other number of classes mode 1
+ * changes nothing: CALIBRATED stays clear.
+ * A host calls it once per device at start-up, BEFORE its first zk_ctx_create (it makes the pool itself), and logs the report.
+ * The engine sees THIS PROCESS only: streams of other processes on the GPU take part in the hardware's scheduling unseen, and
+ * work another process runs during the probe delays the probe's kernels and shows as an ambiguous round (UNRESOLVED).
+ * Errors (out untouched): ZK_EINVAL (device, out == NULL, mode), ZK_ENODEV, ZK_EHIP, ZK_ESTATE: a context of this process is
+ * active on the device (inside a whole-proof call, or enqueued an MSM pass within the last 4 ms) or, for mode 1, exists at all
+ * on a pooled slot.  A bad placement is a verdict - ZK_OK with flags clear -, not an error. */
+typedef struct {
+    uint32_t n_queues;          /* classes among the pool's streams; 0 = unresolved */
+    uint32_t flags;             /* ZK_PLACEMENT_* */
+    uint8_t  main_queue[8];     /* class of slot i's main stream (classes are numbered in order of first appearance) */
+    uint8_t  role_queue[8][3];  /* slot i's tail / transform / MSM stream */
+    uint8_t  spare_queue[8];    /* the fourth side stream of slot i's block, unused */
+    uint32_t rounds, streams;   /* rounds run, streams measured */
+    float    probe_ms;          /* host time of the whole call */
+} zk_placement;
+#define ZK_PLACEMENT_MAINS_OK   1u  /* slots 0..3: four main streams on four classes (four pipelines) */
+#define ZK_PLACEMENT_LONE_OK    2u  /* every slot: main, tail, transform, MSM stream on four classes (a lone proof) */
+#define ZK_PLACEMENT_PAIR_OK    4u  /* slots 0, 1: both mains and both tails on four classes (two pipelines) */
+#define ZK_PLACEMENT_LAYER1_OK  8u  /* slot 7 - i's main on slot i's class (the fifth context doubles up with the first) */
+#define ZK_PLACEMENT_OK        15u
+#define ZK_PLACEMENT_CALIBRATED 16u /* this call re-dealt the pool */
+#define ZK_PLACEMENT_UNRESOLVED 32u
+int zk_stream_placement(int device_id, int mode /* 0 probe, 1 probe + calibrate if not OK */, zk_placement* out);
+/* the streams of one context: its slot in the pool (-1: beyond the eight slots, streams of its own), the class of its main, tail,
+ * transform and MSM stream as the device's last zk_stream_placement measured them (255 = not measured yet), and four counts
+ * since the context was made: MSM passes whose tail ran on the main stream / on the tail stream, proofs that took the transform
+ * stream / the MSM stream */
+typedef struct {
+    int32_t  slot;
+    uint8_t  queue[4];
+    uint64_t counts[4];
+} zk_ctx_streams;
+int zk_ctx_stream_info(zk_ctx* ctx, zk_ctx_streams* out);
+
 #ifdef __cplusplus
 }
 #endif

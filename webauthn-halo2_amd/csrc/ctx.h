@@ -102,6 +102,8 @@ struct zk_ctx {
     hipEvent_t ev_rows = nullptr, ev_xform = nullptr;
     bool xform_pending = false;
     uint32_t opt_xform_stream = 0;  // ZK_OPT_XFORM_STREAM: 0 auto (side stream for a lone context), 1 side stream, 2 main stream
+    // zk_ctx_stream_info, since creation: MSM passes with the tail on the main / on the tail stream, proofs that took the transform / the MSM stream
+    uint64_t stream_counts[4] = {0, 0, 0, 0};
     // MSM lanes: each in-flight MSM owns a workspace and a pinned result buffer
     static constexpr int MSM_LANES = 3;
     struct MsmLane {

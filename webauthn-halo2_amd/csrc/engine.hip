@@ -9,8 +9,11 @@
 #include <new>
 
 #include "ctx.h"
+#include "placement.h"
 
 namespace zk {
+// placement.hip
+placement::Classes placement_probe(const hipStream_t* streams, int n, placement::Stamp* stamps);
 // poly.hip
 uint32_t eval_blocks(uint32_t n);
 void launch_eval(const Fr* c, uint32_t n, const Fr& x, Fr* scratch, hipStream_t st);
@@ -213,14 +216,22 @@ static int get_msm_ws(zk_ctx* c, int lane, size_t n, uint32_t table_window, MsmW
 // its transform and MSM streams on the other two.  zk_ctx_destroy drains the slot's streams and frees the slot for the next
 // context; contexts beyond the eight slots (and a main stream made at its own priority, ZK_OPT_STREAM_PRIORITY) make their streams as
 // before and destroy them.  The pool is never freed (40 idle streams per device for the life of the process).  If another runtime
-// assigns queues differently nothing breaks: this is placement, not correctness.
+// assigns queues differently nothing breaks: this is placement, not correctness.  zk_stream_placement (below) measures which
+// streams really share a queue and, asked to, deals the slots again from what it measured.
 namespace {
-constexpr int POOL_SLOTS = 8;  // two layers of four: slots 4 .. 7 repeat the pattern (their main streams land on queues 3 .. 0)
+constexpr int POOL_SLOTS = placement::POOL_SLOTS;  // two layers of four: slots 4 .. 7 repeat the pattern (their main streams land on queues 3 .. 0)
 struct StreamSlots {
     bool primed = false;
     hipStream_t main[POOL_SLOTS] = {};
     hipStream_t side[POOL_SLOTS][4] = {};  // [slot][j]: block `slot`, j-th made: queue 3 - j
     bool used[POOL_SLOTS] = {};
+    // zk_stream_placement: streams a calibration left over or made beyond its need (never destroyed), the pinned stamps of the
+    // probe, and the class of every stream as last measured
+    bool made = false;  // all forty streams exist
+    hipStream_t parked[placement::MAX_STREAMS] = {};
+    int n_parked = 0;
+    placement::Stamp* stamps = nullptr;
+    std::map<hipStream_t, uint8_t> cls;
 };
 struct StreamPool {
     std::mutex mu;
@@ -232,25 +243,29 @@ StreamPool& stream_pool() {
 }
 // the hardware queue of slot s's main stream under the runtime's rule (first four streams: a queue each; then the least loaded
 // queue, ties to the highest): layer 0 = queues 0 .. 3, layer 1 (made after layer 0's side blocks) = queues 3 .. 0
-constexpr int slot_main_queue(int s) { return s < 4 ? s : 7 - s; }
+using placement::slot_main_queue;
+// makes the device's streams on first use (current device = the pool's; the pool's mutex is held)
+void pool_prime(StreamSlots& d) {
+    if (d.primed) return;
+    d.primed = true;
+    bool ok = true;
+    for (int layer = 0; layer < POOL_SLOTS / 4 && ok; layer++) {
+        for (int i = 4 * layer; i < 4 * layer + 4 && ok; i++) ok = hipStreamCreate(&d.main[i]) == hipSuccess;
+        for (int i = 4 * layer; i < 4 * layer + 4 && ok; i++)
+            for (int j = 0; j < 4 && ok; j++) ok = hipStreamCreate(&d.side[i][j]) == hipSuccess;
+    }
+    d.made = ok;
+    if (!ok) {  // (out of resources: no slots on this device, contexts make their own streams)
+        for (int i = 0; i < POOL_SLOTS; i++) d.used[i] = true;
+    }
+}
 }  // namespace
 // a free slot of the device (current device = `device`), or -1: the caller makes its own streams
 static int pool_take_slot(int device, hipStream_t* main_out) {
     StreamPool& p = stream_pool();
     std::lock_guard<std::mutex> lk(p.mu);
     StreamSlots& d = p.dev[device];
-    if (!d.primed) {
-        d.primed = true;
-        bool ok = true;
-        for (int layer = 0; layer < POOL_SLOTS / 4 && ok; layer++) {
-            for (int i = 4 * layer; i < 4 * layer + 4 && ok; i++) ok = hipStreamCreate(&d.main[i]) == hipSuccess;
-            for (int i = 4 * layer; i < 4 * layer + 4 && ok; i++)
-                for (int j = 0; j < 4 && ok; j++) ok = hipStreamCreate(&d.side[i][j]) == hipSuccess;
-        }
-        if (!ok) {  // (out of resources: no slots on this device, contexts make their own streams)
-            for (int i = 0; i < POOL_SLOTS; i++) d.used[i] = true;
-        }
-    }
+    pool_prime(d);
     // layer 1 is handed out from the top: slot 7's main stream shares queue 0 with slot 0's, so the fifth context doubles up with the
     // FIRST one (the oldest, most likely idle: a set-up or probe context) rather than with the fourth
     static const int order[POOL_SLOTS] = {0, 1, 2, 3, 7, 6, 5, 4};
@@ -276,14 +291,12 @@ static void pool_release_slot(int device, int slot) {
 int ctx_side_stream(zk_ctx* c, hipStream_t* out, int role) {
     if (*out) return ZK_OK;
     if (c->stream_slot >= 0) {
-        const int i = c->stream_slot, mq = slot_main_queue(i);
-        int js[3], m = 0;
-        js[m++] = mq;  // side j sits on queue 3 - j: the tail takes the queue opposite the main's (3 - mq, never mq itself)
-        for (int j = 0; j < 4; j++)
-            if (j != mq && j != 3 - mq) js[m++] = j;  // (j = 3 - mq sits on the main's queue: the block's spare)
+        // side j sits on queue 3 - j: the tail takes the queue opposite the main's, never the main's own, whose side stream is
+        // the block's spare (placement.h role_side)
+        const int i = c->stream_slot;
         StreamPool& p = stream_pool();
         std::lock_guard<std::mutex> lk(p.mu);
-        *out = p.dev[c->device].side[i][js[role]];
+        *out = p.dev[c->device].side[i][placement::role_side(i, role)];
         return ZK_OK;
     }
     return hipStreamCreate(out) == hipSuccess ? ZK_OK : ZK_EHIP;
@@ -333,20 +346,24 @@ void ctx_activity_unregister(zk_ctx* c) {
     g_act_used[c->device].fetch_and(~(1ull << c->act_slot));
     c->act_slot = -1;
 }
+// registered contexts active on a device at `now`: held, or stamped within the window
+static int activity_count(int device, int64_t now) {
+    int active = 0;
+    uint64_t used = g_act_used[device].load();
+    while (used) {
+        const int slot = __builtin_ctzll(used);
+        used &= used - 1;
+        const int64_t ts = g_act_ts[device][slot].load();
+        if (ts && (ts == ACT_HELD || now - ts < ACT_WINDOW_NS)) active++;
+    }
+    return active;
+}
 // stamps this context and returns the number of contexts (this one included) active on its device
 int ctx_activity_touch(zk_ctx* c) {
     if (c->device < 0 || c->device >= ACT_DEVICES) return 1;
     const int64_t now = act_now();
     if (c->act_slot >= 0 && !c->act_held) g_act_ts[c->device][c->act_slot].store(now);
-    int active = c->act_slot >= 0 ? 0 : 1;
-    uint64_t used = g_act_used[c->device].load();
-    while (used) {
-        const int slot = __builtin_ctzll(used);
-        used &= used - 1;
-        const int64_t ts = g_act_ts[c->device][slot].load();
-        if (ts && (ts == ACT_HELD || now - ts < ACT_WINDOW_NS)) active++;
-    }
-    return active;
+    return (c->act_slot >= 0 ? 0 : 1) + activity_count(c->device, now);
 }
 // a whole-proof call begins / ends on this context (prover.hip ProveQuiesce)
 void ctx_activity_hold(zk_ctx* c, bool on) {
@@ -392,6 +409,7 @@ int ctx_msm_begin_batch(zk_ctx* c, int lane, const Fr* const* d_scalars, uint32_
         HIPCHK(c, aud_wait(c, hs, c->ev_msm_in));
         if (L.tail == c->stream) L.tail = c->tail_stream;    // (never a tail behind the main stream's later kernels)
     }
+    c->stream_counts[L.tail == c->stream ? 0 : 1]++;  // zk_ctx_stream_info
     HIPCHK(c, aud_record(c, L.t_head[0], hs));
     msm_ws_set_t1_mode(ws, c->opt_msm_t1);
     HIPCHK(c, msm_run(ws, d_scalars, batch, d_bases, n, hs, L.host_buf, &L.nwin, &L.cw, L.t_acc, table, stride, L.tail,
@@ -516,6 +534,110 @@ ZK_API(zk_device_mem_info, (int device_id, size_t* free_bytes, size_t* total_byt
     const hipError_t e = hipMemGetInfo(free_bytes, total_bytes);
     hipSetDevice(prev);
     return e == hipSuccess ? ZK_OK : ZK_EHIP;
+}
+
+// ---- zk_stream_placement: which hardware queue each pool stream sits on, measured (placement.h / placement.hip), and on
+// request the pool dealt again from the measurement.  The whole call holds the pool's mutex: no context is made, destroyed or
+// given a side stream meanwhile.  PROCESS-LOCAL like the activity table: work of other processes on the GPU is not seen.
+namespace {
+// every stream of the device in the probe's index order: main[0 .. 8), side[0 .. 8)[0 .. 4), parked
+int pool_list(const StreamSlots& d, hipStream_t* list) {
+    int n = 0;
+    for (int i = 0; i < POOL_SLOTS; i++) list[n++] = d.main[i];
+    for (int i = 0; i < POOL_SLOTS; i++)
+        for (int j = 0; j < 4; j++) list[n++] = d.side[i][j];
+    for (int i = 0; i < d.n_parked; i++) list[n++] = d.parked[i];
+    return n;
+}
+placement::Classes pool_measure(StreamSlots& d, zk_placement* rep) {
+    hipStream_t list[placement::MAX_STREAMS];
+    const int n = pool_list(d, list);
+    const placement::Classes c = placement_probe(list, n, d.stamps);
+    d.cls.clear();
+    if (!c.unresolved)
+        for (int i = 0; i < n; i++) d.cls[list[i]] = c.cls[i];
+    const uint32_t rounds = rep->rounds + c.rounds;
+    placement::report(c, rep);
+    rep->rounds = rounds;
+    rep->streams = (uint32_t)n;
+    return c;
+}
+int placement_run(int device, int mode, zk_placement* rep) {
+    const auto h0 = std::chrono::steady_clock::now();
+    StreamPool& p = stream_pool();
+    std::lock_guard<std::mutex> lk(p.mu);
+    if (device < ACT_DEVICES && activity_count(device, act_now()) > 0) return ZK_ESTATE;
+    StreamSlots& d = p.dev[device];
+    if (mode == 1 && d.made)
+        for (int i = 0; i < POOL_SLOTS; i++)
+            if (d.used[i]) return ZK_ESTATE;
+    pool_prime(d);
+    if (!d.made) return ZK_EHIP;  // (the device gave no forty streams: there is no pool to place)
+    if (!d.stamps && hipHostMalloc(&d.stamps, placement::MAX_STREAMS * sizeof(placement::Stamp)) != hipSuccess) return ZK_EHIP;
+    memset(rep, 0, sizeof(*rep));
+    placement::Classes c = pool_measure(d, rep);
+    if (c.error) return ZK_EHIP;
+    bool calibrated = false;
+    while (mode == 1 && !calibrated && !c.unresolved && c.n_classes == 4 && (rep->flags & ZK_PLACEMENT_OK) != ZK_PLACEMENT_OK) {
+        const placement::Deal dl = placement::deal(c);
+        if (dl.dealt) {
+            hipStream_t list[placement::MAX_STREAMS];
+            pool_list(d, list);
+            for (int i = 0; i < POOL_SLOTS; i++) {
+                d.main[i] = list[dl.main[i]];
+                for (int j = 0; j < 4; j++) d.side[i][j] = list[dl.side[i][j]];
+            }
+            for (int i = 0; i < dl.n_parked; i++) d.parked[i] = list[dl.parked[i]];
+            d.n_parked = dl.n_parked;
+            calibrated = true;
+        } else {
+            // a class is short: further streams, wherever the runtime puts them, measured with the rest — at least four at a
+            // time: a runtime that balances its queues fills the short ones within one turn
+            const int make = std::min(std::max(dl.need_more, 4), placement::MAX_STREAMS - c.n);
+            if (make <= 0) break;
+            for (int i = 0; i < make; i++)
+                if (hipStreamCreate(&d.parked[d.n_parked]) == hipSuccess) d.n_parked++;
+                else return ZK_EHIP;
+        }
+        c = pool_measure(d, rep);  // the streams in their new places (or with the new ones)
+        if (c.error) return ZK_EHIP;
+    }
+    if (calibrated) rep->flags |= ZK_PLACEMENT_CALIBRATED;
+    rep->probe_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - h0).count();
+    return ZK_OK;
+}
+}  // namespace
+
+ZK_API(zk_stream_placement, (int device_id, int mode, zk_placement* out), (device_id, mode, out)) {
+    if (!out || (mode != 0 && mode != 1)) return ZK_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ZK_ENODEV;
+    if (device_id < 0 || device_id >= ndev) return ZK_EINVAL;
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device_id) != hipSuccess) return ZK_EHIP;
+    zk_placement rep;
+    const int rc = placement_run(device_id, mode, &rep);
+    hipSetDevice(prev);
+    if (rc == ZK_OK) *out = rep;
+    return rc;
+}
+
+ZK_API(zk_ctx_stream_info, (zk_ctx* c, zk_ctx_streams* out), (c, out)) {
+    if (!c || !out) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s[4] = {c->stream, c->tail_stream, c->xform_stream, c->msm_stream};
+    StreamPool& p = stream_pool();
+    std::lock_guard<std::mutex> lp(p.mu);
+    const StreamSlots& d = p.dev[c->device];
+    out->slot = c->stream_slot;
+    for (int q = 0; q < 4; q++) {
+        // a side stream the context has not asked for yet: the one its slot holds for that role
+        if (!s[q] && q > 0 && c->stream_slot >= 0) s[q] = d.side[c->stream_slot][placement::role_side(c->stream_slot, q - 1)];
+        const auto it = d.cls.find(s[q]);
+        out->queue[q] = it == d.cls.end() ? placement::UNKNOWN : it->second;
+        out->counts[q] = c->stream_counts[q];
+    }
+    return ZK_OK;
 }
 
 // page-locked host memory for the buffers a host hands to zk_poly_upload*: the copy is then one DMA at the bus rate instead of

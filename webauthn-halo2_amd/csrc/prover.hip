@@ -1205,6 +1205,8 @@ struct Prover {
         // (tools/single_ab.py OPTS=9=1 / 9=2, four alternations on one box): 11.40-11.55 -> 11.29-11.38 ms, same bytes
         c->msm_side = !batch_member && (c->opt_msm_stream == 1 || (c->opt_msm_stream == 0 && xside && c->opt_xform_stream == 0));
         if ((xside || c->msm_side || c->audit_fault) && (rc = ctx_lone_streams(c))) return rc;
+        c->stream_counts[2] += xside;  // zk_ctx_stream_info
+        c->stream_counts[3] += c->msm_side;
         if ((rc = ctx_get_twiddles(c, lay.k, &tw)) || (rc = ctx_get_twiddles(c, lay.ext_k, &tw_ext))) return rc;
         // auto: columns of 2^16 rows or more (measured, tools/r6_cosets3_ab.sh: k = 18 / 17 / 16 - 1 / - 3 / - 3 %, k = 17 EVM over four
         // pipelines 196 -> 203 proofs/s; the many-column rows lose — three vectors per column fill the transforms' launches three

@@ -33,13 +33,14 @@ import hashlib
 import os
 import queue
 import threading
+import time
 
 import numpy as np
 
 from . import circuit
 from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_SRS_CONTRIB_LINKS,
                      ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT, ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
-                     ZK_TRANSCRIPT_EVM, Engine)
+                     ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -335,6 +336,41 @@ def shutdown(device=None):
                 m["eng"].close()
             if st["eng"] is not None:
                 st["eng"].close()
+
+
+class PlacementError(ValueError):
+    """The streams of a device's pool do not sit on the hardware queues the engine deals them for (check_placement,
+    proving_server.setup(check_placement=True)): `report` is what engine.stream_placement measured.  Proofs are right either
+    way; four pipelines are slower."""
+
+    def __init__(self, report):
+        self.report = report
+        super().__init__(f"stream placement not as assumed: {report['n_queues']} queue classes, flags {report['flags']:#x}, "
+                         f"main streams on {report['main_queue']}")
+
+
+def check_placement(device=0, calibrate=True):
+    """engine.stream_placement of `device`, once at start-up: returns the report when all four invariants hold, raises
+    PlacementError otherwise.  calibrate=True lets the engine re-deal its pool first - only while the device has no resident
+    engine of this module yet (a pool in use is measured, never re-dealt: the device's pipelines are held meanwhile, and the
+    4 ms for which the engine still counts the last request's context as active are waited out)."""
+    with _STATE_LOCK:
+        st = _STATE.get(device)
+        if not (st and st["eng"] is not None):
+            report = stream_placement(device, calibrate)
+        else:
+            with _Hold(st):
+                for attempt in range(8):
+                    try:
+                        report = stream_placement(device, False)
+                        break
+                    except ZkError as e:
+                        if e.code != -5 or attempt == 7:  # ZK_ESTATE: a context enqueued an MSM pass within the last 4 ms
+                            raise
+                        time.sleep(0.004)
+    if not report["ok"]:
+        raise PlacementError(report)
+    return report
 
 
 def _pipeline(st, i):

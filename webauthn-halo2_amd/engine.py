@@ -32,6 +32,8 @@ ZK_PK_FIXED_POLY, ZK_PK_SIGMA_POLY = 0, 1
 (ZK_PK_PART_FIXED_COMMIT, ZK_PK_PART_SIGMA_COMMIT, ZK_PK_PART_FIXED_POLY, ZK_PK_PART_SIGMA_POLY, ZK_PK_PART_FIXED_COSET,
  ZK_PK_PART_SIGMA_COSET, ZK_PK_PART_L_COSET, ZK_PK_PART_SIGMA_LABEL, ZK_PK_PART_SIGMA_MAP) = range(1, 10)
 ZK_PK_CHECK_COMMITMENTS, ZK_PK_CHECK_POLYS, ZK_PK_CHECK_COSETS, ZK_PK_CHECK_SIGMA, ZK_PK_CHECK_ALL, ZK_PK_CHECK_REPR = 1, 2, 4, 8, 15, 16
+ZK_PLACEMENT_MAINS_OK, ZK_PLACEMENT_LONE_OK, ZK_PLACEMENT_PAIR_OK, ZK_PLACEMENT_LAYER1_OK, ZK_PLACEMENT_OK = 1, 2, 4, 8, 15
+ZK_PLACEMENT_CALIBRATED, ZK_PLACEMENT_UNRESOLVED = 16, 32
 
 
 def device_pci_bus_id(device=0):
@@ -50,6 +52,25 @@ def device_mem_info(device=0):
     if rc:
         raise ZkError(rc, "zk_device_mem_info")
     return free.value, total.value
+
+
+def stream_placement(device=0, calibrate=False) -> dict:
+    """Which hardware queue each stream of the device's pool sits on, measured (zk_stream_placement; ~30 ms on an idle device).
+    calibrate=True re-deals the pool from the measurement when it is not as the engine assumes and four classes were seen
+    (only while no Engine of this process exists on the device).  Returns the report: n_queues (0 = unresolved), flags, the
+    ZK_PLACEMENT_* bits by name, main_queue[8], role_queue[8][3] (tail, transform, MSM), spare_queue[8], rounds, streams,
+    probe_ms.  ok = all four invariants hold.  A host calls it once per device at start-up, before its first Engine, and logs it."""
+    r = PlacementC()
+    rc = load_library().zk_stream_placement(device, 1 if calibrate else 0, ctypes.byref(r))
+    if rc:
+        raise ZkError(rc, "zk_stream_placement")
+    f = r.flags
+    return {"n_queues": r.n_queues, "flags": f, "ok": f & ZK_PLACEMENT_OK == ZK_PLACEMENT_OK,
+            "mains_ok": bool(f & ZK_PLACEMENT_MAINS_OK), "lone_ok": bool(f & ZK_PLACEMENT_LONE_OK),
+            "pair_ok": bool(f & ZK_PLACEMENT_PAIR_OK), "layer1_ok": bool(f & ZK_PLACEMENT_LAYER1_OK),
+            "calibrated": bool(f & ZK_PLACEMENT_CALIBRATED), "unresolved": bool(f & ZK_PLACEMENT_UNRESOLVED),
+            "main_queue": list(r.main_queue), "role_queue": [list(row) for row in r.role_queue], "spare_queue": list(r.spare_queue),
+            "rounds": r.rounds, "streams": r.streams, "probe_ms": r.probe_ms}
 
 
 class PinnedArray:
@@ -96,6 +117,16 @@ class PkFindingC(ctypes.Structure):
 class SrsContributionC(ctypes.Structure):
     _fields_ = [("before_g1", ctypes.c_uint64 * 8), ("after_g1", ctypes.c_uint64 * 8), ("s_g1", ctypes.c_uint64 * 8),
                 ("s_g2", ctypes.c_uint64 * 16)]
+
+
+class PlacementC(ctypes.Structure):
+    _fields_ = [("n_queues", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("main_queue", ctypes.c_uint8 * 8),
+                ("role_queue", (ctypes.c_uint8 * 3) * 8), ("spare_queue", ctypes.c_uint8 * 8), ("rounds", ctypes.c_uint32),
+                ("streams", ctypes.c_uint32), ("probe_ms", ctypes.c_float)]
+
+
+class CtxStreamsC(ctypes.Structure):
+    _fields_ = [("slot", ctypes.c_int32), ("queue", ctypes.c_uint8 * 4), ("counts", ctypes.c_uint64 * 4)]
 
 
 class ZkError(RuntimeError):
@@ -212,11 +243,13 @@ def load_library():
         "zk_witness_check": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(WitnessFailureC), sz,
                               ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
         "zk_pk_check": ([vp, ctypes.c_uint64, ctypes.POINTER(u32), ctypes.POINTER(PkFindingC), sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_stream_placement": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(PlacementC)], ctypes.c_int),
+        "zk_ctx_stream_info": ([vp, ctypes.POINTER(CtxStreamsC)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name, None)
         if fn is None:
-            if name in ("zk_witness_check", "zk_pk_check") and os.environ.get("ZKMI355_LIB"):
+            if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -765,6 +798,14 @@ class Engine:
         msg = ctypes.create_string_buffer(600)
         self._chk(self.L.zk_audit_report(self.ctx, counts, msg, len(msg)), "zk_audit_report")
         return int(counts[0]), int(counts[1]), msg.value.decode(errors="replace")
+
+    def stream_info(self):
+        """This context's streams (zk_ctx_stream_info): its slot in the device's pool (-1: its own streams), the class of its
+        main / tail / transform / MSM stream as stream_placement last measured them (255: not measured yet), and four counts
+        since creation: MSM passes with the tail on the main / on the tail stream, proofs that took the transform / the MSM stream."""
+        r = CtxStreamsC()
+        self._chk(self.L.zk_ctx_stream_info(self.ctx, ctypes.byref(r)), "zk_ctx_stream_info")
+        return {"slot": r.slot, "queue": list(r.queue), "counts": list(r.counts)}
 
     def clock_probe(self, millis=100):
         """(shader-clock ticks, 100 MHz ticks, dependent multiply-adds issued) over ~`millis` ms of one spinning wave (zk_clock_probe)."""

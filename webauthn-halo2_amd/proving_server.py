@@ -50,7 +50,8 @@ def parse_request(body):
     return out
 
 
-def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None, params_path=None, check_keys=False):
+def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None, params_path=None, check_keys=False,
+          check_placement=False):
     """POST /setup (and the server's start-up keygen, main.rs:451-456).  The proving key stays resident on
     `device`, registered under `proving_key_path` (the name later requests carry); the verifying key is
     written only when a path is given (the reference writes ./keys/verifying_key.vk).  `params_path`: a trusted-setup
@@ -58,11 +59,15 @@ def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", ver
     the device's current source (the seed-0 setup unless one was set).  The seed-0 setup's secret is public — anybody can forge
     proofs under it —, so a deployment passes a ceremony file, or one with its own secret multiplied in
     (ecdsa_p256.contribute_params writes such a file, check_contributions checks its receipts).  check_keys=True: download_keys(check=True) - the key is
-    audited (ecdsa_p256.ProvingKeyError names the part, column and index of a key that is not what keygen makes)."""
+    audited (ecdsa_p256.ProvingKeyError names the part, column and index of a key that is not what keygen makes).
+    check_placement=True: before anything is made resident the device's stream placement is measured
+    (ecdsa_p256.check_placement: re-dealt if need be while the device has no engine yet, measured only when it has) and
+    ecdsa_p256.PlacementError raised if the pipelines would share hardware queues; the report is returned instead of "Done"."""
+    report = ecdsa_p256.check_placement(device, calibrate=True) if check_placement else None
     if params_path is not None:
         ecdsa_p256.set_params_file(params_path, device)
     ecdsa_p256.download_keys(degree, proving_key_path, verifying_key_path, device, check=check_keys)
-    return "Done"
+    return report if check_placement else "Done"
 
 
 def _prove(body, evm, device, degree, rng_seed, check=False):

@@ -1,4 +1,4 @@
-"""zk_prove_batch (lock-step proving of B independent proofs on one context, csrc/prover_batch.h): every proof of a batch is
+"""zk_prove_batch (lock-step proving of B independent proofs on one context: csrc/prover_batch.h drives the steps of csrc/prover_steps.h): every proof of a batch is
 byte-identical to the oracle's create_proof — and therefore to zk_prove — for the same witness and ChaCha20 stream, for every
 column shape the engine branches on, both transcripts / multi-open schemes, batch sizes that fill a pass, overflow it, and
 leave a remainder; at BASELINE's size the batch's proofs equal the committed digests of configs[3]."""
@@ -113,6 +113,30 @@ def test_more_lookups_than_one_permutation_launch_takes():
     with pytest.raises(zk.ZkError) as e:  # 7 x 37 grand products: beyond the one-workgroup chain scan
         eng.prove_batch(pk, sets + sets[:2], rng_seeds + rng_seeds[:2])
     assert e.value.code == -1
+    eng.close()
+
+
+@pytest.mark.parametrize("name,B", [("k17like", 3), ("manycols", 2)])
+def test_batch_grand_product_fallback_returns_the_same_bytes(name, B):
+    """ZK_OPT_GP_BATCH_INVERT = 1 sends every grand product of the batch down halo2's batch_invert form (launch_frac +
+    launch_prefix_product, product by product: the ONE fallback of csrc/prover_steps.h grand_products, shared by zk_prove,
+    zk_prove_batch and the phase calls): the batch returns the bytes of option 0 and of zk_prove.  k17like: three chained
+    permutation chunks per proof; manycols: 37 products per proof, chunk and lookup arguments staged in device memory."""
+    eng = zk.Engine(0)
+    pk, sets, asgs, opk = _setup(eng, SHAPES[name], [0x5EED0400 + i for i in range(B)])
+    rng_seeds = [bytes([40 + i]) * 32 for i in range(B)]
+    tr = E.ZK_TRANSCRIPT_EVM
+    want = eng.prove_batch(pk, sets, rng_seeds, tr)
+    single = [eng.prove(pk, sets[j], rng_seeds[j], tr) for j in range(B)]
+    assert want == single
+    try:
+        eng.set_option(E.ZK_OPT_GP_BATCH_INVERT, 1)
+        got = eng.prove_batch(pk, sets, rng_seeds, tr)
+        got_single = [eng.prove(pk, sets[j], rng_seeds[j], tr) for j in range(B)]
+    finally:
+        eng.set_option(E.ZK_OPT_GP_BATCH_INVERT, 0)
+    assert got == want and got_single == single
+    assert eng.prove_batch(pk, sets, rng_seeds, tr) == want  # (the option is off again)
     eng.close()
 
 

@@ -102,3 +102,24 @@ def test_stream_audit_ledger_logic(tmp_path):
                            os.path.join(ROOT, "tests", "audit_logic_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and "audit logic: 0 failures" in out.stdout, out.stdout + out.stderr
+
+
+def test_fr_batch_invert_host_check(tmp_path):
+    """fr_batch_invert (csrc/prover_steps.h), host only: counts 0, 1, 2 and 257; every inverse equals fe_inv_fast of its element;
+    inputs 1 and r - 1; a zero at the first, a middle and the last index is refused and nothing is written outside the scratch.
+    Built twice — plain, and with the host side under AddressSanitizer / UBSan — and run as a program of its own."""
+    import os
+    import shutil
+    import subprocess
+
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if shutil.which("hipcc") is None:
+        import pytest
+
+        pytest.skip("hipcc not on PATH")
+    for tag, extra in (("plain", []), ("san", ["-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"])):
+        exe = str(tmp_path / ("fr_batch_invert_check_" + tag))
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-value", *extra, "-x", "hip", "-I",
+                               os.path.join(ROOT, "webauthn-halo2_amd", "csrc"), os.path.join(ROOT, "tests", "fr_batch_invert_check.cpp"), "-o", exe])
+        out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+        assert out.returncode == 0 and "fr_batch_invert: 0 failures" in out.stdout, tag + ": " + out.stdout + out.stderr

@@ -1,4 +1,4 @@
-// ctx.h — the engine context shared by engine.hip (C-ABI) and prover.hip.
+// ctx.h — the engine context shared by engine.hip (C-ABI) and the prover units (prover.hip, prover_key.hip, prover_phases.hip).
 #pragma once
 #include <map>
 #include <memory>

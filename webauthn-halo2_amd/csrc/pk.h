@@ -1,5 +1,6 @@
-// pk.h — the resident proving key record shared by prover.hip (keygen / create_proof) and serde.hip
-// (ProvingKey / VerifyingKey read & write).  Not part of the public C-ABI.
+// pk.h — the resident proving key record shared by prover_key.hip (keygen, workspace, quotient), prover.hip (create_proof),
+// prover_phases.hip (the phase-level entry points) and serde.hip (ProvingKey / VerifyingKey read & write).  Not part of the
+// public C-ABI.
 #pragma once
 #include <utility>
 #include <vector>
@@ -201,6 +202,7 @@ struct QuotientCosets {
 // the key's extended cosets (fixed, sigma, l_0, l_last, l_active) once more in the [3][n] coset-major order of the three-coset
 // route: made on the first proof that takes it (keygen and zk_pk_read both end up here), kept with the key
 int pk_ensure_cosets3(zk_ctx* c, zk_pk_rec* pk);
+Fr fr_delta();  // 7^(2^28): generator of the odd-order subgroup (the permutation argument's coset shifts)
 int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out);
 void pk_destroy(zk_pk_rec* pk);
 // the per-proof workspace (advice / z / lookup forms, quotient buffer, scan and evaluation scratch): everything a key

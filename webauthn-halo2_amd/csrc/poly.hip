@@ -173,7 +173,7 @@ void launch_eval_batch(EvalItem* h_items, EvalItem* d_items, uint32_t count, uin
 // A circuit whose quotient has THREE pieces (degree 4: every bench_ecdsa.config row with two or more advice columns, the proving
 // server's k = 17 among them) has deg h < 3n, so h is determined by its values on three of the four cosets
 // g_j H, g_j = zeta w_4n^j, that make up halo2's extended domain (EvaluationDomain::extended_k = k + 2: a power of two, one coset
-// more than the degree needs).  The prover's private path (prover.hip, Prover::transforms / quotient) therefore works on
+// more than the degree needs).  The prover's private path (prover.hip Prover::transforms, prover_key.hip pk_quotient) therefore works on
 // [3][n] "coset-major" vectors — v[j n + i] = f(g_j w_n^i), j < 3 — made by three n-point transforms of the coefficients twisted by
 // g_j^m, evaluates the quotient numerator on those 3n rows, and recovers the pieces from three n-point inverse transforms:
 // with c_j = g_j^n = z i^j (z = zeta^n, i = w_4n^n) the interpolant of coset j is r_j = h0 + c_j h1 + c_j^2 h2 coefficient by

@@ -1,5 +1,5 @@
-// prover.h — internal declarations of the device prover (prover_kernels.hip,
-// quotient.hip, prover.hip).  Not part of the public C-ABI.
+// prover.h — internal declarations of the device prover (prover_kernels.hip, quotient.hip; called from prover_steps.h,
+// prover.hip, prover_key.hip, prover_phases.hip).  Not part of the public C-ABI.
 #pragma once
 #include "engine.h"
 

@@ -1,9 +1,10 @@
-// prover.hip — keygen and create_proof on the device-resident engine.
+// prover.hip — create_proof on the device-resident engine: the single prover (Prover::run), the lock-step prover of several
+// proofs (prover_batch.h) and their entry points.  Keygen and the key's workspace are prover_key.hip, the phase-level entry
+// points prover_phases.hip; the steps the three share are prover_steps.h — the two drivers here hold the scheduling only: which
+// step, in which order, on which lane, and when a lane is collected.
 //
 // Host orchestration (C++) of the kernels in msm.hip / ntt.hip / quotient.hip /
-// prover_kernels.hip / poly.hip, mirroring halo2_proofs `plonk::keygen_vk`,
-// `keygen_pk` and `plonk::create_proof` as the reference calls them:
-//   keygen        halo2-circuits/src/ecc/ecdsa_p256.rs:259-260
+// prover_kernels.hip / poly.hip, mirroring halo2_proofs `plonk::create_proof` as the reference calls it:
 //   create_proof  halo2-circuits/src/ecc/ecdsa_p256.rs:366-373 (EvmTranscript + ProverGWC)
 //                 halo2-circuits/src/ecc/ecdsa_p256.rs:416-423 (Blake2bWrite + ProverSHPLONK)
 // Phase structure, transcript order and RNG draw order: SURVEY.md §3.3 / App. A.3
@@ -22,9 +23,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "pk.h"
-#include "transcript.h"
-#include "vkrepr.h"
+#include "prover_steps.h"
 
 using namespace zk;
 
@@ -45,49 +44,11 @@ static std::chrono::steady_clock::time_point& ht_last() {
 #define HT(name) do { } while (0)
 #endif
 
+// ==================================================================== prove ==
+
 namespace {
 
-// ---------------------------------------------------------------- kernels ---
-__global__ void sigma_kernel(const uint2* __restrict__ map, const Fr* __restrict__ tw, const Fr* __restrict__ dpow,
-                             Fr* __restrict__ out, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint2 m = map[i];
-    fe_store(out + i, fe_mul(fe_load(dpow + m.x), fe_load(tw + m.y)));
-}
-
-// ------------------------------------------------------------ small utils ---
-bool commit(zk_ctx* c, const Fr* poly, size_t len, int basis, G1Affine* out) {
-    G1Jac j;
-    if (ctx_msm_device(c, poly, basis == ZK_BASIS_LAGRANGE ? c->g_lagrange : c->g, len, &j) != ZK_OK) return false;
-    *out = g1_jac_to_affine_host(j);
-    return true;
-}
-
 Fr fr_pow(Fr a, uint64_t e) { return fe_pow_u64(a, e); }
-
-Fr fr_delta() {  // 7^(2^28): generator of the odd-order subgroup
-    static const Fr delta = [] {
-        Fr d = fr_from_u64(7);
-        for (int i = 0; i < 28; i++) d = fe_sqr(d);
-        return d;
-    }();
-    return delta;
-}
-
-void fr_to_le_bytes(const Fr& mont, uint8_t out[32]) {
-    const Fr c = fe_from_mont(mont);
-    memcpy(out, c.v, 32);
-}
-
-// Integer order of canonical values (halo2curves Fr: Ord)
-bool fr_less(const Fr& a_mont, const Fr& b_mont) {
-    const Fr a = fe_from_mont(a_mont), b = fe_from_mont(b_mont);
-    for (int i = 7; i >= 0; i--) {
-        if (a.v[i] != b.v[i]) return a.v[i] < b.v[i];
-    }
-    return false;
-}
 
 // The Lagrange basis over `pts` as coefficient vectors: basis[j] = L_j(X) = prod_{i != j} (X - pts_i) / (pts_j - pts_i).  A
 // rotation set's commitments share their points, so this is paid once per set — with ONE field inversion for all the
@@ -96,7 +57,7 @@ bool fr_less(const Fr& a_mont, const Fr& b_mont) {
 std::vector<std::vector<Fr>> lagrange_basis(const std::vector<Fr>& pts) {
     const size_t m = pts.size();
     std::vector<std::vector<Fr>> basis(m);
-    std::vector<Fr> den(m, Fr::one()), pre(m);
+    std::vector<Fr> den(m, Fr::one()), inv(m);
     for (size_t j = 0; j < m; j++) {
         std::vector<Fr> num(1, Fr::one());
         for (size_t i = 0; i < m; i++) {
@@ -111,42 +72,10 @@ std::vector<std::vector<Fr>> lagrange_basis(const std::vector<Fr>& pts) {
         }
         basis[j] = num;
     }
-    // all 1 / den_j from one inversion (distinct points: no denominator is zero)
-    Fr run = Fr::one();
-    for (size_t j = 0; j < m; j++) {
-        pre[j] = run;
-        run = fe_mul(run, den[j]);
-    }
-    Fr inv = fe_inv_fast(run);
-    for (size_t j = m; j-- > 0;) {
-        const Fr dj = fe_mul(inv, pre[j]);
-        inv = fe_mul(inv, den[j]);
-        for (Fr& cf : basis[j]) cf = fe_mul(cf, dj);
-    }
+    fr_batch_invert(den.data(), inv.data(), (uint32_t)m);  // (distinct points: no denominator is zero)
+    for (size_t j = 0; j < m; j++)
+        for (Fr& cf : basis[j]) cf = fe_mul(cf, inv[j]);
     return basis;
-}
-
-// affine forms of `cnt` Jacobian points with ONE field inversion for the whole batch (Montgomery's trick over the z's)
-void jac_batch_to_affine(const G1Jac* js, uint32_t cnt, G1Affine* af) {
-    Fq pre[MSM_MAX_BATCH];
-    Fq run = Fq::one();
-    for (uint32_t q = 0; q < cnt; q++) {
-        pre[q] = run;
-        if (!js[q].z.is_zero()) run = fe_mul(run, js[q].z);
-    }
-    Fq inv = fe_inv_fast(run);
-    for (uint32_t q = cnt; q-- > 0;) {
-        if (js[q].z.is_zero()) {
-            af[q].x = Fq::zero();
-            af[q].y = Fq::zero();
-            continue;
-        }
-        const Fq zi = fe_mul(inv, pre[q]);
-        inv = fe_mul(inv, js[q].z);
-        const Fq zi2 = fe_sqr(zi);
-        af[q].x = fe_mul(js[q].x, zi2);
-        af[q].y = fe_mul(js[q].y, fe_mul(zi2, zi));
-    }
 }
 
 Fr eval_small(const std::vector<Fr>& c, const Fr& x) {
@@ -160,634 +89,6 @@ Fr vanishing_eval(const std::vector<Fr>& pts, const Fr& x) {
     for (const Fr& p : pts) acc = fe_mul(acc, fe_sub(x, p));
     return acc;
 }
-
-}  // namespace
-
-static void bb_destroy(BatchBufs* bb) {
-    if (!bb) return;
-    if (bb->lk_u32) hipFree(bb->lk_u32);
-    if (bb->d_gp_items) hipFree(bb->d_gp_items);
-    if (bb->gp_scal) hipFree(bb->gp_scal);
-    if (bb->gp_host) hipHostFree(bb->gp_host);
-    if (bb->d_evargs) hipFree(bb->d_evargs);
-    if (bb->h_evargs) hipHostFree(bb->h_evargs);
-    if (bb->ev_scratch) hipFree(bb->ev_scratch);
-    if (bb->ev_out) hipFree(bb->ev_out);
-    if (bb->tail_host) hipHostFree(bb->tail_host);
-    delete bb;
-}
-
-void pk_destroy(zk_pk_rec* pk) {
-    if (!pk) return;
-    for (zk_pk_rec* m : pk->members) pk_destroy(m);  // (a member's key half aliases this record's: only its workspace goes)
-    pk->members.clear();
-    bb_destroy(pk->bb);
-    pk->bb = nullptr;
-    wc_destroy(pk->wc);
-    pk->wc = nullptr;
-    pc_destroy(pk->pc);
-    pk->pc = nullptr;
-    for (Fr* p : pk->dev) hipFree(p);
-    if (pk->tail_host) hipHostFree(pk->tail_host);
-    if (pk->rows_host) hipHostFree(pk->rows_host);
-    if (pk->rows_dev) hipFree(pk->rows_dev);
-    if (pk->lk_u32) hipFree(pk->lk_u32);
-    if (pk->gp_host) hipHostFree(pk->gp_host);
-    if (pk->d_gp_items) hipFree(pk->d_gp_items);
-    if (pk->d_qargs) hipFree(pk->d_qargs);
-    if (pk->d_batch_args) hipFree(pk->d_batch_args);
-    if (pk->h_batch_args) hipHostFree(pk->h_batch_args);
-    if (pk->h_qargs) hipHostFree(pk->h_qargs);
-    if (pk->d_lc_terms) hipFree(pk->d_lc_terms);
-    if (pk->h_lc_terms) hipHostFree(pk->h_lc_terms);
-    if (pk->d_evargs) hipFree(pk->d_evargs);
-    if (pk->h_evargs) hipHostFree(pk->h_evargs);
-    delete pk;
-}
-
-void pk_destroy_all(zk_ctx* c) {
-    for (auto& kv : c->pks) pk_destroy(kv.second);
-    c->pks.clear();
-}
-
-// halo2's transcript_repr of a key made (or read) here: the hash of the pinned verifying key's Debug rendering
-// (vkrepr.h) — every shape, never-enabled gate columns included (round 4: their combined selectors are rendered as
-// compress_selectors builds them; the stand-in hash of earlier rounds is gone).  A host-supplied value still replaces it.
-Fr pk_standin_transcript_repr(const zk_pk_rec* pk) { return vkrepr::transcript_repr(pk->lay, pk->fixed_commit, pk->perm_commit); }
-
-int pk_alloc_workspace(zk_ctx* c, zk_pk_rec* pk) {
-    const Layout& lay = pk->lay;
-    const uint32_t n = lay.n, N = 4 * n, T = 1u << lay.lookup_bits;
-    Dev d{c, pk};
-    auto fail = [&](int code) { return code; };  // the caller destroys the key
-    // ---- prover workspace
-    for (uint32_t j = 0; j < lay.n_adv; j++) {
-        pk->adv_val.push_back(d.alloc(n));
-        pk->adv_poly.push_back(d.alloc(n));
-        pk->adv_coset.push_back(d.alloc(N));
-    }
-    for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-        pk->z_val.push_back(d.alloc(n));
-        pk->z_poly.push_back(d.alloc(n));
-        pk->z_coset.push_back(d.alloc(N));
-    }
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        pk->lk_in.push_back(lay.single ? d.alloc(n) : nullptr);
-        pk->lk_ap.push_back(d.alloc(n));
-        pk->lk_ap_poly.push_back(d.alloc(n));
-        pk->lk_ap_coset.push_back(d.alloc(N));
-        pk->lk_sp.push_back(d.alloc(n));
-        pk->lk_sp_poly.push_back(d.alloc(n));
-        pk->lk_sp_coset.push_back(d.alloc(N));
-        pk->lk_z.push_back(d.alloc(n));
-        pk->lk_z_poly.push_back(d.alloc(n));
-        pk->lk_z_coset.push_back(d.alloc(N));
-    }
-    pk->random_poly = d.alloc(n);
-    pk->h_ext = d.alloc(N);
-    pk->h_comb = d.alloc(n);
-    pk->t_num = d.alloc(n);
-    pk->t_den = d.alloc(n);
-    pk->t_frac = d.alloc(n);
-    pk->t_a = d.alloc(n);
-    pk->t_b = d.alloc(n);
-    pk->t_small = d.alloc(n / 16 + 8192);
-    pk->kd_scratch = d.alloc((size_t)KD_MAX_BATCH * kate_division_scratch(n));
-    {
-        const uint32_t nprod = lay.n_chunks + lay.n_lookups;
-        for (uint32_t p = 0; p < nprod; p++) {
-            pk->gp_num.push_back(d.alloc(n));
-            pk->gp_den.push_back(d.alloc(n));
-            pk->gp_loc_p.push_back(d.alloc(n));
-            pk->gp_loc_r.push_back(d.alloc(n));
-        }
-        pk->gp_tot = d.alloc((size_t)2 * gp_blocks(n) * nprod);
-        pk->gp_scal = d.alloc((size_t)4 * nprod);
-        if (hipHostMalloc(&pk->gp_host, (size_t)2 * nprod * sizeof(Fr)) != hipSuccess ||
-            hipMalloc(&pk->d_gp_items, nprod * sizeof(GpItem)) != hipSuccess)
-            return fail(ZK_ENOMEM);
-    }
-    if (d.rc) return fail(d.rc);
-    if (hipHostMalloc(&pk->tail_host, (pk->max_evals + 16) * sizeof(Fr)) != hipSuccess) return fail(ZK_ENOMEM);
-    if (hipHostMalloc(&pk->rows_host, (size_t)ROWS_BLOCKS * ROWS_CAP * sizeof(RowEntry)) != hipSuccess ||
-        hipMalloc(&pk->rows_dev, (size_t)ROWS_BLOCKS * ROWS_CAP * sizeof(RowEntry)) != hipSuccess)
-        return fail(ZK_ENOMEM);
-    if (hipHostMalloc(&pk->h_evargs, pk->max_evals * sizeof(EvalItem)) != hipSuccess ||
-        hipMalloc(&pk->d_evargs, pk->max_evals * sizeof(EvalItem)) != hipSuccess)
-        return fail(ZK_ENOMEM);
-    pk->lc_cap = 2 * (pk->max_evals + 8);
-    if (hipHostMalloc(&pk->h_lc_terms, pk->lc_cap * sizeof(LcTerm)) != hipSuccess ||
-        hipMalloc(&pk->d_lc_terms, pk->lc_cap * sizeof(LcTerm)) != hipSuccess)
-        return fail(ZK_ENOMEM);
-    pk->ev_scratch = d.alloc((size_t)pk->max_evals * eval_blocks(n));
-    pk->ev_out = d.alloc(pk->max_evals);
-    if (d.rc) return fail(d.rc);
-    {
-        // per lookup: six arrays of T + 2 words and 3 x blocks block sums; one error flag for all
-        const uint32_t stride = 6 * (T + 2) + 3 * (T / 1024 + 2);
-        if (hipMalloc(&pk->lk_u32, ((size_t)stride * lay.n_lookups + 4) * 4) != hipSuccess) return fail(ZK_ENOMEM);
-        uint32_t* b = pk->lk_u32;
-        pk->lks.hist = b;
-        pk->lks.present = b + (T + 2);
-        pk->lks.absent = b + 2 * (T + 2);
-        pk->lks.off = b + 3 * (T + 2);
-        pk->lks.dex = b + 4 * (T + 2);
-        pk->lks.aex = b + 5 * (T + 2);
-        pk->lks.bsum = b + 6 * (T + 2);
-        pk->lks.stride = stride;
-        pk->lks.err = b + (size_t)stride * lay.n_lookups;
-    }
-    if (hipMalloc(&pk->d_qargs, sizeof(QuotientArgs)) != hipSuccess || hipHostMalloc(&pk->h_qargs, sizeof(QuotientArgs)) != hipSuccess)
-        return fail(ZK_ENOMEM);
-    {
-        size_t bytes = (size_t)lay.n_chunks * sizeof(PermArgs);
-        bytes = std::max(bytes, (size_t)lay.n_lookups * sizeof(LkNumDenArgs));
-        bytes = std::max(bytes, (size_t)lay.n_adv * sizeof(CopyPair));
-        pk->batch_args_bytes = bytes;
-        if (hipMalloc(&pk->d_batch_args, bytes) != hipSuccess || hipHostMalloc(&pk->h_batch_args, bytes) != hipSuccess) return fail(ZK_ENOMEM);
-    }
-    return ZK_OK;
-}
-
-// a further workspace for the same key: the record is copied (the key half stays shared — nothing of it is in the copy's
-// `dev` list), every workspace member is reset and allocated afresh
-static zk_pk_rec* pk_make_member(zk_ctx* c, const zk_pk_rec* pk) {
-    zk_pk_rec* m = new (std::nothrow) zk_pk_rec(*pk);
-    if (!m) return nullptr;
-    m->is_member = true;
-    m->dev.clear();
-    m->members.clear();
-    m->bb = nullptr;
-    m->wc = nullptr;
-    m->pc = nullptr;
-    for (auto* v : {&m->adv_val, &m->adv_poly, &m->adv_coset, &m->z_val, &m->z_poly, &m->z_coset, &m->lk_in, &m->lk_ap, &m->lk_ap_poly,
-                    &m->lk_ap_coset, &m->lk_sp, &m->lk_sp_poly, &m->lk_sp_coset, &m->lk_z, &m->lk_z_poly, &m->lk_z_coset, &m->lk_in_coset,
-                    &m->gp_num, &m->gp_den, &m->gp_loc_p, &m->gp_loc_r})
-        v->clear();
-    m->random_poly = m->h_ext = m->h_comb = m->t_num = m->t_den = m->t_frac = m->t_a = m->t_b = m->t_small = m->kd_scratch = nullptr;
-    m->tail_host = nullptr;
-    m->rows_host = m->rows_dev = nullptr;
-    m->lk_u32 = nullptr;
-    m->gp_tot = m->gp_scal = m->gp_host = nullptr;
-    m->d_gp_items = nullptr;
-    m->h_batch_args = m->d_batch_args = nullptr;
-    m->d_qargs = m->h_qargs = nullptr;
-    m->d_evargs = m->h_evargs = nullptr;
-    m->d_lc_terms = m->h_lc_terms = nullptr;
-    m->ev_scratch = m->ev_out = nullptr;
-    m->lc_used = 0;
-    if (pk_alloc_workspace(c, m) != ZK_OK) {
-        pk_destroy(m);
-        return nullptr;
-    }
-    return m;
-}
-
-int pk_ensure_batch(zk_ctx* c, zk_pk_rec* pk, uint32_t batch) {
-    if (batch <= 1) return ZK_OK;
-    const Layout& lay = pk->lay;
-    const uint32_t n = lay.n, T = 1u << lay.lookup_bits, nprod = lay.n_chunks + lay.n_lookups;
-    if ((pk->members.size() + 1 < batch || !pk->bb || pk->bb->cap < batch) && !c->poly_spare.empty()) ctx_release_spares(c);
-    while (pk->members.size() + 1 < batch) {
-        zk_pk_rec* m = pk_make_member(c, pk);
-        if (!m) return ZK_ENOMEM;
-        pk->members.push_back(m);
-    }
-    if (pk->bb && pk->bb->cap >= batch) return ZK_OK;
-    aud_sync(c, c->stream);
-    bb_destroy(pk->bb);
-    pk->bb = nullptr;
-    BatchBufs* bb = new (std::nothrow) BatchBufs();
-    if (!bb) return ZK_ENOMEM;
-    pk->bb = bb;  // (freed with the key whatever happens below)
-    const size_t nl = (size_t)batch * lay.n_lookups, np = (size_t)batch * nprod, ne = (size_t)batch * pk->max_evals;
-    const uint32_t stride = 6 * (T + 2) + 3 * (T / 1024 + 2);
-    if (hipMalloc(&bb->lk_u32, ((size_t)stride * nl + 4) * 4) != hipSuccess || hipMalloc(&bb->d_gp_items, np * sizeof(GpItem)) != hipSuccess ||
-        hipMalloc(&bb->gp_scal, 4 * np * sizeof(Fr)) != hipSuccess || hipHostMalloc(&bb->gp_host, 2 * np * sizeof(Fr)) != hipSuccess ||
-        hipMalloc(&bb->d_evargs, ne * sizeof(EvalItem)) != hipSuccess || hipHostMalloc(&bb->h_evargs, ne * sizeof(EvalItem)) != hipSuccess ||
-        hipMalloc(&bb->ev_scratch, ne * eval_blocks(n) * sizeof(Fr)) != hipSuccess || hipMalloc(&bb->ev_out, ne * sizeof(Fr)) != hipSuccess ||
-        hipHostMalloc(&bb->tail_host, ne * sizeof(Fr)) != hipSuccess)
-        return ZK_ENOMEM;
-    uint32_t* b = bb->lk_u32;
-    bb->lks.hist = b;
-    bb->lks.present = b + (T + 2);
-    bb->lks.absent = b + 2 * (T + 2);
-    bb->lks.off = b + 3 * (T + 2);
-    bb->lks.dex = b + 4 * (T + 2);
-    bb->lks.aex = b + 5 * (T + 2);
-    bb->lks.bsum = b + 6 * (T + 2);
-    bb->lks.stride = stride;
-    bb->lks.err = b + (size_t)stride * nl;
-    bb->cap = batch;
-    return ZK_OK;
-}
-
-// =================================================================== keygen ==
-
-ZK_API(zk_keygen, (zk_ctx* c, const zk_circuit_params* params, const uint64_t* fixed_canonical, size_t n_fixed_columns, const uint32_t* copies, size_t n_copies, zk_pk* out), (c, params, fixed_canonical, n_fixed_columns, copies, n_copies, out)) {
-    if (!c || !params || !fixed_canonical || !out || (n_copies && !copies)) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    ctx_release_spares(c);  // parked vectors are reclaimable: give them back before the key and its workspace are allocated
-    Layout lay;
-    if (params->num_advice > 1 && 2 * (uint64_t)params->num_idle_gate_columns > params->num_advice) return ZK_ELAYOUT;  // zkmi355.h: more never-enabled selectors than used ones
-    if (!lay.init(*params)) return ZK_EINVAL;
-    if (n_fixed_columns != lay.n_fix) return ZK_EINVAL;  // fixed_canonical holds n_fixed_columns x n x 4 limbs
-    if (c->srs_k != (int)lay.k) return ZK_ESTATE;
-    const uint32_t n = lay.n, N = 4 * n, T = 1u << lay.lookup_bits;
-    // the lookup path is specialised to halo2-lib's range table: 0..T-1 then zeros
-    {
-        const uint64_t* tab = fixed_canonical + (size_t)lay.fx_table * n * 4;
-        for (uint32_t r = 0; r < n; r++) {
-            const uint64_t want = r < T ? r : 0;
-            if (tab[4 * r] != want || tab[4 * r + 1] || tab[4 * r + 2] || tab[4 * r + 3]) return ZK_EINVAL;
-        }
-    }
-    // the gate selectors must be what the key's closed-form layout assumes of them (pk.h layout_selectors_fit): 0 / 1 columns
-    // that halo2's compress_selectors would leave one fixed column each
-    if (!lay.single) {
-        std::vector<std::vector<uint8_t>> bits(lay.A, std::vector<uint8_t>(n / 8, 0));
-        for (uint32_t j = 0; j < lay.A; j++) {
-            if (lay.fx_sel[j] == NO_SELECTOR) continue;
-            const uint64_t* col = fixed_canonical + (size_t)lay.fx_sel[j] * n * 4;
-            for (uint32_t r = 0; r < n; r++) {
-                if (col[4 * r] > 1 || col[4 * r + 1] || col[4 * r + 2] || col[4 * r + 3]) return ZK_EINVAL;  // not a selector column
-                if (col[4 * r]) bits[j][r >> 3] |= (uint8_t)(1u << (r & 7));
-            }
-        }
-        if (!layout_selectors_fit(lay, bits)) return ZK_ELAYOUT;
-    }
-    const uint32_t m = (uint32_t)lay.perm_cols.size();
-    for (size_t i = 0; i < n_copies; i++) {
-        const uint32_t* e = copies + 4 * i;
-        if (e[0] >= m || e[2] >= m || e[1] >= lay.usable || e[3] >= lay.usable) return ZK_EINVAL;
-    }
-    zk_pk_rec* pk = new (std::nothrow) zk_pk_rec();
-    if (!pk) return ZK_ENOMEM;
-    pk->lay = lay;
-    pk->srs_gen = c->srs_gen;
-    pk->max_evals = (uint32_t)(lay.advice_queries.size() + lay.n_fix + lay.perm_cols.size() + 3 * lay.n_chunks +
-                               5 * lay.n_lookups + 16);
-    Dev d{c, pk};
-    hipStream_t st = c->stream;
-    const Fr* tw = nullptr;
-    const Fr* tw_ext = nullptr;
-    if ((rc = ctx_get_twiddles(c, lay.k, &tw)) || (rc = ctx_get_twiddles(c, lay.ext_k, &tw_ext))) {
-        pk_destroy(pk);
-        return rc;
-    }
-    auto fail = [&](int code) {
-        aud_sync(c, st);
-        pk_destroy(pk);
-        return code;
-    };
-
-    // ---- fixed columns: values -> commitment, coefficients, extended coset
-    for (uint32_t f = 0; f < lay.n_fix; f++) {
-        Fr *v = d.alloc(n), *p = d.alloc(n), *e = d.alloc(N);
-        if (d.rc) return fail(d.rc);
-        pk->fixed_val.push_back(v);
-        pk->fixed_poly.push_back(p);
-        pk->fixed_coset.push_back(e);
-        hipMemcpyAsync(v, fixed_canonical + (size_t)f * n * 4, (size_t)n * sizeof(Fr), hipMemcpyHostToDevice, st);
-        launch_to_mont(v, n, st);
-    }
-    // ---- permutation: halo2 permutation::keygen::Assembly (cycle merging), then sigma = delta^c' w^r'
-    {
-        std::vector<uint2> mapping((size_t)m * n), aux((size_t)m * n);
-        std::vector<uint32_t> sizes((size_t)m * n, 1);
-        for (uint32_t col = 0; col < m; col++)
-            for (uint32_t r = 0; r < n; r++) mapping[(size_t)col * n + r] = aux[(size_t)col * n + r] = make_uint2(col, r);
-        auto at = [&](uint2 p) { return (size_t)p.x * n + p.y; };
-        auto same = [](uint2 a, uint2 b) { return a.x == b.x && a.y == b.y; };
-        for (size_t i = 0; i < n_copies; i++) {
-            uint2 l = make_uint2(copies[4 * i], copies[4 * i + 1]), r = make_uint2(copies[4 * i + 2], copies[4 * i + 3]);
-            uint2 lc = aux[at(l)], rc2 = aux[at(r)];
-            if (same(lc, rc2)) continue;
-            if (sizes[at(lc)] < sizes[at(rc2)]) {
-                std::swap(lc, rc2);
-                std::swap(l, r);
-            }
-            sizes[at(lc)] += sizes[at(rc2)];
-            uint2 it = rc2;
-            for (;;) {
-                aux[at(it)] = lc;
-                it = mapping[at(it)];
-                if (same(it, rc2)) break;
-            }
-            std::swap(mapping[at(l)], mapping[at(r)]);
-        }
-        std::vector<Fr> dpow(m);
-        Fr dl = Fr::one();
-        const Fr delta = fr_delta();
-        for (uint32_t col = 0; col < m; col++) {
-            dpow[col] = dl;
-            dl = fe_mul(dl, delta);
-        }
-        uint2* d_map = nullptr;
-        Fr* d_dpow = d.alloc(m);
-        if (d.rc || hipMalloc(&d_map, (size_t)n * sizeof(uint2)) != hipSuccess) return fail(ZK_ENOMEM);
-        hipMemcpyAsync(d_dpow, dpow.data(), m * sizeof(Fr), hipMemcpyHostToDevice, st);
-        for (uint32_t col = 0; col < m; col++) {
-            Fr *v = d.alloc(n), *p = d.alloc(n), *e = d.alloc(N);
-            if (d.rc) {
-                hipFree(d_map);
-                return fail(d.rc);
-            }
-            pk->sigma_val.push_back(v);
-            pk->sigma_poly.push_back(p);
-            pk->sigma_coset.push_back(e);
-            hipMemcpyAsync(d_map, &mapping[(size_t)col * n], (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, st);
-            hipLaunchKernelGGL(sigma_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_map, tw, d_dpow, v, n);
-            aud_sync(c, st);  // d_map is reused
-        }
-        hipFree(d_map);
-    }
-    // ---- commitments (vk) and polynomial forms (pk)
-    auto finish_col = [&](Fr* v, Fr* p, Fr* e, G1Affine* cm) -> int {
-        if (!commit(c, v, n, ZK_BASIS_LAGRANGE, cm)) return ZK_EHIP;
-        hipMemcpyAsync(p, v, (size_t)n * sizeof(Fr), hipMemcpyDeviceToDevice, st);
-        int r2 = ctx_ntt(c, p, n, p, lay.k, true, false, n);
-        if (r2) return r2;
-        return ctx_ntt(c, p, n, e, lay.ext_k, false, true, N);
-    };
-    pk->fixed_commit.resize(lay.n_fix);
-    pk->perm_commit.resize(m);
-    for (uint32_t f = 0; f < lay.n_fix; f++)
-        if ((rc = finish_col(pk->fixed_val[f], pk->fixed_poly[f], pk->fixed_coset[f], &pk->fixed_commit[f]))) return fail(rc);
-    for (uint32_t col = 0; col < m; col++)
-        if ((rc = finish_col(pk->sigma_val[col], pk->sigma_poly[col], pk->sigma_coset[col], &pk->perm_commit[col]))) return fail(rc);
-    // ---- l_0, l_last, l_active (= 1 - l_last - l_blind) cosets
-    {
-        std::vector<Fr> tmp(n, Fr::zero());
-        Fr* scratch_n = d.alloc(n);
-        pk->l0_coset = d.alloc(N);
-        pk->l_last_coset = d.alloc(N);
-        pk->l_active_coset = d.alloc(N);
-        if (d.rc) return fail(d.rc);
-        auto make = [&](Fr* dst) -> int {
-            hipMemcpyAsync(scratch_n, tmp.data(), (size_t)n * sizeof(Fr), hipMemcpyHostToDevice, st);
-            aud_sync(c, st);
-            int r2 = ctx_ntt(c, scratch_n, n, scratch_n, lay.k, true, false, n);
-            if (r2) return r2;
-            return ctx_ntt(c, scratch_n, n, dst, lay.ext_k, false, true, N);
-        };
-        tmp[0] = Fr::one();
-        if ((rc = make(pk->l0_coset))) return fail(rc);
-        tmp[0] = Fr::zero();
-        tmp[lay.usable] = Fr::one();  // row n - (bf + 1)
-        if ((rc = make(pk->l_last_coset))) return fail(rc);
-        for (uint32_t r = 0; r < n; r++) tmp[r] = r < lay.usable ? Fr::one() : Fr::zero();
-        if ((rc = make(pk->l_active_coset))) return fail(rc);
-    }
-    pk->transcript_repr = pk_standin_transcript_repr(pk);
-    if ((rc = pk_alloc_workspace(c, pk))) return fail(rc);
-    if (aud_sync(c, st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(ZK_EHIP);
-    const uint64_t h = c->next_handle++;
-    c->pks[h] = pk;
-    *out = h;
-    return ZK_OK;
-}
-
-ZK_API(zk_pk_free, (zk_ctx* c, zk_pk h), (c, h)) {
-    if (!c) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    ctx_bind(c);
-    aud_sync(c, c->stream);
-    pk_destroy(it->second);
-    c->pks.erase(it);
-    return ZK_OK;
-}
-
-ZK_API(zk_vk_export, (zk_ctx* c, zk_pk h, uint64_t* fixed_commitments, uint64_t* perm_commitments, uint64_t transcript_repr[4], uint32_t counts[2]), (c, h, fixed_commitments, perm_commitments, transcript_repr, counts)) {
-    if (!c) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    zk_pk_rec* pk = it->second;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made
-    if (counts) {
-        counts[0] = (uint32_t)pk->fixed_commit.size();
-        counts[1] = (uint32_t)pk->perm_commit.size();
-    }
-    if (fixed_commitments) memcpy(fixed_commitments, pk->fixed_commit.data(), pk->fixed_commit.size() * sizeof(G1Affine));
-    if (perm_commitments) memcpy(perm_commitments, pk->perm_commit.data(), pk->perm_commit.size() * sizeof(G1Affine));
-    if (transcript_repr) memcpy(transcript_repr, &pk->transcript_repr, 32);
-    return ZK_OK;
-}
-
-int pk_ensure_cosets3(zk_ctx* c, zk_pk_rec* pk) {
-    const Layout& lay = pk->lay;
-    if (lay.n_h != 3) return ZK_EINVAL;
-    auto to_members = [&]() {  // by-value copies of the record (pk_make_member): the key half is written through
-        for (zk_pk_rec* m : pk->members) {
-            m->fixed_c3 = pk->fixed_c3;
-            m->sigma_c3 = pk->sigma_c3;
-            m->l0_c3 = pk->l0_c3;
-            m->l_last_c3 = pk->l_last_c3;
-            m->l_active_c3 = pk->l_active_c3;
-        }
-    };
-    if (pk->fixed_c3.size() == lay.n_fix && pk->l_active_c3) {
-        to_members();
-        return ZK_OK;
-    }
-    const size_t n = lay.n;
-    Dev d{c, pk};
-    std::vector<const Fr*> src;
-    std::vector<Fr*> dst;
-    auto add = [&](const Fr* s) {
-        Fr* t = d.alloc(3 * n);
-        src.push_back(s);
-        dst.push_back(t);
-        return t;
-    };
-    std::vector<Fr*> fx, sg;
-    for (uint32_t f = 0; f < lay.n_fix; f++) fx.push_back(add(pk->fixed_coset[f]));
-    for (size_t p = 0; p < lay.perm_cols.size(); p++) sg.push_back(add(pk->sigma_coset[p]));
-    Fr *a0 = add(pk->l0_coset), *a1 = add(pk->l_last_coset), *a2 = add(pk->l_active_coset);
-    if (d.rc) return d.rc;  // (what was allocated stays on the key's list and is freed with it)
-    launch_coset3_relayout(src.data(), dst.data(), (uint32_t)src.size(), (uint32_t)n, c->stream);
-    if (c->audit.on) {
-        std::vector<const void*> rd(src.begin(), src.end()), wr(dst.begin(), dst.end());
-        c->audit.op_v(c->stream, rd.data(), rd.size(), wr.data(), wr.size(), "key cosets -> coset-major");
-    }
-    pk->fixed_c3 = fx;
-    pk->sigma_c3 = sg;
-    pk->l0_c3 = a0;
-    pk->l_last_c3 = a1;
-    pk->l_active_c3 = a2;
-    to_members();
-    return ZK_OK;
-}
-
-// Evaluator::evaluate_h (+ divide_by_vanishing_poly when `divide`) over resident extended cosets: the key's fixed /
-// sigma / l_* cosets and the caller's advice, permutation-product and lookup cosets.  Enqueued on the context stream.
-int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out) {
-    const Layout& lay = pk->lay;
-    if (qc.adv.size() != lay.n_adv || qc.z.size() != lay.n_chunks || qc.lk_a.size() != lay.n_lookups ||
-        qc.lk_s.size() != lay.n_lookups || qc.lk_z.size() != lay.n_lookups)
-        return ZK_EINVAL;
-    const Fr* xs = nullptr;
-    int rc = ctx_get_coset_points(c, lay.ext_k, &xs);
-    if (rc) return rc;
-    QuotientArgs& q = *pk->h_qargs;  // pinned: the upload below does not stall the host (the previous use is complete)
-    memset(&q, 0, sizeof(q) - sizeof(q.ypow));
-    q.log_ext = lay.ext_k;
-    q.n_gate = lay.n_gate;
-    q.n_adv = lay.n_adv;
-    q.n_chunks = lay.n_chunks;
-    q.chunk_len = lay.chunk_len;
-    q.n_perm = (uint32_t)lay.perm_cols.size();
-    q.n_lookups = lay.n_lookups;
-    q.single = lay.single ? 1 : 0;
-    q.last_rot = lay.last_rot;
-    q.fx_table = lay.fx_table;
-    q.fx_qlookup = lay.fx_qlookup;
-    for (uint32_t j = 0; j < lay.n_adv; j++) q.adv[j] = qc.adv[j];
-    const bool c3 = qc.cosets3;
-    if (c3 && (lay.n_h != 3 || pk->fixed_c3.size() != lay.n_fix)) return ZK_EINVAL;  // (pk_ensure_cosets3 first)
-    for (uint32_t f = 0; f < lay.n_fix; f++) q.fix[f] = c3 ? pk->fixed_c3[f] : pk->fixed_coset[f];
-    for (uint32_t j = 0; j < lay.n_gate; j++) q.fx_sel[j] = lay.gate_sel[j];
-    for (uint32_t p = 0; p < q.n_perm; p++) {
-        q.sigma[p] = c3 ? pk->sigma_c3[p] : pk->sigma_coset[p];
-        const Col& col = lay.perm_cols[p];
-        q.perm_val[p] = col.fixed ? q.fix[col.idx] : qc.adv[col.idx];
-    }
-    for (uint32_t ci = 0; ci < lay.n_chunks; ci++) q.z[ci] = qc.z[ci];
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        q.lk_z[l] = qc.lk_z[l];
-        q.lk_a[l] = qc.lk_a[l];
-        q.lk_s[l] = qc.lk_s[l];
-        q.lk_in[l] = lay.single ? nullptr : qc.adv[lay.n_gate + l];
-    }
-    q.l0 = c3 ? pk->l0_c3 : pk->l0_coset;
-    q.l_last = c3 ? pk->l_last_c3 : pk->l_last_coset;
-    q.l_active = c3 ? pk->l_active_c3 : pk->l_active_coset;
-    q.xs = xs;
-    // the kernel works in the carry-free field's internal form (x * 2^261): its constants are handed over times 32
-    const Fr k32 = fr_from_u64(32);
-    q.beta = fe_mul(beta, k32);
-    q.gamma = fe_mul(gamma, k32);
-    q.delta = fe_mul(fr_delta(), k32);
-    // 1 / ((zeta w_ext^i)^n - 1): zeta^n * (w_ext^n)^i, w_ext^n is a primitive 4th root
-    if (!pk->t_inv_ready) {  // constants of the key's domain: made once, not once per proof
-        const Fr zn = fe_pow_u64(c->zeta, lay.n);
-        const Fr w4 = fe_pow_u64(fr_omega(lay.ext_k), lay.n);
-        Fr cur = zn;
-        for (int i = 0; i < 4; i++) {
-            pk->t_inv[i] = fe_inv_fast(fe_sub(cur, Fr::one()));
-            cur = fe_mul(cur, w4);
-        }
-        pk->t_inv_ready = true;
-    }
-    // standard form: the product by it also converts the row back (quotient.hip); 1 = no division
-    for (int i = 0; i < 4; i++) q.t_inv[i] = divide ? pk->t_inv[i] : Fr::one();
-    q.divide = divide ? 1 : 0;
-    q.n_terms = quotient_terms(lay.n_gate, lay.n_chunks, lay.n_lookups);
-    if (q.n_terms > MAX_TERMS) return ZK_EINVAL;
-    Fr yp = k32;
-    for (uint32_t j = q.n_terms; j-- > 0;) {  // ypow[j] = 32 y^(T - 1 - j)
-        q.ypow[j] = yp;
-        yp = fe_mul(yp, y);
-    }
-    q.out = out;
-    const uint32_t log_slices = quotient_log_slices(lay.ext_k, lay.n_gate);
-    if (log_slices) {
-        const Fr dstep = fe_pow_u64(fr_delta(), lay.chunk_len);
-        Fr dc = k32;
-        for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-            q.delta_chunk[ci] = dc;
-            dc = fe_mul(dc, dstep);
-        }
-    }
-    hipStream_t st = c->stream;
-    hipEventRecord(c->ev[ZK_T_QUOTIENT][0], st);
-    const size_t bytes = sizeof(q) - sizeof(q.ypow) + (size_t)q.n_terms * sizeof(Fr);
-    if (hipMemcpyAsync(pk->d_qargs, &q, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return ZK_EHIP;
-    launch_quotient_dev(pk->d_qargs, lay.ext_k, log_slices, st, c3);
-    hipEventRecord(c->ev[ZK_T_QUOTIENT][1], st);
-    c->ev_valid[ZK_T_QUOTIENT] = true;
-    return ZK_OK;
-}
-
-ZK_API(zk_pk_shape, (zk_ctx* c, zk_pk h, uint32_t out[8]), (c, h, out)) {
-    if (!c || !out) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    const Layout& lay = it->second->lay;
-    const uint32_t v[8] = {lay.k, lay.ext_k, lay.n_adv, lay.n_fix, (uint32_t)lay.perm_cols.size(), lay.n_chunks, lay.n_lookups, lay.n_h};
-    memcpy(out, v, sizeof(v));
-    return ZK_OK;
-}
-
-ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_advice, const zk_poly* perm_z_ext, size_t n_chunks, const zk_poly* lookup_ext, size_t n_lookups, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], int divide, zk_poly out_ext), (c, h, advice_ext, n_advice, perm_z_ext, n_chunks, lookup_ext, n_lookups, beta, gamma, y, divide, out_ext)) {
-    if (!c || !advice_ext || !perm_z_ext || !lookup_ext || !beta || !gamma || !y) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    zk_pk_rec* pk = it->second;
-    const Layout& lay = pk->lay;
-    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
-    if (n_advice != lay.n_adv || n_chunks != lay.n_chunks || n_lookups != lay.n_lookups) return ZK_EINVAL;
-    const size_t N = (size_t)4 * lay.n;
-    auto ext = [&](zk_poly p) -> Fr* {
-        auto q = c->polys.find(p);
-        return (q == c->polys.end() || q->second.n != N) ? nullptr : q->second.ptr;
-    };
-    QuotientCosets qc;
-    for (size_t j = 0; j < n_advice; j++) qc.adv.push_back(ext(advice_ext[j]));
-    for (size_t j = 0; j < n_chunks; j++) qc.z.push_back(ext(perm_z_ext[j]));
-    for (size_t l = 0; l < n_lookups; l++) {
-        qc.lk_a.push_back(ext(lookup_ext[3 * l]));
-        qc.lk_s.push_back(ext(lookup_ext[3 * l + 1]));
-        qc.lk_z.push_back(ext(lookup_ext[3 * l + 2]));
-    }
-    Fr* out = ext(out_ext);
-    if (!out) return ZK_EINVAL;
-    for (auto* v : {&qc.adv, &qc.z, &qc.lk_a, &qc.lk_s, &qc.lk_z})
-        for (const Fr* p : *v)
-            if (!p || p == out) return ZK_EINVAL;
-    Fr b, g, yy;
-    memcpy(&b, beta, 32);
-    memcpy(&g, gamma, 32);
-    memcpy(&yy, y, 32);
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    if ((rc = pk_quotient(c, pk, qc, b, g, yy, divide != 0, out))) return rc;
-    HIPCHK(c, aud_sync(c, c->stream));  // the argument block is reused by the next call
-    return ZK_OK;
-}
-
-ZK_API(zk_pk_set_transcript_repr, (zk_ctx* c, zk_pk h, const uint64_t transcript_repr[4]), (c, h, transcript_repr)) {
-    if (!c || !transcript_repr) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    Fr v;
-    memcpy(&v, transcript_repr, 32);
-    // a Montgomery image is < r
-    for (int i = 7; i >= 0; i--) {
-        if (v.v[i] != FrParams::P[i]) {
-            if (v.v[i] > FrParams::P[i]) return ZK_EINVAL;
-            break;
-        }
-        if (i == 0) return ZK_EINVAL;
-    }
-    it->second->transcript_repr = v;
-    // the lock-step members are by-value copies of the record (pk_make_member): every key-half field that can change after
-    // they were made has to be written through to them, or proofs j > 0 of the next batch would hash the stale value
-    for (zk_pk_rec* m : it->second->members) m->transcript_repr = v;
-    return ZK_OK;
-}
-
-// ==================================================================== prove ==
-
-namespace {
 
 struct Prover {
     zk_ctx* c;
@@ -810,6 +111,7 @@ struct Prover {
     RowStager* rows = &own_rows;
     bool batch_member = false;  // one of the proofs of a lock-step batch (prover_batch.h): transforms stay on the main stream
 
+    Prover(const Prover&) = delete;  // (cq is bound to this object)
     Prover(zk_ctx* c_, zk_pk_rec* pk_, const uint8_t seed[32], Transcript* t)
         : c(c_), pk(pk_), lay(pk_->lay), st(c_->stream), rng(seed), tr(t), n(pk_->lay.n), N(4 * pk_->lay.n) {
         own_rows.host = pk_->rows_host;
@@ -823,7 +125,7 @@ struct Prover {
 
     // ---- device helpers
     // Blinding rows are staged on the host and written by rows_flush() — one upload and one launch for all
-    // the columns of a phase — before the first kernel that reads those columns (commit_begin_batch and
+    // the columns of a phase — before the first kernel that reads those columns (the commitment queue and
     // transforms() flush; other readers call rows_flush() themselves).
     // ---- stream audit (audit.h, ZK_OPT_STREAM_AUDIT): every enqueue of this prover names the buffers it reads and writes
     void A(std::initializer_list<const void*> r, std::initializer_list<const void*> w, const char* site) {
@@ -866,86 +168,19 @@ struct Prover {
             rows->block = 0;
         }
     }
-    // commitments in flight over a set of MSM lanes, collected (written to the transcript) in the
-    // order they were begun
-    struct LaneFifo {
-        std::vector<int> lanes;
-        std::deque<int> busy;
-    };
-    void fifo_begin_batch(LaneFifo& f, const std::vector<const Fr*>& polys, size_t len, int basis) {
-        if (!ok() || polys.empty()) return;
-        if (f.busy.size() == f.lanes.size()) {
-            commit_end_write(f.busy.front());
-            f.busy.pop_front();
-        }
-        int lane = -1;
-        for (int l : f.lanes)
-            if (std::find(f.busy.begin(), f.busy.end(), l) == f.busy.end()) lane = l;
-        commit_begin_batch(lane, polys, len, basis);
-        f.busy.push_back(lane);
-    }
-    // gathers columns into batches of the size the MSM workspaces take; flush() launches what is pending
-    struct Batcher {
-        LaneFifo* f;
-        int basis;
-        uint32_t cap;
-        std::vector<const Fr*> pend;
-    };
-    void batch_add(Batcher& b, const Fr* poly) {
-        b.pend.push_back(poly);
-        if (b.pend.size() >= b.cap) batch_flush(b);
-    }
-    void batch_flush(Batcher& b) {
-        if (b.pend.size() >= 4 && b.f->lanes.size() >= 2 && !loaded) {
-            // two passes on two lanes instead of one: the first half's reduction tail runs under the second half's head.  Only while
-            // the tails have a stream of their own (a lone proof, two pipelines): under load — tails on the main stream — a second
-            // pass is just a second head and tail (k = 17 EVM over four pipelines: 232.9 -> 236.9 proofs/s unsplit)
-            const size_t h = (b.pend.size() + 1) / 2;
-            fifo_begin_batch(*b.f, std::vector<const Fr*>(b.pend.begin(), b.pend.begin() + h), n, b.basis);
-            fifo_begin_batch(*b.f, std::vector<const Fr*>(b.pend.begin() + h, b.pend.end()), n, b.basis);
-        } else {
-            fifo_begin_batch(*b.f, b.pend, n, b.basis);
-        }
-        b.pend.clear();
-    }
-    void fifo_drain(LaneFifo& f) {
-        while (!f.busy.empty()) {
-            commit_end_write(f.busy.front());
-            f.busy.pop_front();
-        }
+    // commitments in flight over MSM lanes (prover_steps.h): every column of this prover goes to its own transcript
+    using CQ = Commits<Prover>;
+    CQ cq{*this};
+    // one commitment on lane 0, written to the transcript at once
+    void commit_write(const Fr* poly, int basis) {
+        CQ::Fifo f{{0}, {}, nullptr};
+        cq.begin(f, {CommitCol{poly, tr}}, basis);
+        cq.drain(f);
     }
     std::vector<Fr> draw(uint32_t count) {
         std::vector<Fr> v(count);
         for (auto& x : v) x = rng.next_fr();
         return v;
-    }
-    void commit_write(const Fr* poly, size_t len, int basis) { commit_write_lane(0, poly, len, basis); }
-    void commit_write_lane(int lane, const Fr* poly, size_t len, int basis) {
-        commit_begin(lane, poly, len, basis);
-        commit_end_write(lane);
-    }
-    // split commit: the MSM is enqueued on `lane` and its latency-bound tail overlaps whatever is
-    // launched next; the point is written to the transcript when the lane is collected.
-    void commit_begin(int lane, const Fr* poly, size_t len, int basis) { commit_begin_batch(lane, {poly}, len, basis); }
-    // several columns against the same basis in ONE MSM pass (at most ctx_msm_max_batch of them)
-    void commit_begin_batch(int lane, const std::vector<const Fr*>& polys, size_t len, int basis) {
-        rows_flush();
-        if (!ok()) return;
-        int r = ctx_msm_begin_batch(c, lane, polys.data(), (uint32_t)polys.size(), basis == ZK_BASIS_LAGRANGE ? c->g_lagrange : c->g,
-                                    len);
-        if (r) fail(r);
-    }
-    // collects a lane: its commitments are written to the transcript in the order they were given
-    void commit_end_write(int lane) {
-        if (!ok()) return;
-        G1Jac js[MSM_MAX_BATCH];
-        const uint32_t cnt = c->lanes[lane].batch;
-        int r = ctx_msm_end_batch(c, lane, js);
-        if (r) return fail(r);
-        G1Affine af[MSM_MAX_BATCH];
-        jac_batch_to_affine(js, cnt, af);
-        for (uint32_t q = 0; q < cnt && ok(); q++)
-            if (!tr->write_point(af[q])) fail(ZK_EINVAL);  // identity: halo2 refuses to write it
     }
     // Lagrange values -> coefficients -> extended coset for a set of columns, several columns per launch
     struct Forms {
@@ -966,7 +201,7 @@ struct Prover {
     // the columns' coset forms are [3][n] coset-major, made by n-point transforms.  Decided once per proof (begin())
     bool cosets3 = false;
     // three or more contexts busy on the device (the regime in which reduction tails run on the main stream): decided once per
-    // proof (begin()); multi-column commitments are then not split into two passes (batch_flush)
+    // proof (begin()); multi-column commitments are then not split into two passes (Commits::flush)
     bool loaded = false;
     // (audit self-test, ZK_OPT_STREAM_AUDIT = 2: round 5's faulty form on purpose — the stream chosen per CALL, alternating, and no
     // join before a main-stream transform: the ledger must then refuse every proof whose transforms come in more than one call)
@@ -1031,10 +266,6 @@ struct Prover {
         }
     }
     // out = sum_j c_j * in_j (- sub0 on coefficient 0), any number of inputs: MAX_LC per launch
-    struct Term {
-        const Fr* poly;
-        Fr c;
-    };
     void lincomb_many(Fr* out, const std::vector<Term>& terms, bool sub0, const Fr& sub0_val, bool accumulate_first = false,
                       const std::vector<Fr>* sub_low = nullptr) {
         if (c->audit.on) {
@@ -1053,64 +284,20 @@ struct Prover {
             pk->lc_used += (uint32_t)terms.size();
             return;
         }
-        size_t done = 0;
-        bool first = !accumulate_first;
-        do {
-            LincombArgs a;
-            memset(&a, 0, sizeof(a));
-            a.out = out;
-            a.n = n;
-            const size_t take = std::min<size_t>(MAX_LC, terms.size() - done);
-            a.count = (uint32_t)take;
-            a.accumulate = first ? 0 : 1;
-            for (size_t j = 0; j < take; j++) {
-                a.in[j] = terms[done + j].poly;
-                a.len[j] = n;
-                a.c[j] = terms[done + j].c;
-                a.unit[j] = terms[done + j].c == Fr::one();
-            }
-            done += take;
-            if (done == terms.size() && sub0) {
-                a.sub0 = 1;
-                a.sub0_val = sub0_val;
-            }
-            if (done == terms.size() && sub_low) {
-                a.sub_low_n = (uint32_t)sub_low->size();
-                for (size_t t = 0; t < sub_low->size(); t++) a.sub_low[t] = (*sub_low)[t];
-            }
-            launch_lincomb(a, st);
-            first = false;
-        } while (done < terms.size());
+        lincomb_enqueue(st, out, n, terms, accumulate_first, sub0 ? &sub0_val : nullptr, sub_low ? sub_low->data() : nullptr,
+                        sub_low ? (uint32_t)sub_low->size() : 0u);
     }
     Fr xrot(const Fr& x, int r) const {
         Fr w = r >= 0 ? omega : omega_inv;
         return fe_mul(x, fr_pow(w, (uint64_t)(r >= 0 ? r : -r)));
     }
-    const Fr* col_val(const Col& col) const { return col.fixed ? pk->fixed_val[col.idx] : pk->adv_val[col.idx]; }
-    const Fr* col_coset(const Col& col) const { return col.fixed ? pk->fixed_coset[col.idx] : pk->adv_coset[col.idx]; }
 
     // h(X) on the extended coset (one lane per row, quotient.hip), divided by X^n - 1, back to coefficients:
     // the first (degree - 1) * n coefficients of h_ext are the h pieces
     int quotient(const Fr& beta, const Fr& gamma, const Fr& y) {
-        QuotientCosets qc;
-        for (uint32_t j = 0; j < lay.n_adv; j++) qc.adv.push_back(pk->adv_coset[j]);
-        for (uint32_t ci = 0; ci < lay.n_chunks; ci++) qc.z.push_back(pk->z_coset[ci]);
-        for (uint32_t l = 0; l < lay.n_lookups; l++) {
-            qc.lk_a.push_back(pk->lk_ap_coset[l]);
-            qc.lk_s.push_back(pk->lk_sp_coset[l]);
-            qc.lk_z.push_back(pk->lk_z_coset[l]);
-        }
-        qc.cosets3 = cosets3;
         xform_join();  // every coset form is complete
         if (!ok()) return rc;
-        if (c->audit.on) {
-            std::vector<const void*> rd;
-            for (auto* v : {&qc.adv, &qc.z, &qc.lk_a, &qc.lk_s, &qc.lk_z})
-                for (const Fr* q : *v) rd.push_back(q);
-            AV(rd, {pk->h_ext}, "quotient");
-        }
-        int r = pk_quotient(c, pk, qc, beta, gamma, y, true, pk->h_ext);
-        if (r) return r;
+        if (int r = quotient_of_workspace(c, st, pk, cosets3, beta, gamma, y)) return r;
         if (cosets3) return ctx_intt_cosets3(c, pk->h_ext, lay.k);
         return ctx_ntt(c, pk->h_ext, N, pk->h_ext, lay.ext_k, true, true, N);
     }
@@ -1235,27 +422,14 @@ struct Prover {
         // -- 1. advice
         // (many columns: one launch copies them all — the argument staging is reused by the later batched launches, each
         // preceded by a stream-ordered upload, so the host must not overwrite it before the upload has been consumed)
-        const bool many = lay.n_adv > BATCH_ARGS_MIN;
+        const bool many = advice_staged(lay);
         if (many) {
-            CopyPair* h = static_cast<CopyPair*>(pk->h_batch_args);
-            for (uint32_t j = 0; j < lay.n_adv; j++) h[j] = CopyPair{advice_dev[j], pk->adv_val[j]};
-            if (c->audit.on) {
-                std::vector<const void*> rd, wr;
-                for (uint32_t j = 0; j < lay.n_adv; j++) {
-                    rd.push_back(advice_dev[j]);
-                    wr.push_back(pk->adv_val[j]);
-                }
-                AV(rd, wr, "advice columns into the workspace");
-            }
-            if (hipMemcpyAsync(pk->d_batch_args, h, lay.n_adv * sizeof(CopyPair), hipMemcpyHostToDevice, st) != hipSuccess) return ZK_EHIP;
-            launch_copy_columns(static_cast<const CopyPair*>(pk->d_batch_args), lay.n_adv, n, st);
+            if (int r = advice_columns_staged(c, st, pk, advice_dev)) return r;
             if (aud_sync(c, st) != hipSuccess) return ZK_EHIP;
         }
         for (uint32_t j = 0; j < lay.n_adv; j++) {
-            if (!many) {
-                A({advice_dev[j]}, {pk->adv_val[j]}, "advice column into the workspace");
-                hipMemcpyAsync(pk->adv_val[j], advice_dev[j], (size_t)n * sizeof(Fr), hipMemcpyDeviceToDevice, st);
-            }
+            if (!many)
+                if (int r = advice_column(c, st, pk, advice_dev, j)) return r;
             set_rows(pk->adv_val[j], usable, draw(bf + 1));
         }
         draw(lay.n_adv);  // advice blinds (unused by KZG, still drawn)
@@ -1266,8 +440,9 @@ struct Prover {
         // (and the host's transcript work) would otherwise leave it idle.
         const uint32_t max_batch = ctx_msm_max_batch(c);
         bool adv_transformed = false;
+        CQ::Fifo af{{0}, {}, nullptr};  // the pipelined advice pass: in flight on lane 0 until theta is needed
         if (pipe) {
-            commit_begin(0, pk->adv_val[0], n, ZK_BASIS_LAGRANGE);
+            cq.begin(af, {CommitCol{pk->adv_val[0], tr}}, ZK_BASIS_LAGRANGE);
             if (xform_side()) {  // a lone proof: the advice column's forms are made under its own MSM pass
                 transforms({Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]}});
                 adv_transformed = true;
@@ -1275,36 +450,35 @@ struct Prover {
         } else {
             // several advice columns: whole batches of columns per MSM pass, up to MSM_LANES passes in flight,
             // each followed by its columns' transforms; collected in column order
-            LaneFifo f{{0, 1, 2}, {}};
+            CQ::Fifo f{{0, 1, 2}, {}, nullptr};
             for (uint32_t j0 = 0; j0 < lay.n_adv && ok(); j0 += max_batch) {
                 const uint32_t j1 = std::min(lay.n_adv, j0 + max_batch);
-                std::vector<const Fr*> cols;
-                for (uint32_t j = j0; j < j1; j++) cols.push_back(pk->adv_val[j]);
-                fifo_begin_batch(f, cols, n, ZK_BASIS_LAGRANGE);
+                std::vector<CommitCol> cols;
                 std::vector<Forms> fm;
-                for (uint32_t j = j0; j < j1; j++) fm.push_back(Forms{pk->adv_val[j], pk->adv_poly[j], pk->adv_coset[j]});
+                for (uint32_t j = j0; j < j1; j++) {
+                    cols.push_back(CommitCol{pk->adv_val[j], tr});
+                    fm.push_back(Forms{pk->adv_val[j], pk->adv_poly[j], pk->adv_coset[j]});
+                }
+                cq.begin(f, cols, ZK_BASIS_LAGRANGE);
                 transforms(fm);
             }
-            fifo_drain(f);
+            cq.drain(f);
         }
         if (!ok()) return rc;
 
         // -- 2. lookups: permuted input / table (single-expression lookups: theta-compression is the identity)
-        const uint32_t T = 1u << lay.lookup_bits;
-        Fr theta = Fr::zero();
         bool theta_done = false;
         auto squeeze_theta = [&]() {
             if (!theta_done) {
-                if (pipe) commit_end_write(0);
-                theta = tr->squeeze();
+                if (pipe) cq.drain(af);
+                tr->squeeze();
                 theta_done = true;
             }
         };
-        hipMemsetAsync(pk->lks.err, 0, 4, st);
         // a', s' of every lookup: batches of columns per MSM pass; their transforms (and, in the pipelined
         // case, the advice column's) follow the MSM heads so that they cover the tails
-        LaneFifo lf{pipe ? std::vector<int>{1, 2} : std::vector<int>{0, 1, 2}, {}};
-        Batcher lb{&lf, ZK_BASIS_LAGRANGE, max_batch, {}};
+        CQ::Fifo lf{pipe ? std::vector<int>{1, 2} : std::vector<int>{0, 1, 2}, {}, nullptr};
+        CQ::Batcher lb{&lf, ZK_BASIS_LAGRANGE, max_batch, loaded, {}};
         std::vector<uint32_t> due;
         auto lookup_transforms = [&](bool with_advice) {
             std::vector<Forms> fm;
@@ -1318,235 +492,103 @@ struct Prover {
         };
         if (!pipe) squeeze_theta();  // the advice commitments are all written: theta precedes the first a'
         {
-            // every lookup's permuted input / table pair in one set of launches (blockIdx.y = lookup)
-            LkPtrs lp;
-            memset(&lp, 0, sizeof(lp));
-            for (uint32_t l = 0; l < lay.n_lookups; l++) {
-                if (lay.single) {
-                    A({pk->adv_val[0]}, {pk->lk_in[l]}, "lookup input = q_lookup x advice");
-                    launch_mul(pk->lk_in[l], pk->fixed_val[lay.fx_qlookup], pk->adv_val[0], n, st);
-                    lp.inp[l] = pk->lk_in[l];
-                } else {
-                    lp.inp[l] = pk->adv_val[lay.n_gate + l];
-                }
-                lp.ap[l] = pk->lk_ap[l];
-                lp.sp[l] = pk->lk_sp[l];
-            }
-            if (c->audit.on) {
-                std::vector<const void*> rd, wr;
-                for (uint32_t l = 0; l < lay.n_lookups; l++) {
-                    rd.push_back(lp.inp[l]);
-                    wr.push_back(lp.ap[l]);
-                    wr.push_back(lp.sp[l]);
-                }
-                AV(rd, wr, "lookup permutation");
-            }
-            launch_lookup_permute(lp, lay.n_lookups, usable, T, pk->lks, st);
+            std::vector<LkItem> items;
+            for (uint32_t l = 0; l < lay.n_lookups; l++) items.push_back(LkItem{pk, pk->adv_val.data(), l, pk->lk_ap[l], pk->lk_sp[l]});
+            if (int r = lookup_permute(c, st, lay, items, pk->lks)) return r;
         }
         for (uint32_t l = 0; l < lay.n_lookups && ok(); l++) {
             set_rows(pk->lk_ap[l], usable, draw(bf + 1));
             set_rows(pk->lk_sp[l], usable, draw(bf + 1));
             draw(2);
-            batch_add(lb, pk->lk_ap[l]);
-            batch_add(lb, pk->lk_sp[l]);
+            cq.add(lb, pk->lk_ap[l], tr);
+            cq.add(lb, pk->lk_sp[l], tr);
             due.push_back(l);
             if (lb.pend.empty()) lookup_transforms(false);
         }
-        batch_flush(lb);
+        cq.flush(lb);
         lookup_transforms(pipe && !adv_transformed);
         {
             // one check for all lookups (the flag accumulates): an input outside the table is halo2's
             // ConstraintSystemFailure; nothing has been written for the lookups yet
-            uint32_t* err = reinterpret_cast<uint32_t*>(c->host_small);
-            if (hipMemcpyAsync(err, pk->lks.err, 4, hipMemcpyDeviceToHost, st) != hipSuccess || aud_sync(c, st) != hipSuccess)
-                return ZK_EHIP;
-            if (*err) {
+            bool bad = false;
+            if (int r = lookup_permute_failed(c, st, pk->lks, &bad)) return r;
+            if (bad) {
                 ctx_msm_drain(c);
                 return ZK_EWITNESS;
             }
         }
         squeeze_theta();
-        fifo_drain(lf);
-        squeeze_theta();
-        (void)theta;
+        cq.drain(lf);
         if (!ok()) return rc;
         const Fr beta = tr->squeeze();
         const Fr gamma = tr->squeeze();
 
         // -- 5 (early). vanishing argument: the random polynomial does not depend on any challenge.
         // Its n draws come after the grand products' draws in halo2's order: reserve that block range.
+        CQ::Fifo rf{{0}, {}, nullptr};
         {
             const uint64_t skip = (uint64_t)lay.n_chunks * (bf + 1) + (uint64_t)lay.n_lookups * (bf + 1);
             ChaChaKey key;
             memcpy(key.w, rng.key, 32);
             A({}, {pk->random_poly}, "random polynomial");
             launch_chacha_fr(key, rng.block + skip, pk->random_poly, n, st);
-            commit_begin(0, pk->random_poly, n, ZK_BASIS_MONOMIAL);
+            cq.begin(rf, {CommitCol{pk->random_poly, tr}}, ZK_BASIS_MONOMIAL);
         }
 
         // -- 3. permutation grand products.  All z columns (permutation chunks, then lookups) are committed in
         // batches on lanes 1 and 2; their transforms follow each batch's MSM head.
-        LaneFifo zf{{1, 2}, {}};
-        Batcher zb{&zf, ZK_BASIS_LAGRANGE, max_batch, {}};
+        CQ::Fifo zf{{1, 2}, {}, nullptr};
+        CQ::Batcher zb{&zf, ZK_BASIS_LAGRANGE, max_batch, loaded, {}};
         std::vector<Forms> zdue;
         auto z_transforms = [&]() {
             transforms(zdue);
             zdue.clear();
         };
         {
-            // numerators / denominators of every product, then all scans in one batch; a zero denominator
-            // anywhere (or ZKMI355_BATCH_INVERT=1) sends every product down the batch-inversion path
+            // numerators / denominators of every product, then all scans in one batch (the argument staging of the
+            // many-column shapes may still be in use: the host waits before it rewrites it)
             const uint32_t nprod = lay.n_chunks + lay.n_lookups;
-            std::vector<GpItem> items(nprod);
-            std::vector<Fr*> zs;
-            const uint32_t nblk = gp_blocks(n);
-            const Fr delta = fr_delta();
-            Fr dcur = Fr::one();
-            const bool many_chunks = lay.n_chunks > BATCH_ARGS_MIN;
-            if (many_chunks && aud_sync(c, st) != hipSuccess) return ZK_EHIP;  // the argument staging may still be in use
-            for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-                PermArgs a;
-                memset(&a, 0, sizeof(a));
-                a.n = n;
-                const uint32_t lo = ci * lay.chunk_len, hi = std::min<uint32_t>((uint32_t)lay.perm_cols.size(), lo + lay.chunk_len);
-                a.ncols = hi - lo;
-                for (uint32_t p = lo; p < hi; p++) {
-                    a.values[p - lo] = col_val(lay.perm_cols[p]);
-                    a.sigma[p - lo] = pk->sigma_val[p];
-                    a.delta[p - lo] = dcur;
-                    dcur = fe_mul(dcur, delta);
-                }
-                a.tw = tw;
-                a.beta = beta;
-                a.gamma = gamma;
-                a.num = pk->gp_num[ci];
-                a.den = pk->gp_den[ci];
-                if (c->audit.on) {
-                    std::vector<const void*> rd;
-                    for (uint32_t q = 0; q < a.ncols; q++) rd.push_back(a.values[q]);
-                    AV(rd, {a.num, a.den}, "permutation numerators / denominators");  // (the batched form launches below, same stream)
-                }
-                if (many_chunks) static_cast<PermArgs*>(pk->h_batch_args)[ci] = a;
-                else launch_perm_numden(a, st);
-                zs.push_back(pk->z_val[ci]);
-            }
-            if (many_chunks) {
-                if (hipMemcpyAsync(pk->d_batch_args, pk->h_batch_args, lay.n_chunks * sizeof(PermArgs), hipMemcpyHostToDevice, st) != hipSuccess)
-                    return ZK_EHIP;
-                launch_perm_numden_batch(static_cast<const PermArgs*>(pk->d_batch_args), lay.n_chunks, n, st);
-            }
-            const bool many_lookups = lay.n_lookups > BATCH_ARGS_MIN;
-            if (many_lookups && aud_sync(c, st) != hipSuccess) return ZK_EHIP;  // the staging is rewritten below
-            for (uint32_t l = 0; l < lay.n_lookups; l++) {
-                const Fr* inp = lay.single ? pk->lk_in[l] : pk->adv_val[lay.n_gate + l];
-                const uint32_t p = lay.n_chunks + l;
-                A({pk->lk_ap[l], pk->lk_sp[l], inp}, {pk->gp_num[p], pk->gp_den[p]}, "lookup numerators / denominators");
-                if (many_lookups)
-                    static_cast<LkNumDenArgs*>(pk->h_batch_args)[l] =
-                        LkNumDenArgs{pk->lk_ap[l], pk->lk_sp[l], inp, pk->fixed_val[lay.fx_table], pk->gp_num[p], pk->gp_den[p]};
-                else
-                    launch_lk_numden(pk->lk_ap[l], pk->lk_sp[l], inp, pk->fixed_val[lay.fx_table], beta, gamma, pk->gp_num[p], pk->gp_den[p], n,
-                                     st);
-                zs.push_back(pk->lk_z[l]);
-            }
-            if (many_lookups) {
-                if (hipMemcpyAsync(pk->d_batch_args, pk->h_batch_args, lay.n_lookups * sizeof(LkNumDenArgs), hipMemcpyHostToDevice, st) !=
-                    hipSuccess)
-                    return ZK_EHIP;
-                launch_lk_numden_batch(static_cast<const LkNumDenArgs*>(pk->d_batch_args), lay.n_lookups, beta, gamma, n, st);
-            }
-            for (uint32_t p = 0; p < nprod; p++) {
-                items[p].num = pk->gp_num[p];
-                items[p].den = pk->gp_den[p];
-                items[p].loc_p = pk->gp_loc_p[p];
-                items[p].loc_r = pk->gp_loc_r[p];
-                items[p].tot_p = pk->gp_tot + (size_t)2 * nblk * p;
-                items[p].tot_r = items[p].tot_p + nblk;
-                items[p].z = zs[p];
-                items[p].chain = (p > 0 && p < lay.n_chunks) ? 1u : 0u;  // chunk ci starts from chunk ci-1's z at row `usable`
-                items[p].pad_ = 0;
-            }
-            Fr* q_dev = pk->gp_scal;
-            Fr* qinv_dev = pk->gp_scal + nprod;
-            Fr* k_dev = pk->gp_scal + 2 * (size_t)nprod;
-            Fr* init_dev = pk->gp_scal + 3 * (size_t)nprod;
-            if (c->audit.on) {
-                std::vector<const void*> rd, wr;
-                for (uint32_t p = 0; p < nprod; p++) {
-                    rd.push_back(pk->gp_num[p]);
-                    rd.push_back(pk->gp_den[p]);
-                    wr.push_back(zs[p]);
-                }
-                AV(rd, wr, "grand products");  // (scan + apply, or the batch_invert fallback: same buffers, same stream)
-            }
-            bool fast = !c->opt_gp_batch_invert;  // zk_ctx_set_option(ZK_OPT_GP_BATCH_INVERT)
-            if (fast) {
-                if (hipMemcpyAsync(pk->d_gp_items, items.data(), nprod * sizeof(GpItem), hipMemcpyHostToDevice, st) != hipSuccess) return ZK_EHIP;
-                launch_gp_batch_scan(pk->d_gp_items, nprod, n, q_dev, st);
-                if (hipMemcpyAsync(pk->gp_host, q_dev, nprod * sizeof(Fr), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    aud_sync(c, st) != hipSuccess)
-                    return ZK_EHIP;
-                // all inverses with one field inversion
-                Fr* q = pk->gp_host;
-                Fr* qi = pk->gp_host + nprod;
-                Fr run = Fr::one();
-                for (uint32_t p = 0; p < nprod && fast; p++) {
-                    if (q[p].is_zero()) fast = false;
-                    qi[p] = run;
-                    run = fe_mul(run, q[p]);
-                }
-                if (fast) {
-                    Fr inv = fe_inv_fast(run);
-                    for (uint32_t p = nprod; p-- > 0;) {
-                        const Fr t = fe_mul(inv, qi[p]);
-                        inv = fe_mul(inv, q[p]);
-                        qi[p] = t;
-                    }
-                    if (hipMemcpyAsync(qinv_dev, qi, nprod * sizeof(Fr), hipMemcpyHostToDevice, st) != hipSuccess) return ZK_EHIP;
-                    launch_gp_batch_apply(pk->d_gp_items, nprod, n, usable, qinv_dev, k_dev, init_dev, st);
-                }
-            }
-            if (!fast) {
-                // a zero denominator: halo2's batch_invert semantics (0 -> 0), product by product
-                for (uint32_t p = 0; p < nprod; p++) {
-                    launch_frac(pk->gp_num[p], pk->gp_den[p], pk->t_frac, n, st);
-                    const Fr* prev = items[p].chain ? zs[p - 1] + usable : nullptr;
-                    launch_prefix_product(pk->t_frac, zs[p], n, prev, Fr::one(), pk->t_a, pk->t_small, st);
-                }
-            }
+            std::vector<Fr*> zs(pk->z_val);
+            zs.insert(zs.end(), pk->lk_z.begin(), pk->lk_z.end());
+            if (lay.n_chunks > BATCH_ARGS_MIN && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
+            if (int r = perm_numden_enqueue(c, st, pk, pk->adv_val.data(), tw, beta, gamma, true)) return r;
+            if (lay.n_lookups > BATCH_ARGS_MIN && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
+            if (int r = lk_numden_enqueue(c, st, pk, pk->adv_val.data(), pk->lk_ap.data(), pk->lk_sp.data(), beta, gamma, lay.n_chunks, true, false))
+                return r;
+            if (int r = grand_products(c, st, lay, {GpGroup{pk, zs.data(), nprod, lay.n_chunks}}, GpScratch{pk->d_gp_items, pk->gp_scal, pk->gp_host}))
+                return r;
             // blinding rows and commitments, in halo2's order (chunks, then lookups)
             for (uint32_t p = 0; p < nprod && ok(); p++) {
                 set_rows(zs[p], n - bf, draw(bf));
                 draw(1);
-                batch_add(zb, zs[p]);
+                cq.add(zb, zs[p], tr);
                 if (p < lay.n_chunks) zdue.push_back(Forms{pk->z_val[p], pk->z_poly[p], pk->z_coset[p]});
                 else zdue.push_back(Forms{pk->lk_z[p - lay.n_chunks], pk->lk_z_poly[p - lay.n_chunks], pk->lk_z_coset[p - lay.n_chunks]});
                 if (zb.pend.empty()) z_transforms();
             }
         }
-        batch_flush(zb);
+        cq.flush(zb);
         z_transforms();
-        fifo_drain(zf);
+        cq.drain(zf);
         if (!ok()) return rc;
 
         // -- 5. collect the random polynomial's commitment (its draws happen here in stream order)
         rng.block += n;
         draw(1);
-        commit_end_write(0);
+        cq.drain(rf);
         if (!ok()) return rc;
         const Fr y = tr->squeeze();
 
         // -- 6. quotient (every coefficient / coset form was produced behind its commitment above)
-        if (!ok()) return rc;
         if (int r = quotient(beta, gamma, y)) return r;
         draw(lay.n_h);  // h-piece blinds
         {
             // the h pieces are contiguous n-coefficient slices of the quotient: one MSM pass for all of them
-            LaneFifo hf{{0, 1, 2}, {}};
-            Batcher hb{&hf, ZK_BASIS_MONOMIAL, max_batch, {}};
-            for (uint32_t i = 0; i < lay.n_h && ok(); i++) batch_add(hb, pk->h_ext + (size_t)i * n);
-            batch_flush(hb);
-            fifo_drain(hf);
+            CQ::Fifo hf{{0, 1, 2}, {}, nullptr};
+            CQ::Batcher hb{&hf, ZK_BASIS_MONOMIAL, max_batch, loaded, {}};
+            for (uint32_t i = 0; i < lay.n_h && ok(); i++) cq.add(hb, pk->h_ext + (size_t)i * n, tr);
+            cq.flush(hb);
+            cq.drain(hf);
         }
         if (!ok()) return rc;
         const Fr x = tr->squeeze();
@@ -1558,29 +600,14 @@ struct Prover {
         EvIdx ix;
         build_evals(ev, ix);
         if (ev.size() > pk->max_evals) return ZK_ESTATE;
-        {
-            EvalItem* ha = pk->h_evargs;
-            for (size_t i = 0; i < ev.size(); i++) {
-                ha[i].poly = ev[i].poly;
-                ha[i].x = xrot(x, ev[i].rot);
-            }
-            if (c->audit.on) {
-                std::vector<const void*> rd;
-                for (size_t i = 0; i < ev.size(); i++) rd.push_back(ev[i].poly);
-                AV(rd, {pk->ev_out}, "evaluations");
-                A({pk->ev_out}, {pk->tail_host}, "evaluations to the host");
-            }
-            hipEventRecord(c->ev[ZK_T_EVAL][0], st);
-            launch_eval_batch(ha, pk->d_evargs, (uint32_t)ev.size(), n, pk->ev_scratch, pk->ev_out, st);
-            hipEventRecord(c->ev[ZK_T_EVAL][1], st);
-            c->ev_valid[ZK_T_EVAL] = true;
-            if (hipMemcpyAsync(pk->tail_host, pk->ev_out, ev.size() * sizeof(Fr), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                aud_sync(c, st) != hipSuccess)
-                return ZK_EHIP;
-            c->audit.host_read(pk->tail_host, "evaluations read by the host");
-            for (size_t i = 0; i < ev.size(); i++) ev[i].eval = pk->tail_host[i];
-        HT("evals on host");
+        for (size_t i = 0; i < ev.size(); i++) {
+            pk->h_evargs[i].poly = ev[i].poly;
+            pk->h_evargs[i].x = xrot(x, ev[i].rot);
         }
+        if (int r = evaluate_enqueue(c, st, EvalBufs{pk->h_evargs, pk->d_evargs, pk->ev_scratch, pk->ev_out, pk->tail_host}, (uint32_t)ev.size(), n))
+            return r;
+        for (size_t i = 0; i < ev.size(); i++) ev[i].eval = pk->tail_host[i];
+        HT("evals on host");
         for (size_t i = 0; i < ix.n_written; i++) tr->write_scalar(ev[i].eval);
         const std::vector<Q> queries = queries_from_evals(ev, ix);
         if (!ok()) return rc;
@@ -1641,11 +668,11 @@ struct Prover {
         std::vector<const Fr*> wit;
         if (int r = gwc_stage1(queries, x, wit)) return r;
         // the witness polynomials need no challenge in between: all of them go through one MSM pass
-        LaneFifo wf{{0, 1, 2}, {}};
-        Batcher wb{&wf, ZK_BASIS_MONOMIAL, max_batch, {}};
-        for (const Fr* w : wit) batch_add(wb, w);
-        batch_flush(wb);
-        fifo_drain(wf);
+        CQ::Fifo wf{{0, 1, 2}, {}, nullptr};
+        CQ::Batcher wb{&wf, ZK_BASIS_MONOMIAL, max_batch, loaded, {}};
+        for (const Fr* w : wit) cq.add(wb, w, tr);
+        cq.flush(wb);
+        cq.drain(wf);
         return rc;
     }
 
@@ -1841,11 +868,11 @@ struct Prover {
     int open_shplonk(const std::vector<Q>& queries, const Fr& x) {
         Shplonk S;
         if (int r = shplonk_stage1(queries, x, S)) return r;
-        commit_write(S.hx, n, ZK_BASIS_MONOMIAL);
+        commit_write(S.hx, ZK_BASIS_MONOMIAL);
         if (!ok()) return rc;
         const Fr* last = nullptr;
         if (int r = shplonk_stage2(S, &last)) return r;
-        commit_write(last, n, ZK_BASIS_MONOMIAL);
+        commit_write(last, ZK_BASIS_MONOMIAL);
         return rc;
     }
 };
@@ -1938,317 +965,6 @@ ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, co
     return ZK_OK;
 }
 
-// ===================================================== phase-level entry points ==
-// For a host that keeps halo2's own prover flow — its transcript, its RNG, its blinding — and off-loads phase by phase
-// (examples/prove_host_phases.cpp): the provers of plonk/lookup, plonk/permutation and plonk/vanishing that
-// sit between the commitments, over resident columns.  They run the very kernels zk_prove runs; each call is complete on return.
-namespace {
-struct PhaseCtx {
-    zk_ctx* c;
-    zk_pk_rec* pk;
-    std::vector<Fr*> adv;
-};
-// resolves the key and the advice handles (n rows each, Lagrange values, Montgomery)
-int phase_open(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, PhaseCtx& out) {
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    zk_pk_rec* pk = it->second;
-    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
-    if (n_advice != pk->lay.n_adv) return ZK_EINVAL;
-    out.c = c;
-    out.pk = pk;
-    for (size_t j = 0; j < n_advice; j++) {
-        auto pit = c->polys.find(advice[j]);
-        if (pit == c->polys.end() || pit->second.n != pk->lay.n) return ZK_EINVAL;
-        out.adv.push_back(pit->second.ptr);
-    }
-    return ctx_bind(c);
-}
-Fr* phase_vec(zk_ctx* c, zk_poly h, size_t n) {
-    auto it = c->polys.find(h);
-    return (it == c->polys.end() || it->second.n != n) ? nullptr : it->second.ptr;
-}
-// the compressed input expression of lookup l: the lookup advice column, or q_lookup * a for the one-column shape (into pk->lk_in)
-const Fr* phase_lookup_input(PhaseCtx& P, uint32_t l) {
-    const Layout& lay = P.pk->lay;
-    if (!lay.single) return P.adv[lay.n_gate + l];
-    launch_mul(P.pk->lk_in[l], P.pk->fixed_val[lay.fx_qlookup], P.adv[0], lay.n, P.c->stream);
-    return P.pk->lk_in[l];
-}
-// grand products z[p] of `items` (num / den already launched), halo2's semantics: one scan, one host round trip; a zero
-// denominator takes the batch_invert form.  chain[p]: product p starts from product p - 1's value at row `usable`.
-int phase_grand_products(zk_ctx* c, zk_pk_rec* pk, const std::vector<Fr*>& num, const std::vector<Fr*>& den, const std::vector<Fr*>& z,
-                         const std::vector<uint32_t>& chain) {
-    const Layout& lay = pk->lay;
-    const uint32_t n = lay.n, nprod = (uint32_t)z.size(), nblk = gp_blocks(n), usable = lay.usable;
-    hipStream_t st = c->stream;
-    std::vector<GpItem> items(nprod);
-    for (uint32_t p = 0; p < nprod; p++) {
-        items[p].num = num[p];
-        items[p].den = den[p];
-        items[p].loc_p = pk->gp_loc_p[p];
-        items[p].loc_r = pk->gp_loc_r[p];
-        items[p].tot_p = pk->gp_tot + (size_t)2 * nblk * p;
-        items[p].tot_r = items[p].tot_p + nblk;
-        items[p].z = z[p];
-        items[p].chain = chain[p];
-        items[p].pad_ = 0;
-    }
-    Fr *q_dev = pk->gp_scal, *qinv_dev = pk->gp_scal + nprod, *k_dev = pk->gp_scal + 2 * (size_t)nprod, *init_dev = pk->gp_scal + 3 * (size_t)nprod;
-    bool fast = !c->opt_gp_batch_invert;
-    if (fast) {
-        HIPCHK(c, hipMemcpyAsync(pk->d_gp_items, items.data(), nprod * sizeof(GpItem), hipMemcpyHostToDevice, st));
-        launch_gp_batch_scan(pk->d_gp_items, nprod, n, q_dev, st);
-        HIPCHK(c, hipMemcpyAsync(pk->gp_host, q_dev, nprod * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, aud_sync(c, st));
-        Fr *q = pk->gp_host, *qi = pk->gp_host + nprod;
-        Fr run = Fr::one();
-        for (uint32_t p = 0; p < nprod && fast; p++) {
-            if (q[p].is_zero()) fast = false;
-            qi[p] = run;
-            run = fe_mul(run, q[p]);
-        }
-        if (fast) {
-            Fr inv = fe_inv_fast(run);
-            for (uint32_t p = nprod; p-- > 0;) {
-                const Fr t = fe_mul(inv, qi[p]);
-                inv = fe_mul(inv, q[p]);
-                qi[p] = t;
-            }
-            HIPCHK(c, hipMemcpyAsync(qinv_dev, qi, nprod * sizeof(Fr), hipMemcpyHostToDevice, st));
-            launch_gp_batch_apply(pk->d_gp_items, nprod, n, usable, qinv_dev, k_dev, init_dev, st);
-        }
-    }
-    if (!fast) {
-        for (uint32_t p = 0; p < nprod; p++) {
-            launch_frac(num[p], den[p], pk->t_frac, n, st);
-            const Fr* prev = chain[p] ? z[p - 1] + usable : nullptr;
-            launch_prefix_product(pk->t_frac, z[p], n, prev, Fr::one(), pk->t_a, pk->t_small, st);
-        }
-    }
-    HIPCHK(c, aud_sync(c, st));
-    return hipGetLastError() == hipSuccess ? ZK_OK : ZK_EHIP;
-}
-}  // namespace
-
-namespace {
-// every output vector of a phase call is written by its own blocks of a batched launch: the same vector twice among the
-// outputs, or an output that another item of the call reads, is a data race that yields garbage — refused before anything is
-// launched
-bool phase_outputs_ok(const std::vector<const Fr*>& outs, const std::vector<const Fr*>& ins) {
-    for (size_t i = 0; i < outs.size(); i++) {
-        for (size_t j = i + 1; j < outs.size(); j++)
-            if (outs[i] == outs[j]) return false;
-        for (const Fr* v : ins)
-            if (outs[i] == v) return false;
-    }
-    return true;
-}
-}  // namespace
-
-ZK_API(zk_lookup_permute, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, zk_poly* permuted_input, zk_poly* permuted_table, size_t n_lookups), (c, h, advice, n_advice, permuted_input, permuted_table, n_lookups)) {
-    if (!c || !advice || !permuted_input || !permuted_table) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PhaseCtx P;
-    int rc = phase_open(c, h, advice, n_advice, P);
-    if (rc) return rc;
-    const Layout& lay = P.pk->lay;
-    if (n_lookups != lay.n_lookups) return ZK_EINVAL;
-    LkPtrs lp;
-    memset(&lp, 0, sizeof(lp));
-    std::vector<const Fr*> outs, ins(P.adv.begin(), P.adv.end());
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        Fr *a = phase_vec(c, permuted_input[l], lay.n), *s = phase_vec(c, permuted_table[l], lay.n);
-        if (!a || !s) return ZK_EINVAL;
-        lp.ap[l] = a;
-        lp.sp[l] = s;
-        outs.push_back(a);
-        outs.push_back(s);
-    }
-    if (!phase_outputs_ok(outs, ins)) return ZK_EINVAL;  // (a'[l] = s'[m], a repeated handle, an advice column as an output)
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemsetAsync(P.pk->lks.err, 0, 4, st));
-    for (uint32_t l = 0; l < lay.n_lookups; l++) lp.inp[l] = phase_lookup_input(P, l);
-    launch_lookup_permute(lp, lay.n_lookups, lay.usable, 1u << lay.lookup_bits, P.pk->lks, st);
-    uint32_t* err = reinterpret_cast<uint32_t*>(c->host_small);
-    HIPCHK(c, hipMemcpyAsync(err, P.pk->lks.err, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, aud_sync(c, st));
-    return *err ? ZK_EWITNESS : ZK_OK;
-}
-
-ZK_API(zk_lookup_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const zk_poly* permuted_input, const zk_poly* permuted_table, size_t n_lookups, const uint64_t beta[4], const uint64_t gamma[4], zk_poly* z_out), (c, h, advice, n_advice, permuted_input, permuted_table, n_lookups, beta, gamma, z_out)) {
-    if (!c || !advice || !permuted_input || !permuted_table || !beta || !gamma || !z_out) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PhaseCtx P;
-    int rc = phase_open(c, h, advice, n_advice, P);
-    if (rc) return rc;
-    zk_pk_rec* pk = P.pk;
-    const Layout& lay = pk->lay;
-    if (n_lookups != lay.n_lookups) return ZK_EINVAL;
-    Fr b, g;
-    memcpy(&b, beta, 32);
-    memcpy(&g, gamma, 32);
-    std::vector<Fr*> num, den, z;
-    std::vector<uint32_t> chain;
-    std::vector<const Fr*> outs, ins(P.adv.begin(), P.adv.end()), av, sv;
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        const Fr *a = phase_vec(c, permuted_input[l], lay.n), *s = phase_vec(c, permuted_table[l], lay.n);
-        Fr* zl = phase_vec(c, z_out[l], lay.n);
-        if (!a || !s || !zl) return ZK_EINVAL;
-        av.push_back(a);
-        sv.push_back(s);
-        ins.push_back(a);
-        ins.push_back(s);
-        outs.push_back(zl);
-        z.push_back(zl);
-    }
-    if (!phase_outputs_ok(outs, ins)) return ZK_EINVAL;  // (before the first launch: a repeated z, or a z that some lookup reads)
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        const Fr* inp = phase_lookup_input(P, l);
-        launch_lk_numden(av[l], sv[l], inp, pk->fixed_val[lay.fx_table], b, g, pk->gp_num[l], pk->gp_den[l], lay.n, c->stream);
-        num.push_back(pk->gp_num[l]);
-        den.push_back(pk->gp_den[l]);
-        chain.push_back(0);
-    }
-    return phase_grand_products(c, pk, num, den, z, chain);
-}
-
-ZK_API(zk_permutation_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint64_t beta[4], const uint64_t gamma[4], zk_poly* z_out, size_t n_chunks), (c, h, advice, n_advice, beta, gamma, z_out, n_chunks)) {
-    if (!c || !advice || !beta || !gamma || !z_out) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PhaseCtx P;
-    int rc = phase_open(c, h, advice, n_advice, P);
-    if (rc) return rc;
-    zk_pk_rec* pk = P.pk;
-    const Layout& lay = pk->lay;
-    if (n_chunks != lay.n_chunks) return ZK_EINVAL;
-    Fr b, g;
-    memcpy(&b, beta, 32);
-    memcpy(&g, gamma, 32);
-    const Fr* tw = nullptr;
-    if ((rc = ctx_get_twiddles(c, lay.k, &tw))) return rc;
-    std::vector<Fr*> num, den, z;
-    std::vector<uint32_t> chain;
-    const Fr delta = fr_delta();
-    Fr dcur = Fr::one();
-    {
-        std::vector<const Fr*> outs, ins(P.adv.begin(), P.adv.end());
-        for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-            const Fr* zc = phase_vec(c, z_out[ci], lay.n);
-            if (!zc) return ZK_EINVAL;
-            outs.push_back(zc);
-        }
-        if (!phase_outputs_ok(outs, ins)) return ZK_EINVAL;  // (before the first launch: a repeated z, an advice column as z)
-    }
-    for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-        Fr* zc = phase_vec(c, z_out[ci], lay.n);
-        PermArgs a;
-        memset(&a, 0, sizeof(a));
-        a.n = lay.n;
-        const uint32_t lo = ci * lay.chunk_len, hi = std::min<uint32_t>((uint32_t)lay.perm_cols.size(), lo + lay.chunk_len);
-        a.ncols = hi - lo;
-        for (uint32_t p = lo; p < hi; p++) {
-            const Col& col = lay.perm_cols[p];
-            a.values[p - lo] = col.fixed ? pk->fixed_val[col.idx] : P.adv[col.idx];
-            a.sigma[p - lo] = pk->sigma_val[p];
-            a.delta[p - lo] = dcur;
-            dcur = fe_mul(dcur, delta);
-        }
-        a.tw = tw;
-        a.beta = b;
-        a.gamma = g;
-        a.num = pk->gp_num[ci];
-        a.den = pk->gp_den[ci];
-        launch_perm_numden(a, c->stream);
-        num.push_back(pk->gp_num[ci]);
-        den.push_back(pk->gp_den[ci]);
-        z.push_back(zc);
-        chain.push_back(ci > 0 ? 1u : 0u);
-    }
-    return phase_grand_products(c, pk, num, den, z, chain);
-}
-
-// a copy of one of the key's own polynomials (coefficient form) in a caller's vector: what a phase-driving host evaluates and
-// opens beside its own columns (the fixed and permutation polynomials of the ProvingKey)
-ZK_API(zk_pk_export_poly, (zk_ctx* c, zk_pk h, int which, size_t index, zk_poly dst), (c, h, which, index, dst)) {
-    if (!c) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->pks.find(h);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    zk_pk_rec* pk = it->second;
-    if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
-    const std::vector<Fr*>* v = which == ZK_PK_FIXED_POLY ? &pk->fixed_poly : which == ZK_PK_SIGMA_POLY ? &pk->sigma_poly : nullptr;
-    if (!v || index >= v->size()) return ZK_EINVAL;
-    Fr* d = phase_vec(c, dst, pk->lay.n);
-    if (!d) return ZK_EINVAL;
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(d, (*v)[index], (size_t)pk->lay.n * sizeof(Fr), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, aud_sync(c, c->stream));
-    return ZK_OK;
-}
-
-// the vanishing argument's random polynomial: coefficient i = Fr::random of ChaCha20 block first_block + i under `key` — the
-// stream `ChaCha20Rng::from_seed(key)` yields when every draw is an Fr::random (one 64-byte block each), i.e. what the host's
-// RNG would give for draws first_block .. first_block + n - 1; the host then advances its own RNG by n draws
-ZK_API(zk_random_poly, (zk_ctx* c, const uint8_t chacha_key[32], uint64_t first_block, zk_poly out), (c, chacha_key, first_block, out)) {
-    if (!c || !chacha_key) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->polys.find(out);
-    if (it == c->polys.end() || it->second.n == 0 || it->second.n > ((size_t)1 << 28)) return ZK_EINVAL;
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    ChaChaKey key;
-    memcpy(key.w, chacha_key, 32);
-    launch_chacha_fr(key, first_block, it->second.ptr, (uint32_t)it->second.n, c->stream);
-    HIPCHK(c, aud_sync(c, c->stream));
-    return ZK_OK;
-}
-
-// out = sum_j coeffs[j] * in[j] - (sub_low[0] + sub_low[1] X + ..): the multi-open provers' linear combinations (GWC subtracts the
-// combined evaluation, SHPLONK the combined remainder polynomial of a rotation set) and h(X) = sum x^(n i) h_i
-ZK_API(zk_poly_lincomb, (zk_ctx* c, zk_poly out, const zk_poly* in, const uint64_t* coeffs, size_t count, const uint64_t* sub_low, size_t n_low), (c, out, in, coeffs, count, sub_low, n_low)) {
-    if (!c || !in || !coeffs || count == 0 || n_low > 8 || (n_low && !sub_low)) return ZK_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto oit = c->polys.find(out);
-    if (oit == c->polys.end() || oit->second.n > 0xffffffffu) return ZK_EINVAL;
-    const size_t n = oit->second.n;
-    std::vector<const Fr*> src(count);
-    for (size_t j = 0; j < count; j++) {
-        auto it = c->polys.find(in[j]);
-        if (it == c->polys.end() || it->second.n != n || it->second.ptr == oit->second.ptr) return ZK_EINVAL;
-        src[j] = it->second.ptr;
-    }
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    size_t done = 0;
-    bool first = true;
-    do {
-        LincombArgs a;
-        memset(&a, 0, sizeof(a));
-        a.out = oit->second.ptr;
-        a.n = (uint32_t)n;
-        const size_t take = std::min<size_t>(MAX_LC, count - done);
-        a.count = (uint32_t)take;
-        a.accumulate = first ? 0 : 1;
-        for (size_t j = 0; j < take; j++) {
-            a.in[j] = src[done + j];
-            a.len[j] = (uint32_t)n;
-            memcpy(&a.c[j], coeffs + 4 * (done + j), 32);
-            a.unit[j] = a.c[j] == Fr::one();
-        }
-        done += take;
-        if (done == count && n_low) {  // the low-degree polynomial subtracted from the first n_low coefficients
-            a.sub_low_n = (uint32_t)n_low;
-            memcpy(a.sub_low, sub_low, n_low * 32);
-        }
-        launch_lincomb(a, c->stream);
-        first = false;
-    } while (done < count);
-    HIPCHK(c, aud_sync(c, c->stream));
-    return ZK_OK;
-}
-
 // create_proof for `batch` independent proofs of one key in lock-step (prover_batch.h)
 ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, size_t n_advice, const uint8_t* rng_seeds, int transcript, int scheme, uint8_t* proofs_out, size_t proof_stride, size_t* proof_len), (c, h, batch, advice, n_advice, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len)) {
     if (!c || !advice || !rng_seeds || !proof_len || batch == 0 || batch > ZK_PROVE_BATCH_MAX) return ZK_EINVAL;
@@ -2309,14 +1025,3 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     return ZK_OK;
 }
 
-ZK_API(zk_poly_upload_canonical, (zk_ctx* c, zk_poly h, const uint64_t* host_canonical, size_t n), (c, h, host_canonical, n)) {
-    int rc = zk_poly_upload(c, h, host_canonical, n);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->polys.find(h);
-    if (it == c->polys.end()) return ZK_EINVAL;
-    if ((rc = ctx_bind(c))) return rc;
-    launch_to_mont(it->second.ptr, (uint32_t)n, c->stream);
-    if (aud_sync(c, c->stream) != hipSuccess) return ZK_EHIP;
-    return ZK_OK;
-}

@@ -61,7 +61,7 @@ struct Rule {
     std::vector<int> pool(int foreign) {
         for (int i = 0; i < foreign; i++) make();
         std::vector<int> q(POOL_STREAMS);
-        for (int layer = 0; layer < 2; layer++) {  // the pool's creation order (engine.hip pool_prime)
+        for (int layer = 0; layer < 2; layer++) {  // the pool's creation order (streams.hip pool_prime)
             for (int i = 4 * layer; i < 4 * layer + 4; i++) q[main_index(i)] = make();
             for (int i = 4 * layer; i < 4 * layer + 4; i++)
                 for (int j = 0; j < 4; j++) q[side_index(i, j)] = make();
@@ -256,7 +256,7 @@ int main() {
         d = deal(classify(43, w));
         EXPECT(!d.dealt && d.need_more == 3);
     }
-    {   // the side stream of every role: distinct per slot, the spare on the main's own queue (engine.hip ctx_side_stream)
+    {   // the side stream of every role: distinct per slot, the spare on the main's own queue (streams.hip ctx_side_stream)
         for (int sl = 0; sl < POOL_SLOTS; sl++) {
             int seen = 0;
             for (int role = 0; role < 4; role++) seen |= 1 << role_side(sl, role);

@@ -314,3 +314,134 @@ def test_phase_calls_refuse_repeated_output_handles():
     assert L.zk_permutation_product(eng.ctx, pk, advh, len(adv), one, one, arr([zs[0]] * nchunks), nchunks) == EINVAL
     assert L.zk_permutation_product(eng.ctx, pk, advh, len(adv), one, one, arr(zs), nchunks) == 0
     eng.close()
+
+
+def _identity_jac():
+    """The identity the seam returns for an empty sum: Jacobian (1, 1, 0), coordinates in Montgomery form."""
+    return cops.to_mont_arr(cops.ints_to_arr([1, 1, 0]), 1).reshape(12)
+
+
+def _empty_msm(eng, basis=None):
+    out = np.full(12, 7, dtype=np.uint64)
+    if basis is None:
+        rc = eng.L.zk_msm_bn254(eng.ctx, None, None, 0, E._p(out))
+    else:
+        rc = eng.L.zk_msm_srs(eng.ctx, basis, None, 0, E._p(out))
+    return rc, out
+
+
+def test_seam_msm_with_nothing_to_add():
+    """zk_msm_bn254 / zk_msm_srs at n = 0 and n = 1: the empty sum is exactly the identity (1, 1, 0) with or without an SRS,
+    zk_msm_srs needs an SRS (ZK_ESTATE) and a valid basis (ZK_EINVAL) also on a k = 5 SRS, which has no window tables, and one
+    term equals the oracle's MSM on both entry points."""
+    ident = _identity_jac()
+    eng = zk.Engine(0)
+    rc, out = _empty_msm(eng)
+    assert rc == 0 and np.array_equal(out, ident)
+    out = np.full(12, 7, dtype=np.uint64)
+    s1 = cops.fr_mont([0x1234567890ABCDEF1234567890ABCDEF])
+    assert eng.L.zk_msm_srs(eng.ctx, E.ZK_BASIS_MONOMIAL, E._p(s1), 1, E._p(out)) == -5  # ZK_ESTATE
+    assert _empty_msm(eng, E.ZK_BASIS_LAGRANGE)[0] == -5
+    assert (out == 7).all()
+    eng.srs_setup(5)
+    assert eng.srs_msm_plan() == (0, 0)  # no window tables at k = 5
+    rc, out = _empty_msm(eng)
+    assert rc == 0 and np.array_equal(out, ident)
+    for basis in (E.ZK_BASIS_MONOMIAL, E.ZK_BASIS_LAGRANGE):
+        rc, out = _empty_msm(eng, basis)
+        assert rc == 0 and np.array_equal(out, ident)
+    rc, out = _empty_msm(eng, 7)
+    assert rc == -1 and (out == 7).all()
+    assert eng.L.zk_msm_srs(eng.ctx, 7, E._p(s1), 1, E._p(out)) == -1 and (out == 7).all()
+    for basis in (E.ZK_BASIS_MONOMIAL, E.ZK_BASIS_LAGRANGE):
+        b1 = eng.srs_export(basis, 0, 1)
+        want = cops.jac_to_affine_ints(cops.msm(s1, b1))
+        assert want is not None
+        assert cops.jac_to_affine_ints(eng.msm(s1, b1)) == want
+        assert cops.jac_to_affine_ints(eng.msm_srs(s1, basis)) == want
+    eng.close()
+
+
+def _random_fr(seed, n):
+    a = np.frombuffer(np.random.default_rng(seed).bytes(32 * n), dtype=np.uint64).reshape(n, 4).copy()
+    a[:, 3] &= 0x0FFFFFFFFFFFFFFF
+    return a
+
+
+def test_resident_transforms_refusals_and_round_trips(engine):
+    """The four zk_*_to_* entry points: a vector whose length is no power of two is refused and left as it was; coeff_to_extended
+    refuses src == dst and a src longer than dst, extended_to_coeff an n_out beyond the vector; extended_to_coeff of
+    coeff_to_extended gives the input back at 2^3 -> 2^5 (one pass) and 2^8 -> 2^10 (the last pass folds the conversion)."""
+    L, EINVAL = engine.L, -1
+    a24 = _random_fr(24, 24)
+    v, w = engine.poly(24, a24), engine.poly(24, a24)
+    assert L.zk_lagrange_to_coeff(engine.ctx, v.h) == EINVAL
+    assert L.zk_coeff_to_lagrange(engine.ctx, v.h) == EINVAL
+    assert L.zk_coeff_to_extended(engine.ctx, v.h, w.h) == EINVAL
+    assert L.zk_extended_to_coeff(engine.ctx, v.h, 24) == EINVAL
+    assert np.array_equal(engine.download(v), a24) and np.array_equal(engine.download(w), a24)
+    a8, a16 = _random_fr(8, 8), _random_fr(16, 16)
+    p8, p16 = engine.poly(8, a8), engine.poly(16, a16)
+    assert L.zk_coeff_to_extended(engine.ctx, p8.h, p8.h) == EINVAL
+    assert L.zk_coeff_to_extended(engine.ctx, p16.h, p8.h) == EINVAL
+    assert L.zk_extended_to_coeff(engine.ctx, p8.h, 9) == EINVAL
+    assert np.array_equal(engine.download(p8), a8) and np.array_equal(engine.download(p16), a16)
+    for q in (v, w, p8, p16):
+        q.free()
+    for lg in (3, 8):
+        n = 1 << lg
+        a = _random_fr(lg, n)
+        src, ext = engine.poly(n, a), engine.poly(4 * n)
+        engine.coeff_to_extended(src, ext)
+        vals = engine.download(ext)
+        assert not np.array_equal(vals[:n], a)
+        engine.extended_to_coeff(ext, n)
+        assert np.array_equal(engine.download(ext, n), a)
+        assert np.array_equal(engine.download(src), a)
+        src.free()
+        ext.free()
+
+
+# zk_ctx_set_option: option -> (least accepted value above 0, greatest accepted value), as the setter stood before its plain cases
+# became a table.  0 is always accepted.  ZK_OPT_GP_BATCH_INVERT takes any value (non-zero = on) and has no greatest one;
+# ZK_OPT_STREAM_PRIORITY has its own test (test_gpu_streams.py).
+_OPTION_BOUNDS = {
+    E.ZK_OPT_MSM_WINDOW: (9, 17),
+    E.ZK_OPT_MSM_BATCH: (1, 256),
+    E.ZK_OPT_NTT_MAX_RADIX_LOG2: (1, 11),
+    E.ZK_OPT_MSM_TAIL_STREAM: (1, 2),
+    E.ZK_OPT_MSM_TAIL_MAIN_ABOVE: (1, 64),
+    E.ZK_OPT_BATCH_PASS_COLUMNS: (1, 256),
+    E.ZK_OPT_XFORM_STREAM: (1, 2),
+    E.ZK_OPT_MSM_STREAM: (1, 2),
+    E.ZK_OPT_MSM_T1: (1, 2),
+    E.ZK_OPT_STREAM_AUDIT: (1, 2),
+    E.ZK_OPT_QUOTIENT_DOMAIN: (1, 2),
+    E.ZK_OPT_ACTIVITY_HOLD: (1, 2),
+}
+
+
+def test_option_bounds():
+    """Every option of include/zkmi355.h: the greatest value is accepted, the next one refused (ZK_EINVAL), as is the value
+    below the least one where that is not 0, and -1, and an option number nobody defined."""
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "zkmi355.h")).read()
+    defined = {int(v) for v in re.findall(r"^#define ZK_OPT_\w+ (\d+)", hdr, re.M)}
+    assert defined == set(_OPTION_BOUNDS) | {E.ZK_OPT_GP_BATCH_INVERT, E.ZK_OPT_STREAM_PRIORITY}
+    eng = zk.Engine(0)
+    L, EINVAL = eng.L, -1
+    for opt, (lo, hi) in _OPTION_BOUNDS.items():
+        assert L.zk_ctx_set_option(eng.ctx, opt, hi) == 0, opt
+        assert L.zk_ctx_set_option(eng.ctx, opt, hi + 1) == EINVAL, opt
+        assert L.zk_ctx_set_option(eng.ctx, opt, lo) == 0, opt
+        if lo > 1:
+            assert L.zk_ctx_set_option(eng.ctx, opt, lo - 1) == EINVAL, opt
+        assert L.zk_ctx_set_option(eng.ctx, opt, -1) == EINVAL, opt
+        assert L.zk_ctx_set_option(eng.ctx, opt, 0) == 0, opt
+    for v in (1, 2, 1 << 40, 0):
+        assert L.zk_ctx_set_option(eng.ctx, E.ZK_OPT_GP_BATCH_INVERT, v) == 0
+    assert L.zk_ctx_set_option(eng.ctx, E.ZK_OPT_GP_BATCH_INVERT, -1) == EINVAL
+    assert L.zk_ctx_set_option(eng.ctx, E.ZK_OPT_STREAM_PRIORITY, -1) == EINVAL
+    for opt in (0, max(defined) + 1, 99, -3):
+        assert L.zk_ctx_set_option(eng.ctx, opt, 0) == EINVAL and L.zk_ctx_set_option(eng.ctx, opt, 1) == EINVAL
+    eng.close()

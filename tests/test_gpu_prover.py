@@ -550,7 +550,7 @@ def test_k19_batch_of_8_jobs_equals_committed_oracle_proofs():
     wit = batch.synthesize_jobs(p, jobs)
     fixed, copies = batch.structure(p)
     # two pipelines (each MSM pass's reduction tail on its context's side stream), then bench.py's four (three or more proofs
-    # in flight: the tails follow on the main streams — engine.hip ctx_msm_begin_batch)
+    # in flight: the tails follow on the main streams — msm_lanes.hip ctx_msm_begin_batch)
     for npipe in (2, 4):
         pipes = [batch.Pipeline(0, p, fixed, copies, deterministic_seeds=True)]
         for _ in range(npipe - 1):
@@ -655,6 +655,37 @@ def test_shared_srs_contexts():
         second.prove(pk, polys, b"\x09" * 32, E.ZK_TRANSCRIPT_EVM)  # the key was made under the SRS the context let go of
     second.close()
     third.close()
+
+
+def test_shared_context_inherits_the_srs_view_and_keeps_its_own():
+    """zk_ctx_create_shared with ZK_OPT_MSM_WINDOW set on the parent: the child has the parent's window tables and commits the
+    same bytes on both bases; when the child then loads a small SRS of its own (k = 5: no tables), the parent's view — block,
+    tables, window — is what it was."""
+    k = 10
+    parent = zk.Engine(0)
+    parent.set_option(E.ZK_OPT_MSM_WINDOW, 11)
+    parent.srs_setup(k)
+    assert parent.srs_msm_plan()[0] == 11
+    a = np.frombuffer(np.random.default_rng(11).bytes(32 << k), dtype=np.uint64).reshape(-1, 4).copy()
+    a[:, 3] &= 0x0FFFFFFFFFFFFFFF
+    col = parent.poly(1 << k, a)
+    want = [parent.commit(col, basis).tobytes() for basis in (E.ZK_BASIS_MONOMIAL, E.ZK_BASIS_LAGRANGE)]
+    assert want[0] != want[1]
+    child = zk.Engine(0, share_with=parent)
+    assert child.srs_msm_plan() == parent.srs_msm_plan() and _srs_k(child) == k
+    ccol = child.poly(1 << k, a)
+    assert [child.commit(ccol, basis).tobytes() for basis in (E.ZK_BASIS_MONOMIAL, E.ZK_BASIS_LAGRANGE)] == want
+    child.srs_setup(5)
+    assert _srs_k(child) == 5 and child.srs_msm_plan() == (0, 0)
+    assert _srs_k(parent) == k and parent.srs_msm_plan()[0] == 11
+    assert [parent.commit(col, basis).tobytes() for basis in (E.ZK_BASIS_MONOMIAL, E.ZK_BASIS_LAGRANGE)] == want
+    child.close()
+    assert [parent.commit(col, basis).tobytes() for basis in (E.ZK_BASIS_MONOMIAL, E.ZK_BASIS_LAGRANGE)] == want
+    parent.close()
+
+
+def _srs_k(eng):
+    return eng.L.zk_srs_k(eng.ctx)
 
 
 @pytest.mark.gpu

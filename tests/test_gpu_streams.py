@@ -160,7 +160,7 @@ def test_stream_priority_option_leaves_results_unchanged():
 
 
 def test_stream_pool_more_contexts_than_slots_and_reuse():
-    """The per-device stream pool (engine.hip): eight slots of streams made in a fixed order, taken by zk_ctx_create and given back
+    """The per-device stream pool (streams.hip): eight slots of streams made in a fixed order, taken by zk_ctx_create and given back
     by zk_ctx_destroy; contexts beyond the slots make their own streams.  Twelve contexts at once, then again after all were
     destroyed: every context commits the same column to the same point, alone and from twelve threads."""
     k = 12

@@ -104,6 +104,28 @@ def test_stream_audit_ledger_logic(tmp_path):
     assert out.returncode == 0 and "audit logic: 0 failures" in out.stdout, out.stdout + out.stderr
 
 
+def test_activity_table_logic(tmp_path):
+    """csrc/activity.h (which contexts of the process count as active on a device) with made-up clocks, host only: distinct slots,
+    the 65th context of a device, a slot reused, the window's last nanosecond, holds, a device outside the table and the
+    ZK_OPT_ACTIVITY_HOLD rules.  Built twice — plain, and with the host side under AddressSanitizer / UBSan — and run as a program
+    of its own."""
+    import os
+    import shutil
+    import subprocess
+
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if shutil.which("hipcc") is None:
+        import pytest
+
+        pytest.skip("hipcc not on PATH")
+    for tag, extra in (("plain", []), ("san", ["-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"])):
+        exe = str(tmp_path / ("activity_logic_check_" + tag))
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", *extra, "-x", "hip", "-I",
+                               os.path.join(ROOT, "webauthn-halo2_amd", "csrc"), os.path.join(ROOT, "tests", "activity_logic_check.cpp"), "-o", exe])
+        out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+        assert out.returncode == 0 and "activity logic: 0 failures" in out.stdout, tag + ": " + out.stdout + out.stderr
+
+
 def test_fr_batch_invert_host_check(tmp_path):
     """fr_batch_invert (csrc/prover_steps.h), host only: counts 0, 1, 2 and 257; every inverse equals fe_inv_fast of its element;
     inputs 1 and r - 1; a zero at the first, a middle and the last index is refused and nothing is written outside the scratch.

@@ -1,0 +1,68 @@
+"""Every kernel launch of one k = 19 proof in the order the host enqueued it — the check that a refactor of host code moved no
+enqueue (profiles/README.md "dispatch_order").  Two halves:
+
+  dispatch_order.py run lone|lockstep4
+      the traced program: sets up k = 19 (SRS, key, the advice columns uploaded once) and makes ONE zk_prove (Blake2b + SHPLONK),
+      or ONE zk_prove_batch of four; prints the SHA-256 of the proof(s).  ZKMI355_LIB selects another build of the library.
+      Run it under `rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/dispatch_order.py run lone`
+      (no counters, no other tracing).
+  dispatch_order.py order <kernel_trace.csv>
+      the post-processing: the trace sorted by dispatch id, one line per launch: kernel, hardware queue (numbered by first
+      appearance: the ids themselves differ from process to process) and grid.  Two builds launch the same work in the same
+      order iff their outputs are equal line by line."""
+import csv
+import hashlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def run(mode):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import webauthn_halo2_amd as zk
+    from webauthn_halo2_amd import engine as E
+
+    p = zk.circuit.K19
+    eng = zk.Engine(0)
+    eng.srs_setup(p.degree)
+    asg = zk.circuit.synthesize(p, 0x5EED0019)
+    pk = eng.keygen(p, np.stack([asg.to_limbs(c) for c in asg.fixed]), asg.copies)
+    hs = []
+    for col in asg.advice:
+        h = eng.poly(1 << p.degree)
+        eng.upload_canonical(h, asg.to_limbs(col))
+        hs.append(h)
+    if mode == "lone":
+        proofs = [eng.prove(pk, hs, bytes([1]) * 32, E.ZK_TRANSCRIPT_BLAKE2B)]
+    elif mode == "lockstep4":
+        proofs = eng.prove_batch(pk, [hs] * 4, [bytes([j + 1]) * 32 for j in range(4)], E.ZK_TRANSCRIPT_BLAKE2B)
+    else:
+        raise SystemExit(__doc__)
+    print(mode, "library", E.lib_path(), "proofs", " ".join(hashlib.sha256(pf).hexdigest()[:16] for pf in proofs), flush=True)
+    eng.close()
+
+
+def kernel_name(full):
+    s = full.replace("(anonymous namespace)::", "").replace("zk::", "").replace("void ", "")
+    return s.split("(")[0].strip()
+
+
+def order(path):
+    rows = list(csv.DictReader(open(path)))
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
+    queues = {}
+    for r in rows:
+        q = queues.setdefault(r["Queue_Id"], len(queues))
+        grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) * int(r["Grid_Size_Z"])
+        print("%s q%d grid %d" % (kernel_name(r["Kernel_Name"]), q, grid))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "run":
+        run(sys.argv[2])
+    elif len(sys.argv) == 3 and sys.argv[1] == "order":
+        order(sys.argv[2])
+    else:
+        raise SystemExit(__doc__)

@@ -19,7 +19,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "webauthn-halo2_amd", "csrc")
-FILES = ["msm.hip", "ntt.hip", "quotient.hip", "poly.hip", "prover_kernels.hip", "engine.hip", "serde.hip"]
+FILES = ["msm.hip", "ntt.hip", "quotient.hip", "poly.hip", "prover_kernels.hip", "ctx.hip", "serde.hip"]
 CXXFILT = "c++filt"  # (binutils; llvm-cxxfilt is not in the image)
 
 # issue cycles per wave-instruction per SIMD at the nominal 2.4 GHz, four waves per SIMD, every SIMD busy (profiles/r6_ubench_isa.txt;

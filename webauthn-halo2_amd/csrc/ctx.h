@@ -1,4 +1,5 @@
-// ctx.h — the engine context shared by engine.hip (C-ABI) and the prover units (prover.hip, prover_key.hip, prover_phases.hip).
+// ctx.h — the engine context shared by the units of the C-ABI (ctx.hip, streams.hip, msm_lanes.hip, srs.hip, poly_abi.hip) and
+// the prover units (prover.hip, prover_key.hip, prover_phases.hip).
 #pragma once
 #include <map>
 #include <memory>
@@ -9,6 +10,7 @@
 
 #include "../../include/zkmi355.h"
 #include "engine.h"
+#include "activity.h"
 #include "audit.h"
 #include "hostutil.h"
 
@@ -36,10 +38,27 @@ struct SrsBlock {
     }
 };
 
-struct zk_ctx {
+// The SRS as one context sees it.  zk_ctx_create_shared hands the whole view to the child and srs_install keeps it aside as one
+// value: a member added here travels with both.  (The pointers alias the members of `srs`, the owner.)
+struct SrsView {
+    std::shared_ptr<SrsBlock> srs;
+    int srs_k = -1;
+    G1Affine* g = nullptr;
+    G1Affine* g_lagrange = nullptr;
+    G1Affine* g_table = nullptr;           // window multiples of g / g_lagrange (fixed-base MSM)
+    G1Affine* g_lagrange_table = nullptr;
+    uint32_t table_c = 0;
+    bool g_has_identity = true, g_lagrange_has_identity = true;  // set with the tables (msm_bases_have_identity)
+    // G2 half of ParamsKZG (g2, s_g2 = [s]G2) as raw Montgomery images x.c0 || x.c1 || y.c0 || y.c1: the engine never
+    // computes with it, it only travels through the SRS file (zk_srs_write / zk_srs_read)
+    bool g2_valid = false;
+    uint8_t g2_raw[128] = {0}, s_g2_raw[128] = {0};
+};
+
+struct zk_ctx : SrsView {
     int device = -1;
     hipStream_t stream = nullptr;
-    int stream_slot = -1;              // the context's slot in its device's stream pool (engine.hip): main and side streams are the slot's; -1: its own
+    int stream_slot = -1;              // the context's slot in its device's stream pool (streams.hip): main and side streams are the slot's; -1: its own
     bool stream_own_priority = false;  // the main stream was made by ZK_OPT_STREAM_PRIORITY: the context's own, destroyed with it
     int last_hip = 0;
     StreamAudit audit;  // ZK_OPT_STREAM_AUDIT (audit.h): the happens-before ledger of this context's streams, off by default
@@ -53,19 +72,6 @@ struct zk_ctx {
     std::map<uint32_t, Fr*> coset3_pre;    // k -> [2][2^k]: the twists (zeta w_4n^j)^m, j = 1, 2, of the three-coset transforms (poly.hip)
     std::map<uint32_t, Coset3Consts> coset3_consts;  // k -> the constants of the 3 x 3 solve
     uint32_t opt_quotient_domain = 0;      // ZK_OPT_QUOTIENT_DOMAIN: 0 auto (three cosets from k = 16), 1 always the whole extended domain, 2 three cosets wherever h has three pieces
-    // SRS (the pointers below alias the members of `srs`, the owner)
-    std::shared_ptr<SrsBlock> srs;
-    int srs_k = -1;
-    G1Affine* g = nullptr;
-    G1Affine* g_lagrange = nullptr;
-    G1Affine* g_table = nullptr;           // window multiples of g / g_lagrange (fixed-base MSM)
-    G1Affine* g_lagrange_table = nullptr;
-    uint32_t table_c = 0;
-    bool g_has_identity = true, g_lagrange_has_identity = true;  // set with the tables (msm_bases_have_identity)
-    // G2 half of ParamsKZG (g2, s_g2 = [s]G2) as raw Montgomery images x.c0 || x.c1 || y.c0 || y.c1: the engine never
-    // computes with it, it only travels through the SRS file (zk_srs_write / zk_srs_read)
-    bool g2_valid = false;
-    uint8_t g2_raw[128] = {0}, s_g2_raw[128] = {0};
     uint64_t srs_gen = 0;  // bumped by every zk_srs_setup / zk_srs_load / zk_srs_read: keys remember the SRS they were made under
     // tuning options (zk_ctx_set_option); 0 = built-in choice
     uint32_t opt_msm_window = 0, opt_msm_batch = 0, opt_ntt_max_r = 0, opt_gp_batch_invert = 0;
@@ -73,10 +79,7 @@ struct zk_ctx {
     uint32_t opt_tail_main_above = 0;  // ZK_OPT_MSM_TAIL_MAIN_ABOVE: auto mode puts the tails on the main stream with MORE than this many contexts active on the device (0 = the measured default, 2)
     uint32_t opt_batch_pass_cols = 0;  // ZK_OPT_BATCH_PASS_COLUMNS: columns per MSM pass of a lock-step batch (0 = max(min(2 B, 8), the single prover's pass width))
     uint32_t msm_min_cols = 0;         // the lanes' fixed-base workspaces take at least this many columns per pass (raised by zk_prove_batch, never lowered: the wider workspaces are kept)
-    uint32_t opt_no_activity_hold = 0;  // ZK_OPT_ACTIVITY_HOLD = 1
-    bool opt_activity_pinned = false;   // ZK_OPT_ACTIVITY_HOLD = 2: active until the option is changed
-    bool act_held = false;         // inside a whole-proof call: the slot counts as active whatever its last stamp (ctx_activity_hold)
-    int act_slot = -1;             // this context's slot in its device's activity table (engine.hip ctx_activity_*)
+    activity::State act;  // this context's slot in its device's activity table and its ZK_OPT_ACTIVITY_HOLD rules (activity.h, streams.hip ctx_activity_*)
     // The context's TAIL stream (round 4: one, shared by the lanes; rounds 2-3 had one per lane).  Where a pass's reduction tail
     // runs is decided per pass (ctx_msm_begin_batch): on this stream while at most two contexts are ACTIVE on the device (have
     // enqueued an MSM pass within the last 4 ms, through whatever entry point: ctx_activity_touch) — a lone proof hides its
@@ -204,13 +207,41 @@ static inline int aud_verdict(zk_ctx* c, uint64_t violations_before, int rc) {
     } while (0)
 
 
+// the resident vector behind a handle, or nullptr
+static inline PolyRec* ctx_poly(zk_ctx* c, zk_poly h) {
+    auto it = c->polys.find(h);
+    return it == c->polys.end() ? nullptr : &it->second;
+}
+// the resident basis a ZK_BASIS_* value names; nullptr for an invalid basis (and while no SRS is resident)
+static inline const G1Affine* ctx_basis(const zk_ctx* c, int basis) {
+    return basis == ZK_BASIS_MONOMIAL ? c->g : basis == ZK_BASIS_LAGRANGE ? c->g_lagrange : nullptr;
+}
+static inline bool basis_ok(int basis) { return basis == ZK_BASIS_MONOMIAL || basis == ZK_BASIS_LAGRANGE; }
+
 int ctx_bind(zk_ctx* c);
+// ZK_OK for a device this process can use, ZK_ENODEV without any, ZK_EINVAL for an index outside them
+int device_id_ok(int device_id);
+// "set the device, put the previous one back": the entry points that work on a device without a context of theirs
+struct DeviceScope {
+    int prev = -1;
+    bool ok;
+    explicit DeviceScope(int device) { ok = hipGetDevice(&prev) == hipSuccess && hipSetDevice(device) == hipSuccess; }
+    ~DeviceScope() {
+        if (prev >= 0) hipSetDevice(prev);
+    }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+};
+// the device's stream pool (streams.hip): a free slot with its main stream, or -1 (current device = `device`)
+int pool_take_slot(int device, hipStream_t* main_out);
+void pool_release_slot(int device, int slot);
 // contexts active on a device (all contexts of THIS process that enqueued an MSM pass within the last few ms): decides where
-// the MSM reduction tails run (engine.hip)
+// the MSM reduction tails run (streams.hip; the table itself: activity.h)
 void ctx_activity_register(zk_ctx* c);
 void ctx_activity_unregister(zk_ctx* c);
 int ctx_activity_touch(zk_ctx* c);
 void ctx_activity_hold(zk_ctx* c, bool on);
+int ctx_side_stream(zk_ctx* c, hipStream_t* out, int role);  // role: 0 the tail stream, 1 the transform stream, 2 the MSM stream
 int ctx_lone_streams(zk_ctx* c);  // creates the transform / MSM streams of a lone proof on first use
 void ctx_release_spares(zk_ctx* c);  // frees the vectors zk_poly_free parked (caller holds c->mu, device bound)
 int ctx_ensure_scratch(zk_ctx* c, size_t n);
@@ -218,6 +249,9 @@ int ctx_get_twiddles(zk_ctx* c, uint32_t log_n, const Fr** out);
 int ctx_get_twiddles_ntt(zk_ctx* c, uint32_t log_n, const Fr** out);
 int ctx_get_twiddles_ninv(zk_ctx* c, uint32_t log_n, const Fr** out);
 int ctx_get_coset_points(zk_ctx* c, uint32_t log_n, const Fr** out);  // zeta * w^i: the points of the extended coset
+int ctx_get_coset3_pre(zk_ctx* c, uint32_t k, const Fr** out);         // [2][2^k]: the twists of the three-coset transforms
+// device staging buffer `which` of the fine-grained seam, at least `bytes` long (msm_lanes.hip)
+int seam_buffer(zk_ctx* c, int which, size_t bytes, void** out);
 // MSM of device-resident scalars against device-resident bases -> Jacobian on host (synchronises)
 int ctx_msm_device(zk_ctx* c, const Fr* d_scalars, const G1Affine* d_bases, size_t n, G1Jac* out);
 // split form: begin enqueues the MSM on lane `lane` (head on the context stream, tail on the
@@ -241,7 +275,7 @@ int ctx_ntt_batch(zk_ctx* c, const Fr* const* srcs, size_t src_n, Fr* const* dst
                   bool coset, size_t n_out, hipStream_t on = nullptr /* the context's main stream */);
 uint32_t ctx_ntt_max_batch(uint32_t log_n);
 void pk_destroy_all(zk_ctx* c);
-// SRS plumbing shared by engine.hip (setup / load) and serde.hip (read)
+// SRS plumbing shared by srs.hip (setup / load) and serde.hip (read)
 int srs_alloc(zk_ctx* c, uint32_t k);
 // replaces the resident SRS by two decoded, validated bases of 2^k points (device buffers the context takes over);
 // the previous SRS, its window tables and every key made under it are dropped only now

@@ -31,7 +31,7 @@ struct NttJob {
     uint32_t has_pre, has_post;
     Fr pre[3], post[3]; // period-3 scale factors by index (coset zeta powers, 1/N)
     // batch mode, optional per vector: element i of srcs[b] is multiplied by pre_tabs[b][i] (times 2^266 as plain words, like
-    // `pre`) on the way in instead of pre[i % 3]: the twist of a transform over the coset (zeta w_4n^j) H (engine.hip, coset3)
+    // `pre`) on the way in instead of pre[i % 3]: the twist of a transform over the coset (zeta w_4n^j) H (poly_abi.hip ctx_ntt_cosets3)
     const Fr* pre_tabs[NTT_MAX_BATCH];
     uint32_t max_log_r; // 0 = default
 };
@@ -48,6 +48,11 @@ struct Coset3Consts {  // constants of the 3 x 3 solve, standard form
 void launch_coset3_pre(const Fr* tw_ext, uint32_t n, uint32_t j, const Fr zp1024[3], Fr* tab, hipStream_t st);
 void launch_coset3_relayout(const Fr* const* src, Fr* const* dst, uint32_t count, uint32_t n, hipStream_t st);
 void launch_coset3_combine(Fr* h, const Fr* tw_ext, uint32_t n, const Coset3Consts& k, hipStream_t st);
+
+// ---- SRS generation (poly.hip) and RawBytes validation of device points (serde.hip) ----
+void launch_srs_lagrange_scalars(const Fr* tw, uint32_t n, const Fr& s, const Fr& c, Fr* out, hipStream_t st);
+void launch_srs_fixed_base(const Fr* scalars, uint32_t n, const G1Affine* table, G1Affine* out, hipStream_t st);
+hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hipStream_t st);  // *d_err |= 1: a coordinate not below p, a point off the curve
 
 // ---- MSM (msm.hip) ---------------------------------------------------------
 struct MsmWorkspace;  // opaque, sized for a maximum n and a maximum number of columns per launch
@@ -93,7 +98,7 @@ hipError_t msm_wide_redo(MsmWorkspace* ws, uint32_t batch, size_t n, hipStream_t
 // Host-side finish: Horner over windows -> Jacobian (Montgomery).
 G1Jac msm_finish_host(const G1X* window_sums, uint32_t nwin, uint32_t c);
 
-// ---- host helpers (hostmath.cpp) --------------------------------------------
+// ---- host helpers (ctx.hip) --------------------------------------------------
 G1Affine g1_jac_to_affine_host(const G1Jac& p);
 
 }  // namespace zk

@@ -23,11 +23,6 @@
 #include "pairing.h"
 #include "srs_update.h"
 
-namespace zk {
-void launch_twiddles(Fr* tw, const Fr& w, uint32_t n, hipStream_t st);
-hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hipStream_t st);  // serde.hip
-}  // namespace zk
-
 namespace {
 
 __device__ __forceinline__ G1X g1x_of_affine(const G1Affine& p) {

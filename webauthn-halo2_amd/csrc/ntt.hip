@@ -72,7 +72,7 @@ struct NttPassArgs {
     uint32_t has_post;   // multiply out[i] by post[i % 3] on store (last pass)
     Fr pre[3];           // pre-scale factors * 2^266 (plain words): product with a standard-form input is internal
     const Fr* pre_tab[NTT_MAX_BATCH];  // first pass, per vector (nullptr: none): in[i] is multiplied by pre_tab[i] (times 2^266, plain
-                                       // words) instead of pre[i % 3] — the per-element twist of a coset transform (engine.hip coset3)
+                                       // words) instead of pre[i % 3] — the per-element twist of a coset transform (poly_abi.hip ctx_ntt_cosets3)
     Fr post[3];          // post-scale factors in standard Montgomery form: product with an internal value is standard
 };
 

@@ -3,7 +3,7 @@
 // (tests/placement_logic_check.cpp runs it on made-up stamps).  The device half — the kernel that takes the stamps — is placement.hip.
 //
 // THE MEASUREMENT.  Kernels of streams that share a hardware queue run in order; kernels of streams on different queues run side
-// by side (engine.hip "streams are kept").  A one-workgroup kernel stamps the constant 100 MHz counter when it starts, spins for a
+// by side (streams.hip "streams are kept").  A one-workgroup kernel stamps the constant 100 MHz counter when it starts, spins for a
 // given number of ticks and stamps it again.  One ROUND picks a pivot stream, enqueues a LONG spin (T_p) on it and then a SHORT
 // one (T_s) on every other stream that has no class yet:
 //   * a short kernel that started at or after the pivot's end waited behind it: same queue, same class;
@@ -216,4 +216,10 @@ inline Deal deal(const Classes& c) {
 }
 
 }  // namespace placement
+
+#ifdef __HIPCC__
+// the device half (placement.hip): classes of streams[0 .. n) of the current device; `stamps`: pinned host memory for MAX_STREAMS stamps
+placement::Classes placement_probe(const hipStream_t* streams, int n, placement::Stamp* stamps);
+#endif
+
 }  // namespace zk

@@ -943,9 +943,9 @@ ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, co
     if (rc) return rc;
     std::vector<const Fr*> adv(n_advice);
     for (size_t j = 0; j < n_advice; j++) {
-        auto pit = c->polys.find(advice[j]);
-        if (pit == c->polys.end() || pit->second.n != lay.n) return ZK_EINVAL;
-        adv[j] = pit->second.ptr;
+        const PolyRec* r = ctx_poly(c, advice[j]);
+        if (!r || r->n != lay.n) return ZK_EINVAL;
+        adv[j] = r->ptr;
     }
     EvmTranscript evm;
     Blake2bTranscript b2;
@@ -987,9 +987,9 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     if (rc) return rc;
     std::vector<const Fr*> adv(batch * n_advice);
     for (size_t j = 0; j < batch * n_advice; j++) {
-        auto pit = c->polys.find(advice[j]);
-        if (pit == c->polys.end() || pit->second.n != lay.n) return ZK_EINVAL;
-        adv[j] = pit->second.ptr;
+        const PolyRec* r = ctx_poly(c, advice[j]);
+        if (!r || r->n != lay.n) return ZK_EINVAL;
+        adv[j] = r->ptr;
     }
     if ((rc = pk_ensure_batch(c, pk, B))) return rc;
     // columns per MSM pass: the same commitment of all proofs at once, two columns per proof where a phase has them (a', s';

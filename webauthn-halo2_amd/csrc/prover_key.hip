@@ -27,7 +27,7 @@ __global__ void sigma_kernel(const uint2* __restrict__ map, const Fr* __restrict
 // ------------------------------------------------------------ small utils ---
 bool commit(zk_ctx* c, const Fr* poly, size_t len, int basis, G1Affine* out) {
     G1Jac j;
-    if (ctx_msm_device(c, poly, basis == ZK_BASIS_LAGRANGE ? c->g_lagrange : c->g, len, &j) != ZK_OK) return false;
+    if (ctx_msm_device(c, poly, ctx_basis(c, basis), len, &j) != ZK_OK) return false;
     *out = g1_jac_to_affine_host(j);
     return true;
 }
@@ -616,8 +616,8 @@ ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_adv
     if (n_advice != lay.n_adv || n_chunks != lay.n_chunks || n_lookups != lay.n_lookups) return ZK_EINVAL;
     const size_t N = (size_t)4 * lay.n;
     auto ext = [&](zk_poly p) -> Fr* {
-        auto q = c->polys.find(p);
-        return (q == c->polys.end() || q->second.n != N) ? nullptr : q->second.ptr;
+        const PolyRec* q = ctx_poly(c, p);
+        return (!q || q->n != N) ? nullptr : q->ptr;
     };
     QuotientCosets qc;
     for (size_t j = 0; j < n_advice; j++) qc.adv.push_back(ext(advice_ext[j]));

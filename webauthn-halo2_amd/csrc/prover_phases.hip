@@ -28,15 +28,15 @@ int phase_open(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, Phase
     out.c = c;
     out.pk = pk;
     for (size_t j = 0; j < n_advice; j++) {
-        auto pit = c->polys.find(advice[j]);
-        if (pit == c->polys.end() || pit->second.n != pk->lay.n) return ZK_EINVAL;
-        out.adv.push_back(pit->second.ptr);
+        const PolyRec* r = ctx_poly(c, advice[j]);
+        if (!r || r->n != pk->lay.n) return ZK_EINVAL;
+        out.adv.push_back(r->ptr);
     }
     return ctx_bind(c);
 }
 Fr* phase_vec(zk_ctx* c, zk_poly h, size_t n) {
-    auto it = c->polys.find(h);
-    return (it == c->polys.end() || it->second.n != n) ? nullptr : it->second.ptr;
+    const PolyRec* r = ctx_poly(c, h);
+    return (!r || r->n != n) ? nullptr : r->ptr;
 }
 // grand products z[p] of the key's own workspace (num / den already enqueued), complete on return
 int phase_grand_products(zk_ctx* c, zk_pk_rec* pk, const std::vector<Fr*>& z, uint32_t chained) {
@@ -169,13 +169,13 @@ ZK_API(zk_pk_export_poly, (zk_ctx* c, zk_pk h, int which, size_t index, zk_poly 
 ZK_API(zk_random_poly, (zk_ctx* c, const uint8_t chacha_key[32], uint64_t first_block, zk_poly out), (c, chacha_key, first_block, out)) {
     if (!c || !chacha_key) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->polys.find(out);
-    if (it == c->polys.end() || it->second.n == 0 || it->second.n > ((size_t)1 << 28)) return ZK_EINVAL;
+    const PolyRec* r = ctx_poly(c, out);
+    if (!r || r->n == 0 || r->n > ((size_t)1 << 28)) return ZK_EINVAL;
     int rc = ctx_bind(c);
     if (rc) return rc;
     ChaChaKey key;
     memcpy(key.w, chacha_key, 32);
-    launch_chacha_fr(key, first_block, it->second.ptr, (uint32_t)it->second.n, c->stream);
+    launch_chacha_fr(key, first_block, r->ptr, (uint32_t)r->n, c->stream);
     HIPCHK(c, aud_sync(c, c->stream));
     return ZK_OK;
 }
@@ -185,21 +185,21 @@ ZK_API(zk_random_poly, (zk_ctx* c, const uint8_t chacha_key[32], uint64_t first_
 ZK_API(zk_poly_lincomb, (zk_ctx* c, zk_poly out, const zk_poly* in, const uint64_t* coeffs, size_t count, const uint64_t* sub_low, size_t n_low), (c, out, in, coeffs, count, sub_low, n_low)) {
     if (!c || !in || !coeffs || count == 0 || n_low > 8 || (n_low && !sub_low)) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    auto oit = c->polys.find(out);
-    if (oit == c->polys.end() || oit->second.n > 0xffffffffu) return ZK_EINVAL;
-    const size_t n = oit->second.n;
+    const PolyRec* o = ctx_poly(c, out);
+    if (!o || o->n > 0xffffffffu) return ZK_EINVAL;
+    const size_t n = o->n;
     std::vector<Term> terms(count);
     for (size_t j = 0; j < count; j++) {
-        auto it = c->polys.find(in[j]);
-        if (it == c->polys.end() || it->second.n != n || it->second.ptr == oit->second.ptr) return ZK_EINVAL;
-        terms[j].poly = it->second.ptr;
+        const PolyRec* r = ctx_poly(c, in[j]);
+        if (!r || r->n != n || r->ptr == o->ptr) return ZK_EINVAL;
+        terms[j].poly = r->ptr;
         memcpy(&terms[j].c, coeffs + 4 * j, 32);
     }
     int rc = ctx_bind(c);
     if (rc) return rc;
     Fr low[8];  // the low-degree polynomial subtracted from the first n_low coefficients
     if (n_low) memcpy(low, sub_low, n_low * 32);
-    lincomb_enqueue(c->stream, oit->second.ptr, (uint32_t)n, terms, false, nullptr, low, (uint32_t)n_low);
+    lincomb_enqueue(c->stream, o->ptr, (uint32_t)n, terms, false, nullptr, low, (uint32_t)n_low);
     HIPCHK(c, aud_sync(c, c->stream));
     return ZK_OK;
 }
@@ -208,10 +208,10 @@ ZK_API(zk_poly_upload_canonical, (zk_ctx* c, zk_poly h, const uint64_t* host_can
     int rc = zk_poly_upload(c, h, host_canonical, n);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
-    auto it = c->polys.find(h);
-    if (it == c->polys.end()) return ZK_EINVAL;
+    const PolyRec* r = ctx_poly(c, h);
+    if (!r) return ZK_EINVAL;
     if ((rc = ctx_bind(c))) return rc;
-    launch_to_mont(it->second.ptr, (uint32_t)n, c->stream);
+    launch_to_mont(r->ptr, (uint32_t)n, c->stream);
     if (aud_sync(c, c->stream) != hipSuccess) return ZK_EHIP;
     return ZK_OK;
 }

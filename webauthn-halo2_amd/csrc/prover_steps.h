@@ -424,7 +424,7 @@ struct Commits {
             polys.push_back(cl.poly);
             ps.to.push_back(cl.to);
         }
-        int r = ctx_msm_begin_batch(d.c, lane, polys.data(), (uint32_t)polys.size(), basis == ZK_BASIS_LAGRANGE ? d.c->g_lagrange : d.c->g, d.n);
+        int r = ctx_msm_begin_batch(d.c, lane, polys.data(), (uint32_t)polys.size(), ctx_basis(d.c, basis), d.n);
         if (r) return d.fail(r);
         f.busy.push_back(ps);
     }

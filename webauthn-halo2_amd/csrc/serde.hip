@@ -34,10 +34,6 @@
 #include "pk.h"
 #include "vkrepr.h"
 
-namespace zk {
-void launch_to_mont(Fr* a, uint32_t n, hipStream_t st);
-}
-
 namespace {
 
 // ------------------------------------------------------------ device side ---
@@ -330,7 +326,7 @@ hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hi
 }
 }  // namespace zk
 
-// s_g2 = [s]G2 after zk_srs_setup (called from engine.hip with the secret)
+// s_g2 = [s]G2 after zk_srs_setup (called from srs.hip with the secret)
 void srs_set_g2_from_secret(zk_ctx* c, const Fr& s_mont) {
     const G2A g = g2_generator();
     g2_to_raw(g, c->g2_raw);

@@ -342,9 +342,9 @@ ZK_API(zk_witness_check, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_ad
     if (n_advice != lay.n_adv) return ZK_EINVAL;
     std::vector<const Fr*> adv(n_advice);
     for (size_t j = 0; j < n_advice; j++) {
-        auto pit = c->polys.find(advice[j]);
-        if (pit == c->polys.end() || pit->second.n != lay.n) return ZK_EINVAL;
-        adv[j] = pit->second.ptr;
+        const PolyRec* r = ctx_poly(c, advice[j]);
+        if (!r || r->n != lay.n) return ZK_EINVAL;
+        adv[j] = r->ptr;
     }
     int rc = ctx_bind(c);
     if (rc) return rc;

@@ -435,6 +435,33 @@ int zk_prove(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, cons
 int zk_prove_batch(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /* batch x n_advice, proof-major */, size_t n_advice,
                    const uint8_t* rng_seeds /* batch x 32 */, int transcript, int scheme, uint8_t* proofs_out, size_t proof_stride,
                    size_t* proof_len);
+/* replaces plonk::create_proof(&params, &pk, &[c_0 .. c_{N-1}], &[&[]; N], rng, &mut transcript): N circuits under ONE key in ONE
+ * proof - one transcript, one set of challenges, one random polynomial, one quotient, one multi-open - as halo2 makes it for
+ * `circuits: &[ConcreteCircuit]` [RECALLED; not pinned by reference bytes: tests/multi_ref.py restates the rule and the bytes
+ * are compared with it].  c = 0 .. N - 1 in the caller's order:
+ *   transcript  transcript_repr (N is not hashed); for c: the advice commitments; theta; for c, per lookup: a', s'; beta, gamma;
+ *               for c: z of every chunk; for c: zL of every lookup; ONE random-polynomial commitment; y; the h pieces (as many as
+ *               for one circuit); x; evaluations - for c: advice; fixed, once; random; sigma, once; for c: the permutation's; for
+ *               c: the lookups' - then the multi-open over, for c: circuit c's openings in zk_prove's order, then fixed, sigma, h,
+ *               random
+ *   RNG         ONE ChaCha20Rng::from_seed(rng_seed), drawn in the same nesting: every phase's draws for c = 0, 1, ..; then the
+ *               random polynomial's n draws and its blind, then the h blinds
+ *   quotient    the y-Horner chain runs on across the circuits: h = sum_c y^(T (N - 1 - c)) h_c, T = terms of one circuit
+ * `advice` holds n_circuits x n_advice resident columns, circuit-major.  n_circuits == 1 gives zk_prove's bytes.  What is paid
+ * per circuit is its own commitments (5 at the one-column k = 19 shape, 11 at the four-column k = 17 one); the random polynomial,
+ * the h pieces, the opening proof, the inverse coset transform of h and the fixed / sigma evaluations are paid once per proof.
+ * Circuit c > 0 works in the key's further workspaces (shared with zk_prove_batch, allocated on first use and kept: ~1.4 GiB
+ * each at k = 19).  A verifier must expect the same N: zk_verify_multi here, `verify_proof` with N instance slices in halo2, a
+ * verifier generated `with_num_proof(N)` in snark-verifier.
+ * ZK_EINVAL: n_circuits == 0, n_circuits > ZK_PROVE_MULTI_MAX, n_circuits x (#chunks + #lookups) > 256, or zk_prove's own cases;
+ * ZK_ESTATE as zk_prove; ZK_EWITNESS: SOME circuit's lookup input is off the table - the call fails as a whole, the outputs are
+ * untouched (zk_witness_check tells which circuit).  proof_out == NULL: only *proof_len is set.  Follows zk_prove_batch's rules
+ * for ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_BATCH_PASS_COLUMNS and the activity hold.  No instances; no batches of such proofs. */
+#define ZK_PROVE_MULTI_MAX 16
+int zk_proof_size_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, size_t* out);
+int zk_prove_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const zk_poly* advice /* n_circuits x n_advice, circuit-major */,
+                   size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap,
+                   size_t* proof_len);
 /* upload canonical (non-Montgomery) integers and convert on the device */
 int zk_poly_upload_canonical(zk_ctx* ctx, zk_poly p, const uint64_t* host_canonical, size_t n);
 
@@ -532,6 +559,12 @@ int zk_verify(zk_ctx* ctx, zk_pk pk, int transcript, int scheme, const uint8_t* 
 #define ZK_VERIFY_BATCH_MAX 1024
 int zk_verify_batch(zk_ctx* ctx, zk_pk pk, size_t batch, int transcript, int scheme, const uint8_t* const* proofs, const size_t* lens,
                     uint8_t* verdicts);
+
+/* one proof of zk_prove_multi over n_circuits circuits (verify_proof with n_circuits empty instance slices): the proof is read in
+ * zk_prove_multi's order, the expected h(x) is the y-Horner of the n_circuits x T expressions, one pairing.  A bad proof - one of
+ * another circuit count included: it has another length - is a verdict (*ok = 0), never an error.  Full and verifying-only
+ * keys.  n_circuits == 1 is zk_verify.  ZK_EINVAL: n_circuits == 0 or > ZK_PROVE_MULTI_MAX. */
+int zk_verify_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok);
 
 /* ---- timing of the last call of each kind, measured with HIP events on the
  *      context stream (ms); used by bench.py for the roofline figures ---------- */

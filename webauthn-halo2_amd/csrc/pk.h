@@ -204,6 +204,11 @@ struct QuotientCosets {
 int pk_ensure_cosets3(zk_ctx* c, zk_pk_rec* pk);
 Fr fr_delta();  // 7^(2^28): generator of the odd-order subgroup (the permutation argument's coset shifts)
 int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out);
+// One pass of a quotient that several circuits share (prover_multi.h): the y-combination of this workspace's terms times
+// `yscale` (the pass's ypow[j] = 32 yscale y^(T - 1 - j)), stored to `out` or — `accumulate` — added to what `out` holds.
+// pk_quotient is the pass with yscale = 1 that stores.
+int pk_quotient_pass(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, const Fr& yscale,
+                     bool accumulate, bool divide, Fr* out);
 void pk_destroy(zk_pk_rec* pk);
 // the per-proof workspace (advice / z / lookup forms, quotient buffer, scan and evaluation scratch): everything a key
 // needs beyond the key material itself; called at the end of zk_keygen and zk_pk_read
@@ -211,6 +216,10 @@ int pk_alloc_workspace(zk_ctx* c, zk_pk_rec* pk);
 // makes sure `pk` can prove `batch` proofs in lock-step: batch - 1 member workspaces and the shared buffers (allocated on
 // first use, kept with the key); caller holds the context lock, device bound
 int pk_ensure_batch(zk_ctx* c, zk_pk_rec* pk, uint32_t batch);
+// makes sure `pk` can prove ONE proof over `circuits` circuits (zk_prove_multi): the member workspaces and shared buffers of a
+// lock-step batch of that size (circuit j > 0 works in members[j - 1]; allocated once, grown by either call), and the argument
+// lists of the multi-open's linear combinations — sized for one circuit's openings at keygen — for `circuits` times as many
+int pk_ensure_multi(zk_ctx* c, zk_pk_rec* pk, uint32_t circuits);
 // transcript_repr of a key made or read here: halo2.s own hash of the pinned verifying key (vkrepr.h); a stand-in for the shapes
 // that rendering does not cover; a host-supplied value replaces either
 Fr pk_standin_transcript_repr(const zk_pk_rec* pk);

@@ -1,5 +1,5 @@
 // prover.hip — create_proof on the device-resident engine: the single prover (Prover::run), the lock-step prover of several
-// proofs (prover_batch.h) and their entry points.  Keygen and the key's workspace are prover_key.hip, the phase-level entry
+// proofs (prover_batch.h), the prover of one proof over several circuits (prover_multi.h) and their entry points.  Keygen and the key's workspace are prover_key.hip, the phase-level entry
 // points prover_phases.hip; the steps the three share are prover_steps.h — the two drivers here hold the scheduling only: which
 // step, in which order, on which lane, and when a lane is collected.
 //
@@ -878,6 +878,7 @@ struct Prover {
 };
 
 #include "prover_batch.h"
+#include "prover_multi.h"
 
 }  // namespace
 
@@ -922,6 +923,24 @@ ZK_API(zk_proof_size, (zk_ctx* c, zk_pk pkh, int transcript, int scheme, size_t*
     points += scheme == ZK_SCHEME_SHPLONK ? 2 : 5 + (lay.n_chunks > 1 ? 1 : 0);
     const size_t evals = lay.advice_queries.size() + lay.n_fix + 1 + lay.perm_cols.size() + 3 * lay.n_chunks - 1 +
                          5 * lay.n_lookups;
+    *out = points * (transcript == ZK_TRANSCRIPT_EVM ? 64 : 32) + evals * 32;
+    return ZK_OK;
+}
+
+// one proof over n_circuits circuits: per circuit its own commitments (advice, a', s', zL, z) and evaluations (advice, z, lookups);
+// once the random polynomial, the h pieces, the fixed / random / sigma evaluations and the opening proof
+ZK_API(zk_proof_size_multi, (zk_ctx* c, zk_pk pkh, size_t n_circuits, int transcript, int scheme, size_t* out), (c, pkh, n_circuits, transcript, scheme, out)) {
+    if (!c || !out || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->pks.find(pkh);
+    if (it == c->pks.end()) return ZK_EINVAL;
+    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
+    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
+    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    const Layout& lay = it->second->lay;
+    size_t points = n_circuits * (lay.n_adv + 3 * lay.n_lookups + lay.n_chunks) + 1 + lay.n_h;
+    points += scheme == ZK_SCHEME_SHPLONK ? 2 : 5 + (lay.n_chunks > 1 ? 1 : 0);
+    const size_t evals = n_circuits * (lay.advice_queries.size() + 3 * lay.n_chunks - 1 + 5 * lay.n_lookups) + lay.n_fix + 1 + lay.perm_cols.size();
     *out = points * (transcript == ZK_TRANSCRIPT_EVM ? 64 : 32) + evals * 32;
     return ZK_OK;
 }
@@ -1025,3 +1044,63 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     return ZK_OK;
 }
 
+
+// create_proof(&params, &pk, &[c_0 .. c_{N-1}], ..): ONE proof over n_circuits circuits of one key (prover_multi.h)
+ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, n_circuits, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+    if (!c || !advice || !rng_seed || !proof_len || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
+    if (n_circuits == 1) return zk_prove(c, h, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->pks.find(h);
+    if (it == c->pks.end()) return ZK_EINVAL;
+    zk_pk_rec* pk = it->second;
+    const Layout& lay = pk->lay;
+    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
+    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
+    if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
+    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
+    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
+    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    const uint32_t B = (uint32_t)n_circuits;
+    // all grand products of the proof are scanned by one 256-lane workgroup (gp_chain_kernel)
+    if ((uint64_t)B * (lay.n_chunks + lay.n_lookups) > 256) return ZK_EINVAL;
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    std::vector<const Fr*> adv(n_circuits * n_advice);
+    for (size_t j = 0; j < n_circuits * n_advice; j++) {
+        const PolyRec* r = ctx_poly(c, advice[j]);
+        if (!r || r->n != lay.n) return ZK_EINVAL;
+        adv[j] = r->ptr;
+    }
+    if ((rc = pk_ensure_multi(c, pk, B))) return rc;
+    // columns per MSM pass: zk_prove_batch's rule (ZK_OPT_BATCH_PASS_COLUMNS overrides)
+    uint32_t cap = c->opt_batch_pass_cols ? c->opt_batch_pass_cols : std::max(std::min<uint32_t>(2 * B, 8u), ctx_msm_max_batch(c));
+    cap = std::min<uint32_t>(cap, MSM_MAX_BATCH);
+    if (!c->table_c) cap = 1;  // no window tables (k < 10): one column per pass
+    c->msm_min_cols = std::max(c->msm_min_cols, cap);
+    // the proof's transcript and RNG are circuit 0's prover's; circuits 1 .. N - 1 are workspaces: their provers get a scratch
+    // transcript (begin() hashes transcript_repr into it) and a stream that is never drawn from
+    EvmTranscript evm;
+    Blake2bTranscript b2;
+    Transcript* tr = transcript == ZK_TRANSCRIPT_EVM ? (Transcript*)&evm : (Transcript*)&b2;
+    std::vector<std::unique_ptr<Transcript>> scratch;
+    std::vector<std::unique_ptr<Prover>> provers;
+    std::vector<Prover*> P;
+    for (uint32_t q = 0; q < B; q++) {
+        if (q) scratch.emplace_back(new Blake2bTranscript());
+        provers.emplace_back(new Prover(c, q == 0 ? pk : pk->members[q - 1], rng_seed, q == 0 ? tr : scratch.back().get()));
+        P.push_back(provers.back().get());
+    }
+    const uint64_t aud0 = c->audit.violations;
+    c->audit.base_of.clear();
+    {
+        MultiRun run(c, pk, P, cap);
+        ProveQuiesce quiesce(c);
+        rc = run.run(adv.data(), scheme);
+    }
+    if ((rc = aud_verdict(c, aud0, rc))) return rc;
+    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+    *proof_len = tr->out.size();
+    if (!proof_out || proof_cap < tr->out.size()) return proof_out ? ZK_EINVAL : ZK_OK;
+    memcpy(proof_out, tr->out.data(), tr->out.size());
+    return ZK_OK;
+}

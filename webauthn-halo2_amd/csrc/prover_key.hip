@@ -262,6 +262,21 @@ int pk_ensure_batch(zk_ctx* c, zk_pk_rec* pk, uint32_t batch) {
     return ZK_OK;
 }
 
+int pk_ensure_multi(zk_ctx* c, zk_pk_rec* pk, uint32_t circuits) {
+    if (int rc = pk_ensure_batch(c, pk, circuits)) return rc;
+    const uint32_t want = 2 * (circuits * pk->max_evals + 8);  // every opened polynomial twice (pk_alloc_workspace), per circuit
+    if (pk->lc_cap >= want) return ZK_OK;
+    aud_sync(c, c->stream);  // (no proof is in flight between entry points; the lists are idle)
+    if (pk->d_lc_terms) hipFree(pk->d_lc_terms);
+    if (pk->h_lc_terms) hipHostFree(pk->h_lc_terms);
+    pk->d_lc_terms = pk->h_lc_terms = nullptr;
+    pk->lc_cap = 0;
+    if (hipHostMalloc(&pk->h_lc_terms, want * sizeof(LcTerm)) != hipSuccess || hipMalloc(&pk->d_lc_terms, want * sizeof(LcTerm)) != hipSuccess)
+        return ZK_ENOMEM;  // (what was allocated is freed with the key; lc_cap = 0 sends linear combinations down the chunked form)
+    pk->lc_cap = want;
+    return ZK_OK;
+}
+
 // =================================================================== keygen ==
 
 ZK_API(zk_keygen, (zk_ctx* c, const zk_circuit_params* params, const uint64_t* fixed_canonical, size_t n_fixed_columns, const uint32_t* copies, size_t n_copies, zk_pk* out), (c, params, fixed_canonical, n_fixed_columns, copies, n_copies, out)) {
@@ -507,6 +522,11 @@ int pk_ensure_cosets3(zk_ctx* c, zk_pk_rec* pk) {
 // Evaluator::evaluate_h (+ divide_by_vanishing_poly when `divide`) over resident extended cosets: the key's fixed /
 // sigma / l_* cosets and the caller's advice, permutation-product and lookup cosets.  Enqueued on the context stream.
 int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out) {
+    return pk_quotient_pass(c, pk, qc, beta, gamma, y, Fr::one(), false, divide, out);
+}
+
+int pk_quotient_pass(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, const Fr& yscale,
+                     bool accumulate, bool divide, Fr* out) {
     const Layout& lay = pk->lay;
     if (qc.adv.size() != lay.n_adv || qc.z.size() != lay.n_chunks || qc.lk_a.size() != lay.n_lookups ||
         qc.lk_s.size() != lay.n_lookups || qc.lk_z.size() != lay.n_lookups)
@@ -569,8 +589,8 @@ int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& be
     q.divide = divide ? 1 : 0;
     q.n_terms = quotient_terms(lay.n_gate, lay.n_chunks, lay.n_lookups);
     if (q.n_terms > MAX_TERMS) return ZK_EINVAL;
-    Fr yp = k32;
-    for (uint32_t j = q.n_terms; j-- > 0;) {  // ypow[j] = 32 y^(T - 1 - j)
+    Fr yp = fe_mul(k32, yscale);  // (yscale = 1: the Montgomery product by one is exact, yp = 32)
+    for (uint32_t j = q.n_terms; j-- > 0;) {  // ypow[j] = 32 yscale y^(T - 1 - j)
         q.ypow[j] = yp;
         yp = fe_mul(yp, y);
     }
@@ -588,7 +608,8 @@ int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& be
     hipEventRecord(c->ev[ZK_T_QUOTIENT][0], st);
     const size_t bytes = sizeof(q) - sizeof(q.ypow) + (size_t)q.n_terms * sizeof(Fr);
     if (hipMemcpyAsync(pk->d_qargs, &q, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return ZK_EHIP;
-    launch_quotient_dev(pk->d_qargs, lay.ext_k, log_slices, st, c3);
+    if (accumulate) launch_quotient_acc_dev(pk->d_qargs, lay.ext_k, log_slices, st, c3);
+    else launch_quotient_dev(pk->d_qargs, lay.ext_k, log_slices, st, c3);
     hipEventRecord(c->ev[ZK_T_QUOTIENT][1], st);
     c->ev_valid[ZK_T_QUOTIENT] = true;
     return ZK_OK;

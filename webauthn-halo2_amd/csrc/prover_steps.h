@@ -284,7 +284,10 @@ inline int grand_products(zk_ctx* c, hipStream_t st, const Layout& lay, const st
 
 // ---------------------------------------------------------------- quotient ---
 // h(X) on the extended coset (pk_quotient, divided by X^n - 1) from the coset forms of the workspace's own columns, into h_ext
-inline int quotient_of_workspace(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, bool cosets3, const Fr& beta, const Fr& gamma, const Fr& y) {
+// `into` / `yscale` / `accumulate`: one pass of a quotient that several circuits share (prover_multi.h) — this workspace's terms
+// times yscale, stored to `into` or added to it; the plain call below is the pass that stores this workspace's own quotient
+inline int quotient_pass_of_workspace(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, bool cosets3, const Fr& beta, const Fr& gamma, const Fr& y,
+                                      Fr* into, const Fr& yscale, bool accumulate) {
     const Layout& lay = pk->lay;
     QuotientCosets qc;
     qc.adv.assign(pk->adv_coset.begin(), pk->adv_coset.end());
@@ -299,9 +302,13 @@ inline int quotient_of_workspace(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, bool 
         std::vector<const void*> rd;
         for (auto* v : {&qc.adv, &qc.z, &qc.lk_a, &qc.lk_s, &qc.lk_z})
             for (const Fr* q : *v) rd.push_back(q);
-        aud_note(c, st, rd, {pk->h_ext}, "quotient");
+        if (accumulate) rd.push_back(into);
+        aud_note(c, st, rd, {into}, accumulate ? "quotient (accumulating pass)" : "quotient");
     }
-    return pk_quotient(c, pk, qc, beta, gamma, y, true, pk->h_ext);
+    return pk_quotient_pass(c, pk, qc, beta, gamma, y, yscale, accumulate, true, into);
+}
+inline int quotient_of_workspace(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, bool cosets3, const Fr& beta, const Fr& gamma, const Fr& y) {
+    return quotient_pass_of_workspace(c, st, pk, cosets3, beta, gamma, y, pk->h_ext, Fr::one(), false);
 }
 
 // ------------------------------------------------------------- evaluations ---

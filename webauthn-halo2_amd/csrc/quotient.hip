@@ -151,7 +151,18 @@ __device__ __forceinline__ Fr29 quotient_row(const QuotientArgs& a, uint32_t i, 
     return norm29(add29(add29(acc, t0), add29(t1, t2)));  // 66 + 3 * 14 = 108 <= 168
 }
 
-template <bool C3>
+// ACC: the pass ADDS its row to what `out` already holds (one proof over several circuits, prover_multi.h: circuit 0 runs the
+// plain form, circuits 1 .. N - 1 this one on the same vector, each with its own powers of y).  out[i] is a standard-form,
+// canonical value (a previous pass stored it after reduce_once), so one modular addition keeps it canonical.  The lazy-sum
+// bounds above are PER PASS and do not change: the addition happens after the pass has left the carry-free field.
+template <bool ACC>
+__device__ __forceinline__ void q_store(Fr* out, Fr r) {
+    reduce_once(r);
+    if (ACC) r = fe_add(r, fe_load(out));
+    fe_store(out, r);
+}
+
+template <bool C3, bool ACC = false>
 __global__ __launch_bounds__(256) void quotient_kernel(const QuotientArgs* __restrict__ ap) {
     const QuotientArgs& a = *ap;
     const uint32_t N = 1u << a.log_ext;
@@ -159,15 +170,13 @@ __global__ __launch_bounds__(256) void quotient_kernel(const QuotientArgs* __res
     if (i >= (C3 ? 3 * (N >> 2) : N)) return;
     const Fr29 total = quotient_row<false, C3>(a, i, 0, 1);
     // times 1/(X^n - 1) (or 1) in the standard form: the product is the standard form of the result, < 2p
-    Fr r = from29(mul29(total, to29(a.t_inv[C3 ? i >> (a.log_ext - 2) : i & 3])));
-    reduce_once(r);
-    fe_store(a.out + i, r);
+    q_store<ACC>(a.out + i, from29(mul29(total, to29(a.t_inv[C3 ? i >> (a.log_ext - 2) : i & 3]))));
 }
 
 // The many-column shapes (k <= 14: hundreds of gates and lookups over a few thousand rows) have too few rows to fill the chip
 // with one lane per row: 2^log_ns lanes share a row, each takes every 2^log_ns-th gate / chunk / lookup, and the shares are
 // added through LDS (each first brought below 2p by a product with "one").  Lanes of a workgroup: row-major within a slice.
-template <bool C3>
+template <bool C3, bool ACC = false>
 __global__ __launch_bounds__(256) void quotient_sliced_kernel(const QuotientArgs* __restrict__ ap, uint32_t log_ns) {
     __shared__ uint32_t part[256 * 9];
     const QuotientArgs& a = *ap;
@@ -186,9 +195,7 @@ __global__ __launch_bounds__(256) void quotient_sliced_kernel(const QuotientArgs
         for (int l = 0; l < 9; l++) v.l[l] = part[l * 256 + s * rows + row];
         total = norm29(add29(total, v));  // <= 2 * 16 p
     }
-    Fr r = from29(mul29(total, to29(a.t_inv[C3 ? i >> (a.log_ext - 2) : i & 3])));
-    reduce_once(r);
-    fe_store(a.out + i, r);
+    q_store<ACC>(a.out + i, from29(mul29(total, to29(a.t_inv[C3 ? i >> (a.log_ext - 2) : i & 3]))));
 }
 
 // `d_args` is the argument block in device memory (too large for a kernarg segment)
@@ -202,6 +209,18 @@ void launch_quotient_dev(const QuotientArgs* d_args, uint32_t log_ext, uint32_t 
     } else {
         if (cosets3) hipLaunchKernelGGL(quotient_sliced_kernel<true>, dim3(N >> (8 - log_slices)), dim3(256), 0, st, d_args, log_slices);
         else hipLaunchKernelGGL(quotient_sliced_kernel<false>, dim3(N >> (8 - log_slices)), dim3(256), 0, st, d_args, log_slices);
+    }
+}
+
+// the accumulating pass (ACC above): same grid, same argument block; the plain launcher's instantiations are untouched
+void launch_quotient_acc_dev(const QuotientArgs* d_args, uint32_t log_ext, uint32_t log_slices, hipStream_t st, bool cosets3) {
+    const uint32_t N = cosets3 ? 3u << (log_ext - 2) : 1u << log_ext;
+    if (log_slices == 0 || N < 256 || (N & 255)) {
+        if (cosets3) hipLaunchKernelGGL((quotient_kernel<true, true>), dim3((N + 255) / 256), dim3(256), 0, st, d_args);
+        else hipLaunchKernelGGL((quotient_kernel<false, true>), dim3((N + 255) / 256), dim3(256), 0, st, d_args);
+    } else {
+        if (cosets3) hipLaunchKernelGGL((quotient_sliced_kernel<true, true>), dim3(N >> (8 - log_slices)), dim3(256), 0, st, d_args, log_slices);
+        else hipLaunchKernelGGL((quotient_sliced_kernel<false, true>), dim3(N >> (8 - log_slices)), dim3(256), 0, st, d_args, log_slices);
     }
 }
 

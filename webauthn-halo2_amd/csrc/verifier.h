@@ -31,6 +31,7 @@ struct Term {
 // where everything sits in a proof of one key / transcript / scheme
 struct ProofLayout {
     bool evm = false, shplonk = false;
+    uint32_t nc = 1;                   // circuits the proof covers (zk_verify_multi; 1: a proof of zk_prove)
     size_t point_size = 0, len = 0;
     std::vector<uint32_t> point_off;   // byte offset of each point, transcript order
     uint32_t n_points = 0;             // = point_off.size()
@@ -49,17 +50,30 @@ struct Query {
     uint32_t eval;
 };
 
+// One proof over nc circuits of one key [RECALLED: halo2's create_proof / verify_proof over `circuits: &[C]`; restated by
+// tests/multi_ref.py]: every per-circuit group of a phase is written for circuit 0, then circuit 1, ...; what belongs to the key
+// or to the proof (fixed / sigma evaluations, random polynomial, h pieces, the opening) is written once.  The per-circuit
+// groups below hold circuit 0's index; circuit c's is that plus c times the group's stride (`*_of`).  nc = 1: a proof of zk_prove.
 // point indices in transcript order
 struct PointIdx {
     uint32_t adv, lk_perm, perm_z, lk_z, random, h, opening;
+    uint32_t s_adv, s_lk_perm, s_perm_z, s_lk_z;  // strides per circuit
+    uint32_t adv_of(uint32_t c) const { return adv + c * s_adv; }
+    uint32_t lk_perm_of(uint32_t c) const { return lk_perm + c * s_lk_perm; }
+    uint32_t perm_z_of(uint32_t c) const { return perm_z + c * s_perm_z; }
+    uint32_t lk_z_of(uint32_t c) const { return lk_z + c * s_lk_z; }
 };
-inline PointIdx point_idx(const Layout& lay) {
+inline PointIdx point_idx(const Layout& lay, uint32_t nc = 1) {
     PointIdx p;
+    p.s_adv = lay.n_adv;
+    p.s_lk_perm = 2 * lay.n_lookups;              // (a', s') per lookup
+    p.s_perm_z = lay.n_chunks;
+    p.s_lk_z = lay.n_lookups;
     p.adv = 0;
-    p.lk_perm = lay.n_adv;                        // (a', s') per lookup
-    p.perm_z = p.lk_perm + 2 * lay.n_lookups;
-    p.lk_z = p.perm_z + lay.n_chunks;
-    p.random = p.lk_z + lay.n_lookups;
+    p.lk_perm = nc * p.s_adv;
+    p.perm_z = p.lk_perm + nc * p.s_lk_perm;
+    p.lk_z = p.perm_z + nc * p.s_perm_z;
+    p.random = p.lk_z + nc * p.s_lk_z;
     p.h = p.random + 1;
     p.opening = p.h + lay.n_h;
     return p;
@@ -67,42 +81,48 @@ inline PointIdx point_idx(const Layout& lay) {
 // scalar indices (evaluations) in transcript order
 struct EvalIdx {
     uint32_t adv, fix, random, sigma, perm, lookup, count;
+    uint32_t s_adv, s_perm, s_lookup;  // strides per circuit
+    uint32_t adv_of(uint32_t c) const { return adv + c * s_adv; }
+    uint32_t perm_of(uint32_t c) const { return perm + c * s_perm; }
+    uint32_t lookup_of(uint32_t c) const { return lookup + c * s_lookup; }
 };
-inline EvalIdx eval_idx(const Layout& lay) {
+inline EvalIdx eval_idx(const Layout& lay, uint32_t nc = 1) {
     EvalIdx e;
+    e.s_adv = (uint32_t)lay.advice_queries.size();
+    e.s_perm = 3 * lay.n_chunks - 1;  // (z, z_next, z_last) per chunk, the last chunk without z_last
+    e.s_lookup = 5 * lay.n_lookups;
     e.adv = 0;
-    e.fix = (uint32_t)lay.advice_queries.size();
+    e.fix = nc * e.s_adv;
     e.random = e.fix + lay.n_fix;
     e.sigma = e.random + 1;
     e.perm = e.sigma + (uint32_t)lay.perm_cols.size();
-    e.lookup = e.perm + 3 * lay.n_chunks - 1;  // (z, z_next, z_last) per chunk, the last chunk without z_last
-    e.count = e.lookup + 5 * lay.n_lookups;
+    e.lookup = e.perm + nc * e.s_perm;
+    e.count = e.lookup + nc * e.s_lookup;
     return e;
-}
-inline uint32_t perm_eval(const Layout& lay, uint32_t chunk, uint32_t which) {  // which: 0 z, 1 z_next, 2 z_last
-    (void)lay;
-    return eval_idx(lay).perm + 3 * chunk + which;
 }
 
 // the verifier's queries in halo2's order (the pinned verifier's build_queries, then h and the random polynomial)
 inline std::vector<Query> build_queries(const Layout& lay, const ProofLayout& pl) {
-    const PointIdx P = point_idx(lay);
-    const EvalIdx E = eval_idx(lay);
+    const uint32_t nc = pl.nc;
+    const PointIdx P = point_idx(lay, nc);
+    const EvalIdx E = eval_idx(lay, nc);
     std::vector<Query> q;
-    for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
-        q.push_back({P.adv + lay.advice_queries[i].first, lay.advice_queries[i].second, E.adv + i});
-    for (uint32_t i = 0; i < lay.n_chunks; i++) {
-        q.push_back({P.perm_z + i, 0, perm_eval(lay, i, 0)});
-        q.push_back({P.perm_z + i, 1, perm_eval(lay, i, 1)});
-    }
-    for (int i = (int)lay.n_chunks - 2; i >= 0; i--) q.push_back({P.perm_z + i, lay.last_rot, perm_eval(lay, i, 2)});
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        const uint32_t e = E.lookup + 5 * l;  // z, z_next, a', a'(w^-1 x), s'
-        q.push_back({P.lk_z + l, 0, e});
-        q.push_back({P.lk_perm + 2 * l, 0, e + 2});
-        q.push_back({P.lk_perm + 2 * l + 1, 0, e + 4});
-        q.push_back({P.lk_perm + 2 * l, -1, e + 3});
-        q.push_back({P.lk_z + l, 1, e + 1});
+    for (uint32_t c = 0; c < nc; c++) {  // every circuit's own openings, circuit by circuit; then what the circuits share
+        for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
+            q.push_back({P.adv_of(c) + lay.advice_queries[i].first, lay.advice_queries[i].second, E.adv_of(c) + i});
+        for (uint32_t i = 0; i < lay.n_chunks; i++) {
+            q.push_back({P.perm_z_of(c) + i, 0, E.perm_of(c) + 3 * i});
+            q.push_back({P.perm_z_of(c) + i, 1, E.perm_of(c) + 3 * i + 1});
+        }
+        for (int i = (int)lay.n_chunks - 2; i >= 0; i--) q.push_back({P.perm_z_of(c) + i, lay.last_rot, E.perm_of(c) + 3 * i + 2});
+        for (uint32_t l = 0; l < lay.n_lookups; l++) {
+            const uint32_t e = E.lookup_of(c) + 5 * l;  // z, z_next, a', a'(w^-1 x), s'
+            q.push_back({P.lk_z_of(c) + l, 0, e});
+            q.push_back({P.lk_perm_of(c) + 2 * l, 0, e + 2});
+            q.push_back({P.lk_perm_of(c) + 2 * l + 1, 0, e + 4});
+            q.push_back({P.lk_perm_of(c) + 2 * l, -1, e + 3});
+            q.push_back({P.lk_z_of(c) + l, 1, e + 1});
+        }
     }
     for (uint32_t f = 0; f < lay.n_fix; f++) q.push_back({pl.base_fix() + f, 0, E.fix + f});
     for (uint32_t i = 0; i < lay.perm_cols.size(); i++) q.push_back({pl.base_perm() + i, 0, E.sigma + i});
@@ -119,15 +139,16 @@ inline std::vector<int> gwc_rotations(const std::vector<Query>& qs) {
     return rots;
 }
 
-inline ProofLayout proof_layout(const Layout& lay, bool evm, bool shplonk) {
+inline ProofLayout proof_layout(const Layout& lay, bool evm, bool shplonk, uint32_t nc = 1) {
     ProofLayout pl;
+    pl.nc = nc;
     pl.evm = evm;
     pl.shplonk = shplonk;
     pl.point_size = evm ? 64 : 32;
     pl.n_fix = lay.n_fix;
     pl.n_perm = (uint32_t)lay.perm_cols.size();
-    const PointIdx P = point_idx(lay);
-    const EvalIdx E = eval_idx(lay);
+    const PointIdx P = point_idx(lay, nc);
+    const EvalIdx E = eval_idx(lay, nc);
     size_t off = 0;
     auto pts = [&](uint32_t n) {
         for (uint32_t i = 0; i < n; i++) {
@@ -194,20 +215,21 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     EvmTranscript evm;
     Blake2bTranscript b2;
     Transcript* tr = pl.evm ? (Transcript*)&evm : (Transcript*)&b2;
-    const PointIdx P = point_idx(lay);
-    const EvalIdx E = eval_idx(lay);
+    const uint32_t nc = pl.nc;
+    const PointIdx P = point_idx(lay, nc);
+    const EvalIdx E = eval_idx(lay, nc);
     Challenges& ch = out->ch;
     tr->common_scalar(transcript_repr);
     uint32_t np = 0;
     auto absorb_points = [&](uint32_t n) {
         for (uint32_t i = 0; i < n; i++) tr->common_point(pts[np++]);
     };
-    absorb_points(lay.n_adv);
+    absorb_points(nc * lay.n_adv);
     ch.theta = tr->squeeze();
-    absorb_points(2 * lay.n_lookups);
+    absorb_points(nc * 2 * lay.n_lookups);
     ch.beta = tr->squeeze();
     ch.gamma = tr->squeeze();
-    absorb_points(lay.n_chunks + lay.n_lookups + 1);
+    absorb_points(nc * (lay.n_chunks + lay.n_lookups) + 1);
     ch.y = tr->squeeze();
     absorb_points(lay.n_h);
     ch.x = tr->squeeze();
@@ -241,53 +263,55 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     for (int i = 1; i <= (int)BLINDING_FACTORS; i++) l_blind = fe_add(l_blind, L(-i));
     if (zero_div) return false;
     const Fr active = fe_sub(fe_sub(one, l_last), l_blind);
-    auto adv = [&](uint32_t col, int rot) {
-        for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
-            if (lay.advice_queries[i].first == col && lay.advice_queries[i].second == rot) return ev[E.adv + i];
-        return Fr::zero();
-    };
     auto fix = [&](uint32_t f) { return ev[E.fix + f]; };
-    std::vector<Fr> exprs;
-    for (uint32_t j = 0; j < lay.n_gate; j++) {
-        const Fr a = adv(j, 0), b = adv(j, 1), cc = adv(j, 2), d = adv(j, 3);
-        const uint32_t col = lay.gate_sel[j] & 0xffffffu, form = lay.gate_sel[j] >> 24;
-        const Fr q = fix(col);
-        Fr sel = q;
-        if (form) sel = fe_mul(q, fe_sub(fr_from_u64(form == 1 ? 2 : 1), q));
-        exprs.push_back(fe_mul(sel, fe_sub(fe_add(a, fe_mul(b, cc)), d)));
-    }
-    auto col_eval = [&](const Col& col) { return col.fixed ? fix(col.idx) : adv(col.idx, 0); };
-    auto pe = [&](uint32_t i, uint32_t which) { return ev[perm_eval(lay, i, which)]; };
-    exprs.push_back(fe_mul(l0, fe_sub(one, pe(0, 0))));
-    const Fr zl = pe(lay.n_chunks - 1, 0);
-    exprs.push_back(fe_mul(l_last, fe_sub(fe_sqr(zl), zl)));
-    for (uint32_t i = 1; i < lay.n_chunks; i++) exprs.push_back(fe_mul(l0, fe_sub(pe(i, 0), pe(i - 1, 2))));
     const Fr delta = fr_delta_host();
-    Fr cur_base = fe_mul(beta, x);  // beta x delta^(i chunk_len)
-    for (uint32_t i = 0; i < lay.n_chunks; i++) {
-        const uint32_t lo = i * lay.chunk_len, hi = std::min<uint32_t>(lo + lay.chunk_len, (uint32_t)lay.perm_cols.size());
-        Fr left = pe(i, 1), right = pe(i, 0), cur = cur_base;
-        for (uint32_t t = lo; t < hi; t++) {
-            const Fr ce = col_eval(lay.perm_cols[t]);
-            left = fe_mul(left, fe_add(fe_add(ce, fe_mul(beta, ev[E.sigma + t])), gamma));
-            right = fe_mul(right, fe_add(fe_add(ce, cur), gamma));
-            cur = fe_mul(cur, delta);
+    std::vector<Fr> exprs;  // the nc x T expressions of the y-Horner chain: circuit 0's, then circuit 1's, ...
+    for (uint32_t circ = 0; circ < nc; circ++) {
+        auto adv = [&](uint32_t col, int rot) {
+            for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
+                if (lay.advice_queries[i].first == col && lay.advice_queries[i].second == rot) return ev[E.adv_of(circ) + i];
+            return Fr::zero();
+        };
+        for (uint32_t j = 0; j < lay.n_gate; j++) {
+            const Fr a = adv(j, 0), b = adv(j, 1), cc = adv(j, 2), d = adv(j, 3);
+            const uint32_t col = lay.gate_sel[j] & 0xffffffu, form = lay.gate_sel[j] >> 24;
+            const Fr q = fix(col);
+            Fr sel = q;
+            if (form) sel = fe_mul(q, fe_sub(fr_from_u64(form == 1 ? 2 : 1), q));
+            exprs.push_back(fe_mul(sel, fe_sub(fe_add(a, fe_mul(b, cc)), d)));
         }
-        cur_base = cur;
-        exprs.push_back(fe_mul(active, fe_sub(left, right)));
-    }
-    for (uint32_t l = 0; l < lay.n_lookups; l++) {
-        const Fr* le = &ev[E.lookup + 5 * l];
-        const Fr z = le[0], zn = le[1], ap = le[2], ap_inv = le[3], sp = le[4];
-        const Fr inp = lay.single ? fe_mul(fix(lay.fx_qlookup), adv(0, 0)) : adv(lay.n_gate + l, 0);
-        const Fr tab = fix(lay.fx_table);
-        exprs.push_back(fe_mul(l0, fe_sub(one, z)));
-        exprs.push_back(fe_mul(l_last, fe_sub(fe_sqr(z), z)));
-        const Fr left = fe_mul(fe_mul(zn, fe_add(ap, beta)), fe_add(sp, gamma));
-        const Fr right = fe_mul(fe_mul(z, fe_add(inp, beta)), fe_add(tab, gamma));
-        exprs.push_back(fe_mul(active, fe_sub(left, right)));
-        exprs.push_back(fe_mul(l0, fe_sub(ap, sp)));
-        exprs.push_back(fe_mul(fe_mul(active, fe_sub(ap, sp)), fe_sub(ap, ap_inv)));
+        auto col_eval = [&](const Col& col) { return col.fixed ? fix(col.idx) : adv(col.idx, 0); };
+        auto pe = [&](uint32_t i, uint32_t which) { return ev[E.perm_of(circ) + 3 * i + which]; };
+        exprs.push_back(fe_mul(l0, fe_sub(one, pe(0, 0))));
+        const Fr zl = pe(lay.n_chunks - 1, 0);
+        exprs.push_back(fe_mul(l_last, fe_sub(fe_sqr(zl), zl)));
+        for (uint32_t i = 1; i < lay.n_chunks; i++) exprs.push_back(fe_mul(l0, fe_sub(pe(i, 0), pe(i - 1, 2))));
+        Fr cur_base = fe_mul(beta, x);  // beta x delta^(i chunk_len)
+        for (uint32_t i = 0; i < lay.n_chunks; i++) {
+            const uint32_t lo = i * lay.chunk_len, hi = std::min<uint32_t>(lo + lay.chunk_len, (uint32_t)lay.perm_cols.size());
+            Fr left = pe(i, 1), right = pe(i, 0), cur = cur_base;
+            for (uint32_t t = lo; t < hi; t++) {
+                const Fr ce = col_eval(lay.perm_cols[t]);
+                left = fe_mul(left, fe_add(fe_add(ce, fe_mul(beta, ev[E.sigma + t])), gamma));
+                right = fe_mul(right, fe_add(fe_add(ce, cur), gamma));
+                cur = fe_mul(cur, delta);
+            }
+            cur_base = cur;
+            exprs.push_back(fe_mul(active, fe_sub(left, right)));
+        }
+        for (uint32_t l = 0; l < lay.n_lookups; l++) {
+            const Fr* le = &ev[E.lookup_of(circ) + 5 * l];
+            const Fr z = le[0], zn = le[1], ap = le[2], ap_inv = le[3], sp = le[4];
+            const Fr inp = lay.single ? fe_mul(fix(lay.fx_qlookup), adv(0, 0)) : adv(lay.n_gate + l, 0);
+            const Fr tab = fix(lay.fx_table);
+            exprs.push_back(fe_mul(l0, fe_sub(one, z)));
+            exprs.push_back(fe_mul(l_last, fe_sub(fe_sqr(z), z)));
+            const Fr left = fe_mul(fe_mul(zn, fe_add(ap, beta)), fe_add(sp, gamma));
+            const Fr right = fe_mul(fe_mul(z, fe_add(inp, beta)), fe_add(tab, gamma));
+            exprs.push_back(fe_mul(active, fe_sub(left, right)));
+            exprs.push_back(fe_mul(l0, fe_sub(ap, sp)));
+            exprs.push_back(fe_mul(fe_mul(active, fe_sub(ap, sp)), fe_sub(ap, ap_inv)));
+        }
     }
     Fr acc = Fr::zero();
     for (const Fr& e : exprs) acc = fe_add(fe_mul(acc, y), e);

@@ -376,7 +376,10 @@ int settle(Job& J, const std::vector<uint32_t>& S, uint8_t* verdicts) {
 
 }  // namespace
 
-ZK_API(zk_verify_batch, (zk_ctx* c, zk_pk h, size_t batch, int transcript, int scheme, const uint8_t* const* proofs, const size_t* lens, uint8_t* verdicts), (c, h, batch, transcript, scheme, proofs, lens, verdicts)) {
+// `batch` proofs of one key, each over `n_circuits` circuits (1: the proofs of zk_prove; more: those of zk_prove_multi — a longer
+// proof read in the order verifier.h states, the same four steps)
+static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, int transcript, int scheme, const uint8_t* const* proofs,
+                         const size_t* lens, uint8_t* verdicts) {
     if (!c || !proofs || !lens || !verdicts || batch == 0 || batch > ZK_VERIFY_BATCH_MAX) return ZK_EINVAL;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
@@ -397,7 +400,7 @@ ZK_API(zk_verify_batch, (zk_ctx* c, zk_pk h, size_t batch, int transcript, int s
     VerifyWs* w = c->vws;
     if ((rc = pk_vk_bases(c, pk))) return rc;
     const Layout& lay = pk->lay;
-    const verifier::ProofLayout pl = verifier::proof_layout(lay, transcript == ZK_TRANSCRIPT_EVM, scheme == ZK_SCHEME_SHPLONK);
+    const verifier::ProofLayout pl = verifier::proof_layout(lay, transcript == ZK_TRANSCRIPT_EVM, scheme == ZK_SCHEME_SHPLONK, n_circuits);
     std::vector<uint8_t> v(batch, 0);
     Job J{c, pk, w, g2_from_raw(c->g2_raw), g2_from_raw(c->s_g2_raw), {}, {}, {}};
 
@@ -519,6 +522,20 @@ ZK_API(zk_verify_batch, (zk_ctx* c, zk_pk h, size_t batch, int transcript, int s
     }
     memcpy(verdicts, v.data(), batch);
     return aud_verdict(c, aud0, ZK_OK);
+}
+
+ZK_API(zk_verify_batch, (zk_ctx* c, zk_pk h, size_t batch, int transcript, int scheme, const uint8_t* const* proofs, const size_t* lens, uint8_t* verdicts), (c, h, batch, transcript, scheme, proofs, lens, verdicts)) {
+    return verify_proofs(c, h, batch, 1, transcript, scheme, proofs, lens, verdicts);
+}
+
+// verify_proof with n_circuits instance slices (all empty): one proof of zk_prove_multi.  A proof of another circuit count has
+// another length: a verdict of 0, like every bad proof
+ZK_API(zk_verify_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok), (c, h, n_circuits, transcript, scheme, proof, len, ok)) {
+    if (!ok || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
+    uint8_t v = 0;
+    const int rc = verify_proofs(c, h, 1, (uint32_t)n_circuits, transcript, scheme, &proof, &len, &v);
+    if (rc == ZK_OK) *ok = v;
+    return rc;
 }
 
 ZK_API(zk_verify, (zk_ctx* c, zk_pk h, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok), (c, h, transcript, scheme, proof, len, ok)) {

@@ -477,6 +477,40 @@ def create_proof_from_advice(advice_columns, proving_key_path, degree, transcrip
                           lambda st, eng, pk, slots, cols, n: _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check))
 
 
+def create_proof_multi_from_advice(advice_sets, proving_key_path, degree, transcript=ZK_TRANSCRIPT_BLAKE2B, device=0, rng_seed=None,
+                                   check=False) -> bytes:
+    """create_proof(&params, &pk, &[c_0 .. c_{N-1}], &[&[]; N], ..): ONE proof over the N = len(advice_sets) circuits whose
+    host-synthesized advice columns are given (Engine.prove_multi: one transcript, one RNG stream, one quotient, one multi-open)
+    — an extension: the reference proves one circuit per call.  advice_sets[c]: circuit c's columns as
+    create_proof_from_advice takes them.  check=True: every circuit goes through Engine.witness_check first; WitnessError
+    carries the index of the first violated circuit in `.circuit`.  The verifier must expect the same N (verify_multi)."""
+    advice_sets = [list(a) for a in advice_sets]
+    if not advice_sets or any(len(a) != len(advice_sets[0]) for a in advice_sets):
+        raise ValueError("every circuit brings the key's number of advice columns")
+    per = len(advice_sets[0])
+
+    def run(st, eng, pk, slots, cols, n):
+        def prove(sets):
+            if check:
+                for c, polys in enumerate(sets):
+                    counts, failures = eng.witness_check(pk, polys)
+                    if counts[0]:
+                        err = WitnessError(counts, failures)
+                        err.circuit = c
+                        raise err
+            seed = rng_seed if rng_seed is not None else os.urandom(32)
+            return eng.prove_multi(pk, sets, seed, transcript)
+
+        def take(c, sets):  # a set of request slots per circuit, nested so that each is handed back on every way out
+            if c == len(advice_sets):
+                return prove(sets)
+            return _on_slots(st, eng, slots, cols[c * per:(c + 1) * per], n, degree, lambda polys: take(c + 1, sets + [polys]))
+
+        return take(0, [])
+
+    return _with_pipeline([col for a in advice_sets for col in a], proving_key_path, degree, device, run)
+
+
 def mock_verify_advice(advice_columns, proving_key_path, degree, device=0, cap=64):
     """`MockProver::run(degree, &circuit, vec![]).verify()` — the body of the reference's test_secp256r1_ecdsa
     (ecdsa_p256.rs:209-248) — for a host that brings its own advice columns: the resident key and a pipeline's request slots
@@ -683,3 +717,13 @@ def verify_batch(degree: int, proofs, verifying_key_path: str, evm: bool, device
     if evm:
         return eng.verify_batch(vk, [bytes(p) for p in proofs], ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
     return eng.verify_batch(vk, [bytes(p) for p in proofs], ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+
+
+def verify_multi(degree: int, proof: bytes, verifying_key_path: str, n: int, evm: bool, device: int = 0) -> bool:
+    """verify_proof of ONE proof over n circuits (create_proof_multi_from_advice; halo2: n instance slices, snark-verifier:
+    `Config::kzg().with_num_proof(n)`) under the reference's two pairings: evm = Keccak EvmTranscript + GWC, else Blake2b +
+    SHPLONK.  An extension: the reference verifies one circuit per proof.  A proof over another number of circuits is rejected."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device)
+    if evm:
+        return eng.verify_multi(vk, n, bytes(proof), ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
+    return eng.verify_multi(vk, n, bytes(proof), ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)

@@ -25,6 +25,7 @@ ZK_OPT_MSM_TAIL_MAIN_ABOVE, ZK_OPT_BATCH_PASS_COLUMNS, ZK_OPT_XFORM_STREAM, ZK_O
 ZK_OPT_STREAM_PRIORITY, ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_ACTIVITY_HOLD = 12, 13, 14
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
+ZK_PROVE_MULTI_MAX = 16
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 ZK_SRS_CONTRIB_SAME_SECRET, ZK_SRS_CONTRIB_LINKS, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT = 1, 2, 4, 8
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
@@ -207,6 +208,11 @@ def load_library():
                       ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_prove_batch": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_char_p, ctypes.c_int,
                             ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_proof_size_multi": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_prove_multi": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_char_p, ctypes.c_int,
+                            ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_verify_multi": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)],
+                            ctypes.c_int),
         "zk_srs_write": ([vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_srs_read": ([vp, vp, sz, ctypes.c_int], ctypes.c_int),
         "zk_srs_set_g2": ([vp, u64p, u64p], ctypes.c_int),
@@ -249,7 +255,8 @@ def load_library():
     for name, (args, res) in sig.items():
         fn = getattr(L, name, None)
         if fn is None:
-            if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info") and os.environ.get("ZKMI355_LIB"):
+            if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info", "zk_proof_size_multi",
+                        "zk_prove_multi", "zk_verify_multi") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -703,6 +710,35 @@ class Engine:
         self._chk(self.L.zk_prove_batch(self.ctx, pk, B, hs, na, b"".join(bytes(sd) for sd in seeds), transcript, scheme, buf, stride,
                                         ctypes.byref(ln)), "zk_prove_batch")
         return [buf.raw[j * stride:j * stride + ln.value] for j in range(B)]
+
+    def proof_size_multi(self, pk, n_circuits, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
+        ln = ctypes.c_size_t()
+        self._chk(self.L.zk_proof_size_multi(self.ctx, pk, n_circuits, transcript, scheme, ctypes.byref(ln)), "zk_proof_size_multi")
+        return ln.value
+
+    def prove_multi(self, pk, advice_sets, seed=bytes(32), transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
+        """zk_prove_multi: ONE proof over len(advice_sets) circuits of one key (halo2's create_proof with several circuits): one
+        transcript, one RNG stream from `seed`, one quotient, one multi-open.  advice_sets[c]: circuit c's advice columns
+        (resident Polys).  One circuit gives prove()'s bytes."""
+        N = len(advice_sets)
+        if len(seed) != 32:
+            raise ValueError("rng seed must be 32 bytes")
+        na = len(advice_sets[0]) if N else 0
+        if any(len(a) != na for a in advice_sets):
+            raise ValueError("every circuit has the key's number of advice columns")
+        hs = (ctypes.c_uint64 * max(N * na, 1))(*[p.h for a in advice_sets for p in a])
+        ln = ctypes.c_size_t()
+        self._chk(self.L.zk_proof_size_multi(self.ctx, pk, N, transcript, scheme, ctypes.byref(ln)), "zk_proof_size_multi")
+        buf = ctypes.create_string_buffer(ln.value)
+        self._chk(self.L.zk_prove_multi(self.ctx, pk, N, hs, na, seed, transcript, scheme, buf, len(buf), ctypes.byref(ln)), "zk_prove_multi")
+        return buf.raw[:ln.value]
+
+    def verify_multi(self, pk, n_circuits, proof, transcript, scheme=ZK_SCHEME_DEFAULT) -> bool:
+        """zk_verify_multi: verify_proof of one proof over n_circuits circuits (full or verifying-only key)."""
+        proof = bytes(proof)
+        ok = ctypes.c_int(0)
+        self._chk(self.L.zk_verify_multi(self.ctx, pk, n_circuits, transcript, scheme, proof, len(proof), ctypes.byref(ok)), "zk_verify_multi")
+        return bool(ok.value)
 
     def witness_check(self, pk, advice_polys, cap=64):
         """MockProver::verify of resident advice columns against a resident key (zk_witness_check) -> (counts, failures):

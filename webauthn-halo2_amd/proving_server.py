@@ -171,3 +171,41 @@ def verify_batch(bodies, evm=True, device=0, degree=DEGREE):
         for (i, _), ok in zip(items, verdicts):
             out[i] = "verified" if ok else "rejected"
     return out
+
+
+# ---- extensions the reference server does not have: ONE proof over several requests -----------------------------------------
+# halo2's create_proof takes a slice of circuits; N signatures under one key then share one transcript, one quotient, one opening
+# proof and — on chain — one pairing.  The reference's endpoints prove one request per call; these two keep its JSON contract
+# (a list of the existing request bodies in, one hex proof out) for a host that aggregates.
+
+def prove_multi(bodies, evm=True, device=0, degree=DEGREE, rng_seed=None, check=False) -> str:
+    """A list of ProveRequestBody (JSON strings / dicts, all naming ONE proving key) -> the hex of ONE proof over all of them, in
+    list order (ecdsa_p256.create_proof_multi_from_advice).  Each body passes the ES256 check first; one refused body refuses
+    the call.  The proof verifies with verify_multi and the same count only."""
+    reqs = [parse_request(b) for b in bodies]
+    if not reqs:
+        raise ValueError("at least one request")
+    path = reqs[0]["proving_key_path"]
+    if any(q["proving_key_path"] != path for q in reqs):
+        raise ValueError("proving_key_path: the requests of one proof name one key")
+    for i, q in enumerate(reqs):
+        if not ecdsa_p256.es256_verify(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]):
+            raise ValueError(f"request {i}: invalid ES256 signature (or non-canonical field encoding): request refused")
+    _, p, _ = ecdsa_p256._resident_key(path, degree, device)
+    sets = []
+    for q in reqs:
+        asg = ecdsa_p256.circuit.synthesize(p, ecdsa_p256._witness_seed(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]))
+        sets.append([asg.to_limbs(col) for col in asg.advice])
+    transcript = ecdsa_p256.ZK_TRANSCRIPT_EVM if evm else ecdsa_p256.ZK_TRANSCRIPT_BLAKE2B
+    return ecdsa_p256.create_proof_multi_from_advice(sets, path, degree, transcript, device, rng_seed, check).hex()
+
+
+def verify_multi(body, evm=True, device=0, degree=DEGREE) -> str:
+    """VerifyRequestBody plus "num_proof": the number of requests the proof covers -> "verified" or "rejected"."""
+    path, proof = parse_verify_request(body)
+    if isinstance(body, (str, bytes, bytearray)):
+        body = json.loads(body)
+    n = body.get("num_proof")
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+        raise ValueError("num_proof: expected a positive integer")
+    return "verified" if ecdsa_p256.verify_multi(degree, proof, path, n, evm, device) else "rejected"

@@ -330,6 +330,10 @@ typedef struct {
     uint32_t num_idle_gate_columns; /* trailing gate columns whose selector is never enabled (at most half of num_advice):
                                        halo2's selector compression puts the t-th such selector into the fixed column of
                                        gate t — no column of its own — and replaces the pair by q (2 - q) / q (1 - q) */
+    uint32_t num_instance_columns;  /* 0, or 1: ONE instance column for the circuit's public inputs, made after the chips'
+                                       columns and equality-enabled — the LAST permutation column, queried at rotation 0.  Zero
+                                       (what aggregate-initialised and zero-filled callers get) is the reference's circuit.
+                                       Anything above 1 is ZK_EINVAL.  See "public inputs" below */
 } zk_circuit_params;
 typedef uint64_t zk_pk; /* opaque: proving key + verifying key + prover workspace, device resident */
 
@@ -342,7 +346,8 @@ typedef uint64_t zk_pk; /* opaque: proving key + verifying key + prover workspac
 /* replaces keygen_vk + keygen_pk (ecdsa_p256.rs:259-260) for a synthesized circuit: `fixed_canonical`
  * holds the fixed columns (n_fix x n x 4 limbs, canonical integers, column order: constants, range
  * table, selectors); `copies` the copy constraints as (perm_col_a, row_a, perm_col_b, row_b) with
- * permutation columns ordered [constants..., gate advice..., lookup advice...].  Needs the SRS of k. */
+ * permutation columns ordered [constants..., gate advice..., lookup advice..., instance (if the shape has one)] and
+ * rows below the usable n - 7.  Needs the SRS of k. */
 int zk_keygen(zk_ctx* ctx, const zk_circuit_params* params, const uint64_t* fixed_canonical /* n_fixed_columns x n x 4 */,
               size_t n_fixed_columns /* must equal the shape's fixed-column count: ZK_EINVAL otherwise */,
               const uint32_t* copies, size_t n_copies, zk_pk* out);
@@ -371,8 +376,11 @@ int zk_pk_write(zk_ctx* ctx, zk_pk pk, int format, uint8_t* out, size_t cap, siz
 int zk_pk_read(zk_ctx* ctx, const zk_circuit_params* params, const uint8_t* bytes, size_t len, int format,
                const uint64_t transcript_repr_mont[4], zk_pk* out);
 /* the column shape of a key, for a host that drives the phases itself:
- * out = {k, extended k, #advice columns, #fixed columns, #permutation columns, #permutation chunks, #lookups, #h pieces} */
+ * out = {k, extended k, #advice columns, #fixed columns, #permutation columns (the instance column included), #permutation
+ * chunks, #lookups, #h pieces} */
 int zk_pk_shape(zk_ctx* ctx, zk_pk pk, uint32_t out[8]);
+/* instance columns of the key's shape: 0 or 1 */
+int zk_pk_num_instance_columns(zk_ctx* ctx, zk_pk pk, uint32_t* out);
 /* replaces plonk::evaluation::Evaluator::evaluate_h — and, with divide != 0, the EvaluationDomain::divide_by_vanishing_poly
  * that follows it in create_proof — for a Rust host that keeps halo2's own prover flow and off-loads phase by phase (the
  * [patch] route of INTEGRATION.md).  Every operand is a resident vector over the extended coset (2^(k+2) elements, as
@@ -416,12 +424,37 @@ int zk_random_poly(zk_ctx* ctx, const uint8_t chacha_key[32], uint64_t first_blo
  * the reference, e.g. 960 at k=19 Blake2b, halo2-circuits/src/results/ecdsa_bench.csv:2) */
 int zk_proof_size(zk_ctx* ctx, zk_pk pk, int transcript, int scheme, size_t* out);
 /* replaces plonk::create_proof (ecdsa_p256.rs:366-373, 416-423, 555-562) for one circuit with no
- * instances.  `advice` are resident columns (Lagrange values, Montgomery, n rows each; the last 7 rows
+ * instances (a key WITH an instance column: ZK_EINVAL, halo2's InvalidInstances - zk_prove_public).  `advice` are resident columns (Lagrange values, Montgomery, n rows each; the last 7 rows
  * are overwritten by blinding in a private copy).  Randomness: ChaCha20Rng::from_seed(rng_seed), one
  * 64-byte block per Fr::random in halo2's draw order.  Returns the proof bytes the transcript writer
  * would hold after `finalize()`.  proof_out == NULL: only *proof_len is set. */
 int zk_prove(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, const uint8_t rng_seed[32],
              int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
+/* ---- public inputs: create_proof / verify_proof with `instances = &[&[&values]]` for a key whose shape has the instance column
+ * (zk_circuit_params.num_instance_columns = 1) [RECALLED: halo2 with KZG, QUERY_INSTANCE = false; no reference bytes pin it - the
+ * reference circuit has no public inputs.  tests/public_ref.py restates the rule and the bytes are compared with it]:
+ *   vk digest   num_instance_columns: 1, instance_queries: [(Column { index: 0, column_type: Instance }, Rotation(0))], and the
+ *               column at the end of the permutation argument's columns
+ *   transcript  transcript_repr; EVERY instance value as common_scalar, in order (absorbed, not written; the count is not hashed);
+ *               the advice commitments and on as zk_prove
+ *   column      the values fill rows 0 .. m - 1 of a Lagrange column, the rest is zero; it is neither blinded nor committed nor
+ *               evaluated into the proof nor opened, and draws nothing from the RNG.  It enters the permutation grand product as
+ *               its column's values and the quotient as that column's extended coset
+ *   verifier    absorbs the same values and uses inst(x) = sum_i v_i l_i(x) as the column's evaluation in the permutation terms of
+ *               the expected h(x); nothing else changes
+ * [v] and [v, 0] are the same polynomial and different transcripts: neither proof verifies under the other list.  The proof grows
+ * by the column's sigma evaluation and, where the column starts a permutation chunk of its own, by that chunk's z commitment and
+ * evaluations (k = 19 one-column shape: 960 -> 992 bytes Blake2b; k = 17 server shape: 2720 -> 2912 bytes EVM + GWC).
+ * n_instance == 0 is an empty column.  On a key WITHOUT the column n_instance must be 0 and the bytes are zk_prove's.
+ * ZK_EINVAL beyond zk_prove's cases: a value that is not a Montgomery image below the modulus, n_instance > n - 7 (halo2's
+ * InstanceTooLarge), values for a key without the column.  The workspace of a key with the column is three vectors larger (values,
+ * coefficients, extended coset: 96 MiB at k = 19).
+ * OUT OF SCOPE: zk_prove_batch, zk_prove_multi, zk_verify_batch, zk_verify_multi and the phase-level zk_permutation_product /
+ * zk_quotient carry no instances; they - and zk_prove, zk_verify, zk_witness_check - return ZK_EINVAL on a key with the column.
+ * Every other entry point (zk_lookup_permute, zk_lookup_product, the file and key functions, zk_pk_check) works on such a key. */
+int zk_prove_public(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice,
+                    const uint64_t* instance_mont /* n_instance x 4 */, size_t n_instance, const uint8_t rng_seed[32], int transcript,
+                    int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
 /* `batch` independent create_proof calls for ONE key in lock-step on this context: the reference's concurrent requests
  * (one Rocket worker thread per request, proving-server/src/main.rs:457-472, each inside create_proof, ecdsa_p256.rs:366-373 /
  * 416-423) advanced phase by phase together, so that the same commitment of all proofs shares one MSM pass, the same
@@ -456,7 +489,8 @@ int zk_prove_batch(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /*
  * ZK_EINVAL: n_circuits == 0, n_circuits > ZK_PROVE_MULTI_MAX, n_circuits x (#chunks + #lookups) > 256, or zk_prove's own cases;
  * ZK_ESTATE as zk_prove; ZK_EWITNESS: SOME circuit's lookup input is off the table - the call fails as a whole, the outputs are
  * untouched (zk_witness_check tells which circuit).  proof_out == NULL: only *proof_len is set.  Follows zk_prove_batch's rules
- * for ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_BATCH_PASS_COLUMNS and the activity hold.  No instances; no batches of such proofs. */
+ * for ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_BATCH_PASS_COLUMNS and the activity hold.  No instances (a key with an instance column:
+ * ZK_EINVAL; zk_prove_public proves one circuit with them); no batches of such proofs. */
 #define ZK_PROVE_MULTI_MAX 16
 int zk_proof_size_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, size_t* out);
 int zk_prove_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const zk_poly* advice /* n_circuits x n_advice, circuit-major */,
@@ -492,6 +526,13 @@ typedef struct { uint32_t kind, index, row, other_index, other_row, reserved; } 
  * verifying-only key, or a key whose SRS was replaced. */
 int zk_witness_check(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap,
                      uint64_t counts[5]);
+/* MockProver::run(k, &circuit, vec![instance]).verify(): zk_witness_check with the instance column's values (rows 0 ..
+ * n_instance - 1, zero behind them; zk_prove_public's rules for them).  The instance column is the last permutation column: an
+ * advice cell whose sigma-image is an instance cell with another value is a ZK_FAIL_COPY, reported from both sides.  The values
+ * pass through the key's idle instance column; no proof byte depends on a check.  zk_witness_check itself returns ZK_EINVAL on
+ * a key with the column. */
+int zk_witness_check_public(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap,
+                            uint64_t counts[5], const uint64_t* instance_mont /* n_instance x 4 */, size_t n_instance);
 
 /* ---- the key itself: is a resident proving key what keygen would have made of its own values? ---------------------------
  * A ProvingKey holds every column four times - commitment, values, coefficients, extended coset - next to l_0 / l_last /
@@ -537,7 +578,7 @@ int zk_pk_check(zk_ctx* ctx, zk_pk pk, uint32_t* flags, zk_pk_finding* out, size
 
 /* ---- verify_proof ---------------------------------------------------------------------------------------------------
  * plonk::verify_proof with the KZG pairing check (ecdsa_p256.rs:429-469: `verify` = Blake2b + SHPLONK, `verify_evm` = EVM +
- * GWC; no instances).  The check is e(A, [s]G2) = e(B, G2) with g[0], g2 and s_g2 of the context's resident SRS: a proof
+ * GWC; no instances - zk_verify_public takes them).  The check is e(A, [s]G2) = e(B, G2) with g[0], g2 and s_g2 of the context's resident SRS: a proof
  * made under another SRS is rejected.  A bad proof is a verdict (ZK_OK, *ok = 0 / verdicts[j] = 0), never an error; the
  * error codes mean bad arguments (ZK_EINVAL), a full key whose SRS was replaced, or no SRS / no G2 half in the context
  * (ZK_ESTATE: zk_srs_load needs zk_srs_set_g2 first). */
@@ -553,6 +594,12 @@ int zk_vk_from_parts(zk_ctx* ctx, const zk_circuit_params* params, const uint64_
                      const uint64_t transcript_repr_mont[4], zk_pk* out);
 /* one proof of `pk` (full or verifying-only): *ok = 1 if it verifies.  The batch of one below. */
 int zk_verify(zk_ctx* ctx, zk_pk pk, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok);
+/* verify_proof with the public inputs of zk_prove_public (full or verifying-only key): the values are absorbed as the prover
+ * absorbed them and inst(x) is computed on the host with one batch inversion.  Wrong values are a verdict (*ok = 0); a list the
+ * column cannot hold (n_instance > n - 7, or any value for a key without the column) or a value not below the modulus is
+ * ZK_EINVAL.  On a key without the column and n_instance == 0 it is zk_verify. */
+int zk_verify_public(zk_ctx* ctx, zk_pk pk, int transcript, int scheme, const uint64_t* instance_mont /* n_instance x 4 */,
+                     size_t n_instance, const uint8_t* proof, size_t len, int* ok);
 /* `batch` proofs of one key: verdicts[j] = what zk_verify says of proof j.  Points are decoded and the per-proof sums
  * are made on the device, the proofs are folded with random 128-bit weights into one pairing, and a failing set is halved
  * until every verdict is exact.  ZK_EINVAL: batch == 0 or > ZK_VERIFY_BATCH_MAX. */
@@ -560,7 +607,8 @@ int zk_verify(zk_ctx* ctx, zk_pk pk, int transcript, int scheme, const uint8_t* 
 int zk_verify_batch(zk_ctx* ctx, zk_pk pk, size_t batch, int transcript, int scheme, const uint8_t* const* proofs, const size_t* lens,
                     uint8_t* verdicts);
 
-/* one proof of zk_prove_multi over n_circuits circuits (verify_proof with n_circuits empty instance slices): the proof is read in
+/* one proof of zk_prove_multi over n_circuits circuits (verify_proof with n_circuits empty instance slices; a key with an instance
+ * column: ZK_EINVAL): the proof is read in
  * zk_prove_multi's order, the expected h(x) is the y-Horner of the n_circuits x T expressions, one pairing.  A bad proof - one of
  * another circuit count included: it has another length - is a verdict (*ok = 0), never an error.  Full and verifying-only
  * keys.  n_circuits == 1 is zk_verify.  ZK_EINVAL: n_circuits == 0 or > ZK_PROVE_MULTI_MAX. */

@@ -36,6 +36,9 @@ class CircuitParams:
     # never enables.  halo2's selector compression gives those no fixed column, which is what the published
     # proof sizes of the k <= 13 rows imply (ecdsa_bench.csv:8-10 are 1/2/3 evaluations short of the full shape)
     idle_gate_columns: int = 0
+    # not a key of the reference's JSON either (its circuit has no public inputs): 1 = the circuit makes ONE instance column
+    # after the chips' columns and enables equality on it - the last permutation column (zk_circuit_params.num_instance_columns)
+    num_instance_columns: int = 0
 
     @staticmethod
     def from_json(line: str):
@@ -70,8 +73,11 @@ class Layout:
             self.fx_sel = [F + 1 + j for j in range(A - U)] + [None] * U
             self.fx_qlookup = None
             self.n_fix = F + 1 + A - U
-        # permutation columns: constants, gate advice, lookup advice
-        self.perm_cols = [("fixed", f) for f in range(F)] + [("advice", j) for j in range(self.n_adv)]
+        # permutation columns: constants, gate advice, lookup advice, then the instance column of a shape that has one
+        self.n_inst = p.num_instance_columns
+        assert self.n_inst in (0, 1)
+        self.perm_cols = ([("fixed", f) for f in range(F)] + [("advice", j) for j in range(self.n_adv)]
+                          + [("instance", i) for i in range(self.n_inst)])
         self.usable_rows = self.n - (BLINDING_FACTORS + 1)
 
     def perm_index(self, kind, idx):
@@ -81,11 +87,17 @@ class Layout:
 class Assignment:
     """Result of synthesis: canonical integers, column-major."""
 
-    def __init__(self, layout, fixed, copies, advice):
+    def __init__(self, layout, fixed, copies, advice, instance=None):
         self.layout = layout
         self.fixed = fixed      # [n_fix][n]
         self.copies = copies    # [((perm_col, row), (perm_col, row))]
         self.advice = advice    # [n_adv][n]
+        self.instance = instance or []  # the public inputs: rows 0 .. of the instance column (synthesize(n_public=...))
+
+    @staticmethod
+    def to_mont_limbs(vals):
+        """list of ints -> (len, 4) uint64 Montgomery images (what zk_prove_public / zk_verify_public take)."""
+        return Assignment.to_limbs([v * (1 << 256) % R for v in vals]) if vals else np.zeros((0, 4), dtype=np.uint64)
 
     @staticmethod
     def to_limbs(col):
@@ -97,14 +109,22 @@ class Assignment:
 STRUCT_SEED = 0xC1BC0019  # fixes the circuit (selectors, lookup flags, copy constraints); witnesses vary per job
 
 
-def synthesize(p: CircuitParams, seed: int, worst_case: bool = False, struct_seed: int = STRUCT_SEED) -> Assignment:
+def synthesize(p: CircuitParams, seed: int, worst_case: bool = False, struct_seed: int = STRUCT_SEED, n_public: int = 0,
+               public_values=None) -> Assignment:
     """Satisfying assignment of the config's shape.
 
     The circuit structure — which cells are range-checked, which are copies of earlier gate
     outputs or of constants — is drawn from `struct_seed` only, so every job shares one proving
     key, as every request shares the reference's pk (proving-server/src/main.rs:49-63).  The
     witness VALUES are drawn from `seed` (0x5eed0019 + job index).
-    worst_case: every free value uniform in Fr (range-checked cells stay in range)."""
+    worst_case: every free value uniform in Fr (range-checked cells stay in range).
+    n_public: that many gate outputs are exposed as public inputs: instance row i is copy-constrained to the output of the i-th
+    gate (gate columns in order; more rows than gates start over at the first gate) and carries its value, returned as
+    `Assignment.instance`; needs num_instance_columns = 1.  Such a gate keeps its inputs free - none of them a copy or a
+    constant, a not range-checked; n_public is part of the circuit's structure, and n_public = 0 gives exactly the assignment
+    it always gave.
+    public_values: the n_public values the exposed outputs must take (a := value - b c in their gates) instead of what the
+    witness seed gives them - at most one row per gate."""
     lay = Layout(p)
     srng = random.Random(struct_seed)   # structure
     rng = random.Random(seed)           # values
@@ -149,6 +169,12 @@ def synthesize(p: CircuitParams, seed: int, worst_case: bool = False, struct_see
     small_cells = []  # (gate advice col, row) range-checked cells
     d_cells = []      # (col, row) gate outputs available for copying (structure) ...
     d_vals = {}       # ... and their values (witness)
+    if n_public:
+        assert lay.n_inst == 1 and n_public <= usable, "public inputs need the instance column and fit in the usable rows"
+    n_gates = gates_per_col * sum(1 for s in lay.fx_sel if s is not None)
+    if public_values is not None and (len(public_values) != n_public or n_public > n_gates):
+        raise ValueError("public_values: one value per public input, at most one public input per gate")
+    public_cells = []  # the outputs of the first min(n_public, n_gates) gates
     for j in range(lay.n_gate):
         if lay.fx_sel[j] is None:
             continue  # idle gate column: nothing assigned
@@ -159,7 +185,13 @@ def synthesize(p: CircuitParams, seed: int, worst_case: bool = False, struct_see
             ca, cb, cc = pick_class(), pick_class(), pick_class()
             a, b, c = value(ca), value(cb), value(cc)
             u = srng.random()
-            if d_cells and u < 0.5:
+            if len(public_cells) < min(n_public, n_gates):
+                # a public gate: its output is exposed; its inputs stay free (no copy, no constant, a not range-checked)
+                ca = "public"
+                if public_values is not None:
+                    a = (public_values[len(public_cells)] - b * c) % R
+                public_cells.append((j, r0 + 3))
+            elif d_cells and u < 0.5:
                 # a := an earlier gate output (copy constraint)
                 sc, sr = d_cells[srng.randrange(len(d_cells))]
                 a, ca = d_vals[(sc, sr)], "copy"
@@ -198,4 +230,9 @@ def synthesize(p: CircuitParams, seed: int, worst_case: bool = False, struct_see
             for t, (j, row) in enumerate(cells):
                 lc[t] = advice[j][row]
                 copies.append(((lay.perm_index("advice", lay.n_gate + l), t), (lay.perm_index("advice", j), row)))
-    return Assignment(lay, fixed, copies, advice)
+    instance = []
+    for i in range(n_public):
+        j, row = public_cells[i % len(public_cells)]
+        instance.append(advice[j][row])
+        copies.append(((lay.perm_index("instance", 0), i), (lay.perm_index("advice", j), row)))
+    return Assignment(lay, fixed, copies, advice, instance)

@@ -163,6 +163,24 @@ inline Fe<PRM> fe_inv_fast(const Fe<PRM>& a) {
     return fe_mul(t, fe_mul(r2, r2));  // x R^3 / R: a^-1 R^-1 R^2 = a^-1 R
 }
 
+// inv[i] = 1 / v[i], i < count, with ONE field inversion (Montgomery's trick; inv doubles as the scratch of the running
+// products).  False at the first zero: inv[0 .. that index] then holds running products, nothing beyond it is written.
+inline bool fr_batch_invert(const Fr* v, Fr* inv, uint32_t count) {
+    Fr run = Fr::one();
+    for (uint32_t i = 0; i < count; i++) {
+        inv[i] = run;
+        if (v[i].is_zero()) return false;
+        run = fe_mul(run, v[i]);
+    }
+    Fr r = fe_inv_fast(run);
+    for (uint32_t i = count; i-- > 0;) {
+        const Fr t = fe_mul(r, inv[i]);
+        r = fe_mul(r, v[i]);
+        inv[i] = t;
+    }
+    return true;
+}
+
 // halo2curves bn256 Fr::ZETA = 0x30644e72e131a029048b6e193fd84104cc37a73fec2bc5e9b8ca0b2d36636f23 [RECALLED constant; it is a
 // primitive cube root of unity, namely (7^((r-1)/3))^2], the extended-domain coset generator `g_coset` of halo2's
 // EvaluationDomain.  h(X) — and so every proof byte — is the same for either cube root; the extended cosets inside a

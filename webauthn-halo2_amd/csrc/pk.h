@@ -8,13 +8,15 @@
 #include "ctx.h"
 #include "prover.h"
 
+enum ColType { COL_ADVICE = 0, COL_FIXED = 1, COL_INSTANCE = 2 };
 struct Col {
-    int fixed;  // 1 = fixed column, 0 = advice
+    int type;  // ColType
     uint32_t idx;
 };
 
 struct Layout {
     uint32_t k, n, A, L, F, lookup_bits, idle;
+    uint32_t n_inst;  // instance columns: 0, or 1 — made after the chips' columns and equality-enabled, so the LAST permutation column
     bool single;
     uint32_t n_gate, n_lookup_cols, n_adv, fx_table, fx_qlookup, n_fix;
     std::vector<uint32_t> fx_sel;    // the selector column a gate column OWNS (NO_SELECTOR: a never-enabled selector has none)
@@ -30,6 +32,8 @@ struct Layout {
     bool init(const zk_circuit_params& p) {
         k = p.k; A = p.num_advice; L = p.num_lookup_advice; F = p.num_fixed; lookup_bits = p.lookup_bits;
         idle = p.num_idle_gate_columns;
+        n_inst = p.num_instance_columns;
+        if (n_inst > 1) return false;
         if (k < 4 || k > 22 || A < 1 || L < 1 || F < 1 || idle >= A || 2 * idle > A) return false;  // (more idle than used: pairs of their own)
         if (lookup_bits < 1 || lookup_bits >= k) return false;  // the range table 0 .. 2^lookup_bits - 1 must fit in the usable rows
         n = 1u << k;
@@ -56,8 +60,9 @@ struct Layout {
             gate_sel[A - idle + t] = fx_sel[t] | (2u << 24);
         }
         perm_cols.clear();
-        for (uint32_t f = 0; f < F; f++) perm_cols.push_back(Col{1, f});
-        for (uint32_t j = 0; j < n_adv; j++) perm_cols.push_back(Col{0, j});
+        for (uint32_t f = 0; f < F; f++) perm_cols.push_back(Col{COL_FIXED, f});
+        for (uint32_t j = 0; j < n_adv; j++) perm_cols.push_back(Col{COL_ADVICE, j});
+        for (uint32_t i = 0; i < n_inst; i++) perm_cols.push_back(Col{COL_INSTANCE, i});
         n_lookups = single ? 1 : L;
         degree = single ? 5 : 4;
         chunk_len = degree - 2;
@@ -118,6 +123,9 @@ struct zk_pk_rec {
     G1Affine* d_vk_bases = nullptr;    // the commitments on the device, fixed then permutation (verify.hip; listed in `dev`)
     // prover workspace
     std::vector<Fr*> adv_val, adv_poly, adv_coset;
+    // the instance column of a key that has one (Layout::n_inst): values (rows 0 .. m - 1 the caller's, zero behind them),
+    // coefficients, extended coset — neither blinded nor committed; null otherwise
+    Fr *inst_val = nullptr, *inst_poly = nullptr, *inst_coset = nullptr;
     std::vector<Fr*> z_val, z_poly, z_coset;
     std::vector<Fr*> lk_in, lk_ap, lk_ap_poly, lk_ap_coset, lk_sp, lk_sp_poly, lk_sp_coset, lk_z, lk_z_poly, lk_z_coset,
         lk_in_coset;
@@ -197,11 +205,17 @@ struct Dev {
 // extended cosets the quotient reads beside the key's own: advice columns, permutation products, per lookup a', s', zL
 struct QuotientCosets {
     std::vector<const Fr*> adv, z, lk_a, lk_s, lk_z;
+    const Fr* inst = nullptr;  // the instance column's coset (keys with one)
     bool cosets3 = false;  // the operands are [3][n] coset-major vectors (poly.hip "three cosets"); the key's own are taken from its c3 copies
 };
 // the key's extended cosets (fixed, sigma, l_0, l_last, l_active) once more in the [3][n] coset-major order of the three-coset
 // route: made on the first proof that takes it (keygen and zk_pk_read both end up here), kept with the key
 int pk_ensure_cosets3(zk_ctx* c, zk_pk_rec* pk);
+// the caller's instance values for a key: ZK_EINVAL unless the key has the column (or n_instance == 0), n_instance <= usable rows
+// (halo2's InstanceTooLarge) and every value is a Montgomery image below the modulus; `out` receives them
+int pk_instance_values(const Layout& lay, const uint64_t* instance_mont, size_t n_instance, std::vector<Fr>* out);
+// the values into rows 0 .. m - 1 of the workspace's instance column, zero behind them (enqueued on `st`; `vals` must outlive the copy)
+int pk_instance_upload(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<Fr>& vals);
 Fr fr_delta();  // 7^(2^28): generator of the odd-order subgroup (the permutation argument's coset shifts)
 int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out);
 // One pass of a quotient that several circuits share (prover_multi.h): the y-combination of this workspace's terms times

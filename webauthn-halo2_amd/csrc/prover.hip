@@ -109,6 +109,9 @@ struct Prover {
     };
     RowStager own_rows;
     RowStager* rows = &own_rows;
+    // the instance column's values (zk_prove_public; a key with the column and no caller's values proves the empty column).  Absorbed
+    // behind transcript_repr, never written; the column is neither blinded nor committed nor opened, and draws nothing
+    const std::vector<Fr>* instance = nullptr;
     bool batch_member = false;  // one of the proofs of a lock-step batch (prover_batch.h): transforms stay on the main stream
 
     Prover(const Prover&) = delete;  // (cq is bound to this object)
@@ -409,7 +412,14 @@ struct Prover {
         omega = fr_omega(lay.k);
         omega_inv = fe_inv_fast(omega);
         tr->common_scalar(pk->transcript_repr);
+        if (instance)
+            for (const Fr& v : *instance) tr->common_scalar(v);  // (the count is not hashed)
         return ZK_OK;
+    }
+    // the instance column's forms go with the first advice transforms: its values are uploaded on the main stream before the first
+    // flush of blinding rows, which is what a transform on the side stream waits for
+    void with_instance(std::vector<Forms>& fm) const {
+        if (pk->inst_val) fm.push_back(Forms{pk->inst_val, pk->inst_poly, pk->inst_coset});
     }
 
     int run(const Fr* const* advice_dev, int scheme) {
@@ -422,6 +432,10 @@ struct Prover {
         // -- 1. advice
         // (many columns: one launch copies them all — the argument staging is reused by the later batched launches, each
         // preceded by a stream-ordered upload, so the host must not overwrite it before the upload has been consumed)
+        if (pk->inst_val) {
+            static const std::vector<Fr> none;
+            if (int r = pk_instance_upload(c, st, pk, instance ? *instance : none)) return r;
+        }
         const bool many = advice_staged(lay);
         if (many) {
             if (int r = advice_columns_staged(c, st, pk, advice_dev)) return r;
@@ -444,7 +458,9 @@ struct Prover {
         if (pipe) {
             cq.begin(af, {CommitCol{pk->adv_val[0], tr}}, ZK_BASIS_LAGRANGE);
             if (xform_side()) {  // a lone proof: the advice column's forms are made under its own MSM pass
-                transforms({Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]}});
+                std::vector<Forms> fm{Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]}};
+                with_instance(fm);
+                transforms(fm);
                 adv_transformed = true;
             }
         } else {
@@ -459,6 +475,7 @@ struct Prover {
                     cols.push_back(CommitCol{pk->adv_val[j], tr});
                     fm.push_back(Forms{pk->adv_val[j], pk->adv_poly[j], pk->adv_coset[j]});
                 }
+                if (j0 == 0) with_instance(fm);
                 cq.begin(f, cols, ZK_BASIS_LAGRANGE);
                 transforms(fm);
             }
@@ -482,7 +499,10 @@ struct Prover {
         std::vector<uint32_t> due;
         auto lookup_transforms = [&](bool with_advice) {
             std::vector<Forms> fm;
-            if (with_advice) fm.push_back(Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]});
+            if (with_advice) {
+                fm.push_back(Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]});
+                with_instance(fm);
+            }
             for (uint32_t l : due) {
                 fm.push_back(Forms{pk->lk_ap[l], pk->lk_ap_poly[l], pk->lk_ap_coset[l]});
                 fm.push_back(Forms{pk->lk_sp[l], pk->lk_sp_poly[l], pk->lk_sp_coset[l]});
@@ -945,13 +965,21 @@ ZK_API(zk_proof_size_multi, (zk_ctx* c, zk_pk pkh, size_t n_circuits, int transc
     return ZK_OK;
 }
 
-ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+// create_proof for one circuit.  `with_instances`: zk_prove_public — the caller's instance values (none on a key without the
+// column: zk_prove's bytes); otherwise zk_prove, which a key WITH the column refuses (halo2's InvalidInstances)
+static int prove_one(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, bool with_instances, const uint64_t* instance_mont,
+                     size_t n_instance, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap,
+                     size_t* proof_len) {
     if (!c || !advice || !rng_seed || !proof_len) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
+    if (lay.n_inst && !with_instances) return ZK_EINVAL;
+    std::vector<Fr> instance;
+    if (with_instances)
+        if (int r = pk_instance_values(lay, instance_mont, n_instance, &instance)) return r;
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
     if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
@@ -972,6 +1000,7 @@ ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, co
     const uint64_t aud0 = c->audit.violations;
     c->audit.base_of.clear();  // (allocations may have changed hands since the last proof)
     Prover p(c, pk, rng_seed, tr);
+    if (lay.n_inst) p.instance = &instance;
     {
         ProveQuiesce quiesce(c);  // (declared after the prover: it settles the streams while the prover's host buffers are alive)
         rc = p.run(adv.data(), scheme);
@@ -982,6 +1011,15 @@ ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, co
     if (!proof_out || proof_cap < tr->out.size()) return proof_out ? ZK_EINVAL : ZK_OK;
     memcpy(proof_out, tr->out.data(), tr->out.size());
     return ZK_OK;
+}
+
+ZK_API(zk_prove, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+    return prove_one(c, h, advice, n_advice, false, nullptr, 0, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
+}
+
+// create_proof with the circuit's public inputs: one instance column, absorbed into the transcript and copy-constrained
+ZK_API(zk_prove_public, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint64_t* instance_mont, size_t n_instance, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, advice, n_advice, instance_mont, n_instance, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+    return prove_one(c, h, advice, n_advice, true, instance_mont, n_instance, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
 }
 
 // create_proof for `batch` independent proofs of one key in lock-step (prover_batch.h)
@@ -996,6 +1034,7 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
     if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
+    if (lay.n_inst) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
     if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
@@ -1057,6 +1096,7 @@ ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* ad
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
     if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
+    if (lay.n_inst) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
     if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;

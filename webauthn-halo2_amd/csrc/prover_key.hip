@@ -106,6 +106,11 @@ int pk_alloc_workspace(zk_ctx* c, zk_pk_rec* pk) {
         pk->adv_poly.push_back(d.alloc(n));
         pk->adv_coset.push_back(d.alloc(N));
     }
+    if (lay.n_inst) {
+        pk->inst_val = d.alloc(n);
+        pk->inst_poly = d.alloc(n);
+        pk->inst_coset = d.alloc(N);
+    }
     for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
         pk->z_val.push_back(d.alloc(n));
         pk->z_poly.push_back(d.alloc(n));
@@ -204,6 +209,7 @@ static zk_pk_rec* pk_make_member(zk_ctx* c, const zk_pk_rec* pk) {
                     &m->lk_ap_coset, &m->lk_sp, &m->lk_sp_poly, &m->lk_sp_coset, &m->lk_z, &m->lk_z_poly, &m->lk_z_coset, &m->lk_in_coset,
                     &m->gp_num, &m->gp_den, &m->gp_loc_p, &m->gp_loc_r})
         v->clear();
+    m->inst_val = m->inst_poly = m->inst_coset = nullptr;
     m->random_poly = m->h_ext = m->h_comb = m->t_num = m->t_den = m->t_frac = m->t_a = m->t_b = m->t_small = m->kd_scratch = nullptr;
     m->tail_host = nullptr;
     m->rows_host = m->rows_dev = nullptr;
@@ -274,6 +280,42 @@ int pk_ensure_multi(zk_ctx* c, zk_pk_rec* pk, uint32_t circuits) {
     if (hipHostMalloc(&pk->h_lc_terms, want * sizeof(LcTerm)) != hipSuccess || hipMalloc(&pk->d_lc_terms, want * sizeof(LcTerm)) != hipSuccess)
         return ZK_ENOMEM;  // (what was allocated is freed with the key; lc_cap = 0 sends linear combinations down the chunked form)
     pk->lc_cap = want;
+    return ZK_OK;
+}
+
+// ============================================================ instance column ==
+
+int pk_instance_values(const Layout& lay, const uint64_t* instance_mont, size_t n_instance, std::vector<Fr>* out) {
+    if ((n_instance && !instance_mont) || n_instance > (lay.n_inst ? lay.usable : 0u)) return ZK_EINVAL;
+    out->resize(n_instance);
+    if (n_instance) memcpy(out->data(), instance_mont, n_instance * sizeof(Fr));
+    for (const Fr& v : *out) {  // a Montgomery image is < r
+        bool lt = false;
+        for (int i = 7; i >= 0; i--)
+            if (v.v[i] != FrParams::P[i]) {
+                lt = v.v[i] < FrParams::P[i];
+                break;
+            }
+        if (!lt) return ZK_EINVAL;
+    }
+    return ZK_OK;
+}
+
+int pk_instance_upload(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<Fr>& vals) {
+    if (!pk->inst_val) return vals.empty() ? ZK_OK : ZK_EINVAL;
+    if (vals.size() > pk->lay.usable) return ZK_EINVAL;
+    if (c->audit.on) c->audit.op(st, {}, {pk->inst_val}, "instance column into the workspace");
+    HIPCHK(c, hipMemsetAsync(pk->inst_val, 0, (size_t)pk->lay.n * sizeof(Fr), st));  // (the Montgomery image of zero is zero)
+    if (!vals.empty()) HIPCHK(c, hipMemcpyAsync(pk->inst_val, vals.data(), vals.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
+    return ZK_OK;
+}
+
+ZK_API(zk_pk_num_instance_columns, (zk_ctx* c, zk_pk h, uint32_t* out), (c, h, out)) {
+    if (!c || !out) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->pks.find(h);
+    if (it == c->pks.end()) return ZK_EINVAL;
+    *out = it->second->lay.n_inst;
     return ZK_OK;
 }
 
@@ -555,7 +597,8 @@ int pk_quotient_pass(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const F
     for (uint32_t p = 0; p < q.n_perm; p++) {
         q.sigma[p] = c3 ? pk->sigma_c3[p] : pk->sigma_coset[p];
         const Col& col = lay.perm_cols[p];
-        q.perm_val[p] = col.fixed ? q.fix[col.idx] : qc.adv[col.idx];
+        if (col.type == COL_INSTANCE && !qc.inst) return ZK_EINVAL;
+        q.perm_val[p] = col.type == COL_FIXED ? q.fix[col.idx] : col.type == COL_INSTANCE ? qc.inst : qc.adv[col.idx];
     }
     for (uint32_t ci = 0; ci < lay.n_chunks; ci++) q.z[ci] = qc.z[ci];
     for (uint32_t l = 0; l < lay.n_lookups; l++) {
@@ -635,6 +678,7 @@ ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_adv
     const Layout& lay = pk->lay;
     if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
     if (n_advice != lay.n_adv || n_chunks != lay.n_chunks || n_lookups != lay.n_lookups) return ZK_EINVAL;
+    if (lay.n_inst) return ZK_EINVAL;  // (the phase-level forms carry no instance column)
     const size_t N = (size_t)4 * lay.n;
     auto ext = [&](zk_poly p) -> Fr* {
         const PolyRec* q = ctx_poly(c, p);

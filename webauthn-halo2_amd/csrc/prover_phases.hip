@@ -124,6 +124,7 @@ ZK_API(zk_permutation_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_
     zk_pk_rec* pk = P.pk;
     const Layout& lay = pk->lay;
     if (n_chunks != lay.n_chunks) return ZK_EINVAL;
+    if (lay.n_inst) return ZK_EINVAL;  // (the phase-level forms carry no instance column)
     Fr b, g;
     memcpy(&b, beta, 32);
     memcpy(&g, gamma, 32);

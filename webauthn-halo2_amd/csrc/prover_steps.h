@@ -13,23 +13,7 @@
 #include "transcript.h"
 
 // ------------------------------------------------------------ host helpers ---
-// inv[i] = 1 / v[i], i < count, with ONE field inversion (Montgomery's trick; inv doubles as the scratch of the running
-// products).  False at the first zero: inv[0 .. that index] then holds running products, nothing beyond it is written.
-inline bool fr_batch_invert(const Fr* v, Fr* inv, uint32_t count) {
-    Fr run = Fr::one();
-    for (uint32_t i = 0; i < count; i++) {
-        inv[i] = run;
-        if (v[i].is_zero()) return false;
-        run = fe_mul(run, v[i]);
-    }
-    Fr r = fe_inv_fast(run);
-    for (uint32_t i = count; i-- > 0;) {
-        const Fr t = fe_mul(r, inv[i]);
-        r = fe_mul(r, v[i]);
-        inv[i] = t;
-    }
-    return true;
-}
+// (fr_batch_invert — one Montgomery batch inversion, reached through this header by its callers — is hostutil.h's: the verifier shares it)
 
 // affine forms of `cnt` Jacobian points with ONE field inversion for the whole batch (Montgomery's trick over the z's; the
 // identity — z = 0 — is skipped and comes out as (0, 0))
@@ -147,6 +131,10 @@ inline int lookup_permute_failed(zk_ctx* c, hipStream_t st, const LookupScratch&
 }
 
 // ------------------------------------------ numerators and denominators ---
+// the values of a permutation column: a fixed column of the key, an advice column of `adv`, or the workspace's instance column
+inline const Fr* perm_col_values(const zk_pk_rec* pk, const Col& col, const Fr* const* adv) {
+    return col.type == COL_FIXED ? pk->fixed_val[col.idx] : col.type == COL_INSTANCE ? pk->inst_val : adv[col.idx];
+}
 // the arguments of permutation chunk ci: its columns' values (fixed from the key, advice from `adv`), their sigma columns and
 // delta^(global column index) — `dcur` runs over the chunks of a proof, starting at one
 inline PermArgs perm_chunk_args(const Layout& lay, const zk_pk_rec* pk, uint32_t ci, const Fr* const* adv, const Fr* tw, const Fr& beta,
@@ -159,7 +147,7 @@ inline PermArgs perm_chunk_args(const Layout& lay, const zk_pk_rec* pk, uint32_t
     const Fr delta = fr_delta();
     for (uint32_t p = lo; p < hi; p++) {
         const Col& col = lay.perm_cols[p];
-        a.values[p - lo] = col.fixed ? pk->fixed_val[col.idx] : adv[col.idx];
+        a.values[p - lo] = perm_col_values(pk, col, adv);
         a.sigma[p - lo] = pk->sigma_val[p];
         a.delta[p - lo] = dcur;
         dcur = fe_mul(dcur, delta);
@@ -297,9 +285,11 @@ inline int quotient_pass_of_workspace(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, 
         qc.lk_s.push_back(pk->lk_sp_coset[l]);
         qc.lk_z.push_back(pk->lk_z_coset[l]);
     }
+    qc.inst = pk->inst_coset;
     qc.cosets3 = cosets3;
     if (c->audit.on) {
         std::vector<const void*> rd;
+        if (qc.inst) rd.push_back(qc.inst);
         for (auto* v : {&qc.adv, &qc.z, &qc.lk_a, &qc.lk_s, &qc.lk_z})
             for (const Fr* q : *v) rd.push_back(q);
         if (accumulate) rd.push_back(into);

@@ -208,10 +208,31 @@ inline void merge_terms(std::vector<Term>& t) {
         if (!x.s.is_zero()) t.push_back(x);
 }
 
+// inst(x) = sum_i v_i l_i(x), l_i(x) = w^i (x^n - 1) / (n (x - w^i)): the instance column's evaluation, which no proof carries
+// (halo2 with KZG: QUERY_INSTANCE = false).  One batch inversion; false: x is one of the w^i
+inline bool instance_eval(const Layout& lay, const Fr* inst, size_t n_inst, const Fr& x, const Fr& xn1_over_n, Fr* out) {
+    *out = Fr::zero();
+    if (!n_inst) return true;
+    const Fr w = fr_omega(lay.k);
+    std::vector<Fr> den(n_inst), inv(n_inst), wi(n_inst);
+    Fr cur = Fr::one();
+    for (size_t i = 0; i < n_inst; i++) {
+        wi[i] = cur;
+        den[i] = fe_sub(x, cur);
+        cur = fe_mul(cur, w);
+    }
+    if (!fr_batch_invert(den.data(), inv.data(), (uint32_t)n_inst)) return false;
+    Fr acc = Fr::zero();
+    for (size_t i = 0; i < n_inst; i++) acc = fe_add(acc, fe_mul(inst[i], fe_mul(wi[i], inv[i])));
+    *out = fe_mul(acc, xn1_over_n);
+    return true;
+}
+
 // false: the proof is rejected before the pairing (non-canonical scalar, an inverse of zero).  Otherwise `out` holds the two
-// term lists of the KZG check.  proof.len == pl.len is the caller's check.
+// term lists of the KZG check.  proof.len == pl.len is the caller's check.  inst / n_inst: the instance values of a key with the
+// column (Montgomery, at most lay.usable: the caller's check), absorbed behind transcript_repr.
 inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLayout& pl, const uint8_t* proof, const G1Affine* pts,
-                    Prepared* out) {
+                    Prepared* out, const Fr* inst = nullptr, size_t n_inst = 0) {
     EvmTranscript evm;
     Blake2bTranscript b2;
     Transcript* tr = pl.evm ? (Transcript*)&evm : (Transcript*)&b2;
@@ -220,6 +241,7 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     const EvalIdx E = eval_idx(lay, nc);
     Challenges& ch = out->ch;
     tr->common_scalar(transcript_repr);
+    for (size_t i = 0; i < n_inst; i++) tr->common_scalar(inst[i]);  // (the count is not hashed)
     uint32_t np = 0;
     auto absorb_points = [&](uint32_t n) {
         for (uint32_t i = 0; i < n; i++) tr->common_point(pts[np++]);
@@ -263,6 +285,8 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     for (int i = 1; i <= (int)BLINDING_FACTORS; i++) l_blind = fe_add(l_blind, L(-i));
     if (zero_div) return false;
     const Fr active = fe_sub(fe_sub(one, l_last), l_blind);
+    Fr inst_x = Fr::zero();
+    if (lay.n_inst && !instance_eval(lay, inst, n_inst, x, c, &inst_x)) return false;
     auto fix = [&](uint32_t f) { return ev[E.fix + f]; };
     const Fr delta = fr_delta_host();
     std::vector<Fr> exprs;  // the nc x T expressions of the y-Horner chain: circuit 0's, then circuit 1's, ...
@@ -280,7 +304,7 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
             if (form) sel = fe_mul(q, fe_sub(fr_from_u64(form == 1 ? 2 : 1), q));
             exprs.push_back(fe_mul(sel, fe_sub(fe_add(a, fe_mul(b, cc)), d)));
         }
-        auto col_eval = [&](const Col& col) { return col.fixed ? fix(col.idx) : adv(col.idx, 0); };
+        auto col_eval = [&](const Col& col) { return col.type == COL_FIXED ? fix(col.idx) : col.type == COL_INSTANCE ? inst_x : adv(col.idx, 0); };
         auto pe = [&](uint32_t i, uint32_t which) { return ev[E.perm_of(circ) + 3 * i + which]; };
         exprs.push_back(fe_mul(l0, fe_sub(one, pe(0, 0))));
         const Fr zl = pe(lay.n_chunks - 1, 0);

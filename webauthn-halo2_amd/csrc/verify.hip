@@ -378,8 +378,11 @@ int settle(Job& J, const std::vector<uint32_t>& S, uint8_t* verdicts) {
 
 // `batch` proofs of one key, each over `n_circuits` circuits (1: the proofs of zk_prove; more: those of zk_prove_multi — a longer
 // proof read in the order verifier.h states, the same four steps)
+// `with_instances`: zk_verify_public — the caller's instance values (none on a key without the column); the other entry points
+// carry none and refuse a key that has the column (halo2's InvalidInstances)
 static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, int transcript, int scheme, const uint8_t* const* proofs,
-                         const size_t* lens, uint8_t* verdicts) {
+                         const size_t* lens, uint8_t* verdicts, bool with_instances = false, const uint64_t* instance_mont = nullptr,
+                         size_t n_instance = 0) {
     if (!c || !proofs || !lens || !verdicts || batch == 0 || batch > ZK_VERIFY_BATCH_MAX) return ZK_EINVAL;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
@@ -390,6 +393,10 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
+    if (pk->lay.n_inst && !with_instances) return ZK_EINVAL;
+    std::vector<Fr> instance;
+    if (with_instances)
+        if (int r = pk_instance_values(pk->lay, instance_mont, n_instance, &instance)) return r;
     if (!pk->verify_only && pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // a full key under a replaced SRS: its vk is stale
     if (c->srs_k < 0 || !c->g2_valid) return ZK_ESTATE;  // g[0], g2 and s_g2 come from the resident SRS
     int rc = ctx_bind(c);
@@ -441,7 +448,7 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
             try {
                 for (size_t i = 0; i < np; i++)
                     if (!flag[t * np + i]) return;
-                good[t] = verifier::prepare(lay, pk->transcript_repr, pl, proofs[cand[t]], pts.data() + t * np, &prep[t]) ? 1 : 0;
+                good[t] = verifier::prepare(lay, pk->transcript_repr, pl, proofs[cand[t]], pts.data() + t * np, &prep[t], instance.data(), instance.size()) ? 1 : 0;
             } catch (...) {
                 good[t] = 2;  // (allocation failure)
             }
@@ -534,6 +541,15 @@ ZK_API(zk_verify_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, int transcript, 
     if (!ok || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
     uint8_t v = 0;
     const int rc = verify_proofs(c, h, 1, (uint32_t)n_circuits, transcript, scheme, &proof, &len, &v);
+    if (rc == ZK_OK) *ok = v;
+    return rc;
+}
+
+// verify_proof with the circuit's public inputs: wrong values are a verdict, a list the column cannot hold an error
+ZK_API(zk_verify_public, (zk_ctx* c, zk_pk h, int transcript, int scheme, const uint64_t* instance_mont, size_t n_instance, const uint8_t* proof, size_t len, int* ok), (c, h, transcript, scheme, instance_mont, n_instance, proof, len, ok)) {
+    if (!ok) return ZK_EINVAL;
+    uint8_t v = 0;
+    const int rc = verify_proofs(c, h, 1, 1, transcript, scheme, &proof, &len, &v, true, instance_mont, n_instance);
     if (rc == ZK_OK) *ok = v;
     return rc;
 }

@@ -97,8 +97,11 @@ inline std::string pinned_debug(const Layout& lay, const std::vector<G1Affine>& 
         return "(" + column(halo2_fixed_column(lay, i), "Fixed") + ", Rotation(0))";
     });
     const std::string perm_cols = join(lay.perm_cols.begin(), lay.perm_cols.end(), [&](const Col& c) {
-        return c.fixed ? column(halo2_fixed_column(lay, c.idx), "Fixed") : column(c.idx, "Advice");
+        if (c.type == COL_INSTANCE) return column(c.idx, "Instance");
+        return c.type == COL_FIXED ? column(halo2_fixed_column(lay, c.idx), "Fixed") : column(c.idx, "Advice");
     });
+    // enable_equality on the instance column queries it at rotation 0 [RECALLED: no reference bytes pin the instance rendering]
+    const std::string instance_queries = lay.n_inst ? "(" + column(0, "Instance") + ", Rotation(0))" : "";
     const std::string table = fixed(lay, lay.fx_table);
     std::string lookups;
     uint32_t num_selectors;
@@ -117,8 +120,8 @@ inline std::string pinned_debug(const Layout& lay, const std::vector<G1Affine>& 
                     "scalar_modulus: \"0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001\", domain: PinnedEvaluationDomain { k: " +
                     std::to_string(lay.k) + ", extended_k: " + std::to_string(lay.ext_k) + ", omega: " + hex_of(fr_omega(lay.k)) + " }, ";
     s += "cs: PinnedConstraintSystem { num_fixed_columns: " + std::to_string(lay.n_fix) + ", num_advice_columns: " + std::to_string(lay.n_adv) +
-         ", num_instance_columns: 0, num_selectors: " + std::to_string(num_selectors) + ", gates: [" + gates + "], advice_queries: [" +
-         advice_queries + "], instance_queries: [], fixed_queries: [" + fixed_queries + "], permutation: Argument { columns: [" + perm_cols +
+         ", num_instance_columns: " + std::to_string(lay.n_inst) + ", num_selectors: " + std::to_string(num_selectors) + ", gates: [" + gates + "], advice_queries: [" +
+         advice_queries + "], instance_queries: [" + instance_queries + "], fixed_queries: [" + fixed_queries + "], permutation: Argument { columns: [" + perm_cols +
          "] }, lookups: [" + lookups + "], constants: [], minimum_degree: None }, ";
     s += "fixed_commitments: [" + join(order.begin(), order.end(), [&](uint32_t i) { return point(fixed_commit[i]); }) + "], ";
     s += "permutation: VerifyingKey { commitments: [" + join(perm_commit.begin(), perm_commit.end(), [&](const G1Affine& a) { return point(a); }) +

@@ -28,7 +28,7 @@ constexpr uint32_t WC_KINDS = 4;           // bitmap segments, in the list's ord
 
 // argument block of the row kernels (device memory: up to 352 columns do not fit the kernarg segment comfortably)
 struct WcArgs {
-    const Fr* perm_val[MAX_PERM];  // the values of permutation column c: a fixed column of the key or an advice column
+    const Fr* perm_val[MAX_PERM];  // the values of permutation column c: a fixed column of the key, an advice column or the instance column
     const Fr* sigma[MAX_PERM];     // the key's sigma values (decode only)
     const Fr* gate_adv[MAX_ADV];
     const Fr* gate_sel[MAX_ADV];   // the fixed column gate j's selector lives in
@@ -271,7 +271,7 @@ int wc_upload_args(zk_ctx* c, zk_pk_rec* pk, const std::vector<const Fr*>& adv) 
     memset(&a, 0, sizeof(a));
     for (size_t p = 0; p < lay.perm_cols.size(); p++) {
         const Col& col = lay.perm_cols[p];
-        a.perm_val[p] = col.fixed ? pk->fixed_val[col.idx] : adv[col.idx];
+        a.perm_val[p] = col.type == COL_FIXED ? pk->fixed_val[col.idx] : col.type == COL_INSTANCE ? pk->inst_val : adv[col.idx];
         a.sigma[p] = pk->sigma_val[p];
     }
     for (uint32_t j = 0; j < lay.n_gate; j++) {
@@ -331,13 +331,20 @@ int wc_ensure_sigma(zk_ctx* c, zk_pk_rec* pk) {
 
 }  // namespace
 
-ZK_API(zk_witness_check, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap, uint64_t counts[5]), (c, h, advice, n_advice, out, cap, counts)) {
+// `with_instances`: zk_witness_check_public — the caller's instance values go into the workspace's instance column (idle between
+// proofs), the last permutation column of the copy check; zk_witness_check carries none and refuses a key that has the column
+static int witness_check_run(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap,
+                             uint64_t counts[5], bool with_instances, const uint64_t* instance_mont, size_t n_instance) {
     if (!c || !advice || !counts || (cap && !out)) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
+    if (lay.n_inst && !with_instances) return ZK_EINVAL;
+    std::vector<Fr> instance;
+    if (with_instances)
+        if (int r = pk_instance_values(lay, instance_mont, n_instance, &instance)) return r;
     if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;  // (a verifying-only key holds no column values)
     if (n_advice != lay.n_adv) return ZK_EINVAL;
     std::vector<const Fr*> adv(n_advice);
@@ -354,12 +361,14 @@ ZK_API(zk_witness_check, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_ad
     WitnessCheckState* s = pk->wc;
     if ((rc = wc_upload_args(c, pk, adv))) return rc;
     if ((rc = wc_ensure_sigma(c, pk))) return rc;
+    if ((rc = pk_instance_upload(c, c->stream, pk, instance))) return rc;
 
     hipStream_t st = c->stream;
     const uint32_t n = lay.n, W = s->segs.W, gx = (n + 255) / 256, n_perm = (uint32_t)lay.perm_cols.size();
     uint64_t* const seg[WC_KINDS] = {s->bits + s->segs.start[0], s->bits + s->segs.start[1], s->bits + s->segs.start[2], s->bits + s->segs.start[3]};
     std::vector<const void*> rd(adv.begin(), adv.end());
     for (const Fr* f : pk->fixed_val) rd.push_back(f);
+    if (pk->inst_val) rd.push_back(pk->inst_val);
     rd.push_back(s->d_args);
     rd.push_back(s->sigma_map);
     const void* wr[1] = {s->bits};
@@ -417,4 +426,13 @@ ZK_API(zk_witness_check, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_ad
     if (listed) memcpy(out, s->h_out, listed * sizeof(zk_witness_failure));
     memcpy(counts, cnt, sizeof(cnt));
     return ZK_OK;
+}
+
+ZK_API(zk_witness_check, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap, uint64_t counts[5]), (c, h, advice, n_advice, out, cap, counts)) {
+    return witness_check_run(c, h, advice, n_advice, out, cap, counts, false, nullptr, 0);
+}
+
+// MockProver::run(k, &circuit, vec![instance]).verify(): the same check with the instance column's values
+ZK_API(zk_witness_check_public, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, zk_witness_failure* out, size_t cap, uint64_t counts[5], const uint64_t* instance_mont, size_t n_instance), (c, h, advice, n_advice, out, cap, counts, instance_mont, n_instance)) {
+    return witness_check_run(c, h, advice, n_advice, out, cap, counts, true, instance_mont, n_instance);
 }

@@ -28,7 +28,14 @@ What the scope of this repository imposes, stated where a caller
     pairing (zk_verify): the verifying key file is read once into a cached verifying-only key (re-read when the file
     changes), the proof points are decoded and the check's multi-scalar sums made on the device, the pairing on the host.
     `verify_batch` sends many proofs of one key through one zk_verify_batch call.
+  * PUBLIC INPUTS are an extension: the reference circuit has none (`num_instance = vec![]`), so its proofs are bound neither
+    to the message hash nor to the account's key.  `download_keys(public=True)` makes the key of the same shape with ONE instance
+    column; `create_proof_from_advice` / `verify` / `verify_evm` / `mock_verify_advice` take `instances` (canonical integers),
+    the `_synthetic` request functions with public=True expose msghash, pubkey_x and pubkey_y as `public_inputs` gives them,
+    and `encode_calldata` lays instances and proof out as snark-verifier's verifier contracts read them.  The rule is
+    [RECALLED] (include/zkmi355.h "public inputs").
 """
+import dataclasses
 import hashlib
 import os
 import queue
@@ -405,16 +412,49 @@ def _audit_or_raise(eng, pk):
         raise ProvingKeyError(flags, findings)
 
 
-def download_keys(degree: int, proving_key_path=None, verifying_key_path=None, device: int = 0, check: bool = False):
+def public_inputs(msg_hash: bytes, pubkey_x: bytes, pubkey_y: bytes, limb_bits: int = 88, num_limbs: int = 3):
+    """The instance column of a circuit with public inputs: msghash, pubkey_x, pubkey_y (32 little-endian bytes each, as the
+    requests carry them), each as num_limbs limbs of limb_bits bits, least significant first - nine values with the config's
+    88-bit limbs (how halo2-ecc's CRT integers are exposed)."""
+    mask = (1 << limb_bits) - 1
+    out = []
+    for v in (msg_hash, pubkey_x, pubkey_y):
+        x = int.from_bytes(bytes(v), "little")
+        if x >> (limb_bits * num_limbs):
+            raise ValueError("value does not fit the limbs")
+        out += [(x >> (limb_bits * i)) & mask for i in range(num_limbs)]
+    return out
+
+
+def encode_calldata(instances, proof: bytes) -> bytes:
+    """snark-verifier's `encode_calldata`: the instances as 32-byte big-endian words, then the proof - what a generated verifier
+    contract takes as its calldata."""
+    return b"".join(int(v).to_bytes(32, "big") for v in instances) + bytes(proof)
+
+
+def _mont_limbs(instances):
+    vals = [int(v) for v in instances]
+    if any(not 0 <= v < circuit.R for v in vals):
+        raise ValueError("an instance value is not below the scalar modulus")
+    return circuit.Assignment.to_mont_limbs(vals)
+
+
+def download_keys(degree: int, proving_key_path=None, verifying_key_path=None, device: int = 0, check: bool = False,
+                  public: bool = False):
     """keygen_vk + keygen_pk for the ECDSA-shape circuit.  The proving key stays on the device
     (registered under `proving_key_path`; a key already registered under that name is freed first); the
     verifying key is written to `verifying_key_path` if given, as the reference writes it
     (`vk.to_bytes(SerdeFormat::RawBytes)`, ecdsa_p256.rs:266-270: the VerifyingKey::write image of zk_vk_write).
     check=True: the new resident key goes through Engine.pk_check, and so does - when `proving_key_path` names an existing
     ProvingKey file (RawBytes, what the reference reads on every request, ecdsa_p256.rs:338-343) - the key of that file, read
-    beside it and freed again; a key that fails raises ProvingKeyError (a file zk_pk_read itself refuses raises ZkError)."""
+    beside it and freed again; a key that fails raises ProvingKeyError (a file zk_pk_read itself refuses raises ZkError).
+    public=True: the circuit with public inputs - one instance column, its first 3 x num_limbs rows copy-constrained to the
+    cells that hold msghash, pubkey_x and pubkey_y (public_inputs); proofs of such a key need `instances`."""
     p = _config_for(degree)
-    asg = circuit.synthesize(p, 0)  # structure only: fixed columns and copy constraints
+    if public:
+        p = dataclasses.replace(p, num_instance_columns=1)
+    # structure only: fixed columns and copy constraints
+    asg = circuit.synthesize(p, 0, n_public=3 * p.num_limbs if p.num_instance_columns else 0)
     fixed = np.stack([asg.to_limbs(c) for c in asg.fixed])
     with _STATE_LOCK:  # (one set-up / tear-down of a device's state at a time)
         eng = _gen_srs_locked(degree, device)
@@ -468,13 +508,16 @@ class WitnessError(ValueError):
 
 
 def create_proof_from_advice(advice_columns, proving_key_path, degree, transcript=ZK_TRANSCRIPT_BLAKE2B, device=0,
-                             rng_seed=None, check=False) -> bytes:
+                             rng_seed=None, check=False, instances=None) -> bytes:
     """create_proof over host-synthesized advice columns — what an unchanged Rust host hands the engine
     after `ECDSACircuit::synthesize`.  `advice_columns`: sequence of (n, 4) uint64 arrays of canonical
     little-endian limbs, one per advice column of the key's shape.  check=True: the columns go through
-    Engine.witness_check first and a violated circuit raises WitnessError instead of being proved."""
+    Engine.witness_check first and a violated circuit raises WitnessError instead of being proved.
+    instances: the public inputs (canonical integers) of a key made with public=True - Engine.prove_public; None: no instances,
+    which a key with the column refuses (ZkError -1: halo2's InvalidInstances)."""
+    inst = None if instances is None else _mont_limbs(instances)
     return _with_pipeline(advice_columns, proving_key_path, degree, device,
-                          lambda st, eng, pk, slots, cols, n: _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check))
+                          lambda st, eng, pk, slots, cols, n: _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check, inst))
 
 
 def create_proof_multi_from_advice(advice_sets, proving_key_path, degree, transcript=ZK_TRANSCRIPT_BLAKE2B, device=0, rng_seed=None,
@@ -511,14 +554,17 @@ def create_proof_multi_from_advice(advice_sets, proving_key_path, degree, transc
     return _with_pipeline([col for a in advice_sets for col in a], proving_key_path, degree, device, run)
 
 
-def mock_verify_advice(advice_columns, proving_key_path, degree, device=0, cap=64):
+def mock_verify_advice(advice_columns, proving_key_path, degree, device=0, cap=64, instances=None):
     """`MockProver::run(degree, &circuit, vec![]).verify()` — the body of the reference's test_secp256r1_ecdsa
     (ecdsa_p256.rs:209-248) — for a host that brings its own advice columns: the resident key and a pipeline's request slots
     exactly as create_proof_from_advice takes them.  Returns the first `cap` failures as (kind, index, row, other_index,
-    other_row) tuples of engine.ZK_FAIL_*; the empty list is MockProver's Ok(())."""
+    other_row) tuples of engine.ZK_FAIL_*; the empty list is MockProver's Ok(()).  instances: the public inputs of a key made
+    with public=True (`MockProver::run(degree, &circuit, vec![instances])`)."""
+    inst = None if instances is None else _mont_limbs(instances)
+    check = lambda eng, pk, polys: eng.witness_check(pk, polys, cap) if inst is None else eng.witness_check_public(pk, polys, inst, cap)
     return _with_pipeline(advice_columns, proving_key_path, degree, device,
                           lambda st, eng, pk, slots, cols, n: _on_slots(st, eng, slots, cols, n, degree,
-                                                                        lambda polys: eng.witness_check(pk, polys, cap)[1]))
+                                                                        lambda polys: check(eng, pk, polys)[1]))
 
 
 def _with_pipeline(advice_columns, proving_key_path, degree, device, fn):
@@ -553,14 +599,14 @@ def _with_pipeline(advice_columns, proving_key_path, degree, device, fn):
         q.put(which)
 
 
-def _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check=False):
+def _prove_on(st, eng, pk, slots, cols, n, degree, transcript, rng_seed, check=False, inst=None):
     def run(polys):
         if check:
-            counts, failures = eng.witness_check(pk, polys)
+            counts, failures = eng.witness_check(pk, polys) if inst is None else eng.witness_check_public(pk, polys, inst)
             if counts[0]:
                 raise WitnessError(counts, failures)
         seed = rng_seed if rng_seed is not None else os.urandom(32)  # the reference draws from OsRng (ecdsa_p256.rs:362)
-        return eng.prove(pk, polys, seed, transcript)
+        return eng.prove(pk, polys, seed, transcript) if inst is None else eng.prove_public(pk, polys, inst, seed, transcript)
 
     return _on_slots(st, eng, slots, cols, n, degree, run)
 
@@ -649,7 +695,7 @@ def _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash) -> int:
     return int.from_bytes(hashlib.sha256(bytes(pubkey_x) + bytes(pubkey_y) + bytes(r) + bytes(s) + bytes(msg_hash)).digest()[:8], "little")
 
 
-def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, transcript, device, rng_seed, check=False):
+def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, transcript, device, rng_seed, check=False, public=False):
     for name, v in (("pubkey_x", pubkey_x), ("pubkey_y", pubkey_y), ("r", r), ("s", s), ("msg_hash", msg_hash)):
         if len(v) != 32:
             raise ValueError(f"{name} must be 32 little-endian bytes")  # the reference takes &[u8; 32]
@@ -657,29 +703,36 @@ def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degre
         # the real circuit would be unsatisfiable; never let such a request come back with a verifying proof
         raise ValueError("invalid ES256 signature (or non-canonical field encoding): request refused")
     _, p, _ = _resident_key(proving_key_path, degree, device)
-    asg = circuit.synthesize(p, _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash))
+    if bool(p.num_instance_columns) != bool(public):
+        raise ValueError("the resident key was made %s public inputs (download_keys(public=...))" % ("with" if p.num_instance_columns else "without"))
+    vals = public_inputs(msg_hash, pubkey_x, pubkey_y, p.limb_bits, p.num_limbs) if public else None
+    asg = circuit.synthesize(p, _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash), n_public=len(vals) if public else 0, public_values=vals)
     return create_proof_from_advice([asg.to_limbs(col) for col in asg.advice], proving_key_path, degree, transcript, device, rng_seed,
-                                    check)
+                                    check, vals)
 
 
-def generate_proof_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None, check=False) -> bytes:
+def generate_proof_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None, check=False,
+                             public=False) -> bytes:
     """Request shape of `generate_proof` (Blake2b + SHPLONK, the /prove endpoint, proving-server/src/main.rs:65-79)
-    over the SYNTHETIC same-shape circuit — see the module docstring.  check: create_proof_from_advice's."""
-    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_BLAKE2B, device, rng_seed, check)
+    over the SYNTHETIC same-shape circuit — see the module docstring.  check: create_proof_from_advice's.  public=True (a key of
+    download_keys(public=True)): the proof's public inputs are public_inputs(msg_hash, pubkey_x, pubkey_y)."""
+    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_BLAKE2B, device, rng_seed, check, public)
 
 
-def generate_proof_evm_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None, check=False) -> bytes:
+def generate_proof_evm_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, device=0, rng_seed=None, check=False,
+                                 public=False) -> bytes:
     """Request shape of `generate_proof_evm` (Keccak EvmTranscript + GWC, the /prove_evm endpoint,
     proving-server/src/main.rs:49-63) over the SYNTHETIC same-shape circuit — see the module docstring.  check:
-    create_proof_from_advice's."""
-    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_EVM, device, rng_seed, check)
+    create_proof_from_advice's; public: generate_proof_synthetic's."""
+    return _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, ZK_TRANSCRIPT_EVM, device, rng_seed, check, public)
 
 
 # ---- verify / verify_evm (ecdsa_p256.rs:429-469) -----------------------------------------------------------------------------
 
-def _resident_vk(degree, verifying_key_path, device):
+def _resident_vk(degree, verifying_key_path, device, public=False):
     """(engine, verifying-only key) for the file: VerifyingKey::read::<_, ECDSACircuit<Fr>> (ecdsa_p256.rs:431-435) once per file
-    version, cached with the device's resident state (the key is a few kB: commitments and transcript_repr)."""
+    version, cached with the device's resident state (the key is a few kB: commitments and transcript_repr).  public: the file is
+    the key of a circuit with public inputs (the file itself does not say: the shape comes from the circuit's configure)."""
     with _STATE_LOCK:
         eng = _gen_srs_locked(degree, device)
         st = _STATE[device]
@@ -688,26 +741,33 @@ def _resident_vk(degree, verifying_key_path, device):
             stt = os.stat(verifying_key_path)
         except OSError as e:  # the reference panics with "Unable to open verifying key file" (ecdsa_p256.rs:432)
             raise FileNotFoundError(f"Unable to open verifying key file: {verifying_key_path}") from e
-        tag = (os.path.abspath(verifying_key_path), stt.st_mtime_ns, stt.st_size)
+        tag = (os.path.abspath(verifying_key_path), stt.st_mtime_ns, stt.st_size, bool(public))
         if tag not in vks:
-            for old in [t for t in vks if t[0] == tag[0]]:
+            for old in [t for t in vks if t[0] == tag[0] and t[3] == tag[3]]:
                 eng.pk_free(vks.pop(old))
             with open(verifying_key_path, "rb") as f:
                 data = f.read()
-            vks[tag] = eng.vk_read(_config_for(degree), data)
+            p = _config_for(degree)
+            vks[tag] = eng.vk_read(dataclasses.replace(p, num_instance_columns=1) if public else p, data)
         return eng, vks[tag]
 
 
-def verify(degree: int, proof: bytes, verifying_key_path: str, device: int = 0) -> bool:
-    """`verify` (ecdsa_p256.rs:429-447): Blake2b transcript + SHPLONK, no instances, against gen_srs(degree)."""
-    eng, vk = _resident_vk(degree, verifying_key_path, device)
-    return eng.verify(vk, bytes(proof), ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+def _verify(degree, proof, verifying_key_path, device, instances, transcript, scheme):
+    eng, vk = _resident_vk(degree, verifying_key_path, device, instances is not None)
+    if instances is None:
+        return eng.verify(vk, bytes(proof), transcript, scheme)
+    return eng.verify_public(vk, bytes(proof), _mont_limbs(instances), transcript, scheme)
 
 
-def verify_evm(degree: int, proof: bytes, verifying_key_path: str, device: int = 0) -> bool:
-    """`verify_evm` (ecdsa_p256.rs:449-469): Keccak EvmTranscript + GWC, no instances, against gen_srs(degree)."""
-    eng, vk = _resident_vk(degree, verifying_key_path, device)
-    return eng.verify(vk, bytes(proof), ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
+def verify(degree: int, proof: bytes, verifying_key_path: str, device: int = 0, instances=None) -> bool:
+    """`verify` (ecdsa_p256.rs:429-447): Blake2b transcript + SHPLONK against gen_srs(degree); no instances, as the reference -
+    or, for the key of a circuit with public inputs, `instances` (canonical integers): wrong values are a rejected proof."""
+    return _verify(degree, proof, verifying_key_path, device, instances, ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+
+
+def verify_evm(degree: int, proof: bytes, verifying_key_path: str, device: int = 0, instances=None) -> bool:
+    """`verify_evm` (ecdsa_p256.rs:449-469): Keccak EvmTranscript + GWC against gen_srs(degree); `instances` as verify's."""
+    return _verify(degree, proof, verifying_key_path, device, instances, ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
 
 
 def verify_batch(degree: int, proofs, verifying_key_path: str, evm: bool, device: int = 0):

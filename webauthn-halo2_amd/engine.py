@@ -102,7 +102,7 @@ class PinnedArray:
 class CircuitParamsC(ctypes.Structure):
     _fields_ = [("k", ctypes.c_uint32), ("num_advice", ctypes.c_uint32), ("num_lookup_advice", ctypes.c_uint32),
                 ("num_fixed", ctypes.c_uint32), ("lookup_bits", ctypes.c_uint32),
-                ("num_idle_gate_columns", ctypes.c_uint32)]
+                ("num_idle_gate_columns", ctypes.c_uint32), ("num_instance_columns", ctypes.c_uint32)]
 
 
 class WitnessFailureC(ctypes.Structure):
@@ -206,6 +206,13 @@ def load_library():
         "zk_proof_size": ([vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_prove": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_char_p, ctypes.c_int,
                       ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_prove_public": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, u64p, sz, ctypes.c_char_p, ctypes.c_int,
+                             ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_verify_public": ([vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, sz, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)],
+                             ctypes.c_int),
+        "zk_witness_check_public": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(WitnessFailureC), sz,
+                                     ctypes.POINTER(ctypes.c_uint64), u64p, sz], ctypes.c_int),
+        "zk_pk_num_instance_columns": ([vp, ctypes.c_uint64, ctypes.POINTER(u32)], ctypes.c_int),
         "zk_prove_batch": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_char_p, ctypes.c_int,
                             ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_proof_size_multi": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(sz)], ctypes.c_int),
@@ -256,7 +263,8 @@ def load_library():
         fn = getattr(L, name, None)
         if fn is None:
             if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info", "zk_proof_size_multi",
-                        "zk_prove_multi", "zk_verify_multi") and os.environ.get("ZKMI355_LIB"):
+                        "zk_prove_multi", "zk_verify_multi", "zk_prove_public", "zk_verify_public", "zk_witness_check_public",
+                        "zk_pk_num_instance_columns") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -457,8 +465,7 @@ class Engine:
         return self._write(self.L.zk_pk_write, "zk_pk_write", pk, fmt)
 
     def pk_read(self, params, data, fmt=ZK_SERDE_RAW_BYTES, transcript_repr=None):
-        cp = CircuitParamsC(params.degree, params.num_advice, params.num_lookup_advice, params.num_fixed, params.lookup_bits,
-                            getattr(params, "idle_gate_columns", 0))
+        cp = self._params_c(params)
         keep, ptr, n = self._bytes_arg(data)
         t = None if transcript_repr is None else _p(np.ascontiguousarray(transcript_repr, dtype=np.uint64).reshape(4))
         h = ctypes.c_uint64()
@@ -640,9 +647,9 @@ class Engine:
     # ---- keygen / create_proof -------------------------------------------------------
     def keygen(self, params, fixed_canonical, copies):
         """params: circuit.CircuitParams; fixed_canonical: (n_fix, n, 4) uint64 canonical limbs;
-        copies: iterable of ((perm_col, row), (perm_col, row))."""
-        cp = CircuitParamsC(params.degree, params.num_advice, params.num_lookup_advice, params.num_fixed, params.lookup_bits,
-                            getattr(params, "idle_gate_columns", 0))
+        copies: iterable of ((perm_col, row), (perm_col, row)); the instance column of a shape that has one is the last
+        permutation column."""
+        cp = self._params_c(params)
         fx = np.ascontiguousarray(fixed_canonical, dtype=np.uint64)
         if fx.ndim != 3 or fx.shape[1:] != (1 << params.degree, 4):
             raise ValueError("fixed_canonical must have shape (n_fixed_columns, 2^degree, 4)")
@@ -691,6 +698,49 @@ class Engine:
         self._chk(self.L.zk_prove(self.ctx, pk, hs, len(advice_polys), seed, transcript, scheme, buf, len(buf),
                                   ctypes.byref(ln)), "zk_prove")
         return buf.raw[:ln.value]
+
+    @staticmethod
+    def _instance_arg(instance_mont):
+        """(n, 4) uint64 Montgomery images (or None / empty) -> (array kept alive, pointer or None, count)"""
+        a = np.zeros((0, 4), dtype=np.uint64) if instance_mont is None else _arr(instance_mont, 4)
+        return a, (_p(a) if a.shape[0] else None), a.shape[0]
+
+    def pk_num_instance_columns(self, pk):
+        out = ctypes.c_uint32()
+        self._chk(self.L.zk_pk_num_instance_columns(self.ctx, pk, ctypes.byref(out)), "zk_pk_num_instance_columns")
+        return out.value
+
+    def prove_public(self, pk, advice_polys, instance_mont, seed=bytes(32), transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
+        """zk_prove_public: create_proof with the circuit's public inputs - `instance_mont` (m, 4) uint64 Montgomery images, the first
+        m rows of the key's instance column.  A key without the column takes none and gives prove()'s bytes."""
+        if len(seed) != 32:
+            raise ValueError("rng seed must be 32 bytes")
+        hs = (ctypes.c_uint64 * len(advice_polys))(*[p.h for p in advice_polys])
+        keep, iptr, ni = self._instance_arg(instance_mont)
+        ln = ctypes.c_size_t()
+        self._chk(self.L.zk_proof_size(self.ctx, pk, transcript, scheme, ctypes.byref(ln)), "zk_proof_size")
+        buf = ctypes.create_string_buffer(ln.value)
+        self._chk(self.L.zk_prove_public(self.ctx, pk, hs, len(advice_polys), iptr, ni, seed, transcript, scheme, buf, len(buf),
+                                         ctypes.byref(ln)), "zk_prove_public")
+        return buf.raw[:ln.value]
+
+    def verify_public(self, pk, proof, instance_mont, transcript, scheme=ZK_SCHEME_DEFAULT) -> bool:
+        """zk_verify_public: verify_proof with the public inputs (full or verifying-only key).  Wrong values: False."""
+        proof = bytes(proof)
+        keep, iptr, ni = self._instance_arg(instance_mont)
+        ok = ctypes.c_int(0)
+        self._chk(self.L.zk_verify_public(self.ctx, pk, transcript, scheme, iptr, ni, proof, len(proof), ctypes.byref(ok)), "zk_verify_public")
+        return bool(ok.value)
+
+    def witness_check_public(self, pk, advice_polys, instance_mont, cap=64):
+        """zk_witness_check_public: witness_check() with the instance column's values; the column is the last permutation column."""
+        hs = (ctypes.c_uint64 * max(len(advice_polys), 1))(*[p.h for p in advice_polys])
+        keep, iptr, ni = self._instance_arg(instance_mont)
+        out = (WitnessFailureC * cap)() if cap else None
+        counts = (ctypes.c_uint64 * 5)()
+        self._chk(self.L.zk_witness_check_public(self.ctx, pk, hs, len(advice_polys), out, cap, counts, iptr, ni), "zk_witness_check_public")
+        m = min(cap, int(counts[0]))
+        return [int(v) for v in counts], [(f.kind, f.index, f.row, f.other_index, f.other_row) for f in out[:m]] if m else []
 
     def prove_batch(self, pk, advice_sets, seeds, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
         """zk_prove_batch: len(advice_sets) independent proofs of one key in lock-step.  advice_sets[j]: proof j's advice
@@ -767,7 +817,7 @@ class Engine:
     @staticmethod
     def _params_c(params):
         return CircuitParamsC(params.degree, params.num_advice, params.num_lookup_advice, params.num_fixed, params.lookup_bits,
-                              getattr(params, "idle_gate_columns", 0))
+                              getattr(params, "idle_gate_columns", 0), getattr(params, "num_instance_columns", 0))
 
     def vk_read(self, params, data, fmt=ZK_SERDE_RAW_BYTES, transcript_repr=None):
         """VerifyingKey::read: a verifying-only key (commitments + transcript_repr, no prover state) from a zk_vk_write image."""

@@ -51,7 +51,7 @@ def parse_request(body):
 
 
 def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", verifying_key_path=None, params_path=None, check_keys=False,
-          check_placement=False):
+          check_placement=False, public=False):
     """POST /setup (and the server's start-up keygen, main.rs:451-456).  The proving key stays resident on
     `device`, registered under `proving_key_path` (the name later requests carry); the verifying key is
     written only when a path is given (the reference writes ./keys/verifying_key.vk).  `params_path`: a trusted-setup
@@ -62,31 +62,36 @@ def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", ver
     audited (ecdsa_p256.ProvingKeyError names the part, column and index of a key that is not what keygen makes).
     check_placement=True: before anything is made resident the device's stream placement is measured
     (ecdsa_p256.check_placement: re-dealt if need be while the device has no engine yet, measured only when it has) and
-    ecdsa_p256.PlacementError raised if the pipelines would share hardware queues; the report is returned instead of "Done"."""
+    ecdsa_p256.PlacementError raised if the pipelines would share hardware queues; the report is returned instead of "Done".
+    public=True: the key of the circuit with public inputs (download_keys(public=True)), for prove*(public=True)."""
     report = ecdsa_p256.check_placement(device, calibrate=True) if check_placement else None
     if params_path is not None:
         ecdsa_p256.set_params_file(params_path, device)
-    ecdsa_p256.download_keys(degree, proving_key_path, verifying_key_path, device, check=check_keys)
+    ecdsa_p256.download_keys(degree, proving_key_path, verifying_key_path, device, check=check_keys, public=public)
     return report if check_placement else "Done"
 
 
-def _prove(body, evm, device, degree, rng_seed, check=False):
+def _prove(body, evm, device, degree, rng_seed, check=False, public=False):
     """check=True: the request's advice columns go through the witness check first (ecdsa_p256.WitnessError instead of a proof
-    no verifier accepts)."""
+    no verifier accepts).  public=True (an extension; the key of setup(public=True)): the proof is bound to the request's msghash
+    and public key - the answer is the hex of ecdsa_p256.encode_calldata: the nine instance words, then the proof."""
     q = parse_request(body)
     fn = ecdsa_p256.generate_proof_evm_synthetic if evm else ecdsa_p256.generate_proof_synthetic
-    proof = fn(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, device, rng_seed, check)
+    proof = fn(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, device, rng_seed, check, public)
+    if public:
+        _, p, _ = ecdsa_p256._resident_key(q["proving_key_path"], degree, device)
+        proof = ecdsa_p256.encode_calldata(ecdsa_p256.public_inputs(q["msghash"], q["pubkey_x"], q["pubkey_y"], p.limb_bits, p.num_limbs), proof)
     return proof.hex()  # hex::encode: lowercase, no prefix
 
 
-def prove_evm(body, device=0, degree=DEGREE, rng_seed=None, check=False) -> str:
+def prove_evm(body, device=0, degree=DEGREE, rng_seed=None, check=False, public=False) -> str:
     """POST /prove_evm: Keccak EvmTranscript + GWC; the hex string the web client puts into userOp.signature."""
-    return _prove(body, True, device, degree, rng_seed, check)
+    return _prove(body, True, device, degree, rng_seed, check, public)
 
 
-def prove(body, device=0, degree=DEGREE, rng_seed=None, check=False) -> str:
+def prove(body, device=0, degree=DEGREE, rng_seed=None, check=False, public=False) -> str:
     """POST /prove: Blake2b + SHPLONK."""
-    return _prove(body, False, device, degree, rng_seed, check)
+    return _prove(body, False, device, degree, rng_seed, check, public)
 
 
 def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE):
@@ -137,16 +142,32 @@ def parse_verify_request(body):
     return path, bytes.fromhex(proof)
 
 
-def verify(body, device=0, degree=DEGREE) -> str:
-    """POST /verify: Blake2b + SHPLONK; "verified" or "rejected"."""
-    path, proof = parse_verify_request(body)
-    return "verified" if ecdsa_p256.verify(degree, proof, path, device) else "rejected"
+def _split_calldata(proof, public):
+    """(instances or None, proof): `public` leading 32-byte big-endian words of ecdsa_p256.encode_calldata's layout split off."""
+    if not public:
+        return None, proof
+    if len(proof) < 32 * public:
+        raise ValueError("proof: shorter than its instance words")
+    return [int.from_bytes(proof[32 * i:32 * i + 32], "big") for i in range(public)], proof[32 * public:]
 
 
-def verify_evm(body, device=0, degree=DEGREE) -> str:
-    """POST /verify_evm: Keccak EvmTranscript + GWC; "verified" or "rejected"."""
+def _verify(body, fn, device, degree, public):
     path, proof = parse_verify_request(body)
-    return "verified" if ecdsa_p256.verify_evm(degree, proof, path, device) else "rejected"
+    instances, proof = _split_calldata(proof, public)
+    if instances is not None and any(v >= ecdsa_p256.circuit.R for v in instances):
+        return "rejected"  # (a generated verifier contract reverts on a non-canonical instance word)
+    return "verified" if fn(degree, proof, path, device, instances) else "rejected"
+
+
+def verify(body, device=0, degree=DEGREE, public=0) -> str:
+    """POST /verify: Blake2b + SHPLONK; "verified" or "rejected".  public: how many leading instance words the proof string
+    carries (prove(public=True) answers with nine), for the verifying key of a circuit with public inputs."""
+    return _verify(body, ecdsa_p256.verify, device, degree, public)
+
+
+def verify_evm(body, device=0, degree=DEGREE, public=0) -> str:
+    """POST /verify_evm: Keccak EvmTranscript + GWC; "verified" or "rejected".  public: verify's."""
+    return _verify(body, ecdsa_p256.verify_evm, device, degree, public)
 
 
 def verify_batch(bodies, evm=True, device=0, degree=DEGREE):

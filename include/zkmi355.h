@@ -449,8 +449,11 @@ int zk_prove(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, cons
  * ZK_EINVAL beyond zk_prove's cases: a value that is not a Montgomery image below the modulus, n_instance > n - 7 (halo2's
  * InstanceTooLarge), values for a key without the column.  The workspace of a key with the column is three vectors larger (values,
  * coefficients, extended coset: 96 MiB at k = 19).
- * OUT OF SCOPE: zk_prove_batch, zk_prove_multi, zk_verify_batch, zk_verify_multi and the phase-level zk_permutation_product /
- * zk_quotient carry no instances; they - and zk_prove, zk_verify, zk_witness_check - return ZK_EINVAL on a key with the column.
+ * The batch and multi forms WITH instances are zk_prove_batch_public, zk_prove_multi_public, zk_verify_batch_public and
+ * zk_verify_multi_public below.  zk_prove_batch, zk_prove_multi, zk_verify_batch, zk_verify_multi - and zk_prove, zk_verify,
+ * zk_witness_check - carry none and return ZK_EINVAL on a key with the column.
+ * OUT OF SCOPE: the phase-level zk_permutation_product / zk_quotient carry no instances and return ZK_EINVAL on such a key; more than
+ * one instance column; batches of multi proofs.
  * Every other entry point (zk_lookup_permute, zk_lookup_product, the file and key functions, zk_pk_check) works on such a key. */
 int zk_prove_public(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice,
                     const uint64_t* instance_mont /* n_instance x 4 */, size_t n_instance, const uint8_t rng_seed[32], int transcript,
@@ -492,10 +495,43 @@ int zk_prove_batch(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /*
  * for ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_BATCH_PASS_COLUMNS and the activity hold.  No instances (a key with an instance column:
  * ZK_EINVAL; zk_prove_public proves one circuit with them); no batches of such proofs. */
 #define ZK_PROVE_MULTI_MAX 16
+/* the length of a proof over n_circuits circuits.  On a key with an instance column it is the length of zk_prove_multi_public's proof:
+ * the column is one more permutation column (its sigma evaluation once per proof; where it starts a chunk of its own, that chunk's z
+ * commitment and evaluations once per circuit), and nothing else of it is in the proof - the count below takes the shape's
+ * permutation columns and chunks, which include it. */
 int zk_proof_size_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, size_t* out);
 int zk_prove_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const zk_poly* advice /* n_circuits x n_advice, circuit-major */,
                    size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap,
                    size_t* proof_len);
+/* ---- the batch and multi forms with public inputs ----
+ * Lists: instances_mont[j] holds n_instances[j] Montgomery values (x 4 words); the lists of one call may differ in length, 0
+ * included, and instances_mont[j] may be NULL where n_instances[j] == 0.  Every list is validated by zk_prove_public's rules (a
+ * Montgomery image below the modulus, at most n - 7 values); one bad list is ZK_EINVAL for the whole call.  On a key WITHOUT the
+ * column every length must be 0, both arrays may be NULL, and the bytes are those of the form without _public.  Outputs are
+ * untouched on error.  All other limits, errors and options are those of the forms without _public.
+ *
+ * zk_prove_batch_public: zk_prove_batch with list j for proof j; proof j is byte-identical to zk_prove_public with the same key,
+ * advice, list and seed (every proof absorbs its own list into its own transcript).  batch == 1 is zk_prove_public.  The B
+ * instance columns are written by ONE staged upload (a table of `batch` entries and the call's concatenated values: 16 bytes per
+ * proof + 32 bytes per value, pinned and device, kept with the key's batch buffers and grown to the largest call) and ONE launch that
+ * writes every row of every column; their coefficient and coset forms ride in the batched transforms of the first advice forms.
+ *
+ * zk_prove_multi_public: zk_prove_multi with list c for circuit c [RECALLED, as zk_prove_multi's rule: not pinned by reference
+ * bytes; tests/multi_public_ref.py restates it and the bytes are compared with it].  The rule is zk_prove_multi's with
+ *   transcript   transcript_repr; for c = 0 .. N - 1: every value of circuit c's list (absorbed, not written; neither N nor the
+ *                lengths are hashed); then everything else in zk_prove_multi's order.  ALL circuits' instances come before any advice
+ *                commitment: halo2's loop over `instances` at the top of create_proof / verify_proof
+ *   RNG          the instance columns draw nothing: zk_prove_multi's draw order
+ *   permutation  circuit c's grand product reads c's column; quotient pass c reads c's extended coset (or three-coset copy)
+ *   verifier     circuit c's permutation terms of the expected h(x) use inst_c(x)
+ * n_circuits == 1 is zk_prove_public. */
+int zk_prove_batch_public(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /* batch x n_advice, proof-major */, size_t n_advice,
+                          const uint64_t* const* instances_mont /* batch lists, each n_instances[j] x 4 */, const size_t* n_instances,
+                          const uint8_t* rng_seeds /* batch x 32 */, int transcript, int scheme, uint8_t* proofs_out, size_t proof_stride,
+                          size_t* proof_len);
+int zk_prove_multi_public(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const zk_poly* advice /* n_circuits x n_advice, circuit-major */,
+                          size_t n_advice, const uint64_t* const* instances_mont /* n_circuits lists */, const size_t* n_instances,
+                          const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
 /* upload canonical (non-Montgomery) integers and convert on the device */
 int zk_poly_upload_canonical(zk_ctx* ctx, zk_poly p, const uint64_t* host_canonical, size_t n);
 
@@ -613,6 +649,34 @@ int zk_verify_batch(zk_ctx* ctx, zk_pk pk, size_t batch, int transcript, int sch
  * another circuit count included: it has another length - is a verdict (*ok = 0), never an error.  Full and verifying-only
  * keys.  n_circuits == 1 is zk_verify.  ZK_EINVAL: n_circuits == 0 or > ZK_PROVE_MULTI_MAX. */
 int zk_verify_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok);
+
+/* zk_verify_batch with list j for proof j (verdicts[j] = zk_verify_public's of proof j and list j) and zk_verify_multi with list c
+ * for circuit c (n_circuits == 1 is zk_verify_public).  Lists as for the provers above; wrong values are a verdict, a list the
+ * column cannot hold or a value not below the modulus is ZK_EINVAL for the whole call.  inst(x) is evaluated where
+ * zk_verify_instance_eval_mode says (auto: the host; the device path runs every proof's transcript to x on the host, evaluates every
+ * list of the call in one launch, and computes the rest of the term lists on the host).  The fold weights of the batch form are
+ * drawn from a hash of the key, every proof's bytes AND every proof's list (length first), so that the whole statement is fixed
+ * before the weights are; the bisection makes every verdict exact as before. */
+int zk_verify_batch_public(zk_ctx* ctx, zk_pk pk, size_t batch, int transcript, int scheme, const uint64_t* const* instances_mont,
+                           const size_t* n_instances, const uint8_t* const* proofs, const size_t* lens, uint8_t* verdicts);
+int zk_verify_multi_public(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, const uint64_t* const* instances_mont,
+                           const size_t* n_instances, const uint8_t* proof, size_t len, int* ok);
+/* where zk_verify_batch_public / zk_verify_multi_public evaluate inst(x): mode 0 auto, 1 on the host (verifier.h, one batch inversion
+ * per list), 2 on the device (zk_instance_eval's kernel: one launch for every list of the call).  Same verdicts.  Auto is the host:
+ * the two have NOT been measured against each other (tools/verify_public_rate.py is the tool).  zk_verify_public always evaluates
+ * on the host.  A call of its own and not a ZK_OPT_* number: the option numbers of zk_ctx_set_option are a closed set
+ * (tests/test_gpu_abi_errors.py pins it, the first undefined number included).  ZK_EINVAL: mode outside 0 .. 2. */
+#define ZK_VERIFY_INSTANCE_EVAL_AUTO 0
+#define ZK_VERIFY_INSTANCE_EVAL_HOST 1
+#define ZK_VERIFY_INSTANCE_EVAL_DEVICE 2
+int zk_verify_instance_eval_mode(zk_ctx* ctx, int mode);
+/* inst(x) = sum_{i<m} v_i l_i(x), l_i(x) = w^i (x^n - 1) / (n (x - w^i)), n = 2^k, w the engine's primitive n-th root, for `count`
+ * (list, point) pairs in one call on the device.  Needs no SRS and no key.  k <= 26, every m_j <= 2^k, values and points Montgomery
+ * images below the modulus (else ZK_EINVAL).  on_domain[j] = 1 with out j zero exactly when x_j = w^i for some i < m_j (the case
+ * in which the host verifier rejects); m_j = 0 gives zero; x_j^n = 1 with no such i gives zero with the flag clear.  Pairs that
+ * name the same list (address and length) share one upload.  Outputs are untouched on error. */
+int zk_instance_eval(zk_ctx* ctx, uint32_t k, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances,
+                     const uint64_t* x_mont /* count x 4 */, uint64_t* out_mont /* count x 4 */, uint8_t* on_domain /* count */);
 
 /* ---- timing of the last call of each kind, measured with HIP events on the
  *      context stream (ms); used by bench.py for the roofline figures ---------- */

@@ -181,14 +181,21 @@ class Pipeline:
             self.unload(job)
         return proof
 
-    def prove_lockstep(self, jobs, transcript=ZK_TRANSCRIPT_BLAKE2B, keep=False, rng_seeds=None):
+    def prove_lockstep(self, jobs, transcript=ZK_TRANSCRIPT_BLAKE2B, keep=False, rng_seeds=None, instances=None):
         """The proofs of `jobs` (all resident on this pipeline) in ONE lock-step batch (zk_prove_batch): the same commitment of
         every job shares an MSM pass, the same transform an NTT launch.  Returns the proofs in the order of `jobs`; each is
-        byte-identical to prove(job)."""
+        byte-identical to prove(job).  instances: one list of public inputs (canonical integers) per job, for a key with the
+        instance column (zk_prove_batch_public: each proof is Engine.prove_public's); None: no instances."""
         jobs = list(jobs)
         if rng_seeds is None:
             rng_seeds = [job_rng_seed(j) if self.deterministic_seeds else os.urandom(32) for j in jobs]
-        proofs = self.eng.prove_batch(self.pk, [self.resident[j] for j in jobs], rng_seeds, transcript)
+        if instances is None:
+            proofs = self.eng.prove_batch(self.pk, [self.resident[j] for j in jobs], rng_seeds, transcript)
+        else:
+            if len(instances) != len(jobs):
+                raise ValueError("one instance list per job")
+            lists = [circuit.Assignment.to_mont_limbs([int(v) for v in l]) if len(l) else None for l in instances]
+            proofs = self.eng.prove_batch_public(self.pk, [self.resident[j] for j in jobs], lists, rng_seeds, transcript)
         if not keep:
             for j in jobs:
                 self.unload(j)

@@ -71,6 +71,7 @@ struct zk_ctx : SrsView {
     std::map<uint32_t, Fr*> twiddles_ninv; // w^i / 2^log_n (standard form): the last pass of an inverse transform (ntt.hip NTT_FOLD)
     std::map<uint32_t, Fr*> coset3_pre;    // k -> [2][2^k]: the twists (zeta w_4n^j)^m, j = 1, 2, of the three-coset transforms (poly.hip)
     std::map<uint32_t, Coset3Consts> coset3_consts;  // k -> the constants of the 3 x 3 solve
+    uint32_t opt_verify_inst_eval = 0;     // zk_verify_instance_eval_mode: where zk_verify_batch_public / zk_verify_multi_public evaluate inst(x): 0 auto (host: not measured), 1 host, 2 device
     uint32_t opt_quotient_domain = 0;      // ZK_OPT_QUOTIENT_DOMAIN: 0 auto (three cosets from k = 16), 1 always the whole extended domain, 2 three cosets wherever h has three pieces
     uint64_t srs_gen = 0;  // bumped by every zk_srs_setup / zk_srs_load / zk_srs_read: keys remember the SRS they were made under
     // tuning options (zk_ctx_set_option); 0 = built-in choice

@@ -181,6 +181,10 @@ struct BatchBufs {
     Fr* gp_host = nullptr;        // pinned: q and q_inv
     EvalItem *d_evargs = nullptr, *h_evargs = nullptr;  // every opened value of every proof in one launch
     Fr *ev_scratch = nullptr, *ev_out = nullptr, *tail_host = nullptr;
+    // the instance columns of a call (zk_prove_batch_public / zk_prove_multi_public): one staged upload — a table of cap InstEntry,
+    // then the call's concatenated values — pinned and device, inst_vals elements of values (grown to the call's total)
+    void *inst_host = nullptr, *inst_dev = nullptr;
+    size_t inst_vals = 0;
 };
 
 
@@ -216,6 +220,17 @@ int pk_ensure_cosets3(zk_ctx* c, zk_pk_rec* pk);
 int pk_instance_values(const Layout& lay, const uint64_t* instance_mont, size_t n_instance, std::vector<Fr>* out);
 // the values into rows 0 .. m - 1 of the workspace's instance column, zero behind them (enqueued on `st`; `vals` must outlive the copy)
 int pk_instance_upload(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<Fr>& vals);
+// `count` lists of one call (zk_*_batch_public: one per proof; zk_*_multi_public: one per circuit), each by pk_instance_values' rules;
+// lists may differ in length, instances_mont[j] may be NULL where n_instances[j] == 0; both arrays NULL: every list empty, on a key
+// without the column only
+// `same_as` (may be null): same_as[j] = the first list of the call with list j's address and length (j itself where it is the
+// first); a repeated list is validated and copied once, and out[j] of a repeat stays empty
+int pk_instance_lists(const Layout& lay, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances,
+                      std::vector<std::vector<Fr>>* out, std::vector<uint32_t>* same_as = nullptr);
+// the instance columns of the lanes ws[q] (a key with the column; lists[q] validated by pk_instance_values) in ONE staged upload and
+// ONE launch (prover.h launch_instance_columns), enqueued on `st`; the staging is pk->bb's (pk_ensure_batch first) and must not be
+// rewritten before the stream has consumed it (every whole-proof call ends with the main stream idle)
+int pk_instance_upload_lanes(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<zk_pk_rec*>& ws, const std::vector<const std::vector<Fr>*>& lists);
 Fr fr_delta();  // 7^(2^28): generator of the odd-order subgroup (the permutation argument's coset shifts)
 int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out);
 // One pass of a quotient that several circuits share (prover_multi.h): the y-combination of this workspace's terms times

@@ -159,6 +159,13 @@ struct RowEntry {
     uint32_t pad_;
 };
 void launch_scatter_rows(const RowEntry* d_entries, uint32_t count, hipStream_t st);
+// the instance columns of a lock-step batch / of the circuits of one proof: lane q's column gets rows 0 .. len - 1 from
+// vals[off ..) and zero in rows len .. n - 1 (the WHOLE column: a lane that held a longer list before keeps no tail)
+struct InstEntry {
+    Fr* dst;
+    uint32_t off, len;  // in elements of the staged values; len <= n
+};
+void launch_instance_columns(const InstEntry* d_entries, const Fr* d_vals, uint32_t lanes, uint32_t n, hipStream_t st);
 static constexpr uint32_t KD_MAX_BATCH = 6;  // divisions per launch (SHPLONK / GWC have at most six rotation sets)
 uint32_t kate_division_scratch(uint32_t n);  // elements of scratch per division
 void launch_kate_division(const Fr* p, Fr* q, uint32_t n, const Fr& z, Fr* scratch, hipStream_t st);

@@ -112,6 +112,9 @@ struct Prover {
     // the instance column's values (zk_prove_public; a key with the column and no caller's values proves the empty column).  Absorbed
     // behind transcript_repr, never written; the column is neither blinded nor committed nor opened, and draws nothing
     const std::vector<Fr>* instance = nullptr;
+    // begin() absorbs `instance` into this prover's transcript: a lone proof and every proof of a lock-step batch.  The driver of one
+    // proof over several circuits (prover_multi.h) clears it and absorbs every circuit's list itself, once, on the one transcript
+    bool absorb_instance = true;
     bool batch_member = false;  // one of the proofs of a lock-step batch (prover_batch.h): transforms stay on the main stream
 
     Prover(const Prover&) = delete;  // (cq is bound to this object)
@@ -412,7 +415,7 @@ struct Prover {
         omega = fr_omega(lay.k);
         omega_inv = fe_inv_fast(omega);
         tr->common_scalar(pk->transcript_repr);
-        if (instance)
+        if (instance && absorb_instance)
             for (const Fr& v : *instance) tr->common_scalar(v);  // (the count is not hashed)
         return ZK_OK;
     }
@@ -1022,10 +1025,28 @@ ZK_API(zk_prove_public, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_adv
     return prove_one(c, h, advice, n_advice, true, instance_mont, n_instance, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
 }
 
-// create_proof for `batch` independent proofs of one key in lock-step (prover_batch.h)
-ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, size_t n_advice, const uint8_t* rng_seeds, int transcript, int scheme, uint8_t* proofs_out, size_t proof_stride, size_t* proof_len), (c, h, batch, advice, n_advice, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len)) {
+// the one-list forms of the entry points below (batch == 1, n_circuits == 1): zk_prove_public with list 0
+static int prove_one_of_lists(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint64_t* const* instances_mont,
+                              const size_t* n_instances, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap,
+                              size_t* proof_len) {
+    uint32_t cols = 0;
+    if (int r = zk_pk_num_instance_columns(c, h, &cols)) return r;
+    if (cols && !n_instances) return ZK_EINVAL;
+    const size_t m = n_instances ? n_instances[0] : 0;
+    return zk_prove_public(c, h, advice, n_advice, m && instances_mont ? instances_mont[0] : nullptr, m, rng_seed, transcript, scheme, proof_out,
+                           proof_cap, proof_len);
+}
+
+// create_proof for `batch` independent proofs of one key in lock-step (prover_batch.h).  `with_instances`: zk_prove_batch_public —
+// one list per proof; otherwise zk_prove_batch, which a key WITH the column refuses
+static int prove_batch(zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, size_t n_advice, bool with_instances,
+                       const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t* rng_seeds, int transcript, int scheme,
+                       uint8_t* proofs_out, size_t proof_stride, size_t* proof_len) {
     if (!c || !advice || !rng_seeds || !proof_len || batch == 0 || batch > ZK_PROVE_BATCH_MAX) return ZK_EINVAL;
-    if (batch == 1) return zk_prove(c, h, advice, n_advice, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len);
+    if (batch == 1) {
+        if (!with_instances) return zk_prove(c, h, advice, n_advice, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len);
+        return prove_one_of_lists(c, h, advice, n_advice, instances_mont, n_instances, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len);
+    }
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
@@ -1034,7 +1055,10 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
     if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
-    if (lay.n_inst) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
+    if (lay.n_inst && !with_instances) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
+    std::vector<std::vector<Fr>> lists;
+    if (with_instances)
+        if (int r = pk_instance_lists(lay, batch, instances_mont, n_instances, &lists)) return r;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
     if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
@@ -1062,6 +1086,7 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     for (uint32_t q = 0; q < B; q++) {
         trs.emplace_back(transcript == ZK_TRANSCRIPT_EVM ? (Transcript*)new EvmTranscript() : (Transcript*)new Blake2bTranscript());
         provers.emplace_back(new Prover(c, q == 0 ? pk : pk->members[q - 1], rng_seeds + 32 * (size_t)q, trs.back().get()));
+        if (lay.n_inst) provers.back()->instance = &lists[q];  // (its own list, absorbed by its own begin())
         P.push_back(provers.back().get());
     }
     const uint64_t aud0 = c->audit.violations;
@@ -1083,11 +1108,25 @@ ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice,
     return ZK_OK;
 }
 
+ZK_API(zk_prove_batch, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, size_t n_advice, const uint8_t* rng_seeds, int transcript, int scheme, uint8_t* proofs_out, size_t proof_stride, size_t* proof_len), (c, h, batch, advice, n_advice, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len)) {
+    return prove_batch(c, h, batch, advice, n_advice, false, nullptr, nullptr, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len);
+}
 
-// create_proof(&params, &pk, &[c_0 .. c_{N-1}], ..): ONE proof over n_circuits circuits of one key (prover_multi.h)
-ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, n_circuits, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+// the lock-step batch with every proof's public inputs: proof j is zk_prove_public's with list j
+ZK_API(zk_prove_batch_public, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, size_t n_advice, const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t* rng_seeds, int transcript, int scheme, uint8_t* proofs_out, size_t proof_stride, size_t* proof_len), (c, h, batch, advice, n_advice, instances_mont, n_instances, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len)) {
+    return prove_batch(c, h, batch, advice, n_advice, true, instances_mont, n_instances, rng_seeds, transcript, scheme, proofs_out, proof_stride, proof_len);
+}
+
+// create_proof(&params, &pk, &[c_0 .. c_{N-1}], &[inst_0 .. inst_{N-1}], ..): ONE proof over n_circuits circuits of one key
+// (prover_multi.h).  `with_instances`: zk_prove_multi_public — one list per circuit; otherwise zk_prove_multi
+static int prove_multi(zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, bool with_instances,
+                       const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t rng_seed[32], int transcript, int scheme,
+                       uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
     if (!c || !advice || !rng_seed || !proof_len || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
-    if (n_circuits == 1) return zk_prove(c, h, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
+    if (n_circuits == 1) {
+        if (!with_instances) return zk_prove(c, h, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
+        return prove_one_of_lists(c, h, advice, n_advice, instances_mont, n_instances, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
+    }
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
@@ -1096,7 +1135,10 @@ ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* ad
     if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
     if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
     if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
-    if (lay.n_inst) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
+    if (lay.n_inst && !with_instances) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
+    std::vector<std::vector<Fr>> lists;
+    if (with_instances)
+        if (int r = pk_instance_lists(lay, n_circuits, instances_mont, n_instances, &lists)) return r;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
     if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
@@ -1128,6 +1170,7 @@ ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* ad
     for (uint32_t q = 0; q < B; q++) {
         if (q) scratch.emplace_back(new Blake2bTranscript());
         provers.emplace_back(new Prover(c, q == 0 ? pk : pk->members[q - 1], rng_seed, q == 0 ? tr : scratch.back().get()));
+        if (lay.n_inst) provers.back()->instance = &lists[q];  // (circuit q's column; the driver absorbs the lists, no begin() does)
         P.push_back(provers.back().get());
     }
     const uint64_t aud0 = c->audit.violations;
@@ -1143,4 +1186,13 @@ ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* ad
     if (!proof_out || proof_cap < tr->out.size()) return proof_out ? ZK_EINVAL : ZK_OK;
     memcpy(proof_out, tr->out.data(), tr->out.size());
     return ZK_OK;
+}
+
+ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, n_circuits, advice, n_advice, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+    return prove_multi(c, h, n_circuits, advice, n_advice, false, nullptr, nullptr, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
+}
+
+// one proof over n_circuits circuits with every circuit's public inputs (the rule: prover_multi.h / DESIGN.md section 3)
+ZK_API(zk_prove_multi_public, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, n_circuits, advice, n_advice, instances_mont, n_instances, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
+    return prove_multi(c, h, n_circuits, advice, n_advice, true, instances_mont, n_instances, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
 }

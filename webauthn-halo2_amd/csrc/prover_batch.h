@@ -9,10 +9,32 @@
 // one set of permutation launches, all grand products through one scan, all openings through one evaluation launch.  What
 // stays per proof is chip-filling anyway (quotient, linear combinations, Kate divisions) or host work (transcripts, RNG).
 //
+// Public inputs (zk_prove_batch_public): every proof has its own validated instance list, absorbed by its own begin() into its own
+// transcript; the B instance columns are written by ONE staged upload and ONE launch (instance_columns below) and transformed with
+// the lanes' first advice forms.
+//
 // Every proof keeps its own transcript, its own ChaCha20 stream and its own workspace (zk_pk_rec::members); the bytes of
 // proof j are those of zk_prove with the same key, advice and seed (tests/test_gpu_prove_batch.py).  The steps themselves are
 // the single prover's (prover_steps.h): this driver holds the schedule of a batch — the per-proof steps looped, the shared ones
 // given every proof's workspace at once — and the phase order is Prover::run's.
+
+// the instance columns of every lane of a batch or multi run (a key with the column): ONE staged upload and ONE launch, where the
+// lone prover has its memset + copy; every lane's list is its prover's (none: the empty column)
+inline int instance_columns(zk_ctx* c, hipStream_t st, zk_pk_rec* pk0, const std::vector<Prover*>& P) {
+    if (!pk0->inst_val) return ZK_OK;
+    static const std::vector<Fr> none;
+    std::vector<zk_pk_rec*> ws;
+    std::vector<const std::vector<Fr>*> lists;
+    for (Prover* p : P) {
+        ws.push_back(p->pk);
+        lists.push_back(p->instance ? p->instance : &none);
+    }
+    return pk_instance_upload_lanes(c, st, pk0, ws, lists);
+}
+// the columns' coefficient and coset forms ride with the lanes' first advice forms (Prover::with_instance's place)
+inline void with_instances(const std::vector<Prover*>& P, std::vector<Prover::Forms>& fm) {
+    for (Prover* p : P) p->with_instance(fm);
+}
 
 struct BatchRun {
     zk_ctx* c;
@@ -74,6 +96,7 @@ struct BatchRun {
         // copies through their own records
         const bool c3 = P[0]->cosets3;
         if (c3 && (rc = pk_ensure_cosets3(c, pk0))) return rc;
+        if (int r = instance_columns(c, st, pk0, P)) return r;
 
         // -- 1. advice
         const bool many = advice_staged(lay);
@@ -103,6 +126,7 @@ struct BatchRun {
             Fifo f{{0, 1, 2}, {}, nullptr};
             std::vector<Col> cols;
             std::vector<Forms> fm;
+            with_instances(P, fm);  // (with the first pass's transforms)
             auto go = [&]() {
                 cq.begin(f, cols, ZK_BASIS_LAGRANGE);
                 transforms(fm);
@@ -162,8 +186,10 @@ struct BatchRun {
             }
         }
         cq.flush(lb);
-        if (pipe)
+        if (pipe) {
             for (uint32_t q = 0; q < B; q++) due.push_back(Forms{P[q]->pk->adv_val[0], P[q]->pk->adv_poly[0], P[q]->pk->adv_coset[0]});
+            with_instances(P, due);
+        }
         transforms(due);
         due.clear();
         {

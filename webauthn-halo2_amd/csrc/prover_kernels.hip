@@ -799,6 +799,17 @@ void launch_scatter_rows(const RowEntry* d_entries, uint32_t count, hipStream_t 
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(count), dim3(64), 0, st, d_entries);
 }
 
+// ---- instance columns of several lanes: one launch, rows x lanes; every row of every column is written ----
+__global__ __launch_bounds__(256) void instance_columns_kernel(const InstEntry* __restrict__ e, const Fr* __restrict__ vals, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const InstEntry t = e[blockIdx.y];
+    fe_store(t.dst + i, i < t.len ? fe_load(vals + t.off + i) : Fr::zero());  // (the Montgomery image of zero is zero)
+}
+void launch_instance_columns(const InstEntry* d_entries, const Fr* d_vals, uint32_t lanes, uint32_t n, hipStream_t st) {
+    hipLaunchKernelGGL(instance_columns_kernel, dim3((n + 255) / 256, lanes), dim3(256), 0, st, d_entries, d_vals, n);
+}
+
 // ---------------------------------------------------------- Kate division ---
 // q = (p - p(z)) / (X - z):  q[i-1] = p[i] + z*q[i], q[n-1] = 0.  Chunks of KD_L
 // coefficients per thread: (1) chunk value c_t = sum_i p[tL+i] z^i, (2) suffix Horner

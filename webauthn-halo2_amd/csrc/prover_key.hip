@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <unordered_map>
 #include <vector>
 
 #include "pk.h"
@@ -54,6 +55,8 @@ static void bb_destroy(BatchBufs* bb) {
     if (bb->ev_scratch) hipFree(bb->ev_scratch);
     if (bb->ev_out) hipFree(bb->ev_out);
     if (bb->tail_host) hipHostFree(bb->tail_host);
+    if (bb->inst_host) hipHostFree(bb->inst_host);
+    if (bb->inst_dev) hipFree(bb->inst_dev);
     delete bb;
 }
 
@@ -301,12 +304,79 @@ int pk_instance_values(const Layout& lay, const uint64_t* instance_mont, size_t 
     return ZK_OK;
 }
 
+int pk_instance_lists(const Layout& lay, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances,
+                      std::vector<std::vector<Fr>>* out, std::vector<uint32_t>* same_as) {
+    out->assign(count, {});
+    if (same_as) {
+        same_as->resize(count);
+        for (size_t j = 0; j < count; j++) (*same_as)[j] = (uint32_t)j;
+    }
+    if (!n_instances) return lay.n_inst ? ZK_EINVAL : ZK_OK;
+    std::unordered_map<const uint64_t*, uint32_t> first;  // a list's address -> the first list of the call that has it
+    for (size_t j = 0; j < count; j++) {
+        const uint64_t* src = n_instances[j] && instances_mont ? instances_mont[j] : nullptr;
+        if (same_as && src) {
+            auto it = first.find(src);
+            if (it != first.end() && n_instances[it->second] == n_instances[j]) {
+                (*same_as)[j] = it->second;
+                continue;
+            }
+            first.emplace(src, (uint32_t)j);
+        }
+        if (int r = pk_instance_values(lay, src, n_instances[j], &(*out)[j])) return r;
+    }
+    return ZK_OK;
+}
+
 int pk_instance_upload(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<Fr>& vals) {
     if (!pk->inst_val) return vals.empty() ? ZK_OK : ZK_EINVAL;
     if (vals.size() > pk->lay.usable) return ZK_EINVAL;
     if (c->audit.on) c->audit.op(st, {}, {pk->inst_val}, "instance column into the workspace");
     HIPCHK(c, hipMemsetAsync(pk->inst_val, 0, (size_t)pk->lay.n * sizeof(Fr), st));  // (the Montgomery image of zero is zero)
     if (!vals.empty()) HIPCHK(c, hipMemcpyAsync(pk->inst_val, vals.data(), vals.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
+    return ZK_OK;
+}
+
+int pk_instance_upload_lanes(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<zk_pk_rec*>& ws, const std::vector<const std::vector<Fr>*>& lists) {
+    BatchBufs* bb = pk->bb;
+    const uint32_t B = (uint32_t)ws.size(), n = pk->lay.n;
+    if (!bb || bb->cap < B || lists.size() != B) return ZK_EINTERNAL;
+    size_t total = 0;
+    for (uint32_t q = 0; q < B; q++) {
+        if (!ws[q]->inst_val || lists[q]->size() > pk->lay.usable) return ZK_EINVAL;
+        total += lists[q]->size();
+    }
+    const size_t head = (size_t)bb->cap * sizeof(InstEntry);  // (a multiple of 16 bytes: the values behind it stay aligned)
+    if (!bb->inst_host || bb->inst_vals < total) {
+        aud_sync(c, st);  // (an earlier call's upload has long been consumed; the buffers are idle)
+        if (bb->inst_host) hipHostFree(bb->inst_host);
+        if (bb->inst_dev) hipFree(bb->inst_dev);
+        bb->inst_host = bb->inst_dev = nullptr;
+        bb->inst_vals = 0;
+        const size_t want = std::max<size_t>(total, 64);
+        if (hipHostMalloc(&bb->inst_host, head + want * sizeof(Fr)) != hipSuccess || hipMalloc(&bb->inst_dev, head + want * sizeof(Fr)) != hipSuccess)
+            return ZK_ENOMEM;  // (what was allocated is freed with the key)
+        bb->inst_vals = want;
+    }
+    if (c->audit.on) c->audit.host_write(bb->inst_host, "instance columns: the host fills the staging");
+    InstEntry* e = (InstEntry*)bb->inst_host;
+    Fr* hv = (Fr*)((uint8_t*)bb->inst_host + head);
+    uint32_t off = 0;
+    for (uint32_t q = 0; q < B; q++) {
+        const uint32_t len = (uint32_t)lists[q]->size();
+        e[q] = InstEntry{ws[q]->inst_val, off, len};
+        if (len) memcpy(hv + off, lists[q]->data(), (size_t)len * sizeof(Fr));
+        off += len;
+    }
+    if (c->audit.on) {
+        c->audit.op(st, {bb->inst_host}, {bb->inst_dev}, "instance columns: upload of the staging");
+        std::vector<const void*> rd{bb->inst_dev}, wr;
+        for (zk_pk_rec* m : ws) wr.push_back(m->inst_val);
+        c->audit.op_v(st, rd.data(), rd.size(), wr.data(), wr.size(), "instance columns: one launch over the lanes");
+    }
+    HIPCHK(c, hipMemcpyAsync(bb->inst_dev, bb->inst_host, head + (size_t)total * sizeof(Fr), hipMemcpyHostToDevice, st));
+    launch_instance_columns((const InstEntry*)bb->inst_dev, (const Fr*)((const uint8_t*)bb->inst_dev + head), B, n, st);
+    HIPCHK(c, hipGetLastError());
     return ZK_OK;
 }
 

@@ -26,6 +26,11 @@
 //                this list by rotation in order of first appearance, SHPLONK by rotation set: Prover::gwc_stage1 / shplonk_stage1/2
 //                as they stand, on the longer list
 //
+// With public inputs (zk_prove_multi_public; restated by tests/multi_public_ref.py) the rule gains: behind transcript_repr, for c:
+// every value of circuit c's instance list as common_scalar (absorbed, not written; neither N nor the lengths are hashed) — ALL
+// circuits' instances before any advice commitment, halo2's loop over `instances` at the top of create_proof.  The columns draw
+// nothing; circuit c's grand product reads c's column and quotient pass c its coset forms; nothing of them is committed or opened.
+//
 // The schedule is BatchRun's: circuit c works in the key's member record c - 1 (zk_pk_rec::members, shared with zk_prove_batch),
 // the same commitment of all circuits goes through merged MSM passes, the transforms are batched, all lookups share one set of
 // permutation launches, all grand products one scan, all opened values one evaluation launch.  What differs: every point goes to
@@ -90,11 +95,20 @@ struct MultiRun {
         using Forms = Prover::Forms;
         using Q = Prover::Q;
         const uint32_t bf = BLINDING_FACTORS, usable = lay.usable;
-        // transcript_repr is hashed once: circuit 0's begin() writes it to the proof's transcript, the others' to their scratch
-        for (Prover* p : P)
+        // transcript_repr is hashed once: circuit 0's begin() writes it to the proof's transcript, the others' to their scratch.
+        // The instance lists (zk_prove_multi_public) are absorbed HERE, once: all circuits' values in circuit order behind
+        // transcript_repr and before any advice commitment (halo2's loop over `instances` at the top of create_proof); no begin()
+        // absorbs its own, so the scratch transcripts never see a list and nothing is hashed twice
+        for (Prover* p : P) {
+            p->absorb_instance = false;
             if (p->begin()) return p->rc;
+        }
+        for (Prover* p : P)
+            if (p->instance)
+                for (const Fr& v : *p->instance) tr->common_scalar(v);  // (neither N nor the lengths are hashed)
         const bool c3 = P[0]->cosets3;  // (one key, one context, one option: every begin() took the same decision)
         if (c3 && (rc = pk_ensure_cosets3(c, pk0))) return rc;
+        if (int r = instance_columns(c, st, pk0, P)) return r;
 
         // -- 1. advice of every circuit
         const bool many = advice_staged(lay);
@@ -121,6 +135,7 @@ struct MultiRun {
             Fifo f{{0, 1, 2}, {}, nullptr};
             std::vector<Col> cols;
             std::vector<Forms> fm;
+            with_instances(P, fm);  // (with the first pass's transforms)
             auto go = [&]() {
                 cq.begin(f, cols, ZK_BASIS_LAGRANGE);
                 transforms(fm);
@@ -178,8 +193,10 @@ struct MultiRun {
             }
         }
         cq.flush(lb);
-        if (pipe)
+        if (pipe) {
             for (uint32_t q = 0; q < B; q++) due.push_back(Forms{P[q]->pk->adv_val[0], P[q]->pk->adv_poly[0], P[q]->pk->adv_coset[0]});
+            with_instances(P, due);
+        }
         transforms(due);
         due.clear();
         {

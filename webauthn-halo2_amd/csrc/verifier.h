@@ -228,11 +228,59 @@ inline bool instance_eval(const Layout& lay, const Fr* inst, size_t n_inst, cons
     return true;
 }
 
+// the instance lists of one proof (Montgomery values, each at most lay.usable: the caller's check).  ONE list per circuit, in
+// circuit order (pl.nc of them) — or exactly one list for the whole proof, the form the single-list prepare() at the end of this file passes on.  All
+// of them are absorbed behind transcript_repr in list order, before any commitment (neither their number nor their lengths are
+// hashed); circuit c's permutation terms use the evaluation of list c (of the one list, where there is one)
+struct InstanceList {
+    const Fr* vals;
+    size_t n;
+};
+// inst(x) of every list computed elsewhere (zk_instance_eval's kernel, verify.hip): x[i] of list i, and on_domain[i] != 0 where x is
+// one of that list's w^j — the case in which instance_eval returns false, and so does prepare
+struct InstanceEvals {
+    const Fr* x;
+    const uint8_t* on_domain;
+};
+
+// the transcript of a proof from its first word to the challenge x (the points' bytes only: no evaluation is read)
+inline void absorb_to_x(const Layout& lay, const Fr& transcript_repr, uint32_t nc, const G1Affine* pts, const InstanceList* lists, size_t n_lists,
+                        Transcript* tr, Challenges* ch, uint32_t* np_out) {
+    tr->common_scalar(transcript_repr);
+    for (size_t l = 0; l < n_lists; l++)
+        for (size_t i = 0; i < lists[l].n; i++) tr->common_scalar(lists[l].vals[i]);  // (the counts are not hashed)
+    uint32_t np = 0;
+    auto absorb_points = [&](uint32_t n) {
+        for (uint32_t i = 0; i < n; i++) tr->common_point(pts[np++]);
+    };
+    absorb_points(nc * lay.n_adv);
+    ch->theta = tr->squeeze();
+    absorb_points(nc * 2 * lay.n_lookups);
+    ch->beta = tr->squeeze();
+    ch->gamma = tr->squeeze();
+    absorb_points(nc * (lay.n_chunks + lay.n_lookups) + 1);
+    ch->y = tr->squeeze();
+    absorb_points(lay.n_h);
+    ch->x = tr->squeeze();
+    *np_out = np;
+}
+// the challenge x of a proof alone: what a caller needs to have inst(x) computed elsewhere before it calls prepare_lists()
+inline Fr challenge_x(const Layout& lay, const Fr& transcript_repr, const ProofLayout& pl, const G1Affine* pts, const InstanceList* lists,
+                      size_t n_lists) {
+    EvmTranscript evm;
+    Blake2bTranscript b2;
+    Challenges ch;
+    uint32_t np;
+    absorb_to_x(lay, transcript_repr, pl.nc, pts, lists, n_lists, pl.evm ? (Transcript*)&evm : (Transcript*)&b2, &ch, &np);
+    return ch.x;
+}
+
 // false: the proof is rejected before the pairing (non-canonical scalar, an inverse of zero).  Otherwise `out` holds the two
-// term lists of the KZG check.  proof.len == pl.len is the caller's check.  inst / n_inst: the instance values of a key with the
-// column (Montgomery, at most lay.usable: the caller's check), absorbed behind transcript_repr.
-inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLayout& pl, const uint8_t* proof, const G1Affine* pts,
-                    Prepared* out, const Fr* inst = nullptr, size_t n_inst = 0) {
+// term lists of the KZG check.  proof.len == pl.len is the caller's check.  lists / n_lists: see InstanceList (n_lists is 0, 1 or
+// pl.nc).  given: the lists' inst(x) from elsewhere (n_lists of them), or null: computed here by instance_eval — the same term lists
+inline bool prepare_lists(const Layout& lay, const Fr& transcript_repr, const ProofLayout& pl, const uint8_t* proof, const G1Affine* pts,
+                          Prepared* out, const InstanceList* lists, size_t n_lists, const InstanceEvals* given = nullptr) {
+    if (n_lists > 1 && n_lists != pl.nc) return false;
     EvmTranscript evm;
     Blake2bTranscript b2;
     Transcript* tr = pl.evm ? (Transcript*)&evm : (Transcript*)&b2;
@@ -240,21 +288,8 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     const PointIdx P = point_idx(lay, nc);
     const EvalIdx E = eval_idx(lay, nc);
     Challenges& ch = out->ch;
-    tr->common_scalar(transcript_repr);
-    for (size_t i = 0; i < n_inst; i++) tr->common_scalar(inst[i]);  // (the count is not hashed)
     uint32_t np = 0;
-    auto absorb_points = [&](uint32_t n) {
-        for (uint32_t i = 0; i < n; i++) tr->common_point(pts[np++]);
-    };
-    absorb_points(nc * lay.n_adv);
-    ch.theta = tr->squeeze();
-    absorb_points(nc * 2 * lay.n_lookups);
-    ch.beta = tr->squeeze();
-    ch.gamma = tr->squeeze();
-    absorb_points(nc * (lay.n_chunks + lay.n_lookups) + 1);
-    ch.y = tr->squeeze();
-    absorb_points(lay.n_h);
-    ch.x = tr->squeeze();
+    absorb_to_x(lay, transcript_repr, nc, pts, lists, n_lists, tr, &ch, &np);
     std::vector<Fr> ev(E.count + 1);
     const size_t ev_off = (size_t)P.opening * pl.point_size;
     for (uint32_t i = 0; i < E.count; i++) {
@@ -285,12 +320,21 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     for (int i = 1; i <= (int)BLINDING_FACTORS; i++) l_blind = fe_add(l_blind, L(-i));
     if (zero_div) return false;
     const Fr active = fe_sub(fe_sub(one, l_last), l_blind);
-    Fr inst_x = Fr::zero();
-    if (lay.n_inst && !instance_eval(lay, inst, n_inst, x, c, &inst_x)) return false;
+    std::vector<Fr> inst_xs(std::max<size_t>(n_lists, 1), Fr::zero());  // inst(x) per list
+    if (lay.n_inst)
+        for (size_t l = 0; l < n_lists; l++) {
+            if (given) {
+                if (given->on_domain[l]) return false;
+                inst_xs[l] = given->x[l];
+            } else if (!instance_eval(lay, lists[l].vals, lists[l].n, x, c, &inst_xs[l])) {
+                return false;
+            }
+        }
     auto fix = [&](uint32_t f) { return ev[E.fix + f]; };
     const Fr delta = fr_delta_host();
     std::vector<Fr> exprs;  // the nc x T expressions of the y-Horner chain: circuit 0's, then circuit 1's, ...
     for (uint32_t circ = 0; circ < nc; circ++) {
+        const Fr inst_x = inst_xs[n_lists > 1 ? circ : 0];
         auto adv = [&](uint32_t col, int rot) {
             for (uint32_t i = 0; i < lay.advice_queries.size(); i++)
                 if (lay.advice_queries[i].first == col && lay.advice_queries[i].second == rot) return ev[E.adv_of(circ) + i];
@@ -469,6 +513,13 @@ inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLay
     merge_terms(A);
     merge_terms(B);
     return true;
+}
+
+// the single-list form: one list for the whole proof (zk_verify_public; no list: the forms without instances)
+inline bool prepare(const Layout& lay, const Fr& transcript_repr, const ProofLayout& pl, const uint8_t* proof, const G1Affine* pts,
+                    Prepared* out, const Fr* inst = nullptr, size_t n_inst = 0) {
+    const InstanceList one{inst, n_inst};
+    return prepare_lists(lay, transcript_repr, pl, proof, pts, out, &one, lay.n_inst ? (size_t)1 : (n_inst ? (size_t)1 : (size_t)0));
 }
 
 }  // namespace verifier

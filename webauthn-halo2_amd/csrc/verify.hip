@@ -14,6 +14,10 @@
 //      every proof's bytes (the same kernel over the accumulators), ONE host pairing (pairing.h); if it fails, the set is
 //      halved and each half folded and paired again, down to single proofs, so every verdict is the proof's own.
 // zk_verify is the batch of one: the same path, without a fold.
+// Public inputs: every proof (zk_verify_batch_public) or circuit (zk_verify_multi_public) has its instance list; step 2 absorbs them
+// and needs inst(x) per list — on the host inside verifier.h, or (zk_verify_instance_eval_mode 2) every transcript runs to x, ONE
+// launch of instance_eval_kernel evaluates every list of the call, and the term lists take those values.  zk_instance_eval is
+// that kernel alone.  The fold weights then hash every proof's list beside its bytes.
 #include <string.h>
 
 #include <algorithm>
@@ -139,6 +143,135 @@ __global__ __launch_bounds__(64) void verify_msm_kernel(const Fr* __restrict__ s
     if (lane == 0) g1x_store(out + blockIdx.x, sh[0]);
 }
 
+// ---- inst(x) = sum_{i<m} v_i l_i(x), l_i(x) = w^i (x^n - 1) / (n (x - w^i)), for many (list, point) pairs in one launch ----
+// Stage 1, grid (pairs, slices): a workgroup is one 64-lane wave and owns slice `blockIdx.y` of pair `blockIdx.x`: IE_SLICE values,
+// taken in passes of IE_SPAN = IE_WG x IE_LANE.  In a pass lane l owns the IE_LANE contiguous indices from base + l IE_LANE: w^i starts
+// at one power (square-and-multiply) and advances by one product per element; the denominators x - w^i are inverted by Montgomery's
+// trick in groups of IE_GROUP that never leave the lane (IE_GROUP prefix products per lane, ONE field inversion per group, the powers
+// walked back by w^-1 rather than kept).  A zero denominator sets the pair's flag and is replaced by one (the sum is then
+// discarded).  The lanes' sums are added through LDS; the slice's sum and flag go to part / pflag.
+// Stage 2, one wave per pair: adds the slices' sums, multiplies by (x^n - 1) / n and writes the value — zero with the flag set where
+// x is one of the list's w^i.  Field addition is exact and every value is a canonical Montgomery image, so the order of the
+// additions does not show in the bytes: they are verifier::instance_eval's.
+// Registers against occupancy: the compiler reports 110 VGPRs and keeps the IE_GROUP prefix products in 272 bytes of scratch per
+// lane (four waves per SIMD); a longer group would trade more of either for fewer inversions.  One wave per workgroup needs no more
+// occupancy than that: the lists are short (9 values at the server's shape: a single lane works) or long enough to fill the chip
+// with slices (2^19 values: 256 workgroups).  LDS: 64 x 32 B per
+// workgroup, read and written as whole elements per lane (ds_*_b128 pairs): no bank concern at this size.
+constexpr uint32_t IE_GROUP = 8, IE_LANE = 16, IE_WG = 64, IE_SPAN = IE_WG * IE_LANE, IE_SLICE = 2 * IE_SPAN;
+struct IePair {
+    uint32_t off, len;  // the list: vals[off .. off + len)
+};
+
+__device__ __forceinline__ Fr ie_pow(Fr a, uint32_t e) {
+    Fr acc = Fr::one();
+    while (e) {
+        if (e & 1) acc = fe_mul(acc, a);
+        a = fe_sqr(a);
+        e >>= 1;
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(64) void instance_eval_kernel(const Fr* __restrict__ vals, const IePair* __restrict__ pairs, const Fr* __restrict__ xs,
+                                                           Fr omega, Fr omega_inv, uint32_t slices_max, Fr* __restrict__ part,
+                                                           uint8_t* __restrict__ pflag) {
+    __shared__ Fr sh[IE_WG];
+    __shared__ uint32_t shf[IE_WG];
+    const uint32_t j = blockIdx.x, slice = blockIdx.y, lane = threadIdx.x;
+    const IePair pr = pairs[j];
+    const uint64_t first = (uint64_t)slice * IE_SLICE;
+    if (first >= pr.len) return;  // (the whole workgroup: no barrier has been reached; stage 2 reads the list's own slices only)
+    const uint32_t end = (uint32_t)(first + IE_SLICE < pr.len ? first + IE_SLICE : pr.len);
+    const Fr x = fe_load(xs + j);
+    const Fr one = Fr::one();
+    Fr acc = Fr::zero();
+    uint32_t bad = 0;
+    for (uint32_t base = (uint32_t)first + lane * IE_LANE; base < end; base += IE_SPAN) {
+        Fr w = ie_pow(omega, base);
+        const uint32_t stop = end < base + IE_LANE ? end : base + IE_LANE;
+        for (uint32_t g0 = base; g0 < stop; g0 += IE_GROUP) {
+            const uint32_t cnt = stop - g0 < IE_GROUP ? stop - g0 : IE_GROUP;
+            Fr pre[IE_GROUP];
+            Fr run = one;
+#pragma unroll
+            for (uint32_t t = 0; t < IE_GROUP; t++)
+                if (t < cnt) {
+                    Fr d = fe_sub(x, w);
+                    if (d.is_zero()) {
+                        bad = 1;
+                        d = one;
+                    }
+                    pre[t] = run;
+                    run = fe_mul(run, d);
+                    w = fe_mul(w, omega);
+                }
+            Fr inv = fe_inv(run);  // (never zero: the zero denominators were replaced)
+            Fr wb = w;             // w^(g0 + cnt)
+#pragma unroll
+            for (uint32_t u = 0; u < IE_GROUP; u++) {
+                const uint32_t t = IE_GROUP - 1 - u;
+                if (t < cnt) {
+                    wb = fe_mul(wb, omega_inv);
+                    Fr d = fe_sub(x, wb);
+                    if (d.is_zero()) d = one;
+                    const Fr di = fe_mul(inv, pre[t]);
+                    inv = fe_mul(inv, d);
+                    acc = fe_add(acc, fe_mul(fe_load(vals + pr.off + g0 + t), fe_mul(wb, di)));
+                }
+            }
+        }
+    }
+    sh[lane] = acc;
+    shf[lane] = bad;
+    __syncthreads();
+    for (uint32_t s = IE_WG / 2; s > 0; s >>= 1) {
+        if (lane < s) {
+            sh[lane] = fe_add(sh[lane], sh[lane + s]);
+            shf[lane] |= shf[lane + s];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        const size_t o = (size_t)j * slices_max + slice;
+        fe_store(part + o, sh[0]);
+        pflag[o] = (uint8_t)shf[0];
+    }
+}
+
+__global__ __launch_bounds__(64) void instance_eval_finish_kernel(const IePair* __restrict__ pairs, const Fr* __restrict__ xs, const Fr* __restrict__ part,
+                                                                  const uint8_t* __restrict__ pflag, uint32_t slices_max, uint32_t k, Fr n_inv,
+                                                                  Fr* __restrict__ out, uint8_t* __restrict__ on_domain) {
+    __shared__ Fr sh[IE_WG];
+    __shared__ uint32_t shf[IE_WG];
+    const uint32_t j = blockIdx.x, lane = threadIdx.x;
+    const uint32_t ns = (pairs[j].len + IE_SLICE - 1) / IE_SLICE;  // <= slices_max
+    Fr acc = Fr::zero();
+    uint32_t bad = 0;
+    for (uint32_t s = lane; s < ns; s += IE_WG) {
+        const size_t o = (size_t)j * slices_max + s;
+        acc = fe_add(acc, fe_load(part + o));
+        bad |= pflag[o];
+    }
+    sh[lane] = acc;
+    shf[lane] = bad;
+    __syncthreads();
+    for (uint32_t s = IE_WG / 2; s > 0; s >>= 1) {
+        if (lane < s) {
+            sh[lane] = fe_add(sh[lane], sh[lane + s]);
+            shf[lane] |= shf[lane + s];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        Fr xn = fe_load(xs + j);
+        for (uint32_t i = 0; i < k; i++) xn = fe_sqr(xn);
+        const Fr c = fe_mul(fe_sub(xn, Fr::one()), n_inv);
+        fe_store(out + j, shf[0] ? Fr::zero() : fe_mul(sh[0], c));
+        on_domain[j] = (uint8_t)(shf[0] ? 1 : 0);
+    }
+}
+
 Words8 fq_sqrt_exp_words() {  // (p + 1) / 4
     Words8 e;
     uint64_t carry = 1;
@@ -224,11 +357,15 @@ struct VerifyWs {
     void *bytes = nullptr, *off = nullptr, *pts = nullptr, *flag = nullptr, *scal = nullptr, *idx = nullptr, *seg = nullptr, *out = nullptr,
          *fold = nullptr;
     size_t c_bytes = 0, c_off = 0, c_pts = 0, c_flag = 0, c_scal = 0, c_idx = 0, c_seg = 0, c_out = 0, c_fold = 0;
+    // instance_eval_device: the call's distinct lists, the pairs, their points, the slices' sums and flags, the results
+    void *ie_vals = nullptr, *ie_pairs = nullptr, *ie_x = nullptr, *ie_part = nullptr, *ie_pflag = nullptr, *ie_out = nullptr, *ie_flag = nullptr;
+    size_t c_ie_vals = 0, c_ie_pairs = 0, c_ie_x = 0, c_ie_part = 0, c_ie_pflag = 0, c_ie_out = 0, c_ie_flag = 0;
 };
 
 void verify_ws_destroy(VerifyWs* w) {
     if (!w) return;
-    for (void* p : {w->bytes, w->off, w->pts, w->flag, w->scal, w->idx, w->seg, w->out, w->fold})
+    for (void* p : {w->bytes, w->off, w->pts, w->flag, w->scal, w->idx, w->seg, w->out, w->fold, w->ie_vals, w->ie_pairs, w->ie_x, w->ie_part,
+                    w->ie_pflag, w->ie_out, w->ie_flag})
         if (p) hipFree(p);
     delete w;
 }
@@ -374,15 +511,77 @@ int settle(Job& J, const std::vector<uint32_t>& S, uint8_t* verdicts) {
     return settle(J, std::vector<uint32_t>(S.begin() + h, S.end()), verdicts);
 }
 
+// inst(x) of `count` (list, point) pairs on the device in one launch (+ the small second stage): lists[j] at xs[j] over the domain
+// of 2^k rows, every lists[j].n <= 2^k.  The call's DISTINCT lists — by address and length — are uploaded once.  out / on_domain:
+// host arrays of `count`.  Caller holds the context lock, device bound
+int instance_eval_device(zk_ctx* c, uint32_t k, size_t count, const verifier::InstanceList* lists, const Fr* xs, Fr* out, uint8_t* on_domain) {
+    if (!count) return ZK_OK;
+    if (k > 26 || count > 0x7fffffffu) return ZK_EINVAL;
+    if (!c->vws && !(c->vws = new (std::nothrow) VerifyWs())) return ZK_ENOMEM;
+    VerifyWs* w = c->vws;
+    std::vector<IePair> pairs(count);
+    std::vector<Fr> vals;
+    std::vector<std::pair<verifier::InstanceList, uint32_t>> seen;  // (a call has few distinct lists: one per proof or circuit)
+    size_t longest = 0;
+    for (size_t j = 0; j < count; j++) {
+        const verifier::InstanceList& l = lists[j];
+        if (l.n > ((size_t)1 << k) || (l.n && !l.vals)) return ZK_EINVAL;
+        longest = std::max(longest, l.n);
+        uint32_t off = 0;
+        bool have = l.n == 0;
+        for (size_t s = seen.size(); s-- > 0 && !have;)
+            if (seen[s].first.vals == l.vals && seen[s].first.n == l.n) {
+                off = seen[s].second;
+                have = true;
+            }
+        if (!have) {
+            if (vals.size() + l.n > 0xffffffffu) return ZK_EINVAL;
+            off = (uint32_t)vals.size();
+            vals.insert(vals.end(), l.vals, l.vals + l.n);
+            seen.push_back({l, off});
+        }
+        pairs[j] = IePair{off, (uint32_t)l.n};
+    }
+    const uint32_t slices_max = (uint32_t)std::max<size_t>(1, (longest + IE_SLICE - 1) / IE_SLICE);  // <= 2^26 / IE_SLICE: a grid's y extent
+    const size_t np = count * (size_t)slices_max;
+    int rc;
+    if ((rc = ws_grow(c, &w->ie_vals, &w->c_ie_vals, std::max<size_t>(vals.size(), 1) * sizeof(Fr))) ||
+        (rc = ws_grow(c, &w->ie_pairs, &w->c_ie_pairs, count * sizeof(IePair))) || (rc = ws_grow(c, &w->ie_x, &w->c_ie_x, count * sizeof(Fr))) ||
+        (rc = ws_grow(c, &w->ie_part, &w->c_ie_part, np * sizeof(Fr))) || (rc = ws_grow(c, &w->ie_pflag, &w->c_ie_pflag, np)) ||
+        (rc = ws_grow(c, &w->ie_out, &w->c_ie_out, count * sizeof(Fr))) || (rc = ws_grow(c, &w->ie_flag, &w->c_ie_flag, count)))
+        return rc;
+    if (c->audit.on) c->audit.op(c->stream, {}, {w->ie_vals, w->ie_pairs, w->ie_x}, "instance evaluation: lists, pairs and points upload");
+    if (!vals.empty()) HIPCHK(c, hipMemcpyAsync(w->ie_vals, vals.data(), vals.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->ie_pairs, pairs.data(), count * sizeof(IePair), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->ie_x, xs, count * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    const Fr omega = fr_omega(k), omega_inv = fe_inv_fast(omega), n_inv = fe_inv_fast(fr_from_u64((uint64_t)1 << k));
+    if (c->audit.on) c->audit.op(c->stream, {w->ie_vals, w->ie_pairs, w->ie_x}, {w->ie_part, w->ie_pflag}, "instance evaluation (instance_eval_kernel)");
+    hipLaunchKernelGGL(instance_eval_kernel, dim3((uint32_t)count, slices_max), dim3(IE_WG), 0, c->stream, (const Fr*)w->ie_vals, (const IePair*)w->ie_pairs,
+                       (const Fr*)w->ie_x, omega, omega_inv, slices_max, (Fr*)w->ie_part, (uint8_t*)w->ie_pflag);
+    HIPCHK(c, hipGetLastError());
+    if (c->audit.on)
+        c->audit.op(c->stream, {w->ie_pairs, w->ie_x, w->ie_part, w->ie_pflag}, {w->ie_out, w->ie_flag}, "instance evaluation: second stage");
+    hipLaunchKernelGGL(instance_eval_finish_kernel, dim3((uint32_t)count), dim3(IE_WG), 0, c->stream, (const IePair*)w->ie_pairs, (const Fr*)w->ie_x,
+                       (const Fr*)w->ie_part, (const uint8_t*)w->ie_pflag, slices_max, k, n_inv, (Fr*)w->ie_out, (uint8_t*)w->ie_flag);
+    HIPCHK(c, hipGetLastError());
+    if (c->audit.on) c->audit.op(c->stream, {w->ie_out, w->ie_flag}, {}, "instance evaluation: results download");
+    HIPCHK(c, hipMemcpyAsync(out, w->ie_out, count * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(on_domain, w->ie_flag, count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, aud_sync(c, c->stream));  // (the host vectors above are pageable and go out of scope)
+    return ZK_OK;
+}
+
 }  // namespace
 
 // `batch` proofs of one key, each over `n_circuits` circuits (1: the proofs of zk_prove; more: those of zk_prove_multi — a longer
 // proof read in the order verifier.h states, the same four steps)
-// `with_instances`: zk_verify_public — the caller's instance values (none on a key without the column); the other entry points
-// carry none and refuse a key that has the column (halo2's InvalidInstances)
+// `with_instances`: the _public forms — batch x n_circuits instance lists, proof-major (zk_verify_public: one; zk_verify_batch_public:
+// one per proof; zk_verify_multi_public: one per circuit; none on a key without the column); the other entry points carry none and
+// refuse a key that has the column (halo2's InvalidInstances).  `may_device`: the form follows zk_verify_instance_eval_mode (the lone
+// zk_verify_public does not: it evaluates inst(x) on the host as it always did)
 static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, int transcript, int scheme, const uint8_t* const* proofs,
-                         const size_t* lens, uint8_t* verdicts, bool with_instances = false, const uint64_t* instance_mont = nullptr,
-                         size_t n_instance = 0) {
+                         const size_t* lens, uint8_t* verdicts, bool with_instances = false, const uint64_t* const* instances_mont = nullptr,
+                         const size_t* n_instances = nullptr, bool may_device = false) {
     if (!c || !proofs || !lens || !verdicts || batch == 0 || batch > ZK_VERIFY_BATCH_MAX) return ZK_EINVAL;
     if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
     if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
@@ -394,9 +593,16 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
     if (pk->lay.n_inst && !with_instances) return ZK_EINVAL;
-    std::vector<Fr> instance;
+    std::vector<std::vector<Fr>> instance;  // list j * n_circuits + c: proof j, circuit c (a list the caller passes several times: once)
+    std::vector<uint32_t> same_as;
     if (with_instances)
-        if (int r = pk_instance_values(pk->lay, instance_mont, n_instance, &instance)) return r;
+        if (int r = pk_instance_lists(pk->lay, batch * n_circuits, instances_mont, n_instances, &instance, &same_as)) return r;
+    // the lists as verifier.h takes them: per proof n_circuits of them on a key with the column, none otherwise
+    const size_t per_proof = pk->lay.n_inst ? n_circuits : 0;
+    std::vector<verifier::InstanceList> ilists(batch * per_proof);
+    for (size_t i = 0; i < ilists.size(); i++) ilists[i] = verifier::InstanceList{instance[same_as[i]].data(), instance[same_as[i]].size()};
+    // where inst(x) is evaluated: auto is the host (the device path has not been measured against it)
+    const bool on_device = may_device && per_proof && c->opt_verify_inst_eval == 2;
     if (!pk->verify_only && pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // a full key under a replaced SRS: its vk is stale
     if (c->srs_k < 0 || !c->g2_valid) return ZK_ESTATE;  // g[0], g2 and s_g2 come from the resident SRS
     int rc = ctx_bind(c);
@@ -441,14 +647,40 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
         HIPCHK(c, hipMemcpyAsync(flag.data(), w->flag, npts, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, aud_sync(c, c->stream));
 
-        // 2. transcripts and term lists, per proof on the host
+        // 2. transcripts and term lists, per proof on the host.  With inst(x) on the device: every proof's transcript runs to x
+        // first, ONE launch evaluates every (list, x) pair of the batch, and the term lists take those values
         std::vector<verifier::Prepared> prep(cand.size());
         std::vector<uint8_t> good(cand.size(), 0);
+        std::vector<Fr> ie_out(on_device ? cand.size() * per_proof : 0);
+        std::vector<uint8_t> ie_flag(ie_out.size(), 0);
+        if (on_device) {
+            std::vector<Fr> xs(ie_out.size(), Fr::zero());
+            std::vector<verifier::InstanceList> pl_lists(ie_out.size());
+            parallel_for(cand.size(), [&](size_t t) {
+                try {
+                    for (size_t i = 0; i < per_proof; i++) pl_lists[t * per_proof + i] = ilists[cand[t] * per_proof + i];
+                    for (size_t i = 0; i < np; i++)
+                        if (!flag[t * np + i]) return;  // (rejected below; its pairs are evaluated at zero and never read)
+                    const Fr x = verifier::challenge_x(lay, pk->transcript_repr, pl, pts.data() + t * np, ilists.data() + cand[t] * per_proof, per_proof);
+                    for (size_t i = 0; i < per_proof; i++) xs[t * per_proof + i] = x;
+                } catch (...) {
+                    good[t] = 2;
+                }
+            });
+            for (uint8_t g : good)
+                if (g == 2) return ZK_ENOMEM;
+            if ((rc = instance_eval_device(c, lay.k, ie_out.size(), pl_lists.data(), xs.data(), ie_out.data(), ie_flag.data()))) return rc;
+        }
         parallel_for(cand.size(), [&](size_t t) {
             try {
                 for (size_t i = 0; i < np; i++)
                     if (!flag[t * np + i]) return;
-                good[t] = verifier::prepare(lay, pk->transcript_repr, pl, proofs[cand[t]], pts.data() + t * np, &prep[t], instance.data(), instance.size()) ? 1 : 0;
+                verifier::InstanceEvals given{nullptr, nullptr};
+                if (on_device) given = verifier::InstanceEvals{ie_out.data() + t * per_proof, ie_flag.data() + t * per_proof};
+                good[t] = verifier::prepare_lists(lay, pk->transcript_repr, pl, proofs[cand[t]], pts.data() + t * np, &prep[t],
+                                                  ilists.data() + cand[t] * per_proof, per_proof, on_device ? &given : nullptr)
+                              ? 1
+                              : 0;
             } catch (...) {
                 good[t] = 2;  // (allocation failure)
             }
@@ -502,6 +734,15 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
                     const uint64_t ln = lens[j];
                     hs.update((const uint8_t*)&ln, 8);
                     if (ln) hs.update(proofs[j], ln);
+                    // the statement is the proof AND its public inputs: every list, length first, beside the proof's bytes (the forms
+                    // without instances hash what they always hashed)
+                    if (with_instances)
+                        for (size_t i = 0; i < n_circuits; i++) {
+                            const std::vector<Fr>& l = instance[same_as[j * n_circuits + i]];
+                            const uint64_t m = l.size();
+                            hs.update((const uint8_t*)&m, 8);
+                            if (m) hs.update((const uint8_t*)l.data(), m * sizeof(Fr));
+                        }
                 }
                 uint8_t seed[64];
                 hs.finalize_copy(seed);
@@ -549,9 +790,71 @@ ZK_API(zk_verify_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, int transcript, 
 ZK_API(zk_verify_public, (zk_ctx* c, zk_pk h, int transcript, int scheme, const uint64_t* instance_mont, size_t n_instance, const uint8_t* proof, size_t len, int* ok), (c, h, transcript, scheme, instance_mont, n_instance, proof, len, ok)) {
     if (!ok) return ZK_EINVAL;
     uint8_t v = 0;
-    const int rc = verify_proofs(c, h, 1, 1, transcript, scheme, &proof, &len, &v, true, instance_mont, n_instance);
+    const int rc = verify_proofs(c, h, 1, 1, transcript, scheme, &proof, &len, &v, true, &instance_mont, &n_instance);
     if (rc == ZK_OK) *ok = v;
     return rc;
+}
+
+// zk_verify_batch with one instance list per proof: verdict j is zk_verify_public's of (proof j, list j)
+ZK_API(zk_verify_batch_public, (zk_ctx* c, zk_pk h, size_t batch, int transcript, int scheme, const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t* const* proofs, const size_t* lens, uint8_t* verdicts), (c, h, batch, transcript, scheme, instances_mont, n_instances, proofs, lens, verdicts)) {
+    return verify_proofs(c, h, batch, 1, transcript, scheme, proofs, lens, verdicts, true, instances_mont, n_instances, true);
+}
+
+// zk_verify_multi with one instance list per circuit (the multi rule: the lists are absorbed in circuit order behind
+// transcript_repr; circuit c's permutation terms use inst_c(x))
+ZK_API(zk_verify_multi_public, (zk_ctx* c, zk_pk h, size_t n_circuits, int transcript, int scheme, const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t* proof, size_t len, int* ok), (c, h, n_circuits, transcript, scheme, instances_mont, n_instances, proof, len, ok)) {
+    if (!ok || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
+    uint8_t v = 0;
+    const int rc = verify_proofs(c, h, 1, (uint32_t)n_circuits, transcript, scheme, &proof, &len, &v, true, instances_mont, n_instances, true);
+    if (rc == ZK_OK) *ok = v;
+    return rc;
+}
+
+ZK_API(zk_verify_instance_eval_mode, (zk_ctx* c, int mode), (c, mode)) {
+    if (!c || mode < 0 || mode > 2) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->opt_verify_inst_eval = (uint32_t)mode;
+    return ZK_OK;
+}
+
+// inst(x) of `count` (list, point) pairs on the device: no SRS, no key.  Outputs are untouched on error
+ZK_API(zk_instance_eval, (zk_ctx* c, uint32_t k, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances, const uint64_t* x_mont, uint64_t* out_mont, uint8_t* on_domain), (c, k, count, instances_mont, n_instances, x_mont, out_mont, on_domain)) {
+    if (!c || k > 26 || (count && (!n_instances || !x_mont || !out_mont || !on_domain))) return ZK_EINVAL;
+    if (!count) return ZK_OK;
+    auto below_modulus = [](const Fr& v) {
+        for (int i = 7; i >= 0; i--)
+            if (v.v[i] != FrParams::P[i]) return v.v[i] < FrParams::P[i];
+        return false;
+    };
+    std::vector<verifier::InstanceList> lists(count);
+    std::vector<Fr> xs(count);
+    memcpy(xs.data(), x_mont, count * sizeof(Fr));
+    for (size_t j = 0; j < count; j++) {
+        const size_t m = n_instances[j];
+        if (m > ((size_t)1 << k) || (m && (!instances_mont || !instances_mont[j]))) return ZK_EINVAL;
+        lists[j] = verifier::InstanceList{m ? reinterpret_cast<const Fr*>(instances_mont[j]) : nullptr, m};
+        if (!below_modulus(xs[j])) return ZK_EINVAL;
+    }
+    // every value a Montgomery image below the modulus; a list that several pairs share is looked at once
+    for (size_t j = 0; j < count; j++) {
+        bool seen = false;
+        for (size_t i = 0; i < j && !seen; i++) seen = lists[i].vals == lists[j].vals && lists[i].n >= lists[j].n;
+        if (seen) continue;
+        for (size_t i = 0; i < lists[j].n; i++)
+            if (!below_modulus(lists[j].vals[i])) return ZK_EINVAL;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    const uint64_t aud0 = c->audit.violations;
+    c->audit.base_of.clear();
+    std::vector<Fr> out(count);
+    std::vector<uint8_t> flags(count);
+    if ((rc = instance_eval_device(c, k, count, lists.data(), xs.data(), out.data(), flags.data()))) return rc;
+    if ((rc = aud_verdict(c, aud0, ZK_OK))) return rc;
+    memcpy(out_mont, out.data(), count * sizeof(Fr));
+    memcpy(on_domain, flags.data(), count);
+    return ZK_OK;
 }
 
 ZK_API(zk_verify, (zk_ctx* c, zk_pk h, int transcript, int scheme, const uint8_t* proof, size_t len, int* ok), (c, h, transcript, scheme, proof, len, ok)) {

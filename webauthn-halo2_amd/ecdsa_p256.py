@@ -521,28 +521,33 @@ def create_proof_from_advice(advice_columns, proving_key_path, degree, transcrip
 
 
 def create_proof_multi_from_advice(advice_sets, proving_key_path, degree, transcript=ZK_TRANSCRIPT_BLAKE2B, device=0, rng_seed=None,
-                                   check=False) -> bytes:
+                                   check=False, instances=None) -> bytes:
     """create_proof(&params, &pk, &[c_0 .. c_{N-1}], &[&[]; N], ..): ONE proof over the N = len(advice_sets) circuits whose
     host-synthesized advice columns are given (Engine.prove_multi: one transcript, one RNG stream, one quotient, one multi-open)
     — an extension: the reference proves one circuit per call.  advice_sets[c]: circuit c's columns as
     create_proof_from_advice takes them.  check=True: every circuit goes through Engine.witness_check first; WitnessError
-    carries the index of the first violated circuit in `.circuit`.  The verifier must expect the same N (verify_multi)."""
+    carries the index of the first violated circuit in `.circuit`.  The verifier must expect the same N (verify_multi).
+    instances: one list of public inputs (canonical integers) per circuit, for a key made with public=True -
+    Engine.prove_multi_public; None: no instances, which a key with the column refuses."""
     advice_sets = [list(a) for a in advice_sets]
     if not advice_sets or any(len(a) != len(advice_sets[0]) for a in advice_sets):
         raise ValueError("every circuit brings the key's number of advice columns")
+    if instances is not None and len(instances) != len(advice_sets):
+        raise ValueError("one instance list per circuit")
+    insts = None if instances is None else [_mont_limbs(l) for l in instances]
     per = len(advice_sets[0])
 
     def run(st, eng, pk, slots, cols, n):
         def prove(sets):
             if check:
                 for c, polys in enumerate(sets):
-                    counts, failures = eng.witness_check(pk, polys)
+                    counts, failures = eng.witness_check(pk, polys) if insts is None else eng.witness_check_public(pk, polys, insts[c])
                     if counts[0]:
                         err = WitnessError(counts, failures)
                         err.circuit = c
                         raise err
             seed = rng_seed if rng_seed is not None else os.urandom(32)
-            return eng.prove_multi(pk, sets, seed, transcript)
+            return eng.prove_multi(pk, sets, seed, transcript) if insts is None else eng.prove_multi_public(pk, sets, insts, seed, transcript)
 
         def take(c, sets):  # a set of request slots per circuit, nested so that each is handed back on every way out
             if c == len(advice_sets):
@@ -770,20 +775,27 @@ def verify_evm(degree: int, proof: bytes, verifying_key_path: str, device: int =
     return _verify(degree, proof, verifying_key_path, device, instances, ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
 
 
-def verify_batch(degree: int, proofs, verifying_key_path: str, evm: bool, device: int = 0):
+def verify_batch(degree: int, proofs, verifying_key_path: str, evm: bool, device: int = 0, instances=None):
     """Many proofs of one verifying key in one zk_verify_batch call: one verdict per proof, each what verify / verify_evm
-    says of it."""
-    eng, vk = _resident_vk(degree, verifying_key_path, device)
-    if evm:
-        return eng.verify_batch(vk, [bytes(p) for p in proofs], ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
-    return eng.verify_batch(vk, [bytes(p) for p in proofs], ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+    says of it.  instances: one list of public inputs (canonical integers) per proof, for the key of a circuit with public
+    inputs - zk_verify_batch_public; None: no instances."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device, instances is not None)
+    t, s = (ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC) if evm else (ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+    if instances is None:
+        return eng.verify_batch(vk, [bytes(p) for p in proofs], t, s)
+    return eng.verify_batch_public(vk, [bytes(p) for p in proofs], [_mont_limbs(l) for l in instances], t, s)
 
 
-def verify_multi(degree: int, proof: bytes, verifying_key_path: str, n: int, evm: bool, device: int = 0) -> bool:
+def verify_multi(degree: int, proof: bytes, verifying_key_path: str, n: int, evm: bool, device: int = 0, instances=None) -> bool:
     """verify_proof of ONE proof over n circuits (create_proof_multi_from_advice; halo2: n instance slices, snark-verifier:
     `Config::kzg().with_num_proof(n)`) under the reference's two pairings: evm = Keccak EvmTranscript + GWC, else Blake2b +
-    SHPLONK.  An extension: the reference verifies one circuit per proof.  A proof over another number of circuits is rejected."""
-    eng, vk = _resident_vk(degree, verifying_key_path, device)
-    if evm:
-        return eng.verify_multi(vk, n, bytes(proof), ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC)
-    return eng.verify_multi(vk, n, bytes(proof), ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+    SHPLONK.  An extension: the reference verifies one circuit per proof.  A proof over another number of circuits is rejected.
+    instances: one list of public inputs per circuit (n of them), for the key of a circuit with public inputs -
+    zk_verify_multi_public; None: no instances."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device, instances is not None)
+    t, s = (ZK_TRANSCRIPT_EVM, ZK_SCHEME_GWC) if evm else (ZK_TRANSCRIPT_BLAKE2B, ZK_SCHEME_SHPLONK)
+    if instances is None:
+        return eng.verify_multi(vk, n, bytes(proof), t, s)
+    if len(instances) != n:
+        raise ValueError("one instance list per circuit")
+    return eng.verify_multi_public(vk, bytes(proof), [_mont_limbs(l) for l in instances], t, s)

@@ -23,6 +23,7 @@ ZK_SERDE_PROCESSED, ZK_SERDE_RAW_BYTES, ZK_SERDE_RAW_BYTES_UNCHECKED = 0, 1, 2
 ZK_OPT_MSM_WINDOW, ZK_OPT_MSM_BATCH, ZK_OPT_NTT_MAX_RADIX_LOG2, ZK_OPT_GP_BATCH_INVERT, ZK_OPT_MSM_TAIL_STREAM = 1, 2, 3, 4, 5
 ZK_OPT_MSM_TAIL_MAIN_ABOVE, ZK_OPT_BATCH_PASS_COLUMNS, ZK_OPT_XFORM_STREAM, ZK_OPT_MSM_STREAM, ZK_OPT_MSM_T1, ZK_OPT_STREAM_AUDIT = 6, 7, 8, 9, 10, 11
 ZK_OPT_STREAM_PRIORITY, ZK_OPT_QUOTIENT_DOMAIN, ZK_OPT_ACTIVITY_HOLD = 12, 13, 14
+ZK_VERIFY_INSTANCE_EVAL_AUTO, ZK_VERIFY_INSTANCE_EVAL_HOST, ZK_VERIFY_INSTANCE_EVAL_DEVICE = 0, 1, 2
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
 ZK_PROVE_MULTI_MAX = 16
@@ -220,6 +221,16 @@ def load_library():
                             ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_verify_multi": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)],
                             ctypes.c_int),
+        "zk_prove_batch_public": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(u64p), ctypes.POINTER(sz),
+                                   ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_prove_multi_public": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(u64p), ctypes.POINTER(sz),
+                                   ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_verify_batch_public": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u64p), ctypes.POINTER(sz),
+                                    ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_verify_multi_public": ([vp, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u64p), ctypes.POINTER(sz),
+                                    ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        "zk_verify_instance_eval_mode": ([vp, ctypes.c_int], ctypes.c_int),
+        "zk_instance_eval": ([vp, u32, sz, ctypes.POINTER(u64p), ctypes.POINTER(sz), u64p, u64p, ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "zk_srs_write": ([vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_srs_read": ([vp, vp, sz, ctypes.c_int], ctypes.c_int),
         "zk_srs_set_g2": ([vp, u64p, u64p], ctypes.c_int),
@@ -264,7 +275,8 @@ def load_library():
         if fn is None:
             if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info", "zk_proof_size_multi",
                         "zk_prove_multi", "zk_verify_multi", "zk_prove_public", "zk_verify_public", "zk_witness_check_public",
-                        "zk_pk_num_instance_columns") and os.environ.get("ZKMI355_LIB"):
+                        "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
+                        "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -760,6 +772,111 @@ class Engine:
         self._chk(self.L.zk_prove_batch(self.ctx, pk, B, hs, na, b"".join(bytes(sd) for sd in seeds), transcript, scheme, buf, stride,
                                         ctypes.byref(ln)), "zk_prove_batch")
         return [buf.raw[j * stride:j * stride + ln.value] for j in range(B)]
+
+    @staticmethod
+    def _instance_lists_arg(lists, count):
+        """`count` instance lists (each (m, 4) uint64 Montgomery images, None or empty) -> (arrays kept alive, pointer array or None,
+        length array or None).  lists None: both NULL - every list empty, for a key without the column."""
+        if lists is None:
+            return [], None, None
+        if len(lists) != count:
+            raise ValueError("one instance list per proof / circuit")
+        arrs = [np.zeros((0, 4), dtype=np.uint64) if l is None else _arr(l, 4) for l in lists]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        ptrs = (u64p * count)(*[_p(a) if a.shape[0] else ctypes.cast(None, u64p) for a in arrs])
+        lens = (ctypes.c_size_t * count)(*[a.shape[0] for a in arrs])
+        return arrs, ptrs, lens
+
+    def prove_batch_public(self, pk, advice_sets, instance_lists, seeds, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
+        """zk_prove_batch_public: prove_batch with instance_lists[j] the public inputs of proof j (lists may differ in length; None
+        for a key without the column).  Proof j is byte-identical to prove_public(pk, advice_sets[j], instance_lists[j], seeds[j])."""
+        B = len(advice_sets)
+        if B == 0 or len(seeds) != B or any(len(sd) != 32 for sd in seeds):
+            raise ValueError("one 32-byte rng seed per proof")
+        na = len(advice_sets[0])
+        if any(len(a) != na for a in advice_sets):
+            raise ValueError("every proof of a batch has the key's number of advice columns")
+        hs = (ctypes.c_uint64 * (B * na))(*[p.h for a in advice_sets for p in a])
+        keep, iptrs, ilens = self._instance_lists_arg(instance_lists, B)
+        ln = ctypes.c_size_t()
+        self._chk(self.L.zk_proof_size(self.ctx, pk, transcript, scheme, ctypes.byref(ln)), "zk_proof_size")
+        stride = ln.value
+        buf = ctypes.create_string_buffer(stride * B)
+        self._chk(self.L.zk_prove_batch_public(self.ctx, pk, B, hs, na, iptrs, ilens, b"".join(bytes(sd) for sd in seeds), transcript, scheme,
+                                               buf, stride, ctypes.byref(ln)), "zk_prove_batch_public")
+        return [buf.raw[j * stride:j * stride + ln.value] for j in range(B)]
+
+    def prove_multi_public(self, pk, advice_sets, instance_lists, seed=bytes(32), transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
+        """zk_prove_multi_public: prove_multi with instance_lists[c] the public inputs of circuit c (halo2's create_proof with several
+        circuits and their instances).  One circuit gives prove_public()'s bytes."""
+        N = len(advice_sets)
+        if len(seed) != 32:
+            raise ValueError("rng seed must be 32 bytes")
+        na = len(advice_sets[0]) if N else 0
+        if any(len(a) != na for a in advice_sets):
+            raise ValueError("every circuit has the key's number of advice columns")
+        hs = (ctypes.c_uint64 * max(N * na, 1))(*[p.h for a in advice_sets for p in a])
+        keep, iptrs, ilens = self._instance_lists_arg(instance_lists, N)
+        ln = ctypes.c_size_t()
+        self._chk(self.L.zk_proof_size_multi(self.ctx, pk, N, transcript, scheme, ctypes.byref(ln)), "zk_proof_size_multi")
+        buf = ctypes.create_string_buffer(ln.value)
+        self._chk(self.L.zk_prove_multi_public(self.ctx, pk, N, hs, na, iptrs, ilens, seed, transcript, scheme, buf, len(buf), ctypes.byref(ln)),
+                  "zk_prove_multi_public")
+        return buf.raw[:ln.value]
+
+    def verify_multi_public(self, pk, proof, instance_lists, transcript, scheme=ZK_SCHEME_DEFAULT) -> bool:
+        """zk_verify_multi_public: verify_proof of one proof over len(instance_lists) circuits with their public inputs."""
+        proof = bytes(proof)
+        N = len(instance_lists)
+        keep, iptrs, ilens = self._instance_lists_arg(instance_lists, N)
+        ok = ctypes.c_int(0)
+        self._chk(self.L.zk_verify_multi_public(self.ctx, pk, N, transcript, scheme, iptrs, ilens, proof, len(proof), ctypes.byref(ok)),
+                  "zk_verify_multi_public")
+        return bool(ok.value)
+
+    def verify_batch_public(self, pk, proofs, instance_lists, transcript, scheme=ZK_SCHEME_DEFAULT):
+        """zk_verify_batch_public: one verdict per proof, each what verify_public(pk, proofs[j], instance_lists[j]) says (batches above
+        ZK_VERIFY_BATCH_MAX are split).  instance_lists None: a key without the column."""
+        proofs = [bytes(p) for p in proofs]
+        if instance_lists is not None and len(instance_lists) != len(proofs):
+            raise ValueError("one instance list per proof")
+        out = []
+        for lo in range(0, len(proofs), ZK_VERIFY_BATCH_MAX):
+            part = proofs[lo:lo + ZK_VERIFY_BATCH_MAX]
+            keep, iptrs, ilens = self._instance_lists_arg(None if instance_lists is None else instance_lists[lo:lo + len(part)], len(part))
+            ptrs = (ctypes.c_char_p * len(part))(*part)
+            lens = (ctypes.c_size_t * len(part))(*[len(p) for p in part])
+            v = (ctypes.c_uint8 * len(part))()
+            self._chk(self.L.zk_verify_batch_public(self.ctx, pk, len(part), transcript, scheme, iptrs, ilens, ptrs, lens, v), "zk_verify_batch_public")
+            out.extend(bool(x) for x in v)
+        return out
+
+    def set_verify_instance_eval(self, mode):
+        """zk_verify_instance_eval_mode: where verify_batch_public / verify_multi_public evaluate inst(x) - 0 auto (the host), 1 host,
+        2 device.  Same verdicts."""
+        self._chk(self.L.zk_verify_instance_eval_mode(self.ctx, mode), "zk_verify_instance_eval_mode")
+
+    def instance_eval(self, k, instance_lists, xs_mont):
+        """zk_instance_eval: inst(x) of len(instance_lists) (list, point) pairs over the domain of 2^k rows, on the device ->
+        ((count, 4) uint64 Montgomery values, [on_domain flags]).  Lists that are the SAME object are uploaded once."""
+        count = len(instance_lists)
+        xs = _arr(xs_mont, 4)
+        if xs.shape[0] != count:
+            raise ValueError("one point per list")
+        same = {}
+        arrs = []
+        for l in instance_lists:
+            a = same.get(id(l))
+            if a is None:
+                a = same[id(l)] = np.zeros((0, 4), dtype=np.uint64) if l is None else _arr(l, 4)
+            arrs.append(a)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        ptrs = (u64p * max(count, 1))(*[_p(a) if a.shape[0] else ctypes.cast(None, u64p) for a in arrs])
+        lens = (ctypes.c_size_t * max(count, 1))(*[a.shape[0] for a in arrs])
+        out = np.zeros((count, 4), dtype=np.uint64)
+        flags = (ctypes.c_uint8 * max(count, 1))()
+        self._chk(self.L.zk_instance_eval(self.ctx, k, count, ptrs, lens, _p(xs), _p(out), flags), "zk_instance_eval")
+        return out, [bool(flags[j]) for j in range(count)]
 
     def proof_size_multi(self, pk, n_circuits, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
         ln = ctypes.c_size_t()

@@ -94,11 +94,11 @@ def prove(body, device=0, degree=DEGREE, rng_seed=None, check=False, public=Fals
     return _prove(body, False, device, degree, rng_seed, check, public)
 
 
-def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE):
+def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE, public=False):
     """A recorded batch of requests over several GPUs: request i goes to devices[i % len(devices)], and every device proves
     `ecdsa_p256.PIPELINES_PER_DEVICE` of its requests side by side — one host thread per request in flight (the reference:
     one Rocket worker thread per request, main.rs:457-472).  Every device must have been `setup`.  Returns the hex proofs in
-    request order; a failed request yields its exception."""
+    request order; a failed request yields its exception.  public: prove's - every answer carries its nine instance words."""
     bodies = list(bodies)
     out = [None] * len(bodies)
     per = max(1, ecdsa_p256.PIPELINES_PER_DEVICE)
@@ -107,7 +107,7 @@ def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE):
     def work(q):
         for i in range(q, len(bodies), workers):
             try:
-                out[i] = _prove(bodies[i], evm, devices[q % len(devices)], degree, None)
+                out[i] = _prove(bodies[i], evm, devices[q % len(devices)], degree, None, False, public)
             except Exception as e:  # the reference answers 500 for that request and keeps serving
                 out[i] = e
 
@@ -170,27 +170,33 @@ def verify_evm(body, device=0, degree=DEGREE, public=0) -> str:
     return _verify(body, ecdsa_p256.verify_evm, device, degree, public)
 
 
-def verify_batch(bodies, evm=True, device=0, degree=DEGREE):
+def verify_batch(bodies, evm=True, device=0, degree=DEGREE, public=0):
     """A recorded batch of verify requests: the proofs of each verifying key go through ONE zk_verify_batch call.  Returns
-    "verified" / "rejected" per request, in request order; a malformed request yields its exception."""
+    "verified" / "rejected" per request, in request order; a malformed request yields its exception.  public: verify's - every
+    proof string carries that many leading instance words, and the batch goes through zk_verify_batch_public."""
     out = [None] * len(bodies)
     by_key = {}
     for i, b in enumerate(bodies):
         try:
             path, proof = parse_verify_request(b)
+            instances, proof = _split_calldata(proof, public)
         except ValueError as e:
             out[i] = e
             continue
-        by_key.setdefault(path, []).append((i, proof))
+        if instances is not None and any(v >= ecdsa_p256.circuit.R for v in instances):
+            out[i] = "rejected"  # (a generated verifier contract reverts on a non-canonical instance word)
+            continue
+        by_key.setdefault(path, []).append((i, proof, instances))
     for path, items in by_key.items():
         try:
-            verdicts = ecdsa_p256.verify_batch(degree, [p for _, p in items], path, evm, device)
+            verdicts = ecdsa_p256.verify_batch(degree, [it[1] for it in items], path, evm, device,
+                                               [it[2] for it in items] if public else None)
         except Exception as e:  # (an unreadable key file: every request of that key fails)
-            for i, _ in items:
-                out[i] = e
+            for it in items:
+                out[it[0]] = e
             continue
-        for (i, _), ok in zip(items, verdicts):
-            out[i] = "verified" if ok else "rejected"
+        for it, ok in zip(items, verdicts):
+            out[it[0]] = "verified" if ok else "rejected"
     return out
 
 
@@ -199,10 +205,12 @@ def verify_batch(bodies, evm=True, device=0, degree=DEGREE):
 # proof and — on chain — one pairing.  The reference's endpoints prove one request per call; these two keep its JSON contract
 # (a list of the existing request bodies in, one hex proof out) for a host that aggregates.
 
-def prove_multi(bodies, evm=True, device=0, degree=DEGREE, rng_seed=None, check=False) -> str:
+def prove_multi(bodies, evm=True, device=0, degree=DEGREE, rng_seed=None, check=False, public=False) -> str:
     """A list of ProveRequestBody (JSON strings / dicts, all naming ONE proving key) -> the hex of ONE proof over all of them, in
     list order (ecdsa_p256.create_proof_multi_from_advice).  Each body passes the ES256 check first; one refused body refuses
-    the call.  The proof verifies with verify_multi and the same count only."""
+    the call.  The proof verifies with verify_multi and the same count only.  public=True (the key of setup(public=True)): circuit
+    c is bound to request c's msghash and public key; the answer is the hex of ecdsa_p256.encode_calldata over ALL circuits' instance
+    words in circuit order (nine per circuit), then the proof."""
     reqs = [parse_request(b) for b in bodies]
     if not reqs:
         raise ValueError("at least one request")
@@ -213,20 +221,36 @@ def prove_multi(bodies, evm=True, device=0, degree=DEGREE, rng_seed=None, check=
         if not ecdsa_p256.es256_verify(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]):
             raise ValueError(f"request {i}: invalid ES256 signature (or non-canonical field encoding): request refused")
     _, p, _ = ecdsa_p256._resident_key(path, degree, device)
-    sets = []
+    if bool(p.num_instance_columns) != bool(public):
+        raise ValueError("the resident key was made %s public inputs (setup(public=...))" % ("with" if p.num_instance_columns else "without"))
+    sets, lists = [], []
     for q in reqs:
-        asg = ecdsa_p256.circuit.synthesize(p, ecdsa_p256._witness_seed(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]))
+        vals = ecdsa_p256.public_inputs(q["msghash"], q["pubkey_x"], q["pubkey_y"], p.limb_bits, p.num_limbs) if public else None
+        asg = ecdsa_p256.circuit.synthesize(p, ecdsa_p256._witness_seed(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]),
+                                            n_public=len(vals) if public else 0, public_values=vals)
         sets.append([asg.to_limbs(col) for col in asg.advice])
+        lists.append(vals)
     transcript = ecdsa_p256.ZK_TRANSCRIPT_EVM if evm else ecdsa_p256.ZK_TRANSCRIPT_BLAKE2B
-    return ecdsa_p256.create_proof_multi_from_advice(sets, path, degree, transcript, device, rng_seed, check).hex()
+    proof = ecdsa_p256.create_proof_multi_from_advice(sets, path, degree, transcript, device, rng_seed, check, lists if public else None)
+    if public:
+        proof = ecdsa_p256.encode_calldata([v for vals in lists for v in vals], proof)
+    return proof.hex()
 
 
-def verify_multi(body, evm=True, device=0, degree=DEGREE) -> str:
-    """VerifyRequestBody plus "num_proof": the number of requests the proof covers -> "verified" or "rejected"."""
+def verify_multi(body, evm=True, device=0, degree=DEGREE, public=0) -> str:
+    """VerifyRequestBody plus "num_proof": the number of requests the proof covers -> "verified" or "rejected".  public: how many
+    instance words EACH circuit has (prove_multi(public=True): nine); the proof string then starts with num_proof x public words, in
+    circuit order."""
     path, proof = parse_verify_request(body)
     if isinstance(body, (str, bytes, bytearray)):
         body = json.loads(body)
     n = body.get("num_proof")
     if not isinstance(n, int) or isinstance(n, bool) or n < 1:
         raise ValueError("num_proof: expected a positive integer")
-    return "verified" if ecdsa_p256.verify_multi(degree, proof, path, n, evm, device) else "rejected"
+    if not public:
+        return "verified" if ecdsa_p256.verify_multi(degree, proof, path, n, evm, device) else "rejected"
+    words, proof = _split_calldata(proof, n * public)
+    if any(v >= ecdsa_p256.circuit.R for v in words):
+        return "rejected"  # (a generated verifier contract reverts on a non-canonical instance word)
+    lists = [words[c * public:(c + 1) * public] for c in range(n)]
+    return "verified" if ecdsa_p256.verify_multi(degree, proof, path, n, evm, device, lists) else "rejected"

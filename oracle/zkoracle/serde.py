@@ -75,13 +75,88 @@ def g1_parse(b, fmt):
 
 
 def g2_bytes(pt, fmt):
-    """pt: ((x.c0, x.c1), (y.c0, y.c1)) canonical ints."""
+    """pt: ((x.c0, x.c1), (y.c0, y.c1)) canonical ints or None (identity)."""
+    if pt is None:
+        return bytes(64 if fmt == PROCESSED else 128)
     (x0, x1), (y0, y1) = pt
     if fmt == PROCESSED:
         b = bytearray(_le(x0) + _le(x1))
         b[63] |= (y0 & 1) << 7
         return bytes(b)
     return fq_raw(x0) + fq_raw(x1) + fq_raw(y0) + fq_raw(y1)
+
+
+def fq_sqrt(a):
+    """A square root of a in Fq (p = 3 mod 4), or None."""
+    y = pow(a % P, (P + 1) // 4, P)
+    return y if y * y % P == a % P else None
+
+
+def fq2_sqrt(a):
+    """A square root of a = (c0, c1) in Fq2 = Fq[u]/(u^2 + 1) by plain integers, or None if a is no square.  A nonzero a is a
+    square exactly when its norm c0^2 + c1^2 is one in Fq; an element of Fq itself always is (a non-residue c0 has the root
+    sqrt(-c0) u)."""
+    a0, a1 = a[0] % P, a[1] % P
+    if a1 == 0:
+        s = fq_sqrt(a0)
+        return (s, 0) if s is not None else (0, fq_sqrt(-a0))
+    alpha = fq_sqrt(a0 * a0 + a1 * a1)
+    if alpha is None:
+        return None
+    half = inv(2, P)
+    x0 = fq_sqrt((a0 + alpha) * half)
+    if x0 is None:
+        x0 = fq_sqrt((a0 - alpha) * half)
+    x1 = a1 * inv(2 * x0 % P, P) % P
+    assert C.f2mul((x0, x1), (x0, x1)) == (a0, a1)
+    return (x0, x1)
+
+
+G2_B = C.f2mul((3, 0), C.f2inv((9, 1)))  # the twist y^2 = x^3 + 3 / (9 + u)
+
+
+def g2_on_curve(pt):
+    (x, y) = pt
+    return C.f2mul(y, y) == C.f2add(C.f2mul(C.f2mul(x, x), x), G2_B)
+
+
+def g2_parse(b, fmt):
+    """The inverse of g2_bytes: ((x.c0, x.c1), (y.c0, y.c1)), None for the identity (all zero); raises on an encoding that
+    halo2's read refuses.  Processed: both halves of x canonical, y = sqrt(x^3 + b') with the parity of y.c0 from bit 7 of the
+    last byte; RawBytes: the four Montgomery coordinates below p and on the twist; RawBytesUnchecked: nothing is checked."""
+    if fmt == PROCESSED:
+        x0, x1 = int.from_bytes(b[:32], "little"), int.from_bytes(b[32:], "little")
+        sign, x1 = x1 >> 255, x1 & ((1 << 255) - 1)
+        if x0 >= P or x1 >= P:
+            raise ValueError("non-canonical x")
+        if x0 == 0 and x1 == 0 and not sign:
+            return None
+        x = (x0, x1)
+        y = fq2_sqrt(C.f2add(C.f2mul(C.f2mul(x, x), x), G2_B))
+        if y is None:
+            raise ValueError("not on the curve")
+        if (y[0] & 1) != sign:
+            y = ((-y[0]) % P, (-y[1]) % P)
+        return (x, y)
+    m = [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(4)]
+    if fmt == RAW_BYTES and any(v >= P for v in m):
+        raise ValueError("non-canonical coordinate")
+    c = [v * inv(MONT_R, P) % P for v in m]
+    if not any(c):
+        return None
+    pt = ((c[0], c[1]), (c[2], c[3]))
+    if fmt == RAW_BYTES and not g2_on_curve(pt):
+        raise ValueError("not on the curve")
+    return pt
+
+
+def fr_parse(b, fmt):
+    """One scalar of a key image -> its value; raises where halo2's read refuses (Processed: the canonical value, RawBytes: the
+    Montgomery limb image, each below r; RawBytesUnchecked takes any limbs)."""
+    v = int.from_bytes(b, "little")
+    if fmt != RAW_BYTES_UNCHECKED and v >= R:
+        raise ValueError("scalar not below r")
+    return v if fmt == PROCESSED else v * inv(MONT_R, R) % R
 
 
 def fr_vec_bytes(a_mont, fmt):

@@ -59,3 +59,53 @@ def test_reference_k17_vk_image_round_trips():
         assert a == fc and b == pc and s == [[int(v) for v in row] for row in sel]
     with pytest.raises(ValueError):
         serde.vk_parse(plonk.Shape(16, 4, 1, 1, 15), img, serde.RAW_BYTES)
+
+
+def test_g2_parse_inverts_g2_bytes():
+    tau_g2 = C.g2_mul(C.G2_GEN, srs.TAU)
+    neg = lambda p: (p[0], ((-p[1][0]) % F.P, (-p[1][1]) % F.P))
+    pts = [C.G2_GEN, tau_g2, neg(C.G2_GEN), neg(tau_g2)] + [C.g2_mul(C.G2_GEN, m) for m in (2, 3, 5, 0x1234567, F.R - 2)] + [None]
+    assert {p[1][0] & 1 for p in pts if p is not None} == {0, 1}  # both values of the sign bit
+    for fmt in (serde.PROCESSED, serde.RAW_BYTES, serde.RAW_BYTES_UNCHECKED):
+        for p in pts:
+            assert p is None or serde.g2_on_curve(p)
+            b = serde.g2_bytes(p, fmt)
+            assert len(b) == (64 if fmt == serde.PROCESSED else 128)
+            assert serde.g2_parse(b, fmt) == p
+    # bit 7 of the last byte is the parity of y.c0, and the other value of it decodes to the negative
+    b = bytearray(serde.g2_bytes(C.G2_GEN, serde.PROCESSED))
+    assert b[63] >> 7 == C.G2_GEN[1][0] & 1
+    b[63] ^= 0x80
+    assert serde.g2_parse(bytes(b), serde.PROCESSED) == neg(C.G2_GEN)
+    raw = bytearray(serde.g2_bytes(C.G2_GEN, serde.RAW_BYTES))
+    raw[64] ^= 1
+    with pytest.raises(ValueError):
+        serde.g2_parse(bytes(raw), serde.RAW_BYTES)
+    assert serde.g2_parse(bytes(raw), serde.RAW_BYTES_UNCHECKED) is not None
+
+
+def test_fq2_sqrt_by_plain_integers():
+    import random
+    rnd = random.Random(77)
+    sq = lambda a: C.f2mul(a, a)
+    for _ in range(40):
+        a = (rnd.randrange(F.P), rnd.randrange(F.P))
+        r = serde.fq2_sqrt(sq(a))
+        assert r in (a, ((-a[0]) % F.P, (-a[1]) % F.P))
+        norm_is_residue = pow((a[0] ** 2 + a[1] ** 2) % F.P, (F.P - 1) // 2, F.P) == 1
+        assert (serde.fq2_sqrt(a) is not None) == norm_is_residue
+    # every element of Fq is a square in Fq2: a residue has a root in Fq, a non-residue c has sqrt(-c) u
+    for c in (2, 3, 4, F.P - 1):
+        r = serde.fq2_sqrt((c, 0))
+        assert sq(r) == (c, 0)
+    assert serde.fq2_sqrt((0, 0)) == (0, 0)
+
+
+def test_scalar_rule():
+    for fmt in (serde.PROCESSED, serde.RAW_BYTES):
+        for v in (F.R, F.R + 1, (1 << 256) - 1):
+            with pytest.raises(ValueError):
+                serde.fr_parse(v.to_bytes(32, "little"), fmt)
+    assert serde.fr_parse((F.R - 1).to_bytes(32, "little"), serde.PROCESSED) == F.R - 1
+    assert serde.fr_parse((5 * F.MONT_R % F.R).to_bytes(32, "little"), serde.RAW_BYTES) == 5
+    assert serde.fr_parse(((5 * F.MONT_R % F.R) + F.R).to_bytes(32, "little"), serde.RAW_BYTES_UNCHECKED) == 5

@@ -32,14 +32,12 @@
 
 #include "pairing.h"
 #include "pk.h"
+#include "serde_host.h"
 #include "vkrepr.h"
 
 namespace {
 
 // ------------------------------------------------------------ device side ---
-struct Words8 {
-    uint32_t w[8];
-};
 
 __device__ __forceinline__ bool words_lt_p(const uint32_t* v, const uint32_t* p) {
     for (int i = 7; i >= 0; i--) {
@@ -136,185 +134,10 @@ __global__ void fr_to_mont_kernel(Fr* a, size_t n) {
 }
 
 // -------------------------------------------------------------- host side ---
-Words8 fq_sqrt_exp() {  // (p + 1) / 4
-    Words8 e;
-    uint64_t carry = 1;
-    uint32_t t[8];
-    for (int i = 0; i < 8; i++) {
-        const uint64_t s = (uint64_t)FqParams::P[i] + carry;
-        t[i] = (uint32_t)s;
-        carry = s >> 32;
-    }
-    for (int i = 0; i < 8; i++) e.w[i] = (t[i] >> 2) | (i + 1 < 8 ? t[i + 1] << 30 : 0);
-    return e;
-}
-
-bool host_lt_p(const uint32_t* v, const uint32_t* p) {
-    for (int i = 7; i >= 0; i--)
-        if (v[i] != p[i]) return v[i] < p[i];
-    return false;
-}
-
-bool host_g1_on_curve(const G1Affine& p) {
-    return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
-}
-
-// one G1 point <-> bytes in `format`; returns bytes consumed / produced, 0 on a malformed point
-size_t g1_size(int format) { return format == ZK_SERDE_PROCESSED ? 32 : 64; }
-
-bool host_g1_read(const uint8_t* b, int format, G1Affine* out) {
-    if (format == ZK_SERDE_PROCESSED) {
-        Fq x;
-        memcpy(x.v, b, 32);
-        const uint32_t sign = x.v[7] >> 31;
-        x.v[7] &= 0x7fffffffu;
-        if (!host_lt_p(x.v, FqParams::P)) return false;
-        if (x.is_zero() && !sign) {
-            out->x = Fq::zero();
-            out->y = Fq::zero();
-            return true;
-        }
-        const Fq xm = fe_to_mont(x);
-        const Fq rhs = fe_add(fe_mul(fe_sqr(xm), xm), fq_small(3));
-        Fq y = fe_pow(rhs, fq_sqrt_exp().w);
-        if (fe_sqr(y) != rhs) return false;
-        if ((fe_from_mont(y).v[0] & 1u) != sign) y = fe_neg(y);
-        out->x = xm;
-        out->y = y;
-        return true;
-    }
-    memcpy(out, b, 64);
-    if (format == ZK_SERDE_RAW_BYTES) {
-        if (!host_lt_p(out->x.v, FqParams::P) || !host_lt_p(out->y.v, FqParams::P)) return false;
-        if (!affine_is_identity(*out) && !host_g1_on_curve(*out)) return false;
-    }
-    return true;
-}
-
-void host_g1_write(const G1Affine& p, int format, uint8_t* b) {
-    if (format == ZK_SERDE_PROCESSED) {
-        if (affine_is_identity(p)) {
-            memset(b, 0, 32);
-            return;
-        }
-        Fq x = fe_from_mont(p.x);
-        x.v[7] |= (fe_from_mont(p.y).v[0] & 1u) << 31;
-        memcpy(b, x.v, 32);
-        return;
-    }
-    memcpy(b, &p, 64);
-}
-
-
-// sqrt in Fq2 (complex method); false if `a` is not a square
-bool f2_sqrt(const Fq2& a, Fq2* out) {
-    if (f2_is_zero(a)) {
-        *out = a;
-        return true;
-    }
-    const Words8 e = fq_sqrt_exp();
-    auto fq_sqrt = [&](const Fq& v, Fq* r) {
-        *r = fe_pow(v, e.w);
-        return fe_sqr(*r) == v;
-    };
-    Fq alpha;
-    if (!fq_sqrt(fe_add(fe_sqr(a.c0), fe_sqr(a.c1)), &alpha)) return false;
-    const Fq half = fe_inv(fq_small(2));
-    Fq delta = fe_mul(fe_add(a.c0, alpha), half), x0;
-    if (!fq_sqrt(delta, &x0)) {
-        delta = fe_mul(fe_sub(a.c0, alpha), half);
-        if (!fq_sqrt(delta, &x0)) return false;
-    }
-    if (x0.is_zero()) return false;
-    const Fq x1 = fe_mul(a.c1, fe_inv(fe_add(x0, x0)));
-    *out = Fq2{x0, x1};
-    return f2_eq(f2_mul(*out, *out), a);
-}
-
-size_t g2_size(int format) { return format == ZK_SERDE_PROCESSED ? 64 : 128; }
-void host_g2_write(const uint8_t raw[128], int format, uint8_t* b) {
-    if (format != ZK_SERDE_PROCESSED) {
-        memcpy(b, raw, 128);
-        return;
-    }
-    const G2A p = g2_from_raw(raw);
-    if (p.inf) {
-        memset(b, 0, 64);
-        return;
-    }
-    const Fq x0 = fe_from_mont(p.x.c0), x1 = fe_from_mont(p.x.c1);
-    memcpy(b, x0.v, 32);
-    memcpy(b + 32, x1.v, 32);
-    b[63] |= (uint8_t)((fe_from_mont(p.y.c0).v[0] & 1u) << 7);
-}
-bool host_g2_read(const uint8_t* b, int format, uint8_t raw[128]) {
-    if (format != ZK_SERDE_PROCESSED) {
-        memcpy(raw, b, 128);
-        if (format == ZK_SERDE_RAW_BYTES) {
-            const G2A p = g2_from_raw(raw);
-            for (int q = 0; q < 4; q++) {
-                uint32_t w[8];
-                memcpy(w, raw + 32 * q, 32);
-                if (!host_lt_p(w, FqParams::P)) return false;
-            }
-            if (!p.inf && !g2_on_curve(p)) return false;
-        }
-        return true;
-    }
-    Fq x0, x1;
-    memcpy(x0.v, b, 32);
-    memcpy(x1.v, b + 32, 32);
-    const uint32_t sign = x1.v[7] >> 31;
-    x1.v[7] &= 0x7fffffffu;
-    if (!host_lt_p(x0.v, FqParams::P) || !host_lt_p(x1.v, FqParams::P)) return false;
-    G2A p;
-    p.inf = false;
-    if (x0.is_zero() && x1.is_zero() && !sign) {
-        memset(raw, 0, 128);
-        return true;
-    }
-    p.x = Fq2{fe_to_mont(x0), fe_to_mont(x1)};
-    if (!f2_sqrt(f2_add(f2_mul(f2_mul(p.x, p.x), p.x), f2_twist_b()), &p.y)) return false;
-    if ((fe_from_mont(p.y.c0).v[0] & 1u) != sign) p.y = Fq2{fe_neg(p.y.c0), fe_neg(p.y.c1)};
-    g2_to_raw(p, raw);
-    return true;
-}
-
-void put_be32(uint8_t* b, uint32_t v) {
-    b[0] = (uint8_t)(v >> 24);
-    b[1] = (uint8_t)(v >> 16);
-    b[2] = (uint8_t)(v >> 8);
-    b[3] = (uint8_t)v;
-}
-uint32_t get_be32(const uint8_t* b) { return ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | b[3]; }
-
+// (the point codecs, f2_sqrt and the bounded In / Out: serde_host.h)
 bool format_ok(int f) { return f == ZK_SERDE_PROCESSED || f == ZK_SERDE_RAW_BYTES || f == ZK_SERDE_RAW_BYTES_UNCHECKED; }
 
 uint32_t blocks_for(size_t n, uint32_t t = 256) { return (uint32_t)((n + t - 1) / t); }
-
-// a bounded reader / writer over the caller's buffer
-struct Out {
-    uint8_t* p;
-    size_t cap, pos = 0;
-    bool real;  // false: size computation only
-    Out(uint8_t* buf, size_t c) : p(buf), cap(c), real(buf != nullptr) {}
-    uint8_t* take(size_t n) {
-        uint8_t* r = (real && pos + n <= cap) ? p + pos : nullptr;
-        if (real && pos + n > cap) real = false;  // overflow: keep counting, report ZK_EINVAL at the end
-        pos += n;
-        return r;
-    }
-};
-struct In {
-    const uint8_t* p;
-    size_t len, pos = 0;
-    const uint8_t* take(size_t n) {
-        if (n > len - pos) return nullptr;
-        const uint8_t* r = p + pos;
-        pos += n;
-        return r;
-    }
-};
 
 }  // namespace
 

@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")/webauthn-halo2_amd"
 OUT=libzkmi355.so
-SRCS="csrc/ctx.hip csrc/streams.hip csrc/msm_lanes.hip csrc/srs.hip csrc/poly_abi.hip csrc/ntt.hip csrc/msm.hip csrc/poly.hip csrc/prover_kernels.hip csrc/quotient.hip csrc/prover.hip csrc/prover_key.hip csrc/prover_phases.hip csrc/serde.hip csrc/verify.hip csrc/g1_ntt.hip csrc/witness_check.hip csrc/pk_check.hip csrc/placement.hip"
+SRCS="csrc/ctx.hip csrc/streams.hip csrc/msm_lanes.hip csrc/srs.hip csrc/poly_abi.hip csrc/ntt.hip csrc/msm.hip csrc/poly.hip csrc/prover_kernels.hip csrc/quotient.hip csrc/prover.hip csrc/prover_key.hip csrc/prover_phases.hip csrc/serde.hip csrc/verify.hip csrc/g1_ntt.hip csrc/witness_check.hip csrc/pk_check.hip csrc/placement.hip csrc/es256.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result"
 mkdir -p build
 objs=""
@@ -26,10 +26,18 @@ for v in "a0:-DZK_MUL29_ASM=0" "a1:-DZK_MUL29_ASM=1" "a2:-DZK_MUL29_ASM=2" "a2m:
     pids="$pids $!"
   fi
 done
+# the device harness of csrc/p256.hip.h (tests/p256_device_check.hip, run by tests/test_gpu_p256_device.py): the header has one
+# portable form, so one binary
+x=../tests/p256_device_check
+if [ ! -f $x ] || [ ../tests/p256_device_check.hip -nt $x ] || [ ../tests/p256_check_ops.h -nt $x ] || [ csrc/p256.hip.h -nt $x ]; then
+  hipcc $FLAGS -Icsrc ../tests/p256_device_check.hip -o $x &
+  pids="$pids $!"
+fi
 for p in $pids; do wait $p; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs
 echo "built $(pwd)/$OUT"
 echo "built $(cd ../tests && pwd)/field_device_check_{a0,a1,a2,a2m,a2p}"
+echo "built $(cd ../tests && pwd)/p256_device_check"
 # the C++ host example of the same ABI (examples/prove_host.cpp): plain g++, linked against the library above
 cd ..
 g++ -O2 -std=c++17 -Wall -Iinclude examples/prove_host.cpp -Lwebauthn-halo2_amd -lzkmi355 -Wl,-rpath,'$ORIGIN/../webauthn-halo2_amd' -o examples/prove_host

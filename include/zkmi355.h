@@ -678,6 +678,24 @@ int zk_verify_instance_eval_mode(zk_ctx* ctx, int mode);
 int zk_instance_eval(zk_ctx* ctx, uint32_t k, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances,
                      const uint64_t* x_mont /* count x 4 */, uint64_t* out_mont /* count x 4 */, uint8_t* on_domain /* count */);
 
+/* ---- ES256 request check: secp256r1 (NIST P-256) ECDSA verification on the device ------------------------------------------
+ * `count` signatures in one launch, one per lane.  A record is five fields of 32 LITTLE-endian bytes in the order pubkey_x,
+ * pubkey_y, r, s, msghash (the proving server's request fields as the web client encodes them).  verdicts[i] = 1 for a valid
+ * signature, else 0; reasons (may be NULL) names the FIRST failing test:
+ *   ZK_ES256_RANGE      x >= p, y >= p, msghash >= n, r not in [1, n) or s not in [1, n)
+ *   ZK_ES256_OFF_CURVE  y^2 != x^3 - 3 x + b ((0, 0) is off the curve)
+ *   ZK_ES256_MISMATCH   u1 G + u2 Q (u1 = msghash / s, u2 = r / s mod n) is the identity, or its affine x mod n is not r
+ * A bad signature is a verdict, never an error.  Needs no SRS and no key.  The first call on a context builds a 60 KiB table of
+ * multiples of G on the device and keeps it with the context.  Public data only: the arithmetic is NOT constant time.
+ * ZK_EINVAL: ctx, sigs or verdicts NULL, count == 0 or > ZK_ES256_BATCH_MAX.  Outputs are untouched on every error. */
+#define ZK_ES256_VALID 0
+#define ZK_ES256_RANGE 1
+#define ZK_ES256_OFF_CURVE 2
+#define ZK_ES256_MISMATCH 3
+#define ZK_ES256_BATCH_MAX 16384
+int zk_es256_verify(zk_ctx* ctx, size_t count, const uint8_t* sigs /* count x 160 */, uint8_t* verdicts /* count: 1 = valid */,
+                    uint8_t* reasons /* count, may be NULL */);
+
 /* ---- timing of the last call of each kind, measured with HIP events on the
  *      context stream (ms); used by bench.py for the roofline figures ---------- */
 #define ZK_T_MSM 0

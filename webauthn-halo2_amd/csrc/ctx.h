@@ -134,6 +134,7 @@ struct zk_ctx : SrsView {
     size_t seam_bytes[2] = {0, 0};
     Fr* small = nullptr;  // 2048 + 8 elements for reductions
     struct VerifyWs* vws = nullptr;  // zk_verify_batch's device buffers (verify.hip), grow-only
+    struct Es256Ws* es256 = nullptr;  // zk_es256_verify's comb table of G and staging buffers (es256.hip), made on first use
     Fr* host_small = nullptr;  // pinned, 8 elements
     // polys
     std::unordered_map<uint64_t, PolyRec> polys;
@@ -288,3 +289,4 @@ int srs_install(zk_ctx* c, uint32_t k, G1Affine* g, G1Affine* g_lagrange);
 int ctx_g1_to_lagrange(zk_ctx* c, const G1Affine* d_in, uint32_t k, G1Affine* d_out);
 void srs_set_g2_from_secret(zk_ctx* c, const Fr& s_mont);
 void verify_ws_destroy(struct VerifyWs* w);
+void es256_ws_destroy(struct Es256Ws* w);

@@ -291,6 +291,7 @@ void zk_ctx_destroy(zk_ctx* c) {
         if (c->seam_buf[i]) hipFree(c->seam_buf[i]);
     if (c->small) hipFree(c->small);
     verify_ws_destroy(c->vws);
+    es256_ws_destroy(c->es256);
     for (int i = 0; i < ZK_T_COUNT; i++)
         for (int j = 0; j < 2; j++)
             if (c->ev[i][j]) hipEventDestroy(c->ev[i][j]);

@@ -1,0 +1,107 @@
+// es256.hip — zk_es256_verify: secp256r1 ECDSA verification of `count` requests in one launch, one signature per lane.
+//
+// The rule itself is p256_verify_one (p256.hip.h, host and device): the kernel is a loop-less wrapper around it.  Shape:
+// workgroups of ONE wave, so a batch spreads over the CUs and up to 16 384 signatures cost about one signature's latency (the
+// ~252 doublings under u2 Q are serial, and P-256 has no endomorphism to split them).  Each lane's table Q .. 15 Q is indexed by
+// that lane's own digit, so it lives in LDS (15 Jacobian points x 64 lanes = 90 KiB of the CU's 160), never in a register array.
+// u1 G comes from a comb of G (64 windows x 15 affine multiples, 60 KiB) that es256_comb_kernel builds on the first call of a
+// context — one window per lane, each lane normalising its 15 points with one inversion — and that stays with the context.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ctx.h"
+#include "p256.hip.h"
+
+// the context's ES256 state: the comb of G and the grow-only staging buffers
+struct Es256Ws {
+    P256Affine* table = nullptr;
+    void *in = nullptr, *out = nullptr;
+    size_t c_in = 0, c_out = 0;
+};
+
+void es256_ws_destroy(Es256Ws* w) {
+    if (!w) return;
+    for (void* p : {(void*)w->table, w->in, w->out})
+        if (p) hipFree(p);
+    delete w;
+}
+
+namespace {
+
+constexpr uint32_t ES256_WG = 64;  // one wave: p256_verify_one's LDS block is laid out for it
+
+// the comb of G: lane w builds window w (4 w doublings of G, its 15 multiples through the LDS block, one inversion)
+__global__ __launch_bounds__(ES256_WG) void es256_comb_kernel(P256Affine* table) {
+    const uint32_t w = threadIdx.x;
+    if (blockIdx.x != 0 || w >= (uint32_t)P256_COMB_WINDOWS) return;
+    P256LdsStore st = p256_lds_store();
+    p256_comb_window((int)w, st, table + (size_t)w * P256_COMB_ENTRIES);
+}
+
+__global__ __launch_bounds__(ES256_WG) void es256_verify_kernel(const uint8_t* sigs, uint32_t count, const P256Affine* table, uint8_t* reasons) {
+    const uint32_t i = blockIdx.x * ES256_WG + threadIdx.x;
+    if (i >= count) return;  // the tail lanes of the last wave touch no memory
+    reasons[i] = p256_verify_one(sigs + (size_t)i * 160, table);
+}
+
+int es_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
+    if (*cap >= bytes) return ZK_OK;
+    if (*p) {
+        hipStreamSynchronize(c->stream);
+        hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+    }
+    const size_t want = std::max<size_t>(bytes, 4096);
+    if (hipMalloc(p, want) != hipSuccess) return ZK_ENOMEM;
+    *cap = want;
+    return ZK_OK;
+}
+
+// made once per context on its main stream and waited for, like the twiddle tables (ctx.hip ctx_cached_table)
+int es256_table(zk_ctx* c, Es256Ws* w) {
+    if (w->table) return ZK_OK;
+    P256Affine* t = nullptr;
+    if (hipMalloc(&t, (size_t)P256_COMB_POINTS * sizeof(P256Affine)) != hipSuccess) return ZK_ENOMEM;
+    if (c->audit.on) c->audit.op(c->stream, {}, {t}, "es256: comb of G (es256_comb_kernel)");
+    hipLaunchKernelGGL(es256_comb_kernel, dim3(1), dim3(ES256_WG), 0, c->stream, t);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = aud_sync(c, c->stream);
+    if (e != hipSuccess) {
+        c->last_hip = (int)e;
+        hipFree(t);
+        return ZK_EHIP;
+    }
+    w->table = t;
+    return ZK_OK;
+}
+
+}  // namespace
+
+ZK_API(zk_es256_verify, (zk_ctx* c, size_t count, const uint8_t* sigs, uint8_t* verdicts, uint8_t* reasons), (c, count, sigs, verdicts, reasons)) {
+    if (!c || !sigs || !verdicts || count == 0 || count > ZK_ES256_BATCH_MAX) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    const uint64_t aud0 = c->audit.violations;
+    c->audit.base_of.clear();
+    if (!c->es256 && !(c->es256 = new (std::nothrow) Es256Ws())) return ZK_ENOMEM;
+    Es256Ws* w = c->es256;
+    if ((rc = es256_table(c, w)) || (rc = es_grow(c, &w->in, &w->c_in, count * 160)) || (rc = es_grow(c, &w->out, &w->c_out, count))) return rc;
+    std::vector<uint8_t> res(count);
+    if (c->audit.on) c->audit.op(c->stream, {}, {w->in}, "es256: signatures upload");
+    HIPCHK(c, hipMemcpyAsync(w->in, sigs, count * 160, hipMemcpyHostToDevice, c->stream));
+    if (c->audit.on) c->audit.op(c->stream, {w->in, w->table}, {w->out}, "es256: verification (es256_verify_kernel)");
+    hipLaunchKernelGGL(es256_verify_kernel, dim3((uint32_t)((count + ES256_WG - 1) / ES256_WG)), dim3(ES256_WG), 0, c->stream, (const uint8_t*)w->in,
+                       (uint32_t)count, (const P256Affine*)w->table, (uint8_t*)w->out);
+    HIPCHK(c, hipGetLastError());
+    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "es256: reasons download");
+    HIPCHK(c, hipMemcpyAsync(res.data(), w->out, count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, aud_sync(c, c->stream));  // (the caller's records and `res` are pageable)
+    if ((rc = aud_verdict(c, aud0, ZK_OK))) return rc;
+    for (size_t i = 0; i < count; i++) verdicts[i] = res[i] == ZK_ES256_VALID ? 1 : 0;
+    if (reasons) memcpy(reasons, res.data(), count);
+    return ZK_OK;
+}

@@ -47,7 +47,7 @@ import numpy as np
 from . import circuit
 from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_SRS_CONTRIB_LINKS,
                      ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT, ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
-                     ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
+                     ZK_ES256_BATCH_MAX, ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -332,6 +332,11 @@ def check_contributions(params_path, receipts, device: int = 0) -> bool:
 def shutdown(device=None):
     """Release the resident state (every pipeline's context, keys and request slots) of `device`, or of all devices."""
     with _STATE_LOCK:
+        with _ES256_LOCK:  # the signature check's own context
+            for d in ([device] if device is not None else list(_ES256_ENGINES)):
+                eng = _ES256_ENGINES.pop(d, None)
+                if eng is not None:
+                    eng.close()
         for d in ([device] if device is not None else list(_STATE)):
             st = _STATE.get(d)
             if not st:
@@ -696,17 +701,77 @@ def es256_verify(pubkey_x: bytes, pubkey_y: bytes, r: bytes, s: bytes, msg_hash:
     return pt is not None and pt[0] % _N == ri
 
 
+# ---- the same check on the device (opt-in) --------------------------------------------------------------
+# es256_verify above is affine Python with one modular inversion per point operation and runs under the GIL: the threads of
+# proving_server.prove_batch and the bodies of prove_multi pay for it one after another.  zk_es256_verify (csrc/es256.hip) checks
+# up to 16 384 requests in one launch, one signature per lane.  Which of the two the prover entry points use is a process-wide
+# setting; the default is the host, exactly the path above (tools/es256_rate.py measures both; a later change may flip it).
+_SIGNATURE_CHECK = "host"
+_REFUSED = "invalid ES256 signature (or non-canonical field encoding): request refused"
+_ES256_ENGINES = {}  # device -> an Engine of its own for the check (no SRS, no key), used under _ES256_LOCK: contexts are not thread-safe
+_ES256_LOCK = threading.Lock()
+
+
+def set_signature_check(mode: str):
+    """Where _prove_synthetic, proving_server.prove_multi and prove_batch check a request's ES256 signature: "host" (es256_verify,
+    the default) or "device" (es256_verify_many: all bodies of a call in one zk_es256_verify launch before any proof starts).
+    The same requests are refused with the same ValueError either way."""
+    global _SIGNATURE_CHECK
+    if mode not in ("host", "device"):
+        raise ValueError('signature check: "host" or "device"')
+    _SIGNATURE_CHECK = mode
+
+
+def signature_check() -> str:
+    return _SIGNATURE_CHECK
+
+
+def _es256_record(q):
+    """The 160-byte record of a request: a (pubkey_x, pubkey_y, r, s, msg_hash) tuple (es256_verify's argument order) or a parsed
+    request body (proving_server.parse_request)."""
+    if isinstance(q, dict):
+        q = (q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"])
+    if len(q) != 5 or any(len(v) != 32 for v in q):
+        raise ValueError("a request is five fields of 32 little-endian bytes")
+    return b"".join(bytes(v) for v in q)
+
+
+def es256_verify_many(requests, device: int = 0):
+    """es256_verify of every request on the device, in one zk_es256_verify call per ZK_ES256_BATCH_MAX requests -> [bool], in order.
+    requests: (pubkey_x, pubkey_y, r, s, msg_hash) tuples, or parsed request bodies."""
+    recs = [_es256_record(q) for q in requests]
+    out = []
+    with _ES256_LOCK:
+        eng = _ES256_ENGINES.get(device)
+        if eng is None:
+            eng = _ES256_ENGINES[device] = Engine(device)
+        for lo in range(0, len(recs), ZK_ES256_BATCH_MAX):
+            out += eng.es256_verify(b"".join(recs[lo:lo + ZK_ES256_BATCH_MAX]))[0]
+    return out
+
+
+def _signature_ok(pubkey_x, pubkey_y, r, s, msg_hash, device):
+    if _SIGNATURE_CHECK == "device":
+        return es256_verify_many([(pubkey_x, pubkey_y, r, s, msg_hash)], device)[0]
+    return es256_verify(pubkey_x, pubkey_y, r, s, msg_hash)
+
+
 def _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash) -> int:
     return int.from_bytes(hashlib.sha256(bytes(pubkey_x) + bytes(pubkey_y) + bytes(r) + bytes(s) + bytes(msg_hash)).digest()[:8], "little")
 
 
-def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, transcript, device, rng_seed, check=False, public=False):
+def _prove_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key_path, degree, transcript, device, rng_seed, check=False, public=False,
+                     signature_ok=None):
+    """signature_ok: the verdict of a check the caller already made for this request (proving_server.prove_batch under
+    set_signature_check("device") checks all its requests in one launch); None: checked here."""
     for name, v in (("pubkey_x", pubkey_x), ("pubkey_y", pubkey_y), ("r", r), ("s", s), ("msg_hash", msg_hash)):
         if len(v) != 32:
             raise ValueError(f"{name} must be 32 little-endian bytes")  # the reference takes &[u8; 32]
-    if not es256_verify(pubkey_x, pubkey_y, r, s, msg_hash):
+    if signature_ok is None:
+        signature_ok = _signature_ok(pubkey_x, pubkey_y, r, s, msg_hash, device)
+    if not signature_ok:
         # the real circuit would be unsatisfiable; never let such a request come back with a verifying proof
-        raise ValueError("invalid ES256 signature (or non-canonical field encoding): request refused")
+        raise ValueError(_REFUSED)
     _, p, _ = _resident_key(proving_key_path, degree, device)
     if bool(p.num_instance_columns) != bool(public):
         raise ValueError("the resident key was made %s public inputs (download_keys(public=...))" % ("with" if p.num_instance_columns else "without"))

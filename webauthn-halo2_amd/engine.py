@@ -27,6 +27,8 @@ ZK_VERIFY_INSTANCE_EVAL_AUTO, ZK_VERIFY_INSTANCE_EVAL_HOST, ZK_VERIFY_INSTANCE_E
 ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK = 0, 1, 2
 ZK_VERIFY_BATCH_MAX = 1024
 ZK_PROVE_MULTI_MAX = 16
+ZK_ES256_VALID, ZK_ES256_RANGE, ZK_ES256_OFF_CURVE, ZK_ES256_MISMATCH = 0, 1, 2, 3
+ZK_ES256_BATCH_MAX = 16384
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 ZK_SRS_CONTRIB_SAME_SECRET, ZK_SRS_CONTRIB_LINKS, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT = 1, 2, 4, 8
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
@@ -231,6 +233,7 @@ def load_library():
                                     ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "zk_verify_instance_eval_mode": ([vp, ctypes.c_int], ctypes.c_int),
         "zk_instance_eval": ([vp, u32, sz, ctypes.POINTER(u64p), ctypes.POINTER(sz), u64p, u64p, ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_es256_verify": ([vp, sz, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "zk_srs_write": ([vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_srs_read": ([vp, vp, sz, ctypes.c_int], ctypes.c_int),
         "zk_srs_set_g2": ([vp, u64p, u64p], ctypes.c_int),
@@ -276,7 +279,7 @@ def load_library():
             if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info", "zk_proof_size_multi",
                         "zk_prove_multi", "zk_verify_multi", "zk_prove_public", "zk_verify_public", "zk_witness_check_public",
                         "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
-                        "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode") and os.environ.get("ZKMI355_LIB"):
+                        "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -877,6 +880,21 @@ class Engine:
         flags = (ctypes.c_uint8 * max(count, 1))()
         self._chk(self.L.zk_instance_eval(self.ctx, k, count, ptrs, lens, _p(xs), _p(out), flags), "zk_instance_eval")
         return out, [bool(flags[j]) for j in range(count)]
+
+    def es256_verify(self, sigs):
+        """zk_es256_verify: secp256r1 ECDSA verification of len(sigs) // 160 requests in one launch, one signature per lane.  sigs:
+        the records back to back (bytes), each pubkey_x || pubkey_y || r || s || msghash as 32 little-endian bytes - or a sequence
+        of such 160-byte records.  -> ([bool verdicts], [ZK_ES256_* reasons]); a bad signature is a verdict, not an error."""
+        if not isinstance(sigs, (bytes, bytearray, memoryview)):
+            sigs = b"".join(bytes(r) for r in sigs)
+        sigs = bytes(sigs)
+        if len(sigs) % 160:
+            raise ValueError("a record is 160 bytes")
+        count = len(sigs) // 160
+        verdicts = (ctypes.c_uint8 * max(count, 1))()
+        reasons = (ctypes.c_uint8 * max(count, 1))()
+        self._chk(self.L.zk_es256_verify(self.ctx, count, sigs, verdicts, reasons), "zk_es256_verify")
+        return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
 
     def proof_size_multi(self, pk, n_circuits, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
         ln = ctypes.c_size_t()

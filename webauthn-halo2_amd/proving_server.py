@@ -71,13 +71,18 @@ def setup(device=0, degree=DEGREE, proving_key_path="./keys/proving_key.pk", ver
     return report if check_placement else "Done"
 
 
-def _prove(body, evm, device, degree, rng_seed, check=False, public=False):
+def _prove(body, evm, device, degree, rng_seed, check=False, public=False, signature_ok=None):
     """check=True: the request's advice columns go through the witness check first (ecdsa_p256.WitnessError instead of a proof
     no verifier accepts).  public=True (an extension; the key of setup(public=True)): the proof is bound to the request's msghash
     and public key - the answer is the hex of ecdsa_p256.encode_calldata: the nine instance words, then the proof."""
     q = parse_request(body)
-    fn = ecdsa_p256.generate_proof_evm_synthetic if evm else ecdsa_p256.generate_proof_synthetic
-    proof = fn(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, device, rng_seed, check, public)
+    if signature_ok is None:
+        fn = ecdsa_p256.generate_proof_evm_synthetic if evm else ecdsa_p256.generate_proof_synthetic
+        proof = fn(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, device, rng_seed, check, public)
+    else:  # prove_batch under the device check: this request's signature went through the batch's one launch already
+        transcript = ecdsa_p256.ZK_TRANSCRIPT_EVM if evm else ecdsa_p256.ZK_TRANSCRIPT_BLAKE2B
+        proof = ecdsa_p256._prove_synthetic(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"], q["proving_key_path"], degree, transcript,
+                                            device, rng_seed, check, public, signature_ok=signature_ok)
     if public:
         _, p, _ = ecdsa_p256._resident_key(q["proving_key_path"], degree, device)
         proof = ecdsa_p256.encode_calldata(ecdsa_p256.public_inputs(q["msghash"], q["pubkey_x"], q["pubkey_y"], p.limb_bits, p.num_limbs), proof)
@@ -98,16 +103,29 @@ def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE, public=False):
     """A recorded batch of requests over several GPUs: request i goes to devices[i % len(devices)], and every device proves
     `ecdsa_p256.PIPELINES_PER_DEVICE` of its requests side by side — one host thread per request in flight (the reference:
     one Rocket worker thread per request, main.rs:457-472).  Every device must have been `setup`.  Returns the hex proofs in
-    request order; a failed request yields its exception.  public: prove's - every answer carries its nine instance words."""
+    request order; a failed request yields its exception.  public: prove's - every answer carries its nine instance words.
+    Under ecdsa_p256.set_signature_check("device") the signatures of ALL requests are checked in one launch on devices[0] before any
+    proof starts (a body that does not parse is left to its own slot's error)."""
     bodies = list(bodies)
     out = [None] * len(bodies)
+    checked = [None] * len(bodies)
+    if ecdsa_p256.signature_check() == "device":
+        parsed = []
+        for i, b in enumerate(bodies):
+            try:
+                parsed.append((i, parse_request(b)))
+            except Exception:
+                pass
+        if parsed:
+            for (i, _), ok in zip(parsed, ecdsa_p256.es256_verify_many([q for _, q in parsed], devices[0])):
+                checked[i] = ok
     per = max(1, ecdsa_p256.PIPELINES_PER_DEVICE)
     workers = len(devices) * per
 
     def work(q):
         for i in range(q, len(bodies), workers):
             try:
-                out[i] = _prove(bodies[i], evm, devices[q % len(devices)], degree, None, False, public)
+                out[i] = _prove(bodies[i], evm, devices[q % len(devices)], degree, None, False, public, checked[i])
             except Exception as e:  # the reference answers 500 for that request and keeps serving
                 out[i] = e
 
@@ -217,8 +235,12 @@ def prove_multi(bodies, evm=True, device=0, degree=DEGREE, rng_seed=None, check=
     path = reqs[0]["proving_key_path"]
     if any(q["proving_key_path"] != path for q in reqs):
         raise ValueError("proving_key_path: the requests of one proof name one key")
-    for i, q in enumerate(reqs):
-        if not ecdsa_p256.es256_verify(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]):
+    if ecdsa_p256.signature_check() == "device":  # all bodies in one launch
+        verdicts = ecdsa_p256.es256_verify_many(reqs, device)
+    else:
+        verdicts = (ecdsa_p256.es256_verify(q["pubkey_x"], q["pubkey_y"], q["r"], q["s"], q["msghash"]) for q in reqs)
+    for i, ok in enumerate(verdicts):
+        if not ok:
             raise ValueError(f"request {i}: invalid ES256 signature (or non-canonical field encoding): request refused")
     _, p, _ = ecdsa_p256._resident_key(path, degree, device)
     if bool(p.num_instance_columns) != bool(public):

@@ -46,3 +46,6 @@ echo "built $(pwd)/examples/prove_host"
 # which carry HIP's function attributes — hence hipcc; it links against the same library through the public ABI only
 hipcc --offload-arch=gfx950 -O2 -std=c++17 -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result -x hip examples/prove_host_phases.cpp -Lwebauthn-halo2_amd -lzkmi355 -Wl,-rpath,'$ORIGIN/../webauthn-halo2_amd' -o examples/prove_host_phases
 echo "built $(pwd)/examples/prove_host_phases"
+# the phase-level host for N circuits and public inputs (examples/prove_host_phases_multi.cpp; examples/phase_host.h is shared by the two)
+hipcc --offload-arch=gfx950 -O2 -std=c++17 -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result -x hip examples/prove_host_phases_multi.cpp -Lwebauthn-halo2_amd -lzkmi355 -Wl,-rpath,'$ORIGIN/../webauthn-halo2_amd' -o examples/prove_host_phases_multi
+echo "built $(pwd)/examples/prove_host_phases_multi"

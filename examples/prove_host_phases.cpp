@@ -10,7 +10,8 @@
 //     permutation argument   zk_permutation_product
 //     vanishing argument     zk_random_poly (the host hands over its ChaCha20 key and position), zk_quotient, zk_extended_to_coeff
 //     domain                 zk_lagrange_to_coeff, zk_coeff_to_extended
-//     openings               zk_eval, zk_poly_lincomb, zk_kate_division   (ProverGWC and ProverSHPLONK)
+//     openings               zk_eval, zk_poly_lincomb, zk_kate_division   (ProverGWC and ProverSHPLONK: phase_host.h, shared with
+//                            prove_host_phases_multi.cpp)
 // No column crosses PCIe after the advice upload: the blinding rows go up as 7-row ranges (zk_poly_upload_range).  The proof
 // is byte-identical to zk_prove's with the same key, advice and seed (tests/test_gpu_host_phases.py) — here the seed feeds
 // THIS file's ChaCha20Rng, drawn in halo2's order.
@@ -22,71 +23,16 @@
 // usage: prove_host_phases <srs.bin> <pk.bin> <advice.bin> <proof.out> k num_advice num_lookup_advice num_fixed lookup_bits idle
 //                          <transcript: blake2b|evm> <rng seed: 64 hex digits> [gwc|shplonk]
 //   multi-open: the reference's pairings by default — GWC under the EVM transcript (ecdsa_p256.rs:368), SHPLONK under Blake2b (:418)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <algorithm>
-#include <string>
-#include <utility>
-#include <vector>
+#include "phase_host.h"
 
-#include "../include/zkmi355.h"
-#include "../webauthn-halo2_amd/csrc/transcript.h"
-
-using namespace zk;
-
-static std::vector<uint8_t> slurp(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) {
-        fprintf(stderr, "prove_host_phases: cannot open %s\n", path);
-        exit(2);
-    }
-    fseek(f, 0, SEEK_END);
-    const long len = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    std::vector<uint8_t> buf((size_t)len);
-    if (len && fread(buf.data(), 1, (size_t)len, f) != (size_t)len) {
-        fprintf(stderr, "prove_host_phases: short read of %s\n", path);
-        exit(2);
-    }
-    fclose(f);
-    return buf;
-}
-
-static zk_ctx* ctx = nullptr;
-#define CHECK(call)                                                                                                      \
-    do {                                                                                                                 \
-        const int rc_ = (call);                                                                                          \
-        if (rc_ != ZK_OK) {                                                                                              \
-            fprintf(stderr, "prove_host_phases: %s failed: %d (%s)\n", #call, rc_, zk_strerror(rc_));                    \
-            exit(1);                                                                                                     \
-        }                                                                                                                \
-    } while (0)
-
-static const uint64_t* limbs(const Fr& a) { return reinterpret_cast<const uint64_t*>(a.v); }
-static zk_poly alloc(size_t n) {
-    zk_poly p = 0;
-    CHECK(zk_poly_alloc(ctx, n, &p));
-    return p;
-}
 static Fr eval(zk_poly p, const Fr& x) {
     Fr out;
     CHECK(zk_eval(ctx, p, limbs(x), reinterpret_cast<uint64_t*>(out.v)));
     return out;
 }
-// commits `polys` and writes the points to the transcript, in order
-static void commit_write(Transcript& tr, const std::vector<zk_poly>& polys, int basis) {
-    std::vector<G1Affine> pts(polys.size());
-    CHECK(zk_commit_batch(ctx, polys.data(), polys.size(), basis, reinterpret_cast<uint64_t*>(pts.data())));
-    for (const G1Affine& p : pts)
-        if (!tr.write_point(p)) {
-            fprintf(stderr, "prove_host_phases: a commitment is the identity\n");
-            exit(1);
-        }
-}
 
 int main(int argc, char** argv) {
+    prog = "prove_host_phases";
     if (argc != 13 && argc != 14) {
         fprintf(stderr, "usage: %s srs.bin pk.bin advice.bin proof.out k A L F lookup_bits idle blake2b|evm seedhex [gwc|shplonk]\n", argv[0]);
         return 2;
@@ -102,12 +48,7 @@ int main(int argc, char** argv) {
     const bool evm = strcmp(argv[11], "evm") == 0;
     const bool shplonk = argc == 14 ? strcmp(argv[13], "shplonk") == 0 : !evm;
     uint8_t seed[32];
-    if (strlen(argv[12]) != 64) return 2;
-    for (int i = 0; i < 32; i++) {
-        unsigned v;
-        sscanf(argv[12] + 2 * i, "%2x", &v);
-        seed[i] = (uint8_t)v;
-    }
+    if (!parse_seed(argv[12], seed)) return 2;
     CHECK(zk_ctx_create(0, &ctx));
     {
         const std::vector<uint8_t> srs = slurp(argv[1]);
@@ -132,8 +73,8 @@ int main(int argc, char** argv) {
         uint32_t counts[2];
         CHECK(zk_vk_export(ctx, pk, nullptr, nullptr, reinterpret_cast<uint64_t*>(repr.v), counts));
     }
-    const Fr omega = fr_omega(k), omega_inv = fe_inv(omega);
-    auto xrot = [&](const Fr& x, int r) { return fe_mul(x, fe_pow_u64(r >= 0 ? omega : omega_inv, (uint64_t)(r >= 0 ? r : -r))); };
+    const Rotations xrot(k);
+    const size_t calls_before = abi_calls;  // what follows is the proof
 
     EvmTranscript evm_tr;
     Blake2bTranscript b2_tr;
@@ -271,11 +212,6 @@ int main(int argc, char** argv) {
         }
         CHECK(zk_poly_lincomb(ctx, h_comb, h_piece.data(), reinterpret_cast<const uint64_t*>(c.data()), n_h, nullptr, 0));
     }
-    struct Q {
-        zk_poly poly;
-        int rot;
-        Fr eval;
-    };
     std::vector<Q> ev;
     for (uint32_t j = 0; j < A; j++)
         for (int r = 0; r < 4; r++) ev.push_back(Q{adv_p[j], r, Fr::zero()});
@@ -305,7 +241,7 @@ int main(int argc, char** argv) {
     for (Q& q : ev) q.eval = eval(q.poly, xrot(x, q.rot));
     for (size_t i = 0; i < n_written; i++) tr.write_scalar(ev[i].eval);
 
-    // ---- 7. multi-open (ProverGWC): queries in the prover's order, one witness polynomial per distinct rotation
+    // ---- 7. multi-open (ProverGWC or ProverSHPLONK, phase_host.h): queries in the prover's order
     std::vector<Q> queries(ev.begin(), ev.begin() + i_fix);
     {
         std::vector<Q> lastq(n_chunks);
@@ -329,189 +265,7 @@ int main(int argc, char** argv) {
         queries.push_back(ev[n_written]);  // h
         queries.push_back(ev[i_rand]);     // the random polynomial
     }
-    if (!shplonk) {
-        const Fr v = tr.squeeze();
-        std::vector<std::pair<int, std::vector<Q>>> sets;
-        for (const Q& q : queries) {
-            bool found = false;
-            for (auto& s : sets)
-                if (s.first == q.rot) {
-                    s.second.push_back(q);
-                    found = true;
-                    break;
-                }
-            if (!found) sets.push_back({q.rot, {q}});
-        }
-        std::vector<zk_poly> wit;
-        for (auto& s : sets) {
-            // (sum_i v^i p_i(X) - sum_i v^i e_i) / (X - x w^rot).  A polynomial opened twice in one set (none here) would appear twice.
-            std::vector<zk_poly> in;
-            std::vector<Fr> c;
-            Fr pv = Fr::one(), eb = Fr::zero();
-            for (const Q& q : s.second) {
-                in.push_back(q.poly);
-                c.push_back(pv);
-                eb = fe_add(eb, fe_mul(pv, q.eval));
-                pv = fe_mul(pv, v);
-            }
-            zk_poly w = alloc(n);
-            CHECK(zk_poly_lincomb(ctx, w, in.data(), reinterpret_cast<const uint64_t*>(c.data()), in.size(), limbs(eb), 1));
-            const Fr pt = xrot(x, s.first);
-            CHECK(zk_kate_division(ctx, w, limbs(pt), w));
-            wit.push_back(w);
-        }
-        commit_write(tr, wit, ZK_BASIS_MONOMIAL);
-    } else {
-        // ---- 7'. multi-open (ProverSHPLONK): polynomials grouped by their set of rotations; h(X) = sum_i v^i (sum_j y^j (P_ij - R_ij)) / Z_i
-        struct CR {
-            zk_poly poly;
-            std::vector<int> rots;
-            std::vector<Fr> evals;
-        };
-        std::vector<CR> com;
-        for (const Q& q : queries) {
-            size_t at = com.size();
-            for (size_t i = 0; i < com.size(); i++)
-                if (com[i].poly == q.poly) at = i;
-            if (at == com.size()) com.push_back(CR{q.poly, {}, {}});
-            com[at].rots.push_back(q.rot);
-            com[at].evals.push_back(q.eval);
-        }
-        auto canon_less = [&](int ra, int rb) {  // BTreeSet<Fr>: the points ordered by their canonical integer value
-            const Fr a = fe_from_mont(xrot(x, ra)), b = fe_from_mont(xrot(x, rb));
-            for (int i = 7; i >= 0; i--)
-                if (a.v[i] != b.v[i]) return a.v[i] < b.v[i];
-            return false;
-        };
-        struct RS {
-            std::vector<int> rots;
-            std::vector<size_t> coms;
-        };
-        std::vector<RS> rsets;
-        std::vector<int> all_rots;
-        for (size_t ci = 0; ci < com.size(); ci++) {
-            CR& cr = com[ci];
-            std::vector<size_t> order(cr.rots.size());
-            for (size_t i = 0; i < order.size(); i++) order[i] = i;
-            std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return canon_less(cr.rots[a], cr.rots[b]); });
-            std::vector<int> r2;
-            std::vector<Fr> e2;
-            for (size_t i : order) {
-                r2.push_back(cr.rots[i]);
-                e2.push_back(cr.evals[i]);
-            }
-            cr.rots = r2;
-            cr.evals = e2;
-            for (int r : cr.rots)
-                if (std::find(all_rots.begin(), all_rots.end(), r) == all_rots.end()) all_rots.push_back(r);
-            size_t hit = rsets.size();
-            for (size_t si = 0; si < rsets.size(); si++)
-                if (rsets[si].rots == cr.rots) hit = si;
-            if (hit == rsets.size()) rsets.push_back(RS{cr.rots, {}});
-            rsets[hit].coms.push_back(ci);
-        }
-        std::sort(all_rots.begin(), all_rots.end(), canon_less);
-        const Fr yc = tr.squeeze(), v = tr.squeeze();
-        // the Lagrange basis over a set's points as coefficient vectors, one inversion for all denominators (lagrange_interpolate)
-        auto lagrange_basis = [&](const std::vector<Fr>& pts) {
-            const size_t m = pts.size();
-            std::vector<std::vector<Fr>> basis(m);
-            std::vector<Fr> den(m, Fr::one());
-            for (size_t j = 0; j < m; j++) {
-                std::vector<Fr> num(1, Fr::one());
-                for (size_t i = 0; i < m; i++) {
-                    if (i == j) continue;
-                    std::vector<Fr> nn(num.size() + 1, Fr::zero());
-                    for (size_t t = 0; t < num.size(); t++) {
-                        nn[t + 1] = fe_add(nn[t + 1], num[t]);
-                        nn[t] = fe_sub(nn[t], fe_mul(pts[i], num[t]));
-                    }
-                    num.swap(nn);
-                    den[j] = fe_mul(den[j], fe_sub(pts[j], pts[i]));
-                }
-                basis[j] = num;
-            }
-            for (size_t j = 0; j < m; j++) {
-                const Fr dj = fe_inv(den[j]);
-                for (Fr& cf : basis[j]) cf = fe_mul(cf, dj);
-            }
-            return basis;
-        };
-        std::vector<std::vector<Fr>> low(com.size());  // every polynomial's remainder over its set's points
-        std::vector<zk_poly> sbuf;
-        for (RS& rs : rsets) {
-            std::vector<Fr> pts;
-            for (int r : rs.rots) pts.push_back(xrot(x, r));
-            const std::vector<std::vector<Fr>> basis = lagrange_basis(pts);
-            std::vector<zk_poly> in;
-            std::vector<Fr> c, rsum(pts.size(), Fr::zero());
-            Fr py = Fr::one();
-            for (size_t ci : rs.coms) {
-                std::vector<Fr>& lo = low[ci];
-                lo.assign(pts.size(), Fr::zero());
-                for (size_t j = 0; j < pts.size(); j++)
-                    for (size_t t = 0; t < pts.size(); t++) lo[t] = fe_add(lo[t], fe_mul(basis[j][t], com[ci].evals[j]));
-                in.push_back(com[ci].poly);
-                c.push_back(py);
-                for (size_t t = 0; t < pts.size(); t++) rsum[t] = fe_add(rsum[t], fe_mul(py, lo[t]));
-                py = fe_mul(py, yc);
-            }
-            zk_poly sb = alloc(n);
-            CHECK(zk_poly_lincomb(ctx, sb, in.data(), reinterpret_cast<const uint64_t*>(c.data()), in.size(),
-                                  reinterpret_cast<const uint64_t*>(rsum.data()), rsum.size()));
-            for (const Fr& pt : pts) CHECK(zk_kate_division(ctx, sb, limbs(pt), sb));  // exact: the numerator vanishes on the set
-            sbuf.push_back(sb);
-        }
-        zk_poly hx = alloc(n);
-        {
-            std::vector<Fr> c;
-            Fr pv = Fr::one();
-            for (size_t si = 0; si < rsets.size(); si++) {
-                c.push_back(pv);
-                pv = fe_mul(pv, v);
-            }
-            CHECK(zk_poly_lincomb(ctx, hx, sbuf.data(), reinterpret_cast<const uint64_t*>(c.data()), sbuf.size(), nullptr, 0));
-        }
-        commit_write(tr, {hx}, ZK_BASIS_MONOMIAL);
-        const Fr u = tr.squeeze();
-        // L(X) = sum_i v^i z_i(u) sum_j y^j (P_ij(X) - R_ij(u)) - Z_T(u) h(X);  the proof's last point commits to L(X) / ((X - u) z_0(u))
-        auto vanishing_eval = [&](const std::vector<Fr>& pts, const Fr& at) {
-            Fr acc = Fr::one();
-            for (const Fr& p : pts) acc = fe_mul(acc, fe_sub(at, p));
-            return acc;
-        };
-        std::vector<zk_poly> in;
-        std::vector<Fr> c, z_diffs;
-        Fr sub = Fr::zero(), pv = Fr::one();
-        for (RS& rs : rsets) {
-            std::vector<Fr> diffs;
-            for (int r : all_rots)
-                if (std::find(rs.rots.begin(), rs.rots.end(), r) == rs.rots.end()) diffs.push_back(xrot(x, r));
-            const Fr zi = vanishing_eval(diffs, u);
-            z_diffs.push_back(zi);
-            Fr py = Fr::one();
-            for (size_t ci : rs.coms) {
-                const Fr coef = fe_mul(fe_mul(pv, zi), py);
-                in.push_back(com[ci].poly);
-                c.push_back(coef);
-                Fr ru = Fr::zero();  // R_ij(u)
-                for (size_t t = low[ci].size(); t-- > 0;) ru = fe_add(fe_mul(ru, u), low[ci][t]);
-                sub = fe_add(sub, fe_mul(coef, ru));
-                py = fe_mul(py, yc);
-            }
-            pv = fe_mul(pv, v);
-        }
-        std::vector<Fr> all_pts;
-        for (int r : all_rots) all_pts.push_back(xrot(x, r));
-        in.push_back(hx);
-        c.push_back(fe_neg(vanishing_eval(all_pts, u)));
-        zk_poly lx = alloc(n), fin = alloc(n);
-        CHECK(zk_poly_lincomb(ctx, lx, in.data(), reinterpret_cast<const uint64_t*>(c.data()), in.size(), limbs(sub), 1));
-        CHECK(zk_kate_division(ctx, lx, limbs(u), lx));
-        const Fr zinv = fe_inv(z_diffs[0]);
-        CHECK(zk_poly_lincomb(ctx, fin, &lx, limbs(zinv), 1, nullptr, 0));
-        commit_write(tr, {fin}, ZK_BASIS_MONOMIAL);
-    }
+    multi_open(tr, queries, x, n, xrot, shplonk);
 
     FILE* out = fopen(argv[4], "wb");
     if (!out || fwrite(tr.out.data(), 1, tr.out.size(), out) != tr.out.size()) {
@@ -520,6 +274,7 @@ int main(int argc, char** argv) {
     }
     fclose(out);
     printf("prove_host_phases: %zu proof bytes\n", tr.out.size());
+    fprintf(stderr, "prove_host_phases: %zu ABI calls for the proof\n", abi_calls - calls_before);
     zk_pk_free(ctx, pk);
     zk_ctx_destroy(ctx);  // (frees every vector of the context)
     return 0;

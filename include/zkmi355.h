@@ -144,7 +144,7 @@ int zk_sync(zk_ctx* ctx);                 /* hipStreamSynchronize on the context
                                         more (the proving server's k = 17 among them; the many-column rows below lose by it), 1 = always the
                                         whole extended domain (round 5's route), 2 = three cosets wherever h has three pieces.
                                         zk_prove_batch follows the same rule; the phase-level entry points (zk_coeff_to_extended, zk_quotient,
-                                        zk_extended_to_coeff) always work on the whole domain in halo2's order */
+                                        zk_quotient_multi, zk_extended_to_coeff) always work on the whole domain in halo2's order */
 #define ZK_OPT_ACTIVITY_HOLD 14      /* how a context inside zk_prove / zk_prove_batch counts for the automatic stream rules of the OTHER contexts
                                         of its device (ZK_OPT_MSM_TAIL_STREAM, ZK_OPT_XFORM_STREAM): 0 (default) active for the whole call — its
                                         quotient / evaluation / multi-open phases enqueue no MSM pass for longer than the 4 ms window under load,
@@ -314,6 +314,14 @@ int zk_coeff_to_extended(zk_ctx* ctx, zk_poly src, zk_poly dst_ext);
 int zk_extended_to_coeff(zk_ctx* ctx, zk_poly ext, size_t n_out);
 /* replaces arithmetic::eval_polynomial(poly, x) */
 int zk_eval(zk_ctx* ctx, zk_poly p, const uint64_t x_mont[4], uint64_t out_mont[4]);
+/* `count` >= 1 evaluations in one call: out_mont[4 i ..] = polys[i](points_mont[4 i ..]), each bit-identical to zk_eval of its pair.
+ * It is the whole-proof provers' batched evaluation (one launch and one wait per 64 pairs; further pairs take further launches
+ * inside the call), so a phase-driving host reads all opened values of a proof - of N circuits' columns - with one call instead of
+ * one zk_eval and one wait each.  Handles may repeat (a polynomial opened at several rotations).  That launch takes ONE length:
+ * every polynomial must have the same number of coefficients (ZK_EINVAL otherwise, as for count == 0, a bad handle or a NULL
+ * argument); out_mont is written only when every pair has been evaluated. */
+int zk_eval_batch(zk_ctx* ctx, const zk_poly* polys, const uint64_t* points_mont /* count x 4 */, size_t count,
+                  uint64_t* out_mont /* count x 4 */);
 /* replaces arithmetic::kate_division(p, z): q = (p - p(z)) / (X - z).  q has p's length (its top coefficient is 0: the
  * quotient is one coefficient shorter); q may be p (in place).  The multi-open provers (GWC / SHPLONK) divide with it. */
 int zk_kate_division(zk_ctx* ctx, zk_poly p, const uint64_t z_mont[4], zk_poly q);
@@ -392,6 +400,25 @@ int zk_pk_num_instance_columns(zk_ctx* ctx, zk_pk pk, uint32_t* out);
 int zk_quotient(zk_ctx* ctx, zk_pk pk, const zk_poly* advice_ext, size_t n_advice, const zk_poly* perm_z_ext, size_t n_chunks,
                 const zk_poly* lookup_ext, size_t n_lookups, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4],
                 int divide, zk_poly out_ext);
+/* zk_quotient for ONE proof over n_circuits circuits of the key (1 .. ZK_PROVE_MULTI_MAX), with their public inputs where the key has
+ * the instance column: the h of zk_prove_public / zk_prove_multi / zk_prove_multi_public.  Every handle array is circuit-major,
+ * circuit 0 first: advice_ext n_circuits x n_advice, perm_z_ext n_circuits x n_chunks, lookup_ext n_circuits x 3 n_lookups (per
+ * lookup a', s', zL), instance_ext n_circuits - circuit c's instance polynomial on the extended coset.  The y-combination runs on
+ * through the circuits in order into ONE h, h = sum_c y^(T (N - 1 - c)) h_c with T the terms of one circuit: circuit 0's pass stores,
+ * every later pass adds its own terms (the accumulating pass of zk_prove_multi; no linear combination of N quotients is formed);
+ * `divide` applies to every pass.  n_circuits == 1 on a key without the column gives zk_quotient's bytes.
+ * The instance vector of a circuit is built with the calls above: zk_poly_alloc(n) and a zeroed host column with the Montgomery
+ * values in rows 0 .. m - 1 through zk_poly_upload (or canonical integers through zk_poly_upload_canonical; zk_poly_upload_range
+ * writes rows 0 .. m - 1 of a vector that is already zero) - that Lagrange vector is zk_permutation_product_public's `instance`;
+ * a copy of it through zk_lagrange_to_coeff and zk_coeff_to_extended is the handle of instance_ext.  Nothing of it is blinded.
+ * ZK_EINVAL: n_circuits outside 1 .. ZK_PROVE_MULTI_MAX, a count that is not the shape's, a handle that is not a 2^(k+2) vector,
+ * out_ext among the inputs (checked before anything is launched), instance_ext != NULL for a key without the column or NULL for
+ * a key with it (the whole-proof rule, halo2's InvalidInstances); ZK_ESTATE: a verifying-only key, or a key whose SRS was replaced.
+ * zk_quotient itself keeps returning ZK_EINVAL on a key with the column. */
+int zk_quotient_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const zk_poly* advice_ext /* n_circuits x n_advice */, size_t n_advice,
+                      const zk_poly* instance_ext /* n_circuits, or NULL */, const zk_poly* perm_z_ext /* n_circuits x n_chunks */,
+                      size_t n_chunks, const zk_poly* lookup_ext /* n_circuits x 3 n_lookups */, size_t n_lookups, const uint64_t beta[4],
+                      const uint64_t gamma[4], const uint64_t y[4], int divide, zk_poly out_ext);
 /* ---- the provers between the commitments, for a host that drives the phases itself (its transcript, its RNG, its blinding:
  * examples/prove_host_phases.cpp builds a whole proof from these and the calls above) ------------------------------------------
  * replaces plonk::lookup::prover's `permute_expression_pair` for every lookup of the key (halo2_proofs
@@ -408,6 +435,17 @@ int zk_lookup_product(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_adv
  * (zk_pk_shape), chunk c starting from chunk c - 1's value at the last usable row (rows 0 .. n - 7; the host blinds the rest) */
 int zk_permutation_product(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, const uint64_t beta[4],
                            const uint64_t gamma[4], zk_poly* z_out /* n_chunks */, size_t n_chunks);
+/* the same for a key WITH the instance column (zk_circuit_params.num_instance_columns = 1): `instance` is a resident vector of n
+ * rows, Lagrange values as Montgomery images - the public inputs in rows 0 .. m - 1, zero in every other row (how to build it:
+ * zk_quotient_multi above) - and enters the product as the LAST permutation column, unblinded, as in zk_prove_public.  The chunks
+ * and the start of chunk c from chunk c - 1 are zk_permutation_product's.  One call serves one circuit: a host proving N circuits
+ * calls it once per circuit with that circuit's advice and instance vector.  For a key WITHOUT the column `instance` must be 0 and
+ * the result is zk_permutation_product's, byte for byte.  ZK_EINVAL beyond zk_permutation_product's cases: no instance vector for a
+ * key with the column, one for a key without (the whole-proof rule, halo2's InvalidInstances), a vector of another length, the
+ * instance vector among z_out (checked before anything is launched).  zk_permutation_product itself keeps returning ZK_EINVAL on a
+ * key with the column. */
+int zk_permutation_product_public(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, zk_poly instance, const uint64_t beta[4],
+                                  const uint64_t gamma[4], zk_poly* z_out /* n_chunks */, size_t n_chunks);
 /* a copy of one of the key's own polynomials (coefficient form, n coefficients) into the caller's vector: the fixed columns
  * (index in QUERY order: constants, lookup table, selector columns — the order of the fixed evaluations in a proof) and the
  * permutation polynomials sigma (permutation-column order) that create_proof evaluates at x and opens (`pk.fixed_polys`,
@@ -452,8 +490,9 @@ int zk_prove(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, cons
  * The batch and multi forms WITH instances are zk_prove_batch_public, zk_prove_multi_public, zk_verify_batch_public and
  * zk_verify_multi_public below.  zk_prove_batch, zk_prove_multi, zk_verify_batch, zk_verify_multi - and zk_prove, zk_verify,
  * zk_witness_check - carry none and return ZK_EINVAL on a key with the column.
- * OUT OF SCOPE: the phase-level zk_permutation_product / zk_quotient carry no instances and return ZK_EINVAL on such a key; more than
- * one instance column; batches of multi proofs.
+ * The phase-level forms WITH instances are zk_permutation_product_public and zk_quotient_multi (examples/prove_host_phases_multi.cpp
+ * builds these proofs from them); zk_permutation_product / zk_quotient carry none and return ZK_EINVAL on such a key.
+ * OUT OF SCOPE: more than one instance column; batches of multi proofs.
  * Every other entry point (zk_lookup_permute, zk_lookup_product, the file and key functions, zk_pk_check) works on such a key. */
 int zk_prove_public(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice,
                     const uint64_t* instance_mont /* n_instance x 4 */, size_t n_instance, const uint8_t rng_seed[32], int transcript,

@@ -136,6 +136,7 @@ struct zk_ctx : SrsView {
     struct VerifyWs* vws = nullptr;  // zk_verify_batch's device buffers (verify.hip), grow-only
     struct Es256Ws* es256 = nullptr;  // zk_es256_verify's comb table of G and staging buffers (es256.hip), made on first use
     Fr* host_small = nullptr;  // pinned, 8 elements
+    void* eval_batch_host = nullptr;  // pinned: zk_eval_batch's items and results (prover_phases.hip), made on first use
     // polys
     std::unordered_map<uint64_t, PolyRec> polys;
     // vectors given back by zk_poly_free, handed out again by zk_poly_alloc for the same length: hipFree waits for the whole

@@ -286,6 +286,7 @@ void zk_ctx_destroy(zk_ctx* c) {
         if (L.tail_done) hipEventDestroy(L.tail_done);
     }
     if (c->host_small) hipHostFree(c->host_small);
+    if (c->eval_batch_host) hipHostFree(c->eval_batch_host);
     if (c->scratch) hipFree(c->scratch);
     for (int i = 0; i < 2; i++)
         if (c->seam_buf[i]) hipFree(c->seam_buf[i]);

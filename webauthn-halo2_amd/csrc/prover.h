@@ -189,6 +189,8 @@ struct EvalItem {
 void launch_eval_batch(EvalItem* h_items, EvalItem* d_items, uint32_t count, uint32_t n, Fr* scratch, Fr* out,
                        hipStream_t st);
 uint32_t eval_blocks(uint32_t n);
+// pairs per launch of zk_eval_batch (its staging is sized for them; more pairs take further launches inside the call)
+#define EVAL_BATCH_PAIRS 64
 void launch_eval(const Fr* c, uint32_t n, const Fr& x, Fr* scratch, hipStream_t st);
 
 }  // namespace zk

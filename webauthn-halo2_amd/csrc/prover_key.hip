@@ -739,7 +739,13 @@ ZK_API(zk_pk_shape, (zk_ctx* c, zk_pk h, uint32_t out[8]), (c, h, out)) {
     return ZK_OK;
 }
 
-ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_advice, const zk_poly* perm_z_ext, size_t n_chunks, const zk_poly* lookup_ext, size_t n_lookups, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], int divide, zk_poly out_ext), (c, h, advice_ext, n_advice, perm_z_ext, n_chunks, lookup_ext, n_lookups, beta, gamma, y, divide, out_ext)) {
+// zk_quotient and zk_quotient_multi: n_circuits passes into ONE h — circuit 0 the plain kernel, circuits 1 .. N - 1 the
+// accumulating one, each with its own powers of y (prover_multi.h's chain: pass q carries y^(T (N - 1 - q))).  `with_instance`
+// false: the key must have no instance column (zk_quotient); true: instance_ext holds one coset per circuit for a key with the
+// column and is null for a key without
+static int quotient_passes(zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice_ext, size_t n_advice, bool with_instance,
+                           const zk_poly* instance_ext, const zk_poly* perm_z_ext, size_t n_chunks, const zk_poly* lookup_ext, size_t n_lookups,
+                           const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], int divide, zk_poly out_ext) {
     if (!c || !advice_ext || !perm_z_ext || !lookup_ext || !beta || !gamma || !y) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     auto it = c->pks.find(h);
@@ -747,35 +753,61 @@ ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_adv
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
     if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;
+    if (n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
     if (n_advice != lay.n_adv || n_chunks != lay.n_chunks || n_lookups != lay.n_lookups) return ZK_EINVAL;
-    if (lay.n_inst) return ZK_EINVAL;  // (the phase-level forms carry no instance column)
+    if (lay.n_inst && !with_instance) return ZK_EINVAL;  // (zk_quotient carries no instance column)
+    if (with_instance && (instance_ext != nullptr) != (lay.n_inst != 0)) return ZK_EINVAL;  // (the whole-proof rule: InvalidInstances)
     const size_t N = (size_t)4 * lay.n;
     auto ext = [&](zk_poly p) -> Fr* {
         const PolyRec* q = ctx_poly(c, p);
         return (!q || q->n != N) ? nullptr : q->ptr;
     };
-    QuotientCosets qc;
-    for (size_t j = 0; j < n_advice; j++) qc.adv.push_back(ext(advice_ext[j]));
-    for (size_t j = 0; j < n_chunks; j++) qc.z.push_back(ext(perm_z_ext[j]));
-    for (size_t l = 0; l < n_lookups; l++) {
-        qc.lk_a.push_back(ext(lookup_ext[3 * l]));
-        qc.lk_s.push_back(ext(lookup_ext[3 * l + 1]));
-        qc.lk_z.push_back(ext(lookup_ext[3 * l + 2]));
-    }
     Fr* out = ext(out_ext);
     if (!out) return ZK_EINVAL;
-    for (auto* v : {&qc.adv, &qc.z, &qc.lk_a, &qc.lk_s, &qc.lk_z})
-        for (const Fr* p : *v)
-            if (!p || p == out) return ZK_EINVAL;
+    std::vector<QuotientCosets> qcs(n_circuits);
+    for (size_t q = 0; q < n_circuits; q++) {
+        QuotientCosets& qc = qcs[q];
+        for (size_t j = 0; j < n_advice; j++) qc.adv.push_back(ext(advice_ext[q * n_advice + j]));
+        for (size_t j = 0; j < n_chunks; j++) qc.z.push_back(ext(perm_z_ext[q * n_chunks + j]));
+        for (size_t l = 0; l < n_lookups; l++) {
+            const zk_poly* t = lookup_ext + 3 * (q * n_lookups + l);
+            qc.lk_a.push_back(ext(t[0]));
+            qc.lk_s.push_back(ext(t[1]));
+            qc.lk_z.push_back(ext(t[2]));
+        }
+        if (lay.n_inst) {
+            qc.inst = ext(instance_ext[q]);
+            if (!qc.inst || qc.inst == out) return ZK_EINVAL;
+        }
+        for (auto* v : {&qc.adv, &qc.z, &qc.lk_a, &qc.lk_s, &qc.lk_z})
+            for (const Fr* p : *v)
+                if (!p || p == out) return ZK_EINVAL;
+    }
     Fr b, g, yy;
     memcpy(&b, beta, 32);
     memcpy(&g, gamma, 32);
     memcpy(&yy, y, 32);
     int rc = ctx_bind(c);
     if (rc) return rc;
-    if ((rc = pk_quotient(c, pk, qc, b, g, yy, divide != 0, out))) return rc;
-    HIPCHK(c, aud_sync(c, c->stream));  // the argument block is reused by the next call
+    std::vector<Fr> scale(n_circuits);
+    scale[n_circuits - 1] = Fr::one();
+    if (n_circuits > 1) {
+        const Fr yT = fe_pow_u64(yy, quotient_terms(lay.n_gate, lay.n_chunks, lay.n_lookups));
+        for (size_t q = n_circuits - 1; q-- > 0;) scale[q] = fe_mul(scale[q + 1], yT);
+    }
+    for (size_t q = 0; q < n_circuits; q++) {
+        if ((rc = pk_quotient_pass(c, pk, qcs[q], b, g, yy, scale[q], q > 0, divide != 0, out))) return rc;
+        HIPCHK(c, aud_sync(c, c->stream));  // the argument block is reused by the next pass and the next call
+    }
     return ZK_OK;
+}
+
+ZK_API(zk_quotient, (zk_ctx* c, zk_pk h, const zk_poly* advice_ext, size_t n_advice, const zk_poly* perm_z_ext, size_t n_chunks, const zk_poly* lookup_ext, size_t n_lookups, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], int divide, zk_poly out_ext), (c, h, advice_ext, n_advice, perm_z_ext, n_chunks, lookup_ext, n_lookups, beta, gamma, y, divide, out_ext)) {
+    return quotient_passes(c, h, 1, advice_ext, n_advice, false, nullptr, perm_z_ext, n_chunks, lookup_ext, n_lookups, beta, gamma, y, divide, out_ext);
+}
+
+ZK_API(zk_quotient_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice_ext, size_t n_advice, const zk_poly* instance_ext, const zk_poly* perm_z_ext, size_t n_chunks, const zk_poly* lookup_ext, size_t n_lookups, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t y[4], int divide, zk_poly out_ext), (c, h, n_circuits, advice_ext, n_advice, instance_ext, perm_z_ext, n_chunks, lookup_ext, n_lookups, beta, gamma, y, divide, out_ext)) {
+    return quotient_passes(c, h, n_circuits, advice_ext, n_advice, true, instance_ext, perm_z_ext, n_chunks, lookup_ext, n_lookups, beta, gamma, y, divide, out_ext);
 }
 
 ZK_API(zk_pk_set_transcript_repr, (zk_ctx* c, zk_pk h, const uint64_t transcript_repr[4]), (c, h, transcript_repr)) {

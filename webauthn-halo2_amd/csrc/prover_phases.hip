@@ -115,7 +115,11 @@ ZK_API(zk_lookup_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_a
     return phase_grand_products(c, pk, z, 0);
 }
 
-ZK_API(zk_permutation_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint64_t beta[4], const uint64_t gamma[4], zk_poly* z_out, size_t n_chunks), (c, h, advice, n_advice, beta, gamma, z_out, n_chunks)) {
+namespace {
+// zk_permutation_product and zk_permutation_product_public: `with_instance` says which rule the key's instance column follows —
+// false: the key must have none; true: `instance` is the column of a key that has one and 0 for a key that has none
+int permutation_product(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, bool with_instance, zk_poly instance, const uint64_t beta[4],
+                        const uint64_t gamma[4], zk_poly* z_out, size_t n_chunks) {
     if (!c || !advice || !beta || !gamma || !z_out) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     PhaseCtx P;
@@ -124,7 +128,13 @@ ZK_API(zk_permutation_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_
     zk_pk_rec* pk = P.pk;
     const Layout& lay = pk->lay;
     if (n_chunks != lay.n_chunks) return ZK_EINVAL;
-    if (lay.n_inst) return ZK_EINVAL;  // (the phase-level forms carry no instance column)
+    if (lay.n_inst && !with_instance) return ZK_EINVAL;  // (zk_permutation_product carries no instance column)
+    const Fr* inst = nullptr;
+    if (with_instance) {
+        // the whole-proof rule (halo2's InvalidInstances): a column for a key with one, none for a key without
+        if ((instance != 0) != (lay.n_inst != 0)) return ZK_EINVAL;
+        if (lay.n_inst && !(inst = phase_vec(c, instance, lay.n))) return ZK_EINVAL;
+    }
     Fr b, g;
     memcpy(&b, beta, 32);
     memcpy(&g, gamma, 32);
@@ -138,10 +148,67 @@ ZK_API(zk_permutation_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_
     }
     {
         std::vector<const Fr*> outs(z.begin(), z.end()), ins(P.adv.begin(), P.adv.end());
-        if (!phase_outputs_ok(outs, ins)) return ZK_EINVAL;  // (before the first launch: a repeated z, an advice column as z)
+        if (inst) ins.push_back(inst);
+        if (!phase_outputs_ok(outs, ins)) return ZK_EINVAL;  // (before the first launch: a repeated z, an advice or the instance column as z)
     }
-    if ((rc = perm_numden_enqueue(c, c->stream, pk, P.adv.data(), tw, b, g, false))) return rc;  // (one launch per chunk, as above)
+    if ((rc = perm_numden_enqueue(c, c->stream, pk, P.adv.data(), tw, b, g, false, inst))) return rc;  // (one launch per chunk, as above)
     return phase_grand_products(c, pk, z, lay.n_chunks);
+}
+}  // namespace
+
+ZK_API(zk_permutation_product, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, const uint64_t beta[4], const uint64_t gamma[4], zk_poly* z_out, size_t n_chunks), (c, h, advice, n_advice, beta, gamma, z_out, n_chunks)) {
+    return permutation_product(c, h, advice, n_advice, false, 0, beta, gamma, z_out, n_chunks);
+}
+
+ZK_API(zk_permutation_product_public, (zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, zk_poly instance, const uint64_t beta[4], const uint64_t gamma[4], zk_poly* z_out, size_t n_chunks), (c, h, advice, n_advice, instance, beta, gamma, z_out, n_chunks)) {
+    return permutation_product(c, h, advice, n_advice, true, instance, beta, gamma, z_out, n_chunks);
+}
+
+// `count` (polynomial, point) pairs through the provers' batched evaluation step (evaluate_enqueue: one launch and one host
+// round trip for up to EVAL_BATCH_PAIRS pairs), over staging the context keeps: pinned items and results, their device twins
+// in the context's scratch.  Nothing is written to `out` before every pair is evaluated.
+ZK_API(zk_eval_batch, (zk_ctx* c, const zk_poly* polys, const uint64_t* points, size_t count, uint64_t* out), (c, polys, points, count, out)) {
+    if (!c || !polys || !points || !out || count == 0) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::vector<const Fr*> ptr(count);
+    size_t n = 0;
+    for (size_t i = 0; i < count; i++) {
+        const PolyRec* r = ctx_poly(c, polys[i]);
+        if (!r || r->n == 0 || r->n > 0xffffffffu || (i && r->n != n)) return ZK_EINVAL;  // (the step takes ONE length per launch)
+        n = r->n;
+        ptr[i] = r->ptr;
+    }
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    constexpr size_t PAIRS = EVAL_BATCH_PAIRS;
+    const size_t item_words = (PAIRS * sizeof(EvalItem) + sizeof(Fr) - 1) / sizeof(Fr);  // the device items, in elements of the scratch
+    const uint32_t blocks = eval_blocks((uint32_t)n);
+    if (!c->eval_batch_host) {
+        void* p = nullptr;
+        HIPCHK(c, hipHostMalloc(&p, (item_words + PAIRS) * sizeof(Fr)));
+        c->eval_batch_host = p;
+    }
+    if ((rc = ctx_ensure_scratch(c, item_words + PAIRS * blocks + PAIRS))) return rc;
+    EvalBufs b;
+    b.h_items = static_cast<EvalItem*>(c->eval_batch_host);
+    b.host = static_cast<Fr*>(c->eval_batch_host) + item_words;
+    b.d_items = reinterpret_cast<EvalItem*>(c->scratch);
+    b.scratch = c->scratch + item_words;
+    b.out = b.scratch + PAIRS * blocks;
+    std::vector<Fr> res(count);
+    for (size_t i0 = 0; i0 < count; i0 += PAIRS) {
+        const size_t cnt = std::min(PAIRS, count - i0);
+        for (size_t i = 0; i < cnt; i++) {
+            b.h_items[i].poly = ptr[i0 + i];
+            b.h_items[i].pad_ = 0;
+            memcpy(&b.h_items[i].x, points + 4 * (i0 + i), 32);
+        }
+        if ((rc = evaluate_enqueue(c, c->stream, b, (uint32_t)cnt, (uint32_t)n))) return rc;  // (has waited: the staging is free again)
+        if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+        memcpy(res.data() + i0, b.host, cnt * sizeof(Fr));
+    }
+    memcpy(out, res.data(), count * sizeof(Fr));
+    return ZK_OK;
 }
 
 // a copy of one of the key's own polynomials (coefficient form) in a caller's vector: what a phase-driving host evaluates and

@@ -131,14 +131,15 @@ inline int lookup_permute_failed(zk_ctx* c, hipStream_t st, const LookupScratch&
 }
 
 // ------------------------------------------ numerators and denominators ---
-// the values of a permutation column: a fixed column of the key, an advice column of `adv`, or the workspace's instance column
-inline const Fr* perm_col_values(const zk_pk_rec* pk, const Col& col, const Fr* const* adv) {
-    return col.type == COL_FIXED ? pk->fixed_val[col.idx] : col.type == COL_INSTANCE ? pk->inst_val : adv[col.idx];
+// the values of a permutation column: a fixed column of the key, an advice column of `adv`, or the instance column — `inst`, a
+// caller's own vector (the phase-level zk_permutation_product_public), or the workspace's when that is null
+inline const Fr* perm_col_values(const zk_pk_rec* pk, const Col& col, const Fr* const* adv, const Fr* inst = nullptr) {
+    return col.type == COL_FIXED ? pk->fixed_val[col.idx] : col.type == COL_INSTANCE ? (inst ? inst : pk->inst_val) : adv[col.idx];
 }
 // the arguments of permutation chunk ci: its columns' values (fixed from the key, advice from `adv`), their sigma columns and
 // delta^(global column index) — `dcur` runs over the chunks of a proof, starting at one
 inline PermArgs perm_chunk_args(const Layout& lay, const zk_pk_rec* pk, uint32_t ci, const Fr* const* adv, const Fr* tw, const Fr& beta,
-                                const Fr& gamma, Fr& dcur) {
+                                const Fr& gamma, Fr& dcur, const Fr* inst = nullptr) {
     PermArgs a;
     memset(&a, 0, sizeof(a));
     a.n = lay.n;
@@ -147,7 +148,7 @@ inline PermArgs perm_chunk_args(const Layout& lay, const zk_pk_rec* pk, uint32_t
     const Fr delta = fr_delta();
     for (uint32_t p = lo; p < hi; p++) {
         const Col& col = lay.perm_cols[p];
-        a.values[p - lo] = perm_col_values(pk, col, adv);
+        a.values[p - lo] = perm_col_values(pk, col, adv, inst);
         a.sigma[p - lo] = pk->sigma_val[p];
         a.delta[p - lo] = dcur;
         dcur = fe_mul(dcur, delta);
@@ -160,14 +161,15 @@ inline PermArgs perm_chunk_args(const Layout& lay, const zk_pk_rec* pk, uint32_t
     return a;
 }
 // numerators / denominators of every permutation chunk of one proof into gp_num / gp_den [0, n_chunks): one launch per chunk,
-// or — `may_stage` and many chunks — one launch over the argument blocks staged in h_batch_args / d_batch_args
+// or — `may_stage` and many chunks — one launch over the argument blocks staged in h_batch_args / d_batch_args.  `inst`: the
+// instance column's values where they are not the workspace's own (perm_col_values)
 inline int perm_numden_enqueue(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const Fr* const* adv, const Fr* tw, const Fr& beta, const Fr& gamma,
-                               bool may_stage) {
+                               bool may_stage, const Fr* inst = nullptr) {
     const Layout& lay = pk->lay;
     const bool staged = may_stage && lay.n_chunks > BATCH_ARGS_MIN;
     Fr dcur = Fr::one();
     for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-        const PermArgs a = perm_chunk_args(lay, pk, ci, adv, tw, beta, gamma, dcur);
+        const PermArgs a = perm_chunk_args(lay, pk, ci, adv, tw, beta, gamma, dcur, inst);
         if (c->audit.on) {
             std::vector<const void*> rd(a.values, a.values + a.ncols);
             aud_note(c, st, rd, {a.num, a.den}, "permutation numerators / denominators");  // (the staged form launches below, same stream)

@@ -260,6 +260,12 @@ def load_library():
                                ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
         "zk_permutation_product": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p,
                                     ctypes.POINTER(ctypes.c_uint64), sz], ctypes.c_int),
+        "zk_permutation_product_public": ([vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_uint64, u64p, u64p,
+                                           ctypes.POINTER(ctypes.c_uint64), sz], ctypes.c_int),
+        "zk_quotient_multi": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_uint64),
+                               ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_uint64), sz, u64p, u64p, u64p, ctypes.c_int,
+                               ctypes.c_uint64], ctypes.c_int),
+        "zk_eval_batch": ([vp, ctypes.POINTER(ctypes.c_uint64), u64p, sz, u64p], ctypes.c_int),
         "zk_pk_export_poly": ([vp, ctypes.c_uint64, ctypes.c_int, sz, ctypes.c_uint64], ctypes.c_int),
         "zk_random_poly": ([vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
         "zk_vk_read": ([vp, ctypes.POINTER(CircuitParamsC), vp, sz, ctypes.c_int, u64p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
@@ -627,6 +633,41 @@ class Engine:
             self._drop(z)
         self._chk(rc, "zk_permutation_product")
         return z
+
+    def permutation_product_public(self, pk, advice, instance, beta, gamma, z_out=None):
+        """zk_permutation_product_public: permutation_product for a key with the instance column; `instance`: the resident column
+        (public inputs in rows 0 .. m - 1, zero behind them), None for a key without one -> list of new Polys the caller frees,
+        or z_out (one Poly per chunk) where the caller brings the outputs."""
+        sh = self.pk_shape(pk)
+        z = self._outputs(sh["n_chunks"], 1 << sh["k"]) if z_out is None else list(z_out)
+        rc = self.L.zk_permutation_product_public(self.ctx, pk, self._handles(advice), len(advice), instance.h if instance is not None else 0,
+                                                  self._fr(beta), self._fr(gamma), self._handles(z), len(z))
+        if rc and z_out is None:
+            self._drop(z)
+        self._chk(rc, "zk_permutation_product_public")
+        return z
+
+    def quotient_multi(self, pk, advice_ext, instance_ext, perm_z_ext, lookup_ext, beta, gamma, y, out_ext, divide=True):
+        """zk_quotient_multi: ONE h over len(advice_ext) circuits.  Per circuit: advice_ext[c] its advice cosets, perm_z_ext[c] its
+        z cosets, lookup_ext[c] its (a', s', zL) triples, instance_ext[c] its instance coset (instance_ext None: a key without the
+        column)."""
+        N = len(advice_ext)
+        flat = lambda sets: [p for one in sets for p in one]
+        lk = [p for one in lookup_ext for trip in one for p in trip]
+        self._chk(self.L.zk_quotient_multi(self.ctx, pk, N, self._handles(flat(advice_ext)), len(advice_ext[0]) if N else 0,
+                                           None if instance_ext is None else self._handles(instance_ext),
+                                           self._handles(flat(perm_z_ext)), len(perm_z_ext[0]) if N else 0, self._handles(lk),
+                                           len(lookup_ext[0]) if N else 0, self._fr(beta), self._fr(gamma), self._fr(y),
+                                           1 if divide else 0, out_ext.h), "zk_quotient_multi")
+
+    def eval_batch(self, polys, points_mont):
+        """zk_eval_batch: polys[i] at points_mont[i] (count, 4) -> (count, 4) Montgomery images, each what eval gives for its pair."""
+        x = _arr(points_mont, 4)
+        if x.shape[0] != len(polys):
+            raise ValueError("one point per polynomial")
+        out = np.zeros((len(polys), 4), dtype=np.uint64)
+        self._chk(self.L.zk_eval_batch(self.ctx, self._handles(polys), _p(x), len(polys), _p(out)), "zk_eval_batch")
+        return out
 
     def poly_lincomb(self, out, ins, coeffs, sub_low=None):
         """zk_poly_lincomb: out = sum_j coeffs[j] * ins[j] - (sub_low[0] + sub_low[1] X + ..); coeffs (count, 4), sub_low (n_low <= 8, 4),

@@ -85,7 +85,7 @@ int zk_sync(zk_ctx* ctx);                 /* hipStreamSynchronize on the context
 /* tuning options (measurement tools, tests); value 0 restores the built-in choice.  The engine reads no
  * environment variables. */
 #define ZK_OPT_MSM_WINDOW 1          /* signed window bits of the fixed-base MSM, 9..17; takes effect at the next SRS load */
-#define ZK_OPT_MSM_BATCH 2           /* columns per fixed-base MSM pass, 1..256 */
+#define ZK_OPT_MSM_BATCH 2           /* columns per fixed-base MSM pass, 1..256 (an SRS of 2^22 points or more runs one column per pass whatever is asked) */
 #define ZK_OPT_NTT_MAX_RADIX_LOG2 3  /* largest radix of one NTT pass, as its log2: v = 1..11 (anything else is ZK_EINVAL).  Every value is
                                         honoured at every size the transforms accept (log_n <= 26), by every entry point that transforms
                                         (zk_ntt_bn254_fr, the zk_poly transforms, keygen, zk_prove, ...): a 2^log_n transform runs

@@ -1,12 +1,16 @@
 """GPU parity for the wide MSM path (15 / 16-bit windows over the resident SRS: msm.hip "wide path"): every commitment
 equals the oracle's (tau-oracle / C Pippenger), bit-exact after affine normalisation.  The path is selected with
 ZK_OPT_MSM_WINDOW before the SRS (and its window tables) is loaded; 16 bits is the default at k = 19."""
+import os
 import random
+import sys
 
 import numpy as np
 import pytest
 
-from zkoracle import cops, curve as C, field as F, srs
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import msm_cases as MC  # noqa: E402
+from zkoracle import cops, curve as C, field as F, srs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +28,7 @@ def windowed(engine):
     engine.srs_setup(10)  # tables of the default plan for whoever comes next
 
 
-def rand_col(rng, n):
-    a = np.frombuffer(rng.bytes(n * 32), dtype=np.uint64).reshape(n, 4).copy()
-    a[:, 3] &= 0x0FFFFFFFFFFFFFFF
-    return a
-
-
-def tau_commit(a):
-    return srs.g1_of_scalar(srs.commit_scalar_monomial(cops.fr_ints(a)))
+rand_col, tau_commit = MC.rand_col, MC.tau_commit  # the shared case set (tests/msm_cases.py)
 
 
 @pytest.mark.parametrize("bits", [15, 16, 17])
@@ -41,30 +38,9 @@ def test_wide_commit_matches_tau_oracle(windowed, bits, k):
     n = 1 << k
     eng.srs_setup(k)
     assert eng.srs_msm_plan()[0] == bits
-    rng = np.random.default_rng(1000 * bits + k)
-    cols = [rand_col(rng, n) for _ in range(5)]
-    cols[1][:] = 0                                   # the zero column: the identity
-    cols[2][:, 1:] = 0                               # 16-bit values: one window, a few hot buckets
-    cols[2][:, 0] &= 0xFFFF
-    cols[2][::3] = 0
-    pr = random.Random(k)
-    mix = []                                         # the advice-column mix of SURVEY.md 8d
-    for _ in range(n):
-        u = pr.random()
-        mix.append(pr.randrange(1 << 18) if u < 0.4 else pr.randrange(1 << 88) if u < 0.75 else pr.randrange(F.R) if u < 0.9 else 0)
-    mixm = cops.fr_mont(mix)
-    boolc = cops.fr_mont([pr.randrange(2) for _ in range(n)])   # one giant bucket
-    top = cops.fr_mont([F.R - 1 - pr.randrange(3) for _ in range(n)])  # largest scalars: every window's top digits, carries
-    # a handful of distinct digits: non-empty buckets hundreds apart and whole coarse bins empty — every first-of-bucket entry
-    # takes the escape of the lanes' bucket tracking (distance field saturated / first bucket of a bin)
-    vals = [1, 40000, (3 << 16) | 7, (12345 << 32) | (65535 << 16) | 200, (1 << 253) | (9 << 128), F.R - 2]
-    sparse = cops.fr_mont([vals[pr.randrange(len(vals))] if pr.random() < 0.7 else 0 for _ in range(n)])
-    # every digit of every scalar the same: ALL 16 n entries of the column in one bucket (one bin, one bucket, every
-    # accumulation lane a slot of it, thousands of parts); and the digit 0x8000 throughout (-2^15 with a carry into every window)
-    ones = cops.fr_mont([sum(1 << (bits * w) for w in range(250 // bits))] * n)
-    halves = cops.fr_mont([sum((1 << (bits - 1)) << (bits * w) for w in range(250 // bits))] * n)
-    polys = [eng.poly(n, c) for c in cols[:3]] + [eng.poly(n, x) for x in (mixm, boolc, top, sparse, ones, halves)]
-    data = cols[:3] + [mixm, boolc, top, sparse, ones, halves]
+    # random, zero, 16-bit hot buckets, the SURVEY 8d mix, boolean, R - 1 - j, six-value sparse, ones(bits), halves(bits)
+    data = [d for _, d in MC.columns(bits, k)]
+    polys = [eng.poly(n, d) for d in data]
     want = [tau_commit(d) for d in data]
     for j, p in enumerate(polys):
         got = cops.affine_arr_to_ints(eng.commit(p, 0))[0]

@@ -228,8 +228,10 @@ def test_srs_setup_matches_reference_known_answers(engine):
 
 @pytest.mark.parametrize("k", [18, 19])
 def test_commit_tau_oracle_k19(engine, k):
-    """MSM(s, SRS) == [sum s_i tau^i] G1 at the BASELINE size 2^19 (any-n oracle); 2^18 is the shortest column that
-    takes the two-level counting sort (msm.hip sort2_applies)."""
+    """MSM(s, SRS) == [sum s_i tau^i] G1 at the BASELINE size 2^19 and at 2^18 (any-n oracle): the commit takes the wide
+    path's 16-bit plan, the seam with exported bases the generic 12- and 13-bit windows.  (The two-level counting sort of the
+    standard plan, which 2^18 used to be the shortest column of, is reached under ZK_OPT_MSM_WINDOW only:
+    tests/test_gpu_msm_plans.py.)"""
     n = 1 << k
     engine.srs_setup(k)
     a = np.frombuffer(np.random.default_rng(0x5EED0019).bytes(n * 32), dtype=np.uint64).reshape(n, 4).copy()
@@ -248,7 +250,9 @@ def test_commit_tau_oracle_k19(engine, k):
 def test_commit_batch_equals_single_commits(engine, k, count):
     """Column-batched MSM passes (how the prover commits advice columns, grand products, h pieces): every
     result equals the one-column commitment, both bases; columns include zeros, a sparse one and full ones;
-    `count` exceeds the per-pass batch at k = 10 and k = 19 (several passes)."""
+    the per-pass batch is 2^20 / 2^k, at most 256: 70 columns at k = 10 and 9 at k = 14 are ONE pass, 5 at k = 17 too (8),
+    `count` exceeds it at k = 19 only (3 columns, passes of 2 and 1).  Several passes at a small k, a full 256-column pass and
+    ZK_OPT_MSM_BATCH: tests/test_gpu_msm_plans.py."""
     n = 1 << k
     engine.srs_setup(k)
     rng = np.random.default_rng(k * 1000 + count)

@@ -266,6 +266,7 @@ int ctx_msm_end(zk_ctx* c, int lane, G1Jac* out);
 int ctx_msm_begin_batch(zk_ctx* c, int lane, const Fr* const* d_scalars, uint32_t batch, const G1Affine* d_bases, size_t n);
 int ctx_msm_end_batch(zk_ctx* c, int lane, G1Jac* out);
 uint32_t ctx_msm_max_batch(const zk_ctx* c);
+uint32_t ctx_msm_pass_cap(const zk_ctx* c, uint32_t want);  // the widest pass the resident plan takes when `want` columns are asked for (msm_plan.h msm_max_pass)
 void ctx_msm_drain(zk_ctx* c);  // error paths: wait for every MSM in flight and drop its result
 // NTT between device buffers: inverse => x 1/N; coset => zeta scaling (coeff_to_extended / extended_to_coeff)
 int ctx_ntt(zk_ctx* c, const Fr* src, size_t src_n, Fr* dst, uint32_t log_n, bool inverse, bool coset, size_t n_out);

@@ -7,6 +7,7 @@
 
 #include "ec.hip.h"
 #include "field.hip.h"
+#include "msm_plan.h"  // MSM_MAX_BATCH, msm_auto_window, msm_auto_window_generic: the plan rules, host only
 
 namespace zk {
 
@@ -56,11 +57,8 @@ hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hi
 
 // ---- MSM (msm.hip) ---------------------------------------------------------
 struct MsmWorkspace;  // opaque, sized for a maximum n and a maximum number of columns per launch
-static constexpr uint32_t MSM_MAX_BATCH = 256;
 MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, hipError_t* err, uint32_t max_batch = 1);
 void msm_workspace_destroy(MsmWorkspace* ws);
-uint32_t msm_auto_window(size_t n, uint32_t override_c = 0);  // fixed-base mode (the resident SRS's window tables)
-uint32_t msm_auto_window_generic(size_t n);                   // arbitrary bases
 uint32_t msm_num_windows(uint32_t c);
 size_t msm_ws_max_n(const MsmWorkspace* ws);
 uint32_t msm_ws_max_batch(const MsmWorkspace* ws);

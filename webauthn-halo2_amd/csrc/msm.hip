@@ -8,8 +8,10 @@
 //
 // Layout of the source (round 6; one translation unit — the parts are textual includes that share the constants and the
 // workspace record defined here):
-//   msm.hip             constants, the workspace, the choice of the window plan, msm_run / msm_run_wide (the launch sequences),
-//                       the host's finish (Horner over the bit sums)
+//   msm.hip             constants, the workspace, msm_run / msm_run_wide (the launch sequences), the host's finish (Horner over
+//                       the bit sums)
+//   msm_plan.h          the choice of the plan as host code without HIP types: window by size, wide / fused / swept path, which
+//                       sort and scatter, bit-sum split, columns per pass (walked by tests/msm_plan_check.cpp)
 //   msm_wide.hip.h      THE path of every proof of the reference's configurations (2^16 .. 2^21 points over the resident SRS):
 //                       15 .. 17-bit windows on precomputed window tables, ONE bucket set per column, a dense two-level sort,
 //                       restartable accumulation lanes, the three-kernel reduction tail
@@ -59,7 +61,6 @@ static constexpr uint32_t SKIP_ENTRY = 0xffffffffu;  // padding entry (no base)
 // wide path: an entry is sign << 31 | first-of-bucket << 30 | delta << 24 | table index (24 bits)
 static constexpr uint32_t WIDE_FLAG = 0x40000000u;  // index bits ib = 24 .. 26 (WideGeo): delta field [ib, 30), escape = all ones
 static constexpr uint32_t CHUNK = 16384;  // scalars per histogram / scatter workgroup
-static constexpr uint32_t SORT_LDS_BUCKETS = 8192;  // 32 KiB of LDS counters per sort workgroup
 #ifndef ZK_SEG0  // build-time tuning knobs (tools/ab_variants.sh)
 #define ZK_SEG0 16
 #endif
@@ -133,59 +134,7 @@ struct MsmWorkspace {
     G1X29S* w_rc;               // [max_batch][nb / 256 + 256] row and column sums of the bucket matrix
 };
 
-static inline uint32_t nwin_for(uint32_t c) { return 254 / c + 1; }
-// smallest log2(n) that takes 17-bit windows by default.  99 = never: measured end to end (round 4, tools/bench_ab.sh, same box,
-// new head in both): 17 bits make the accumulation 6 % shorter (0.627 against 0.666 ms per launch: 15 additions per scalar
-// instead of 16) and the proof NOT faster — 94.2 / 94.7 proofs/s against 95.7 / 95.5 at 16 bits, single proof 12.3 against 12.0 ms:
-// twice the buckets (65 536) double the row / column sums and the parts of the reduction tail, which run at one or two waves per
-// SIMD.  The 17-bit plan stays selectable (ZK_OPT_MSM_WINDOW = 17) and tested.
-#ifndef ZK_W17_MIN_LG
-#define ZK_W17_MIN_LG 99
-#endif
-// the wide path (below): 15 / 16 / 17-bit windows over a resident basis.  An entry holds the table index in ib = 24 .. 26 bits
-// and a fine key of fb = 31 - ib bits (at most 7); the buckets / 2^fb coarse bins must not exceed 512
-static bool msm_wide_shape(uint32_t c, size_t table_stride, uint32_t* ib_out, uint32_t* fb_out) {
-    if (c < 15 || c > 17 || table_stride == 0) return false;
-    const uint64_t idx = (uint64_t)nwin_for(c) * table_stride;
-    uint32_t ib = 24;
-    while (((uint64_t)1 << ib) < idx) ib++;
-    if (ib > 26) return false;
-    const uint32_t fb = 31 - ib > 7 ? 7 : 31 - ib;
-    if (((1u << (c - 1)) >> fb) > 512) return false;
-    if (ib_out) *ib_out = ib;
-    if (fb_out) *fb_out = fb;
-    return true;
-}
-static bool msm_wide_applies(uint32_t c, size_t table_stride) { return msm_wide_shape(c, table_stride, nullptr, nullptr); }
-uint32_t msm_auto_window(size_t n, uint32_t override_c) {
-    uint32_t lg = 0;
-    while (((size_t)1 << (lg + 1)) <= n) lg++;
-    // measured on MI355X with whole proofs (tools/single_ab.py, tools/window_exp.py, tools/bench_rows.py): the wide path's 16-bit
-    // windows at 2^16 .. 2^20 (16 bucket additions per scalar instead of 20 / 22: k = 19 single proof 13.7 -> 12.3 ms, k = 18
-    // 10.3 -> 9.2, k = 17 7.5 -> 6.95 ms and 160 -> 169 proofs/s, k = 16 7.4 -> 7.0); below, lg - 5 bits on the 13-bit plan (k = 15:
-    // 7.0 ms against 7.6 / 7.9 with 15 / 16 bits); 2^21 and up (window table indexes beyond 24 bits) 15 bits on the swept sort
-    // round 4: 16 bits also at 2^21 (table indexes of 25 bits; was: 15 bits on the swept sort); 17 bits only on request (below)
-    int c = lg >= 22 ? 15 : (lg == 21 ? 16 : (lg >= ZK_W17_MIN_LG ? 17 : (lg >= 16 ? 16 : (int)lg - 5)));
-    if (override_c) c = (int)override_c;  // zk_ctx_set_option(ZK_OPT_MSM_WINDOW)
-    if (c < 9) c = 9;
-    if (c > 17) c = 17;
-    while (c > 15 && !msm_wide_applies(c, n)) c--;  // 16 / 17-bit digits exist on the wide path only
-    // the MSM workspaces are at least 1024 scalars long (get_msm_ws), the wide path needs table stride == workspace length:
-    // below that a 15 / 16-bit override would build internal-form tables that msm_run reads on the standard path
-    if (c >= 15 && n < 1024) c = 14;
-    return (uint32_t)c;
-}
-
-// arbitrary bases (generic mode: a bucket set per window, host Horner over the windows): the round-2 rule — lg - 6 from 2^19
-// (13 bits at 2^19), 12 at 2^16 .. 2^18, lg - 5 below, at most 14 (15 from 2^21)
-uint32_t msm_auto_window_generic(size_t n) {
-    uint32_t lg = 0;
-    while (((size_t)1 << (lg + 1)) <= n) lg++;
-    int c = lg >= 19 ? (int)lg - 6 : (lg >= 16 ? 12 : (int)lg - 5);
-    if (c > 14) c = lg >= 21 ? 15 : 14;
-    if (c < 9) c = 9;
-    return (uint32_t)c;
-}
+// the plan rules (nwin_for, msm_wide_shape, msm_auto_window .., sort2_applies, bitsum_split, msm_max_pass): msm_plan.h, host only
 
 uint32_t msm_num_windows(uint32_t c) { return nwin_for(c); }
 size_t msm_ws_max_n(const MsmWorkspace* ws) { return ws->max_n; }
@@ -496,7 +445,7 @@ hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t bat
                             head_done, bases_may_be_identity);
     if (c > 15) return hipErrorInvalidValue;  // 16 / 17-bit digits exist on the wide path only
     ws->w_clean = false;                       // this plan shares totals / cursors / counts with the wide path and leaves them used
-    const bool fused = fixed && nb <= SORT_LDS_BUCKETS;  // one-kernel digits + histogram; 15-bit windows take the swept sort
+    const bool fused = msm_fused(fixed, nb);  // one-kernel digits + histogram; 15-bit windows take the swept sort
     if (!fused && batch != 1) return hipErrorInvalidValue;  // columns are batched on the fused fixed-base path only
     const Fr* scalars = scalars_list[0];
     const uint32_t slices = fixed ? batch : nwin;
@@ -547,10 +496,8 @@ hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t bat
             hipLaunchKernelGGL(msm_recode_hist_kernel, dim3(nblk, batch), dim3(256), (nb + 256 * 9) * 4, st, mb, n32, stride, c,
                                nwin, nb, ws->digits, ws->totals, ws->blockbase);
             hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, ws->totals, ws->bucket_start, nbt, ws->counts);
-            // Long columns: one scatter launch per column — a column's 4-byte stores land in its own ~40 MB of the
-            // entry list and combine in the cache; all columns at once thrash it (0.8 ms instead of 4 x 0.1 ms at
-            // four columns of 2^19).  Short columns: one launch for all (launch-bound otherwise).
-            const uint32_t per_launch = n32 >= (1u << 18) ? 1 : batch;
+            // long columns: one scatter launch per column (msm_plan.h msm_scatter_per_launch)
+            const uint32_t per_launch = msm_scatter_per_launch(n32, batch);
             for (uint32_t q = 0; q < batch; q += per_launch)
                 hipLaunchKernelGGL(msm_scatter_fixed_kernel, dim3(nblk, per_launch), dim3(SCAT_T), nb * 4, st,
                                    ws->digits + (size_t)q * nwin * stride, n32, stride, nwin, nb, table_stride,

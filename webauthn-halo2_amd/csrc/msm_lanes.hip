@@ -5,20 +5,19 @@
 
 #include "ctx.h"
 
-// columns per fixed-base launch.  Batching makes the accumulate launch bigger (fuller waves: -15 % per column
-// already at two columns of 2^19) and replaces several reduction tails by one longer one; measured best
-// (whole proofs): 2 at 2^19, growing as the columns get shorter and launch overheads dominate
-static uint32_t batch_for(const zk_ctx* c, size_t n) {
-    size_t b = ((size_t)1 << 20) / (n ? n : 1);
-    if (c->opt_msm_batch) b = c->opt_msm_batch;  // zk_ctx_set_option(ZK_OPT_MSM_BATCH)
-    if (b < 1) b = 1;
-    if (b > MSM_MAX_BATCH) b = MSM_MAX_BATCH;
-    return (uint32_t)b;
+// columns per fixed-base launch asked for (msm_plan.h msm_batch_width; zk_ctx_set_option(ZK_OPT_MSM_BATCH) overrides)
+static uint32_t batch_for(const zk_ctx* c, size_t n) { return msm_batch_width(n, c->opt_msm_batch); }
+
+// the widest pass the resident SRS's plan takes when `want` columns are asked for: `want` on the wide path and on the fused
+// plan, 1 on the swept sort (every SRS from 2^22), which msm_run runs one column at a time, and without window tables
+uint32_t ctx_msm_pass_cap(const zk_ctx* c, uint32_t want) {
+    if (c->srs_k < 0 || !c->table_c) return 1;
+    return msm_max_pass(c->table_c, (size_t)1 << c->srs_k, want);
 }
 
 uint32_t ctx_msm_max_batch(const zk_ctx* c) {
-    if (c->srs_k < 0 || !c->table_c) return 1;
-    return batch_for(c, (size_t)1 << c->srs_k);
+    if (c->srs_k < 0) return 1;
+    return ctx_msm_pass_cap(c, batch_for(c, (size_t)1 << c->srs_k));
 }
 
 // device staging buffer `which` of at least `bytes` (kept for the next call: a Rust host patched at best_multiexp /
@@ -42,14 +41,15 @@ int seam_buffer(zk_ctx* c, int which, size_t bytes, void** out) {
 // `table_window` != 0: the workspace serves the fixed-base mode over the resident SRS (window = the tables'); otherwise
 // arbitrary bases, whose windows stop at 15 bits
 static int get_msm_ws(zk_ctx* c, int lane, size_t n, uint32_t table_window, MsmWorkspace** out) {
-    size_t want = 1;
-    while (want < n) want <<= 1;
-    if (want < 1024) want = 1024;
+    const size_t want = msm_ws_len(n);
     const uint32_t cw = table_window ? table_window : msm_auto_window_generic(want);
     zk_ctx::MsmLane& L = c->lanes[lane];
     MsmWorkspace*& slot = table_window ? L.ws : L.ws_gen;
     // columns per pass the workspace must take: the single prover's batches, or a lock-step batch's wider passes
-    const uint32_t cols = table_window ? std::max(batch_for(c, want), std::min<uint32_t>(c->msm_min_cols, MSM_MAX_BATCH)) : 1u;
+    // (a plan that runs one column per pass gets a one-column workspace: msm_max_pass, by the resident SRS's length as
+    // ctx_msm_pass_cap asks it — not by `n`, which is that length only because the one caller passes it so)
+    const uint32_t cols =
+        table_window ? msm_max_pass(table_window, (size_t)1 << c->srs_k, std::max(batch_for(c, want), std::min<uint32_t>(c->msm_min_cols, MSM_MAX_BATCH))) : 1u;
     if (slot && (msm_ws_max_n(slot) != want || msm_ws_window(slot) != cw || msm_ws_max_batch(slot) < cols)) {
         aud_sync(c, c->stream);  // (a pass of the lane that has been collected may still have kernels of its tail queued behind others)
         if (c->tail_stream) aud_sync(c, c->tail_stream);

@@ -5,6 +5,13 @@
 // k = 15 7.0 ms on this plan against 7.6 / 7.9 with 15 / 16-bit windows on the wide path), n >= 2^22 (table indexes beyond
 // 26 bits: 15 bits on the swept sort), and zk_msm_bn254 (arbitrary bases: W windows x 2^(c-1) buckets, host Horner).
 // The k = 16 .. 21 proofs of the reference's configurations run on msm_wide.hip.h.
+// Which rule picks what: msm_plan.h (host only; tests/msm_plan_check.cpp).  What is tested where (tests/test_gpu_msm_plans.py,
+// grid in tests/msm_cases.py): by default this plan runs at 9 bits (k <= 14), 10 (k = 15) and 15 on the swept sort (k >= 22:
+// tested at 2^22, one column per pass); ZK_OPT_MSM_WINDOW = 9 .. 14 selects it at any size — windows 9 .. 14 at 2^10 and 2^13
+// (bit-sum splits 1, 2, 4 and the capped 4), the two-level sort at (2^18, 9), (2^18, 14), (2^19, 13), (2^19, 9) and zk_msm_srs
+// lengths 2^18 - 1 .. 2^18 + 1 (NO default route reaches it since the wide path took k >= 16), the per-column launches of
+// msm_scatter_fixed_kernel at (2^20, 13); arbitrary bases at windows 9, 10 (n <= 2^15), 12 (2^16 .. 2^18, 2^16 + 1), 13 (2^19),
+// 14 (2^20 - 1, 2^20) and 15 (2^21: two sweeps of msm_sort_kernel).
 // ---------------------------------------------------------------- recode ---
 
 __global__ __launch_bounds__(256) void msm_recode_kernel(const Fr* __restrict__ scalars, uint32_t n, uint32_t stride,
@@ -160,23 +167,10 @@ __global__ __launch_bounds__(256) void msm_recode_hist_kernel(MsmBatch batch, ui
 // both levels a workgroup sorts 4096 entries in LDS by a 6-bit key and writes them out in runs (~64 entries = 256 B per key),
 // so that consecutive lanes store to consecutive addresses.  The 6-bit fine key rides in bits 24..29 of the entry between
 // the two levels (an entry is sign << 31 | window * n + i, which needs 24 bits up to 20 windows x 2^19).
-#ifndef ZK_SORT2
-#define ZK_SORT2 1
-#endif
-static constexpr uint32_t CBINS_MAX = 256;   // coarse bins: buckets / 64 (64 at 13-bit windows, 128 at 14); buckets / 128 on the wide path (256 at 16)
+// ZK_SORT2, ZK_SORT2_MIN_N, CBINS_MAX and the rule that selects this sort (sort2_applies): msm_plan.h
 #ifndef ZK_SORT_SUB
 #define ZK_SORT_SUB 4096
 #endif
-#ifndef ZK_SORT2_MIN_N
-#define ZK_SORT2_MIN_N (1u << 18)
-#endif
-// The two extra launches and the 4096-entry sub-rounds only pay for long columns: single proofs of the k <= 16 rows of
-// bench_ecdsa.config are 2-6 % slower with it, k = 17 1-2 %, k >= 18 equal, and batches of k = 19 proofs 4 % faster.
-static bool sort2_applies(bool fused, size_t n, uint32_t nb, uint32_t nwin, size_t table_stride) {
-    return ZK_SORT2 && fused && n >= ZK_SORT2_MIN_N && nb >= 64 && (nb >> 6) <= CBINS_MAX &&
-           (uint64_t)nwin * table_stride <= (1u << 24);
-}
-
 static constexpr uint32_t SUB = ZK_SORT_SUB;  // entries sorted in LDS at a time
 static constexpr uint32_t COARSE_WORDS = 5 * (CBINS_MAX + 1);  // per column, CBINS_MAX + 1 words each: bin starts, chunk prefix, append cursors, (unused), wide path: the bins' part regions
 
@@ -706,21 +700,7 @@ __global__ __launch_bounds__(256) void msm_gather_kernel(const uint32_t* __restr
 // tree is no deeper than the data and small bucket sets do not launch idle waves.  The host adds the
 // `split` partials of a bit and runs the c-term Horner (on the standard form: the one lane that writes a
 // bit sum converts it).
-static constexpr uint32_t BITSUM_MAX_SPLIT = 4;
-// One wave per workgroup.  Measured on the 4 x 2048 multipliers of a 13-bit window (tools/ubench_bitsum.hip): workgroups of
-// 512 lanes (one multiplier per lane, a cross-wave step through LDS) 205 us, 256 lanes 140, 128 lanes 113, 64 lanes 107 —
-// the hardware packs the waves of a workgroup two or three to a SIMD even on an idle chip, each tree step then costs two or
-// three additions, and the others wait at the barrier; a lone wave per workgroup gets a SIMD to itself.
-static uint32_t bitsum_threads(uint32_t nb) {
-    (void)nb;
-    return 64;
-}
-static uint32_t bitsum_split(uint32_t nb) {
-    uint32_t s = (nb >> 1) / 512;
-    if (s < 1) s = 1;
-    if (s > BITSUM_MAX_SPLIT) s = BITSUM_MAX_SPLIT;
-    return s;
-}
+// BITSUM_MAX_SPLIT, bitsum_threads (one wave per workgroup) and bitsum_split: msm_plan.h
 template <uint32_t THREADS>
 __global__ __launch_bounds__(THREADS) void msm_bitsum_kernel(const G1X29S* __restrict__ part, uint32_t parts, uint32_t nb,
                                                              uint32_t c, uint32_t split, const uint32_t* __restrict__ bucket_start,

@@ -1077,8 +1077,7 @@ static int prove_batch(zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, 
     // columns per MSM pass: the same commitment of all proofs at once, two columns per proof where a phase has them (a', s';
     // z, zL) — ZK_OPT_BATCH_PASS_COLUMNS overrides; the lanes' workspaces grow to that on their next pass
     uint32_t cap = c->opt_batch_pass_cols ? c->opt_batch_pass_cols : std::max(std::min<uint32_t>(2 * B, 8u), ctx_msm_max_batch(c));
-    cap = std::min<uint32_t>(cap, MSM_MAX_BATCH);
-    if (!c->table_c) cap = 1;  // no window tables (k < 10): one column per pass
+    cap = ctx_msm_pass_cap(c, cap);  // at most MSM_MAX_BATCH; one column per pass without window tables (k < 10) and on the swept sort (k >= 22)
     c->msm_min_cols = std::max(c->msm_min_cols, cap);
     std::vector<std::unique_ptr<Transcript>> trs;
     std::vector<std::unique_ptr<Prover>> provers;
@@ -1156,8 +1155,7 @@ static int prove_multi(zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* adv
     if ((rc = pk_ensure_multi(c, pk, B))) return rc;
     // columns per MSM pass: zk_prove_batch's rule (ZK_OPT_BATCH_PASS_COLUMNS overrides)
     uint32_t cap = c->opt_batch_pass_cols ? c->opt_batch_pass_cols : std::max(std::min<uint32_t>(2 * B, 8u), ctx_msm_max_batch(c));
-    cap = std::min<uint32_t>(cap, MSM_MAX_BATCH);
-    if (!c->table_c) cap = 1;  // no window tables (k < 10): one column per pass
+    cap = ctx_msm_pass_cap(c, cap);  // at most MSM_MAX_BATCH; one column per pass without window tables (k < 10) and on the swept sort (k >= 22)
     c->msm_min_cols = std::max(c->msm_min_cols, cap);
     // the proof's transcript and RNG are circuit 0's prover's; circuits 1 .. N - 1 are workspaces: their provers get a scratch
     // transcript (begin() hashes transcript_repr into it) and a stream that is never drawn from

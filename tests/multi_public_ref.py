@@ -1,7 +1,7 @@
 """One proof over N circuits of one key WITH public inputs, restated in plain Python: halo2's `create_proof(params, pk, &[c_0 ..
 c_{N-1}], &[inst_0 .. inst_{N-1}], rng, transcript)` and `verify_proof(.., instances: &[&[&[Fr]]], ..)` with one instance column
 per circuit [RECALLED: halo2_proofs plonk/prover.rs, plonk/verifier.rs - no reference bytes pin it].  The reference of
-zk_prove_multi_public / zk_verify_multi_public (csrc/prover_multi.h, csrc/verifier.h).  It is tests/multi_ref.py's flow with
+zk_prove_multi_public / zk_verify_multi_public (csrc/prover_lockstep.h, csrc/verifier.h).  It is tests/multi_ref.py's flow with
 tests/public_ref.py's column in it; tests/test_multi_public_ref.py ties it to both (N = 1: public_ref.create_proof byte for byte; a
 shape without the column: multi_ref.create_proof_multi byte for byte) and checks what its own verifier accepts and rejects.
 

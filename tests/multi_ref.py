@@ -1,6 +1,6 @@
 """One proof over N circuits of one key, restated in plain Python: halo2's `create_proof` with `circuits: &[C]` and `verify_proof`
 with N (empty) instance slices [RECALLED: halo2_proofs plonk/prover.rs, plonk/verifier.rs — no reference bytes pin it].  The
-reference of zk_prove_multi / zk_verify_multi (csrc/prover_multi.h, csrc/verifier.h); tests/test_multi_ref.py ties it to the
+reference of zk_prove_multi / zk_verify_multi (csrc/prover_lockstep.h, csrc/verifier.h); tests/test_multi_ref.py ties it to the
 pinned oracle at N = 1 (byte for byte) and checks that its own verifier accepts and rejects what it should.
 
 The rule, c = 0 .. N - 1 in the caller's order, T = terms of one circuit's y-combination, bf = BLINDING_FACTORS:

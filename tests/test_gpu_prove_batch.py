@@ -1,4 +1,4 @@
-"""zk_prove_batch (lock-step proving of B independent proofs on one context: csrc/prover_batch.h drives the steps of csrc/prover_steps.h): every proof of a batch is
+"""zk_prove_batch (lock-step proving of B independent proofs on one context: csrc/prover_lockstep.h drives the steps of csrc/prover_steps.h): every proof of a batch is
 byte-identical to the oracle's create_proof — and therefore to zk_prove — for the same witness and ChaCha20 stream, for every
 column shape the engine branches on, both transcripts / multi-open schemes, batch sizes that fill a pass, overflow it, and
 leave a remainder; at BASELINE's size the batch's proofs equal the committed digests of configs[3]."""

@@ -1,4 +1,4 @@
-"""zk_prove_batch_public (csrc/prover_batch.h): the lock-step batch with every proof's public inputs.  Proof j is zk_prove_public's
+"""zk_prove_batch_public (csrc/prover_lockstep.h): the lock-step batch with every proof's public inputs.  Proof j is zk_prove_public's
 with the same key, advice, list and seed on the same engine - every lane has its own witness seed and the lists have different
 lengths - and, at the shapes the plain-Python prover reaches, tests/public_ref.py's.  Shapes: k19like (n = 128), k18like (n = 64:
 fewer rows than a workgroup of the kernel that writes the columns), k17like (the column has a permutation chunk of its own), wide and

@@ -1,4 +1,4 @@
-"""zk_prove_multi (csrc/prover_multi.h): ONE proof over N circuits of one key — halo2's create_proof with several circuits.
+"""zk_prove_multi (csrc/prover_lockstep.h): ONE proof over N circuits of one key — halo2's create_proof with several circuits.
 
 With one circuit the call is zk_prove, byte for byte, at every prover shape and all four transcript x scheme pairs.  With more it is
 compared byte for byte with tests/multi_ref.py, the plain-Python statement of the rule (tied to the pinned oracle at N = 1 by
@@ -106,6 +106,47 @@ def test_batched_msm_passes(name, N):
         sizes = [eng.proof_size_multi(pk, m, t, s) for m in range(1, E.ZK_PROVE_MULTI_MAX + 1)]
         assert {b - a for a, b in zip(sizes, sizes[1:])} == {per}
         assert len(proof) == sizes[N - 1]
+    eng.close()
+
+
+_DEFAULT_WIDTH = {}
+
+
+def _default_width_proofs(name, N):
+    """(witnesses, {pairing: proof}) of a fresh engine at the default pass width, made once per shape: each proof is accepted by
+    zk_verify_multi and by the reference verifier (O(1) in n)."""
+    if name not in _DEFAULT_WIDTH:
+        eng = zk.Engine(0)
+        asgs = witnesses(name, N)
+        opk = oracle_key(name, asgs[0])
+        pk, sets = engine_key(eng, name, asgs)
+        proofs = {}
+        for kind, scheme in PAIRINGS:
+            proof = eng.prove_multi(pk, sets, SEED, KIND[kind], SCHEME[scheme])
+            assert eng.verify_multi(pk, N, proof, KIND[kind], SCHEME[scheme]), (kind, scheme)
+            assert multi_ref.verify_multi(opk.vk, proof, N, kind, scheme), (kind, scheme)
+            proofs[kind, scheme] = proof
+        eng.close()
+        _DEFAULT_WIDTH[name] = (asgs, proofs)
+    return _DEFAULT_WIDTH[name]
+
+
+@pytest.mark.parametrize("name", ["k10batched", "k10single"])
+@pytest.mark.parametrize("cols", [1, 3, 6, 16])
+def test_pass_width_does_not_change_the_proof(cols, name):
+    """ZK_OPT_BATCH_PASS_COLUMNS under zk_prove_multi, which shares its passes with zk_prove_batch (tests/test_gpu_prove_batch.py
+    test_pass_width_does_not_change_proofs: the same widths).  Six circuits at k = 10, the smallest size at which passes are merged at
+    all.  Width 1: every commitment its own pass, and the pipelined route of the one-column key is off (more lanes than a pass
+    takes); 3: a circuit's columns split across passes; 6: the pipelined route with as many lanes as a pass takes — the twelve a' /
+    s' columns need four passes on two lanes, so the queue collects the advice pass and squeezes theta before it writes any a' —;
+    16: wider than the default.  The bytes are those of a fresh engine at the default width, which both verifiers accept."""
+    N = 6
+    asgs, want = _default_width_proofs(name, N)
+    eng = zk.Engine(0)
+    eng.set_option(E.ZK_OPT_BATCH_PASS_COLUMNS, cols)
+    pk, sets = engine_key(eng, name, asgs)
+    for kind, scheme in PAIRINGS:
+        assert eng.prove_multi(pk, sets, SEED, KIND[kind], SCHEME[scheme]) == want[kind, scheme], (cols, kind, scheme)
     eng.close()
 
 

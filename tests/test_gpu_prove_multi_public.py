@@ -1,4 +1,4 @@
-"""zk_prove_multi_public (csrc/prover_multi.h): ONE proof over N circuits with every circuit's public inputs, byte for byte what
+"""zk_prove_multi_public (csrc/prover_lockstep.h): ONE proof over N circuits with every circuit's public inputs, byte for byte what
 tests/multi_public_ref.py - the plain-Python statement of the rule, tied to public_ref and multi_ref by
 tests/test_multi_public_ref.py - makes: N = 2 and 3 at k19like (the column joins a permutation chunk), k17like (it has a chunk of its
 own) and wide, with lists of different lengths; the committed k = 10 fixture through the column-batched passes.  One circuit is

@@ -1,9 +1,11 @@
-"""Every kernel launch of one k = 19 proof in the order the host enqueued it — the check that a refactor of host code moved no
+"""Every kernel launch of one call in the order the host enqueued it — the check that a refactor of host code moved no
 enqueue (profiles/README.md "dispatch_order").  Two halves:
 
-  dispatch_order.py run lone|lockstep4
-      the traced program: sets up k = 19 (SRS, key, the advice columns uploaded once) and makes ONE zk_prove (Blake2b + SHPLONK),
-      or ONE zk_prove_batch of four; prints the SHA-256 of the proof(s).  ZKMI355_LIB selects another build of the library.
+  dispatch_order.py run lone|lockstep4|multi4 [k19|k17]
+      the traced program: sets up the shape (SRS, key, the advice columns uploaded once) and makes ONE zk_prove, ONE zk_prove_batch
+      of four, or ONE zk_prove_multi over four circuits; prints the SHA-256 of the proof(s).  k19 (the default): circuit.K19 with
+      Blake2b + SHPLONK — one advice column, one lookup: the pipelined route; k17: circuit.K17 with EVM + GWC — four advice
+      columns, three chained chunks: the plain route.  ZKMI355_LIB selects another build of the library.
       Run it under `rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/dispatch_order.py run lone`
       (no counters, no other tracing).
   dispatch_order.py order <kernel_trace.csv>
@@ -18,13 +20,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(mode):
+def run(mode, shape="k19"):
     sys.path.insert(0, ROOT)
     import numpy as np
     import webauthn_halo2_amd as zk
     from webauthn_halo2_amd import engine as E
 
-    p = zk.circuit.K19
+    if shape not in ("k19", "k17"):
+        raise SystemExit(__doc__)
+    p, tr = (zk.circuit.K19, E.ZK_TRANSCRIPT_BLAKE2B) if shape == "k19" else (zk.circuit.K17, E.ZK_TRANSCRIPT_EVM)
     eng = zk.Engine(0)
     eng.srs_setup(p.degree)
     asg = zk.circuit.synthesize(p, 0x5EED0019)
@@ -35,12 +39,14 @@ def run(mode):
         eng.upload_canonical(h, asg.to_limbs(col))
         hs.append(h)
     if mode == "lone":
-        proofs = [eng.prove(pk, hs, bytes([1]) * 32, E.ZK_TRANSCRIPT_BLAKE2B)]
+        proofs = [eng.prove(pk, hs, bytes([1]) * 32, tr)]
     elif mode == "lockstep4":
-        proofs = eng.prove_batch(pk, [hs] * 4, [bytes([j + 1]) * 32 for j in range(4)], E.ZK_TRANSCRIPT_BLAKE2B)
+        proofs = eng.prove_batch(pk, [hs] * 4, [bytes([j + 1]) * 32 for j in range(4)], tr)
+    elif mode == "multi4":
+        proofs = [eng.prove_multi(pk, [hs] * 4, bytes([1]) * 32, tr)]
     else:
         raise SystemExit(__doc__)
-    print(mode, "library", E.lib_path(), "proofs", " ".join(hashlib.sha256(pf).hexdigest()[:16] for pf in proofs), flush=True)
+    print(mode, shape, "library", E.lib_path(), "proofs", " ".join(hashlib.sha256(pf).hexdigest()[:16] for pf in proofs), flush=True)
     eng.close()
 
 
@@ -60,8 +66,8 @@ def order(path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "run":
-        run(sys.argv[2])
+    if len(sys.argv) in (3, 4) and sys.argv[1] == "run":
+        run(*sys.argv[2:])
     elif len(sys.argv) == 3 and sys.argv[1] == "order":
         order(sys.argv[2])
     else:

@@ -8,6 +8,15 @@
 #include "ctx.h"
 #include "prover.h"
 
+// the transcript / scheme pair of every proving, sizing and verifying entry point: ZK_EINVAL on an unknown transcript, the
+// transcript's default scheme (the reference's pairings: GWC for EVM, SHPLONK for Blake2b) for ZK_SCHEME_DEFAULT, ZK_EINVAL on an
+// unknown scheme
+inline int resolve_scheme(int transcript, int* scheme) {
+    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
+    if (*scheme == ZK_SCHEME_DEFAULT) *scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
+    return *scheme == ZK_SCHEME_GWC || *scheme == ZK_SCHEME_SHPLONK ? ZK_OK : ZK_EINVAL;
+}
+
 enum ColType { COL_ADVICE = 0, COL_FIXED = 1, COL_INSTANCE = 2 };
 struct Col {
     int type;  // ColType
@@ -155,7 +164,7 @@ struct zk_pk_rec {
     LcTerm *d_lc_terms = nullptr, *h_lc_terms = nullptr;  // argument lists of the multi-open's long linear combinations
     uint32_t lc_cap = 0, lc_used = 0;                     // slots, and how many this proof has used so far
     Fr *ev_scratch = nullptr, *ev_out = nullptr;
-    // ---- lock-step batches (zk_prove_batch, prover_batch.h): proof j > 0 of a batch works in members[j - 1], a record whose
+    // ---- lock-step batches (zk_prove_batch, prover_lockstep.h): proof j > 0 of a batch works in members[j - 1], a record whose
     // key half (fixed / sigma / l_* vectors, commitments, transcript_repr) ALIASES this key's and whose workspace is its own
     // (`dev` of a member lists its workspace only); `bb` holds what the merged launches of a batch need across proofs
     bool is_member = false;
@@ -233,7 +242,7 @@ int pk_instance_lists(const Layout& lay, size_t count, const uint64_t* const* in
 int pk_instance_upload_lanes(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, const std::vector<zk_pk_rec*>& ws, const std::vector<const std::vector<Fr>*>& lists);
 Fr fr_delta();  // 7^(2^28): generator of the odd-order subgroup (the permutation argument's coset shifts)
 int pk_quotient(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, bool divide, Fr* out);
-// One pass of a quotient that several circuits share (prover_multi.h): the y-combination of this workspace's terms times
+// One pass of a quotient that several circuits share (prover_lockstep.h): the y-combination of this workspace's terms times
 // `yscale` (the pass's ypow[j] = 32 yscale y^(T - 1 - j)), stored to `out` or — `accumulate` — added to what `out` holds.
 // pk_quotient is the pass with yscale = 1 that stores.
 int pk_quotient_pass(zk_ctx* c, zk_pk_rec* pk, const QuotientCosets& qc, const Fr& beta, const Fr& gamma, const Fr& y, const Fr& yscale,

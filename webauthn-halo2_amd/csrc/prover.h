@@ -172,7 +172,7 @@ void launch_kate_division(const Fr* p, Fr* q, uint32_t n, const Fr& z, Fr* scrat
 void launch_kate_division_batch(const Fr* const* p, Fr* const* q, const Fr* z, uint32_t count, uint32_t n, Fr* scratch,
                                 hipStream_t st);
 void launch_quotient_dev(const QuotientArgs* d_args, uint32_t log_ext, uint32_t log_slices, hipStream_t st, bool cosets3 = false);
-// the same pass ADDED to what `out` of the argument block already holds (one proof over several circuits: prover_multi.h)
+// the same pass ADDED to what `out` of the argument block already holds (one proof over several circuits: prover_lockstep.h)
 void launch_quotient_acc_dev(const QuotientArgs* d_args, uint32_t log_ext, uint32_t log_slices, hipStream_t st, bool cosets3 = false);
 uint32_t quotient_log_slices(uint32_t log_ext, uint32_t n_gate);
 

@@ -1,5 +1,5 @@
 // prover.hip — create_proof on the device-resident engine: the single prover (Prover::run), the lock-step prover of several
-// proofs (prover_batch.h), the prover of one proof over several circuits (prover_multi.h) and their entry points.  Keygen and the key's workspace are prover_key.hip, the phase-level entry
+// proofs or of one proof over several circuits (prover_lockstep.h) and their entry points.  Keygen and the key's workspace are prover_key.hip, the phase-level entry
 // points prover_phases.hip; the steps the three share are prover_steps.h — the two drivers here hold the scheduling only: which
 // step, in which order, on which lane, and when a lane is collected.
 //
@@ -113,9 +113,9 @@ struct Prover {
     // behind transcript_repr, never written; the column is neither blinded nor committed nor opened, and draws nothing
     const std::vector<Fr>* instance = nullptr;
     // begin() absorbs `instance` into this prover's transcript: a lone proof and every proof of a lock-step batch.  The driver of one
-    // proof over several circuits (prover_multi.h) clears it and absorbs every circuit's list itself, once, on the one transcript
+    // proof over several circuits (prover_lockstep.h, its one-proof mode) clears it and absorbs every circuit's list itself, once, on the one transcript
     bool absorb_instance = true;
-    bool batch_member = false;  // one of the proofs of a lock-step batch (prover_batch.h): transforms stay on the main stream
+    bool batch_member = false;  // one of the proofs of a lock-step batch (prover_lockstep.h): transforms stay on the main stream
 
     Prover(const Prover&) = delete;  // (cq is bound to this object)
     Prover(zk_ctx* c_, zk_pk_rec* pk_, const uint8_t seed[32], Transcript* t)
@@ -315,48 +315,71 @@ struct Prover {
         Fr eval;
     };
 
-    // every opened value of a proof in transcript order, then h(x) (not written); where the groups start
+    // ---- the opened values and the query order of a proof over one or more circuits of this key (`circuits`: this prover's own
+    // workspace first; the lone prover and every proof of a lock-step batch have the one, prover_lockstep.h's one-proof mode B).
+    // The verifier (verifier.h) reads both orders; they are stated here and nowhere else.
+    // Every opened value in transcript order — for c: advice; fixed; random; sigma; for c: z; for c: lookups — then h(x) (not
+    // written); where the groups start
     struct EvIdx {
-        size_t i_fix = 0, i_rand = 0, i_sig = 0, i_z = 0, i_lk = 0, n_written = 0;
+        std::vector<size_t> i_adv, i_z, i_lk;  // per circuit
+        size_t i_fix = 0, i_rand = 0, i_sig = 0, n_written = 0;
     };
-    void build_evals(std::vector<Q>& ev, EvIdx& ix) const {
-        for (auto& aq : lay.advice_queries) ev.push_back(Q{pk->adv_poly[aq.first], aq.second, Fr::zero()});
+    // the per-circuit parts: its advice queries; per chunk z(x), z(wx) and, but for the last chunk, z(w^last x); five openings per lookup
+    void advice_evals(const zk_pk_rec* w, std::vector<Q>& ev) const {
+        for (auto& aq : lay.advice_queries) ev.push_back(Q{w->adv_poly[aq.first], aq.second, Fr::zero()});
+    }
+    void z_evals(const zk_pk_rec* w, std::vector<Q>& ev) const {
+        for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
+            ev.push_back(Q{w->z_poly[ci], 0, Fr::zero()});
+            ev.push_back(Q{w->z_poly[ci], 1, Fr::zero()});
+            if (ci != lay.n_chunks - 1) ev.push_back(Q{w->z_poly[ci], lay.last_rot, Fr::zero()});
+        }
+    }
+    void lookup_evals(const zk_pk_rec* w, std::vector<Q>& ev) const {
+        for (uint32_t l = 0; l < lay.n_lookups; l++) {
+            ev.push_back(Q{w->lk_z_poly[l], 0, Fr::zero()});
+            ev.push_back(Q{w->lk_z_poly[l], 1, Fr::zero()});
+            ev.push_back(Q{w->lk_ap_poly[l], 0, Fr::zero()});
+            ev.push_back(Q{w->lk_ap_poly[l], -1, Fr::zero()});
+            ev.push_back(Q{w->lk_sp_poly[l], 0, Fr::zero()});
+        }
+    }
+    void build_evals(const std::vector<const zk_pk_rec*>& circuits, std::vector<Q>& ev, EvIdx& ix) const {
+        for (const zk_pk_rec* w : circuits) {
+            ix.i_adv.push_back(ev.size());
+            advice_evals(w, ev);
+        }
+        // once, from this prover's workspace: fixed, random, sigma
         ix.i_fix = ev.size();
         for (uint32_t f = 0; f < lay.n_fix; f++) ev.push_back(Q{pk->fixed_poly[f], 0, Fr::zero()});
         ix.i_rand = ev.size();
         ev.push_back(Q{pk->random_poly, 0, Fr::zero()});
         ix.i_sig = ev.size();
         for (uint32_t p = 0; p < lay.perm_cols.size(); p++) ev.push_back(Q{pk->sigma_poly[p], 0, Fr::zero()});
-        ix.i_z = ev.size();
-        for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
-            ev.push_back(Q{pk->z_poly[ci], 0, Fr::zero()});
-            ev.push_back(Q{pk->z_poly[ci], 1, Fr::zero()});
-            if (ci != lay.n_chunks - 1) ev.push_back(Q{pk->z_poly[ci], lay.last_rot, Fr::zero()});
+        for (const zk_pk_rec* w : circuits) {
+            ix.i_z.push_back(ev.size());
+            z_evals(w, ev);
         }
-        ix.i_lk = ev.size();
-        for (uint32_t l = 0; l < lay.n_lookups; l++) {
-            ev.push_back(Q{pk->lk_z_poly[l], 0, Fr::zero()});
-            ev.push_back(Q{pk->lk_z_poly[l], 1, Fr::zero()});
-            ev.push_back(Q{pk->lk_ap_poly[l], 0, Fr::zero()});
-            ev.push_back(Q{pk->lk_ap_poly[l], -1, Fr::zero()});
-            ev.push_back(Q{pk->lk_sp_poly[l], 0, Fr::zero()});
+        for (const zk_pk_rec* w : circuits) {
+            ix.i_lk.push_back(ev.size());
+            lookup_evals(w, ev);
         }
         ix.n_written = ev.size();
         ev.push_back(Q{pk->h_comb, 0, Fr::zero()});
     }
-    // prover query order (== verifier's): advice, perm z (x, wx per chunk; then `last` in reverse), lookups
-    // (zL@x, a'@x, s'@x, a'@w^-1 x, zL@wx), fixed, sigma, h, random
-    std::vector<Q> queries_from_evals(const std::vector<Q>& ev, const EvIdx& ix) const {
-        std::vector<Q> queries(ev.begin(), ev.begin() + ix.i_fix);
+    // prover query order (== verifier's): for c: advice, perm z (x, wx per chunk; then `last` in reverse), lookups
+    // (zL@x, a'@x, s'@x, a'@w^-1 x, zL@wx); then once fixed, sigma, h, random
+    void circuit_queries(const std::vector<Q>& ev, size_t i_adv, size_t i_z, size_t i_lk, std::vector<Q>& queries) const {
+        queries.insert(queries.end(), ev.begin() + i_adv, ev.begin() + i_adv + lay.advice_queries.size());
         std::vector<Q> lastq(lay.n_chunks);
-        size_t pos = ix.i_z;
+        size_t pos = i_z;
         for (uint32_t ci = 0; ci < lay.n_chunks; ci++) {
             queries.push_back(ev[pos++]);
             queries.push_back(ev[pos++]);
             if (ci != lay.n_chunks - 1) lastq[ci] = ev[pos++];
         }
         for (int ci = (int)lay.n_chunks - 2; ci >= 0; ci--) queries.push_back(lastq[ci]);
-        pos = ix.i_lk;
+        pos = i_lk;
         for (uint32_t l = 0; l < lay.n_lookups; l++, pos += 5) {
             queries.push_back(ev[pos]);      // zL @ x
             queries.push_back(ev[pos + 2]);  // a' @ x
@@ -364,8 +387,12 @@ struct Prover {
             queries.push_back(ev[pos + 3]);  // a' @ w^-1 x
             queries.push_back(ev[pos + 1]);  // zL @ w x
         }
+    }
+    std::vector<Q> queries_from_evals(const std::vector<Q>& ev, const EvIdx& ix) const {
+        std::vector<Q> queries;
+        for (size_t ci = 0; ci < ix.i_adv.size(); ci++) circuit_queries(ev, ix.i_adv[ci], ix.i_z[ci], ix.i_lk[ci], queries);
         for (size_t i = ix.i_fix; i < ix.i_rand; i++) queries.push_back(ev[i]);
-        for (size_t i = ix.i_sig; i < ix.i_z; i++) queries.push_back(ev[i]);
+        for (size_t i = ix.i_sig; i < ix.i_z[0]; i++) queries.push_back(ev[i]);
         queries.push_back(ev[ix.n_written]);  // h
         queries.push_back(ev[ix.i_rand]);     // random poly
         return queries;
@@ -404,7 +431,7 @@ struct Prover {
         // auto: columns of 2^16 rows or more (measured, tools/r6_cosets3_ab.sh: k = 18 / 17 / 16 - 1 / - 3 / - 3 %, k = 17 EVM over four
         // pipelines 196 -> 203 proofs/s; the many-column rows lose — three vectors per column fill the transforms' launches three
         // times as fast: k = 13 / 12 / 11 + 5 / + 5 / + 12 %)
-        // (the members of a lock-step batch get the key's coset-major copies from the batch driver: prover_batch.h)
+        // (the members of a lock-step batch get the key's coset-major copies from the batch driver: prover_lockstep.h)
         {
             const uint32_t above = c->opt_tail_main_above ? c->opt_tail_main_above : 2u;
             loaded = c->opt_tail_stream == 2 || (c->opt_tail_stream == 0 && (uint32_t)ctx_activity_touch(c) > above);
@@ -621,7 +648,7 @@ struct Prover {
         combine_h(x);
         std::vector<Q> ev;  // transcript order, then h(x) (not written)
         EvIdx ix;
-        build_evals(ev, ix);
+        build_evals({pk}, ev, ix);
         if (ev.size() > pk->max_evals) return ZK_ESTATE;
         for (size_t i = 0; i < ev.size(); i++) {
             pk->h_evargs[i].poly = ev[i].poly;
@@ -642,7 +669,7 @@ struct Prover {
     }
 
     // ---- multi-open, in stages: each stage ends with polynomials launched whose commitments the transcript needs next, so
-    // that a lock-step prover of several proofs (prover_batch.h) can put the same commitment of all its proofs into ONE MSM
+    // that a lock-step prover of several proofs (prover_lockstep.h) can put the same commitment of all its proofs into ONE MSM
     // pass; open_gwc / open_shplonk below run the stages of one proof back to back.
 
     // GWC (ProverGWC, halo2_proofs poly/kzg/multiopen/gwc): one witness polynomial per rotation.
@@ -900,8 +927,7 @@ struct Prover {
     }
 };
 
-#include "prover_batch.h"
-#include "prover_multi.h"
+#include "prover_lockstep.h"
 
 }  // namespace
 
@@ -931,40 +957,59 @@ struct ProveQuiesce {
 };
 }  // namespace
 
-ZK_API(zk_proof_size, (zk_ctx* c, zk_pk pkh, int transcript, int scheme, size_t* out), (c, pkh, transcript, scheme, out)) {
-    if (!c || !out) return ZK_EINVAL;
+// the bytes of one proof over n_circuits circuits (zk_prove: one).  Per circuit its own commitments — advice, (a', s', zL) per
+// lookup, z per chunk — and evaluations (advice, z, lookups); once the random polynomial, the h pieces, the fixed / random / sigma
+// evaluations and the opening proof: SHPLONK two points, GWC one per distinct rotation {0,1,2,3,-1} (+ `last` once there is a
+// chunk link)
+static int proof_size(zk_ctx* c, zk_pk pkh, size_t n_circuits, int transcript, int scheme, size_t* out) {
     std::lock_guard<std::mutex> g(c->mu);
     auto it = c->pks.find(pkh);
     if (it == c->pks.end()) return ZK_EINVAL;
-    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
-    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
-    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
-    const Layout& lay = it->second->lay;
-    // commitments: advice, (a', s', zL) per lookup, z per chunk, random, h pieces; then the opening proof:
-    // SHPLONK two points, GWC one per distinct rotation {0,1,2,3,-1} (+ `last` once there is a chunk link)
-    size_t points = lay.n_adv + 3 * lay.n_lookups + lay.n_chunks + 1 + lay.n_h;
-    points += scheme == ZK_SCHEME_SHPLONK ? 2 : 5 + (lay.n_chunks > 1 ? 1 : 0);
-    const size_t evals = lay.advice_queries.size() + lay.n_fix + 1 + lay.perm_cols.size() + 3 * lay.n_chunks - 1 +
-                         5 * lay.n_lookups;
-    *out = points * (transcript == ZK_TRANSCRIPT_EVM ? 64 : 32) + evals * 32;
-    return ZK_OK;
-}
-
-// one proof over n_circuits circuits: per circuit its own commitments (advice, a', s', zL, z) and evaluations (advice, z, lookups);
-// once the random polynomial, the h pieces, the fixed / random / sigma evaluations and the opening proof
-ZK_API(zk_proof_size_multi, (zk_ctx* c, zk_pk pkh, size_t n_circuits, int transcript, int scheme, size_t* out), (c, pkh, n_circuits, transcript, scheme, out)) {
-    if (!c || !out || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->pks.find(pkh);
-    if (it == c->pks.end()) return ZK_EINVAL;
-    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
-    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
-    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    if (int r = resolve_scheme(transcript, &scheme)) return r;
     const Layout& lay = it->second->lay;
     size_t points = n_circuits * (lay.n_adv + 3 * lay.n_lookups + lay.n_chunks) + 1 + lay.n_h;
     points += scheme == ZK_SCHEME_SHPLONK ? 2 : 5 + (lay.n_chunks > 1 ? 1 : 0);
     const size_t evals = n_circuits * (lay.advice_queries.size() + 3 * lay.n_chunks - 1 + 5 * lay.n_lookups) + lay.n_fix + 1 + lay.perm_cols.size();
     *out = points * (transcript == ZK_TRANSCRIPT_EVM ? 64 : 32) + evals * 32;
+    return ZK_OK;
+}
+
+ZK_API(zk_proof_size, (zk_ctx* c, zk_pk pkh, int transcript, int scheme, size_t* out), (c, pkh, transcript, scheme, out)) {
+    if (!c || !out) return ZK_EINVAL;
+    return proof_size(c, pkh, 1, transcript, scheme, out);
+}
+
+ZK_API(zk_proof_size_multi, (zk_ctx* c, zk_pk pkh, size_t n_circuits, int transcript, int scheme, size_t* out), (c, pkh, n_circuits, transcript, scheme, out)) {
+    if (!c || !out || n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
+    return proof_size(c, pkh, n_circuits, transcript, scheme, out);
+}
+
+// ---- admission: the checks every whole-proof entry point makes, each in the order it always made them (which code comes back
+// when two faults coincide is behaviour: prove_one has the instances first, the lock-step forms the key)
+// key state and shape
+static int admit_key(const zk_ctx* c, const zk_pk_rec* pk, size_t n_advice) {
+    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
+    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
+    if (n_advice != pk->lay.n_adv || c->srs_k != (int)pk->lay.k) return ZK_EINVAL;
+    return ZK_OK;
+}
+// the `count` instance lists of a call (pk_instance_lists' rules); the forms without instances carry none and refuse a key WITH the
+// column (halo2's InvalidInstances)
+static int admit_instances(const Layout& lay, bool with_instances, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances,
+                           std::vector<std::vector<Fr>>* lists) {
+    if (lay.n_inst && !with_instances) return ZK_EINVAL;
+    return with_instances ? pk_instance_lists(lay, count, instances_mont, n_instances, lists) : ZK_OK;
+}
+// (transcript and scheme: resolve_scheme, pk.h)
+
+// the advice handles of a call, as device pointers
+static int resolve_advice(zk_ctx* c, const Layout& lay, const zk_poly* advice, size_t count, std::vector<const Fr*>* adv) {
+    adv->resize(count);
+    for (size_t j = 0; j < count; j++) {
+        const PolyRec* r = ctx_poly(c, advice[j]);
+        if (!r || r->n != lay.n) return ZK_EINVAL;
+        (*adv)[j] = r->ptr;
+    }
     return ZK_OK;
 }
 
@@ -979,31 +1024,21 @@ static int prove_one(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice,
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
-    if (lay.n_inst && !with_instances) return ZK_EINVAL;
-    std::vector<Fr> instance;
-    if (with_instances)
-        if (int r = pk_instance_values(lay, instance_mont, n_instance, &instance)) return r;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
-    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
-    if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
-    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
-    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
-    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    std::vector<std::vector<Fr>> lists;  // (the one list)
+    if (int r = admit_instances(lay, with_instances, 1, &instance_mont, &n_instance, &lists)) return r;
+    if (int r = admit_key(c, pk, n_advice)) return r;
+    if (int r = resolve_scheme(transcript, &scheme)) return r;
     int rc = ctx_bind(c);
     if (rc) return rc;
-    std::vector<const Fr*> adv(n_advice);
-    for (size_t j = 0; j < n_advice; j++) {
-        const PolyRec* r = ctx_poly(c, advice[j]);
-        if (!r || r->n != lay.n) return ZK_EINVAL;
-        adv[j] = r->ptr;
-    }
+    std::vector<const Fr*> adv;
+    if ((rc = resolve_advice(c, lay, advice, n_advice, &adv))) return rc;
     EvmTranscript evm;
     Blake2bTranscript b2;
     Transcript* tr = transcript == ZK_TRANSCRIPT_EVM ? (Transcript*)&evm : (Transcript*)&b2;
     const uint64_t aud0 = c->audit.violations;
     c->audit.base_of.clear();  // (allocations may have changed hands since the last proof)
     Prover p(c, pk, rng_seed, tr);
-    if (lay.n_inst) p.instance = &instance;
+    if (lay.n_inst) p.instance = &lists[0];
     {
         ProveQuiesce quiesce(c);  // (declared after the prover: it settles the streams while the prover's host buffers are alive)
         rc = p.run(adv.data(), scheme);
@@ -1037,7 +1072,50 @@ static int prove_one_of_lists(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t 
                            proof_cap, proof_len);
 }
 
-// create_proof for `batch` independent proofs of one key in lock-step (prover_batch.h).  `with_instances`: zk_prove_batch_public —
+// ---- the lock-step entry (prover_lockstep.h): what zk_prove_batch and zk_prove_multi do alike once a call is admitted.  Lane q —
+// proof q, or circuit q of the one proof — gets a prover on the key's own workspace (q = 0) or on member q - 1, with the
+// caller's transcript and seed for it and, on a key with the column, list q.  The callers keep what is their own: whose
+// transcripts and seeds these are, and the copy of the output
+struct LockstepLane {
+    Transcript* tr;
+    const uint8_t* seed;
+};
+static int prove_lockstep(zk_ctx* c, zk_pk_rec* pk, bool one_proof, const std::vector<LockstepLane>& lanes, const std::vector<std::vector<Fr>>& lists,
+                          const zk_poly* advice, int scheme) {
+    const Layout& lay = pk->lay;
+    const uint32_t B = (uint32_t)lanes.size();
+    // all grand products of the call are scanned by one 256-lane workgroup (gp_chain_kernel)
+    if ((uint64_t)B * (lay.n_chunks + lay.n_lookups) > 256) return ZK_EINVAL;
+    int rc = ctx_bind(c);
+    if (rc) return rc;
+    std::vector<const Fr*> adv;
+    if ((rc = resolve_advice(c, lay, advice, (size_t)B * lay.n_adv, &adv))) return rc;
+    if ((rc = one_proof ? pk_ensure_multi(c, pk, B) : pk_ensure_batch(c, pk, B))) return rc;
+    // columns per MSM pass: the same commitment of all lanes at once, two columns per lane where a phase has them (a', s';
+    // z, zL) — ZK_OPT_BATCH_PASS_COLUMNS overrides; the lanes' workspaces grow to that on their next pass
+    uint32_t cap = c->opt_batch_pass_cols ? c->opt_batch_pass_cols : std::max(std::min<uint32_t>(2 * B, 8u), ctx_msm_max_batch(c));
+    cap = ctx_msm_pass_cap(c, cap);  // at most MSM_MAX_BATCH; one column per pass without window tables (k < 10) and on the swept sort (k >= 22)
+    c->msm_min_cols = std::max(c->msm_min_cols, cap);
+    std::vector<std::unique_ptr<Prover>> provers;
+    std::vector<Prover*> P;
+    for (uint32_t q = 0; q < B; q++) {
+        provers.emplace_back(new Prover(c, q == 0 ? pk : pk->members[q - 1], lanes[q].seed, lanes[q].tr));
+        if (lay.n_inst) provers.back()->instance = &lists[q];
+        P.push_back(provers.back().get());
+    }
+    const uint64_t aud0 = c->audit.violations;
+    c->audit.base_of.clear();  // (allocations may have changed hands since the last proof)
+    {
+        LockstepRun run(c, pk, P, one_proof, cap);
+        ProveQuiesce quiesce(c);  // (declared after the provers: it settles the streams while their host buffers are alive)
+        rc = run.run(adv.data(), scheme);
+    }
+    if ((rc = aud_verdict(c, aud0, rc))) return rc;
+    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+    return ZK_OK;
+}
+
+// create_proof for `batch` independent proofs of one key in lock-step.  `with_instances`: zk_prove_batch_public —
 // one list per proof; otherwise zk_prove_batch, which a key WITH the column refuses
 static int prove_batch(zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, size_t n_advice, bool with_instances,
                        const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t* rng_seeds, int transcript, int scheme,
@@ -1051,52 +1129,19 @@ static int prove_batch(zk_ctx* c, zk_pk h, size_t batch, const zk_poly* advice, 
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
-    const Layout& lay = pk->lay;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
-    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
-    if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
-    if (lay.n_inst && !with_instances) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
-    std::vector<std::vector<Fr>> lists;
-    if (with_instances)
-        if (int r = pk_instance_lists(lay, batch, instances_mont, n_instances, &lists)) return r;
-    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
-    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
-    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    if (int r = admit_key(c, pk, n_advice)) return r;
+    std::vector<std::vector<Fr>> lists;  // (proof q's own list, absorbed by its own begin())
+    if (int r = admit_instances(pk->lay, with_instances, batch, instances_mont, n_instances, &lists)) return r;
+    if (int r = resolve_scheme(transcript, &scheme)) return r;
     const uint32_t B = (uint32_t)batch;
-    // all grand products of the batch are scanned by one 256-lane workgroup (gp_chain_kernel)
-    if ((uint64_t)B * (lay.n_chunks + lay.n_lookups) > 256) return ZK_EINVAL;
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    std::vector<const Fr*> adv(batch * n_advice);
-    for (size_t j = 0; j < batch * n_advice; j++) {
-        const PolyRec* r = ctx_poly(c, advice[j]);
-        if (!r || r->n != lay.n) return ZK_EINVAL;
-        adv[j] = r->ptr;
-    }
-    if ((rc = pk_ensure_batch(c, pk, B))) return rc;
-    // columns per MSM pass: the same commitment of all proofs at once, two columns per proof where a phase has them (a', s';
-    // z, zL) — ZK_OPT_BATCH_PASS_COLUMNS overrides; the lanes' workspaces grow to that on their next pass
-    uint32_t cap = c->opt_batch_pass_cols ? c->opt_batch_pass_cols : std::max(std::min<uint32_t>(2 * B, 8u), ctx_msm_max_batch(c));
-    cap = ctx_msm_pass_cap(c, cap);  // at most MSM_MAX_BATCH; one column per pass without window tables (k < 10) and on the swept sort (k >= 22)
-    c->msm_min_cols = std::max(c->msm_min_cols, cap);
+    // every proof its own transcript and its own seed
     std::vector<std::unique_ptr<Transcript>> trs;
-    std::vector<std::unique_ptr<Prover>> provers;
-    std::vector<Prover*> P;
+    std::vector<LockstepLane> lanes;
     for (uint32_t q = 0; q < B; q++) {
         trs.emplace_back(transcript == ZK_TRANSCRIPT_EVM ? (Transcript*)new EvmTranscript() : (Transcript*)new Blake2bTranscript());
-        provers.emplace_back(new Prover(c, q == 0 ? pk : pk->members[q - 1], rng_seeds + 32 * (size_t)q, trs.back().get()));
-        if (lay.n_inst) provers.back()->instance = &lists[q];  // (its own list, absorbed by its own begin())
-        P.push_back(provers.back().get());
+        lanes.push_back(LockstepLane{trs.back().get(), rng_seeds + 32 * (size_t)q});
     }
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
-    {
-        BatchRun run(c, pk, P, cap);
-        ProveQuiesce quiesce(c);
-        rc = run.run(adv.data(), scheme);
-    }
-    if ((rc = aud_verdict(c, aud0, rc))) return rc;
-    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+    if (int r = prove_lockstep(c, pk, false, lanes, lists, advice, scheme)) return r;
     const size_t len = trs[0]->out.size();
     for (uint32_t q = 0; q < B; q++)
         if (trs[q]->out.size() != len) return ZK_EINTERNAL;  // (one shape, one length)
@@ -1117,7 +1162,7 @@ ZK_API(zk_prove_batch_public, (zk_ctx* c, zk_pk h, size_t batch, const zk_poly* 
 }
 
 // create_proof(&params, &pk, &[c_0 .. c_{N-1}], &[inst_0 .. inst_{N-1}], ..): ONE proof over n_circuits circuits of one key
-// (prover_multi.h).  `with_instances`: zk_prove_multi_public — one list per circuit; otherwise zk_prove_multi
+// (prover_lockstep.h).  `with_instances`: zk_prove_multi_public — one list per circuit; otherwise zk_prove_multi
 static int prove_multi(zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, bool with_instances,
                        const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t rng_seed[32], int transcript, int scheme,
                        uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
@@ -1130,56 +1175,19 @@ static int prove_multi(zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* adv
     auto it = c->pks.find(h);
     if (it == c->pks.end()) return ZK_EINVAL;
     zk_pk_rec* pk = it->second;
-    const Layout& lay = pk->lay;
-    if (pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // the SRS was replaced after this key was made: its vk is stale
-    if (pk->verify_only) return ZK_ESTATE;  // a verifying-only key (zk_vk_read / zk_vk_from_parts) has no key polynomials
-    if (n_advice != lay.n_adv || c->srs_k != (int)lay.k) return ZK_EINVAL;
-    if (lay.n_inst && !with_instances) return ZK_EINVAL;  // (no instances in this form: halo2's InvalidInstances)
-    std::vector<std::vector<Fr>> lists;
-    if (with_instances)
-        if (int r = pk_instance_lists(lay, n_circuits, instances_mont, n_instances, &lists)) return r;
-    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
-    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
-    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
-    const uint32_t B = (uint32_t)n_circuits;
-    // all grand products of the proof are scanned by one 256-lane workgroup (gp_chain_kernel)
-    if ((uint64_t)B * (lay.n_chunks + lay.n_lookups) > 256) return ZK_EINVAL;
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    std::vector<const Fr*> adv(n_circuits * n_advice);
-    for (size_t j = 0; j < n_circuits * n_advice; j++) {
-        const PolyRec* r = ctx_poly(c, advice[j]);
-        if (!r || r->n != lay.n) return ZK_EINVAL;
-        adv[j] = r->ptr;
-    }
-    if ((rc = pk_ensure_multi(c, pk, B))) return rc;
-    // columns per MSM pass: zk_prove_batch's rule (ZK_OPT_BATCH_PASS_COLUMNS overrides)
-    uint32_t cap = c->opt_batch_pass_cols ? c->opt_batch_pass_cols : std::max(std::min<uint32_t>(2 * B, 8u), ctx_msm_max_batch(c));
-    cap = ctx_msm_pass_cap(c, cap);  // at most MSM_MAX_BATCH; one column per pass without window tables (k < 10) and on the swept sort (k >= 22)
-    c->msm_min_cols = std::max(c->msm_min_cols, cap);
+    if (int r = admit_key(c, pk, n_advice)) return r;
+    std::vector<std::vector<Fr>> lists;  // (circuit q's column; the driver absorbs the lists, no begin() does)
+    if (int r = admit_instances(pk->lay, with_instances, n_circuits, instances_mont, n_instances, &lists)) return r;
+    if (int r = resolve_scheme(transcript, &scheme)) return r;
     // the proof's transcript and RNG are circuit 0's prover's; circuits 1 .. N - 1 are workspaces: their provers get a scratch
     // transcript (begin() hashes transcript_repr into it) and a stream that is never drawn from
     EvmTranscript evm;
     Blake2bTranscript b2;
     Transcript* tr = transcript == ZK_TRANSCRIPT_EVM ? (Transcript*)&evm : (Transcript*)&b2;
-    std::vector<std::unique_ptr<Transcript>> scratch;
-    std::vector<std::unique_ptr<Prover>> provers;
-    std::vector<Prover*> P;
-    for (uint32_t q = 0; q < B; q++) {
-        if (q) scratch.emplace_back(new Blake2bTranscript());
-        provers.emplace_back(new Prover(c, q == 0 ? pk : pk->members[q - 1], rng_seed, q == 0 ? tr : scratch.back().get()));
-        if (lay.n_inst) provers.back()->instance = &lists[q];  // (circuit q's column; the driver absorbs the lists, no begin() does)
-        P.push_back(provers.back().get());
-    }
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
-    {
-        MultiRun run(c, pk, P, cap);
-        ProveQuiesce quiesce(c);
-        rc = run.run(adv.data(), scheme);
-    }
-    if ((rc = aud_verdict(c, aud0, rc))) return rc;
-    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+    std::vector<Blake2bTranscript> scratch(n_circuits - 1);
+    std::vector<LockstepLane> lanes;
+    for (size_t q = 0; q < n_circuits; q++) lanes.push_back(LockstepLane{q == 0 ? tr : &scratch[q - 1], rng_seed});
+    if (int r = prove_lockstep(c, pk, true, lanes, lists, advice, scheme)) return r;
     *proof_len = tr->out.size();
     if (!proof_out || proof_cap < tr->out.size()) return proof_out ? ZK_EINVAL : ZK_OK;
     memcpy(proof_out, tr->out.data(), tr->out.size());
@@ -1190,7 +1198,7 @@ ZK_API(zk_prove_multi, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* ad
     return prove_multi(c, h, n_circuits, advice, n_advice, false, nullptr, nullptr, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
 }
 
-// one proof over n_circuits circuits with every circuit's public inputs (the rule: prover_multi.h / DESIGN.md section 3)
+// one proof over n_circuits circuits with every circuit's public inputs (the rule: prover_lockstep.h / DESIGN.md section 3)
 ZK_API(zk_prove_multi_public, (zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice, size_t n_advice, const uint64_t* const* instances_mont, const size_t* n_instances, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len), (c, h, n_circuits, advice, n_advice, instances_mont, n_instances, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len)) {
     return prove_multi(c, h, n_circuits, advice, n_advice, true, instances_mont, n_instances, rng_seed, transcript, scheme, proof_out, proof_cap, proof_len);
 }

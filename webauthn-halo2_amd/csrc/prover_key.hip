@@ -740,7 +740,7 @@ ZK_API(zk_pk_shape, (zk_ctx* c, zk_pk h, uint32_t out[8]), (c, h, out)) {
 }
 
 // zk_quotient and zk_quotient_multi: n_circuits passes into ONE h — circuit 0 the plain kernel, circuits 1 .. N - 1 the
-// accumulating one, each with its own powers of y (prover_multi.h's chain: pass q carries y^(T (N - 1 - q))).  `with_instance`
+// accumulating one, each with its own powers of y (prover_lockstep.h's chain: pass q carries y^(T (N - 1 - q))).  `with_instance`
 // false: the key must have no instance column (zk_quotient); true: instance_ext holds one coset per circuit for a key with the
 // column and is null for a key without
 static int quotient_passes(zk_ctx* c, zk_pk h, size_t n_circuits, const zk_poly* advice_ext, size_t n_advice, bool with_instance,

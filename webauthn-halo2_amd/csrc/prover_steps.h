@@ -1,5 +1,5 @@
 // prover_steps.h — the steps of create_proof that more than one driver takes: ONE definition each, called by the single prover
-// (prover.hip Prover::run), the lock-step prover (prover_batch.h BatchRun::run) and the phase-level entry points
+// (prover.hip Prover::run), the lock-step prover (prover_lockstep.h LockstepRun::run) and the phase-level entry points
 // (prover_phases.hip).  A step enqueues on the stream it is given and names its buffers to the stream audit (audit.h) when that is
 // on; WHICH step runs, in which order, on which lane, and when the host waits is the drivers' business — no step synchronises
 // except where its result is read by the host (the grand products' scan totals, the lookup error flag, the evaluations).
@@ -274,7 +274,7 @@ inline int grand_products(zk_ctx* c, hipStream_t st, const Layout& lay, const st
 
 // ---------------------------------------------------------------- quotient ---
 // h(X) on the extended coset (pk_quotient, divided by X^n - 1) from the coset forms of the workspace's own columns, into h_ext
-// `into` / `yscale` / `accumulate`: one pass of a quotient that several circuits share (prover_multi.h) — this workspace's terms
+// `into` / `yscale` / `accumulate`: one pass of a quotient that several circuits share (prover_lockstep.h) — this workspace's terms
 // times yscale, stored to `into` or added to it; the plain call below is the pass that stores this workspace's own quotient
 inline int quotient_pass_of_workspace(zk_ctx* c, hipStream_t st, zk_pk_rec* pk, bool cosets3, const Fr& beta, const Fr& gamma, const Fr& y,
                                       Fr* into, const Fr& yscale, bool accumulate) {

@@ -151,7 +151,7 @@ __device__ __forceinline__ Fr29 quotient_row(const QuotientArgs& a, uint32_t i, 
     return norm29(add29(add29(acc, t0), add29(t1, t2)));  // 66 + 3 * 14 = 108 <= 168
 }
 
-// ACC: the pass ADDS its row to what `out` already holds (one proof over several circuits, prover_multi.h: circuit 0 runs the
+// ACC: the pass ADDS its row to what `out` already holds (one proof over several circuits, prover_lockstep.h: circuit 0 runs the
 // plain form, circuits 1 .. N - 1 this one on the same vector, each with its own powers of y).  out[i] is a standard-form,
 // canonical value (a previous pass stored it after reduce_once), so one modular addition keeps it canonical.  The lazy-sum
 // bounds above are PER PASS and do not change: the addition happens after the pass has left the carry-free field.

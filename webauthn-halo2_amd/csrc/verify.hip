@@ -583,9 +583,7 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
                          const size_t* lens, uint8_t* verdicts, bool with_instances = false, const uint64_t* const* instances_mont = nullptr,
                          const size_t* n_instances = nullptr, bool may_device = false) {
     if (!c || !proofs || !lens || !verdicts || batch == 0 || batch > ZK_VERIFY_BATCH_MAX) return ZK_EINVAL;
-    if (transcript != ZK_TRANSCRIPT_BLAKE2B && transcript != ZK_TRANSCRIPT_EVM) return ZK_EINVAL;
-    if (scheme == ZK_SCHEME_DEFAULT) scheme = transcript == ZK_TRANSCRIPT_EVM ? ZK_SCHEME_GWC : ZK_SCHEME_SHPLONK;
-    if (scheme != ZK_SCHEME_GWC && scheme != ZK_SCHEME_SHPLONK) return ZK_EINVAL;
+    if (int r = resolve_scheme(transcript, &scheme)) return r;
     for (size_t j = 0; j < batch; j++)
         if (!proofs[j] && lens[j]) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);

@@ -470,7 +470,7 @@ int zk_prove(zk_ctx* ctx, zk_pk pk, const zk_poly* advice, size_t n_advice, cons
              int transcript, int scheme, uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
 /* ---- public inputs: create_proof / verify_proof with `instances = &[&[&values]]` for a key whose shape has the instance column
  * (zk_circuit_params.num_instance_columns = 1) [RECALLED: halo2 with KZG, QUERY_INSTANCE = false; no reference bytes pin it - the
- * reference circuit has no public inputs.  tests/public_ref.py restates the rule and the bytes are compared with it]:
+ * reference circuit has no public inputs.  tests/halo2_ref.py restates the rule and the bytes are compared with it]:
  *   vk digest   num_instance_columns: 1, instance_queries: [(Column { index: 0, column_type: Instance }, Rotation(0))], and the
  *               column at the end of the permutation argument's columns
  *   transcript  transcript_repr; EVERY instance value as common_scalar, in order (absorbed, not written; the count is not hashed);
@@ -512,7 +512,7 @@ int zk_prove_batch(zk_ctx* ctx, zk_pk pk, size_t batch, const zk_poly* advice /*
                    size_t* proof_len);
 /* replaces plonk::create_proof(&params, &pk, &[c_0 .. c_{N-1}], &[&[]; N], rng, &mut transcript): N circuits under ONE key in ONE
  * proof - one transcript, one set of challenges, one random polynomial, one quotient, one multi-open - as halo2 makes it for
- * `circuits: &[ConcreteCircuit]` [RECALLED; not pinned by reference bytes: tests/multi_ref.py restates the rule and the bytes
+ * `circuits: &[ConcreteCircuit]` [RECALLED; not pinned by reference bytes: tests/halo2_ref.py restates the rule and the bytes
  * are compared with it].  c = 0 .. N - 1 in the caller's order:
  *   transcript  transcript_repr (N is not hashed); for c: the advice commitments; theta; for c, per lookup: a', s'; beta, gamma;
  *               for c: z of every chunk; for c: zL of every lookup; ONE random-polynomial commitment; y; the h pieces (as many as
@@ -556,7 +556,7 @@ int zk_prove_multi(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const zk_poly* advi
  * writes every row of every column; their coefficient and coset forms ride in the batched transforms of the first advice forms.
  *
  * zk_prove_multi_public: zk_prove_multi with list c for circuit c [RECALLED, as zk_prove_multi's rule: not pinned by reference
- * bytes; tests/multi_public_ref.py restates it and the bytes are compared with it].  The rule is zk_prove_multi's with
+ * bytes; tests/halo2_ref.py restates it and the bytes are compared with it].  The rule is zk_prove_multi's with
  *   transcript   transcript_repr; for c = 0 .. N - 1: every value of circuit c's list (absorbed, not written; neither N nor the
  *                lengths are hashed); then everything else in zk_prove_multi's order.  ALL circuits' instances come before any advice
  *                commitment: halo2's loop over `instances` at the top of create_proof / verify_proof

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generates tests/golden/multi_public_proofs.json: ONE proof over two circuits of the k10batched shape of tests/prover_shapes.py
-with the instance column - lists of 9 and 1 values - made by tests/multi_public_ref.py (the plain-Python statement of the multi
+with the instance column - lists of 9 and 1 values - made by tests/halo2_ref.py (the plain-Python statement of the multi
 rule with public inputs) under both reference pairings.  tests/test_gpu_prove_multi_public.py makes the same key and witnesses on
 the device - at k = 10 the commitments go through the column-batched MSM passes and the batched transforms - and compares
 zk_prove_multi_public's bytes; tests/test_gpu_verify_public_forms.py verifies them.  The fixture keeps the Python prover out of
@@ -17,8 +17,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 
 from zkoracle.hashes import ChaCha20Rng  # noqa: E402
-import multi_public_ref  # noqa: E402
-import multi_ref  # noqa: E402
+import halo2_ref  # noqa: E402
 from multi_public_cases import lanes  # noqa: E402  (witness generator only; no engine is touched)
 from public_cases import PAIRINGS, SEED, reference_key  # noqa: E402
 
@@ -32,9 +31,9 @@ def main():
     out = {"shape": NAME, "lengths": list(LENGTHS), "instances": [[hex(v) for v in l] for l in lists],
            "transcript_repr": hex(pk.vk.transcript_repr), "proofs": {}}
     for kind, scheme in PAIRINGS:
-        proof = multi_public_ref.create_proof_multi(pk, [a.advice for a, _ in made], lists, ChaCha20Rng(SEED), kind, scheme)
-        assert multi_public_ref.verify_multi(pk.vk, proof, lists, kind, scheme)
-        assert len(proof) == multi_ref.proof_offsets(pk.shape, len(lists), kind, scheme)["length"]
+        proof = halo2_ref.create_proof(pk, [a.advice for a, _ in made], lists, ChaCha20Rng(SEED), kind, scheme)
+        assert halo2_ref.verify(pk.vk, proof, lists, kind, scheme)
+        assert len(proof) == halo2_ref.proof_size(pk.shape, len(lists), kind, scheme)
         out["proofs"][kind + "/" + scheme] = proof.hex()
         print("%s / %s  %d bytes" % (kind, scheme, len(proof)), flush=True)
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "multi_public_proofs.json"), "w") as f:

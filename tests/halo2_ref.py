@@ -1,38 +1,179 @@
-"""One proof over N circuits of one key WITH public inputs, restated in plain Python: halo2's `create_proof(params, pk, &[c_0 ..
-c_{N-1}], &[inst_0 .. inst_{N-1}], rng, transcript)` and `verify_proof(.., instances: &[&[&[Fr]]], ..)` with one instance column
-per circuit [RECALLED: halo2_proofs plonk/prover.rs, plonk/verifier.rs - no reference bytes pin it].  The reference of
-zk_prove_multi_public / zk_verify_multi_public (csrc/prover_lockstep.h, csrc/verifier.h).  It is tests/multi_ref.py's flow with
-tests/public_ref.py's column in it; tests/test_multi_public_ref.py ties it to both (N = 1: public_ref.create_proof byte for byte; a
-shape without the column: multi_ref.create_proof_multi byte for byte) and checks what its own verifier accepts and rejects.
+"""halo2's `create_proof(params, pk, &[c_0 .. c_{N-1}], &[inst_0 .. inst_{N-1}], rng, transcript)` and `verify_proof(.., instances:
+&[&[&[Fr]]], ..)` under KZG (`QUERY_INSTANCE = false`) for N >= 1 circuits of one key, with or without ONE instance column,
+restated in plain Python over zkoracle primitives [RECALLED: halo2_proofs plonk/{keygen,prover,verifier}.rs, plonk/permutation - no
+reference bytes pin it: the reference circuit has one circuit per proof and no public inputs].  The reference of zk_prove_public,
+zk_prove_multi, zk_prove_multi_public and the zk_verify* forms (csrc/prover.hip, csrc/prover_lockstep.h, csrc/verifier.h,
+csrc/vkrepr.h).  tests/test_halo2_ref.py and tests/test_multi_ref.py tie it to the pinned oracle where they overlap (a shape
+without the column: key and proof byte for byte; N = 1: proof byte for byte), to recorded digests of its proofs
+(tests/golden/ref_proof_sha256.json) and check that its own verifier accepts and rejects what it should.  The oracle's own keygen,
+prover and rendering know neither N nor an instance column and stay untouched.
 
-The rule is multi_ref's (transcript order, ONE RNG stream, the y-Horner chain across circuits, the multi-open) with:
-  transcript   transcript_repr; for c = 0 .. N - 1: every value of circuit c's list as common_scalar (absorbed, not written; neither N
-               nor the lengths are hashed); then everything else in multi_ref's order.  ALL circuits' instances come before any
-               advice commitment: halo2's loop over `instances` at the top of create_proof and verify_proof.
-  RNG          the instance columns draw nothing.
-  permutation  circuit c's grand product reads c's column (rows 0 .. m_c - 1 its values, zero behind them).
-  quotient     circuit c's terms read c's column on the extended coset.
-  verifier     circuit c's permutation terms of the expected h(x) use inst_c(x) (public_ref.instance_eval).
-Nothing of the columns is committed, evaluated into the proof or opened: the query list is multi_ref.query_list over the shape's
-permutation columns, which include the instance column's sigma.  Everything is canonical Python ints."""
+The rule, c = 0 .. N - 1 in the caller's order, T = terms of one circuit's y-combination, bf = BLINDING_FACTORS:
+  shape       the circuit makes the instance column after the chips' columns and enables equality on it: the LAST permutation
+              column, [constants.., gate advice.., lookup advice.., instance], queried at rotation 0.  cs.degree(), the blinding
+              factors and the chunk length do not change; n_chunks = ceil(#perm columns / chunk_len) may grow by one.
+  vk digest   the pinned rendering with num_instance_columns: 1, instance_queries: [(Column { index: 0, column_type: Instance },
+              Rotation(0))] and the instance column at the end of permutation: Argument { columns: [..] }
+  transcript  transcript_repr; for c: every value of circuit c's list as common_scalar (absorbed, not written; neither N nor the
+              lengths are hashed; ALL circuits' instances come before any advice commitment: halo2's loop over `instances` at the
+              top of create_proof and verify_proof); for c: advice commitments; theta; for c, per lookup: a', s'; beta, gamma; for
+              c: z of every chunk; for c: zL of every lookup; ONE random-polynomial commitment; y; the h pieces; x; evaluations -
+              for c: advice in query order; fixed, once; random; sigma, once; for c: per chunk z(x), z(wx) and (not the last
+              chunk) z(w^last x); for c, per lookup: zL(x), zL(wx), a'(x), a'(w^-1 x), s'(x) - then the multi-open
+  RNG         one stream: for c: (bf + 1) rows per advice column, then n_adv blinds; for c, per lookup: (bf + 1) rows for a',
+              (bf + 1) for s', 2 blinds; for c, per chunk: bf rows, 1 blind; for c, per lookup: bf rows, 1 blind; n draws for
+              the random polynomial, 1 blind; n_h blinds.  The instance columns draw nothing.
+  instances   circuit c's m_c values fill rows 0 .. m_c - 1 of a Lagrange column, the rest is zero; the column is neither blinded
+              nor committed, not evaluated into the proof and not opened.  It enters c's permutation grand product as its column's
+              values and c's quotient terms as that column's extended coset.  m_c > n - 7 is halo2's InstanceTooLarge; on a shape
+              without the column every m_c > 0 is.
+  quotient    the y-Horner chain runs on across circuits (term j of circuit c has weight y^(N T - 1 - (c T + j)))
+  multi-open  queries: for c: advice queries, per chunk z@0, z@1, then z@last for chunks n_chunks - 2 .. 0, per lookup zL@0, a'@0,
+              s'@0, a'@-1, zL@1; then fixed, sigma (over the shape's permutation columns, the instance column's included), h,
+              random.  GWC groups by rotation in order of first appearance, SHPLONK by rotation set.
+  verifier    absorbs the same values; inst_c(x) = sum_i v_i l_i(x), l_i(x) = w^i (x^n - 1) / (n (x - w^i)), is that column's
+              evaluation in circuit c's permutation terms of the expected h(x).
+
+Both kinds of key are taken: a zkoracle.prover.ProvingKey, whose plonk.Shape has no n_inst, and the keys of keygen below.
+Commitments are made with the known trusted-setup secret, as the oracle's; the verifier's pairing is the equivalent check with
+tau and costs O(1) in n.  Everything is canonical Python ints."""
+import copy
+import hashlib
+
 from zkoracle import curve as C
+from zkoracle import vkrepr
 from zkoracle.field import DELTA, R, ZETA, batch_inv, inv, omega
-from zkoracle.plonk import (BLINDING_FACTORS, eval_poly, lagrange_evals_at, lagrange_interpolate, make_transcript, msm_points,
-                            selector_value, vanishing_eval)
-from zkoracle.prover import (Committer, coeff_to_extended, commit_coeff, extended_to_coeff, kate_division, lagrange_to_coeff,
-                             permute_expression_pair)
+from zkoracle.plonk import (BLINDING_FACTORS, Shape, VerifyingKey, eval_poly, lagrange_evals_at, lagrange_interpolate, make_transcript,
+                            msm_points, selector_value, vanishing_eval)
+from zkoracle.prover import (Committer, ProvingKey, build_sigma, coeff_to_extended, commit_coeff, extended_to_coeff, kate_division,
+                             lagrange_to_coeff, permute_expression_pair)
 from zkoracle.srs import TAU
 
-from multi_ref import gwc_sets, query_list, quotient_terms, shplonk_sets  # (the query list and its grouping are multi_ref's own)
-from public_ref import instance_column, instance_eval
+INSTANCE = ("instance", 0)
 
 
-def create_proof_multi(pk, advices, instances, rng, kind="evm", scheme=None):
-    """The proof bytes of N = len(advices) circuits under `pk` (public_ref.keygen) with instances[c] the public inputs of circuit c;
-    rng.fr() = one Fr::random.  A list the column cannot hold raises public_ref.InstanceTooLarge."""
+class InstanceTooLarge(ValueError):
+    pass
+
+
+def public_shape(k, A, L, F, lookup_bits, idle=0, n_inst=1):
+    """The oracle's Shape with the instance column as the last permutation column (n_inst = 0: the oracle's Shape itself)."""
+    sh = Shape(k, A, L, F, lookup_bits, idle)
+    sh.n_inst = n_inst
+    assert n_inst in (0, 1)
+    if n_inst:
+        sh.perm_cols = sh.perm_cols + [INSTANCE]
+        sh.n_chunks = (len(sh.perm_cols) + sh.chunk_len - 1) // sh.chunk_len
+    return sh
+
+
+def pinned_debug(sh, fixed_commitments, permutation_commitments):
+    """format!("{:?}", vk.pinned()): the oracle's rendering of the shape without the column, with the three changes of the rule."""
+    if not sh.n_inst:
+        return vkrepr.pinned_debug(sh, fixed_commitments, permutation_commitments)
+    base = copy.copy(sh)
+    base.perm_cols = sh.perm_cols[:-1]
+    s = vkrepr.pinned_debug(base, fixed_commitments, permutation_commitments)
+    col = "Column { index: 0, column_type: Instance }"
+    for old, new in (("num_instance_columns: 0", "num_instance_columns: 1"),
+                     ("instance_queries: []", "instance_queries: [(%s, Rotation(0))]" % col),
+                     ("] }, lookups: [", ", %s] }, lookups: [" % col)):
+        assert s.count(old) == 1
+        s = s.replace(old, new)
+    return s
+
+
+def transcript_repr(sh, fixed_commitments, permutation_commitments):
+    s = pinned_debug(sh, fixed_commitments, permutation_commitments).encode()
+    h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
+    h.update(len(s).to_bytes(8, "little"))
+    h.update(s)
+    return int.from_bytes(h.digest(), "little") % R
+
+
+def keygen(sh, fixed, copies):
+    """keygen_vk + keygen_pk over the shape's permutation columns (the instance column included): copies may name it."""
+    cm = Committer(sh.k)
+    sigma = build_sigma(sh, copies)
+    fc = [cm.lagrange(col) for col in fixed]
+    pc = [cm.lagrange(col) for col in sigma]
+    return ProvingKey(sh, fixed, sigma, VerifyingKey(sh, fc, pc, transcript_repr(sh, fc, pc)))
+
+
+def instance_column(sh, instances):
+    holds = sh.usable_rows if getattr(sh, "n_inst", 0) else 0
+    if len(instances) > holds:
+        raise InstanceTooLarge("%d instance values, the column holds %d" % (len(instances), holds))
+    if any(not 0 <= v < R for v in instances):
+        raise ValueError("instance value not below the modulus")
+    return list(instances) + [0] * (sh.n - len(instances))
+
+
+def instance_eval(sh, instances, x):
+    """inst(x) = sum_i v_i l_i(x), l_i(x) = w^i (x^n - 1) / (n (x - w^i)), with one batch inversion."""
+    if not instances:
+        return 0
+    w = omega(sh.k)
+    wi = [1] * len(instances)
+    for i in range(1, len(wi)):
+        wi[i] = wi[i - 1] * w % R
+    if any((x - p) % R == 0 for p in wi):
+        raise ValueError("x on the domain")
+    dinv = batch_inv([(x - p) % R for p in wi], R)
+    c = (pow(x, sh.n, R) - 1) * inv(sh.n, R) % R
+    return sum(v * p % R * d for v, p, d in zip(instances, wi, dinv)) % R * c % R
+
+
+def quotient_terms(sh):
+    return sh.n_gate + 2 + (sh.n_chunks - 1) + sh.n_chunks + 5 * sh.n_lookups
+
+
+def query_list(sh, N):
+    """[(key, rotation)] of the multi-open; keys of a circuit's own polynomials carry the circuit index."""
+    q = []
+    for c in range(N):
+        q += [(("adv", c, col), r) for col, r in sh.advice_queries]
+        for ci in range(sh.n_chunks):
+            q += [(("z", c, ci), 0), (("z", c, ci), 1)]
+        for ci in reversed(range(sh.n_chunks - 1)):
+            q.append((("z", c, ci), sh.last_rot))
+        for l in range(sh.n_lookups):
+            q += [(("lz", c, l), 0), (("la", c, l), 0), (("ls", c, l), 0), (("la", c, l), -1), (("lz", c, l), 1)]
+    q += [(("fix", col), r) for col, r in sh.fixed_queries]
+    q += [(("sigma", i), 0) for i in range(len(sh.perm_cols))]
+    q += [(("h",), 0), (("rand",), 0)]
+    return q
+
+
+def gwc_sets(queries):
+    sets = []
+    for key, r in queries:
+        for s in sets:
+            if s[0] == r:
+                s[1].append(key)
+                break
+        else:
+            sets.append((r, [key]))
+    return sets
+
+
+def shplonk_sets(queries):
+    com_rots = {}
+    for key, r in queries:  # (dicts keep the order of first appearance)
+        com_rots.setdefault(key, set()).add(r)
+    rsets = {}
+    for key, rots in com_rots.items():
+        rsets.setdefault(frozenset(rots), []).append(key)
+    return list(rsets.items())
+
+
+def create_proof(pk, advices, instances, rng, kind="evm", scheme=None):
+    """The proof bytes of N = len(advices) circuits under `pk` with instances[c] the public inputs of circuit c (None: N empty
+    lists); rng.fr() = one Fr::random.  A list the column cannot hold raises InstanceTooLarge."""
     scheme = scheme or ("gwc" if kind == "evm" else "shplonk")
     sh = pk.shape
     N = len(advices)
+    instances = [[]] * N if instances is None else instances
     assert len(instances) == N, "one instance list per circuit"
     n, k, bf = sh.n, sh.k, BLINDING_FACTORS
     w = omega(k)
@@ -79,7 +220,7 @@ def create_proof_multi(pk, advices, instances, rng, kind="evm", scheme=None):
     beta = tr.squeeze()
     gamma = tr.squeeze()
 
-    # -- 3. permutation grand products of every circuit
+    # -- 3. permutation grand products of every circuit: the instance column is a column like the others
     wp = [1] * n
     for i in range(1, n):
         wp[i] = wp[i - 1] * w % R
@@ -133,7 +274,8 @@ def create_proof_multi(pk, advices, instances, rng, kind="evm", scheme=None):
     tr.write_point(commit_coeff(random_poly))
     y = tr.squeeze()
 
-    # -- 6. ONE quotient: the Horner chain runs on across the circuits
+    # -- 6. ONE quotient: the Horner chain runs on across the circuits; the instance column through lagrange_to_coeff and
+    #       coeff_to_extended, as an advice column
     ext_k, NE = sh.ext_k, 1 << sh.ext_k
     step = 1 << (ext_k - k)
     coeff = lambda v: lagrange_to_coeff(v, k)
@@ -213,7 +355,7 @@ def create_proof_multi(pk, advices, instances, rng, kind="evm", scheme=None):
         tr.write_point(commit_coeff(hp))
     x = tr.squeeze()
 
-    # -- 7. evaluations
+    # -- 7. evaluations: nothing of the instance columns
     xr = lambda r: x * pow(w, r, R) % R
     xn = pow(x, n, R)
     h_comb = [0] * n
@@ -323,10 +465,10 @@ def create_proof_multi(pk, advices, instances, rng, kind="evm", scheme=None):
     return tr.finalize()
 
 
-def verify_multi(vk, proof, instances, kind="evm", scheme=None):
+def verify(vk, proof, instances, kind="evm", scheme=None):
     """True iff `proof` verifies as ONE proof over N = len(instances) circuits of `vk` with instances[c] the public inputs of circuit
-    c; the pairing is the equivalent check with tau.  A list the column cannot hold raises InstanceTooLarge (halo2's error, not a
-    verdict)."""
+    c ([[]] * N: none); the pairing is the equivalent check with tau.  A list the column cannot hold raises InstanceTooLarge
+    (halo2's error, not a verdict)."""
     scheme = scheme or ("gwc" if kind == "evm" else "shplonk")
     sh = vk.shape
     N = len(instances)
@@ -386,7 +528,7 @@ def verify_multi(vk, proof, instances, kind="evm", scheme=None):
         acc = 0
         for c in range(N):
             adv = lambda col, r: evals[(("adv", c, col), r)]
-            inst_x = instance_eval(sh, list(instances[c]), x) if getattr(sh, "n_inst", 0) else 0
+            inst_x = instance_eval(sh, list(instances[c]), x)
             col_eval = lambda col: fix(col[1]) if col[0] == "fixed" else inst_x if col[0] == "instance" else adv(col[1], 0)
             z = lambda ci, r: evals[(("z", c, ci), r)]
             exprs = []
@@ -486,3 +628,34 @@ def verify_multi(vk, proof, instances, kind="evm", scheme=None):
         return bool(ok and tr.done())
     except ValueError:
         return False
+
+
+def proof_offsets(sh, N, kind, scheme=None):
+    """The proof length by formula (points before the evaluations, the evaluations, the opening proof) and the byte offsets of the
+    places the tests tamper with, by name: the LAST z commitment (the new chunk's where the column starts one), the LAST sigma
+    evaluation (the instance column's), and - N >= 2 - places of circuit 1 and of what the circuits share."""
+    scheme = scheme or ("gwc" if kind == "evm" else "shplonk")
+    ps = 64 if kind == "evm" else 32
+    per_pts = sh.n_adv + 3 * sh.n_lookups + sh.n_chunks
+    n_pts = N * per_pts + 1 + sh.n_h
+    ev0 = n_pts * ps
+    n_aq = len(sh.advice_queries)
+    n_ev = N * (n_aq + 3 * sh.n_chunks - 1 + 5 * sh.n_lookups) + sh.n_fix + 1 + len(sh.perm_cols)
+    z0 = N * n_aq + sh.n_fix + 1 + len(sh.perm_cols)  # evaluations before the first z's
+    lk0 = z0 + N * (3 * sh.n_chunks - 1)
+    n_open = 2 if scheme == "shplonk" else sh.gwc_sets()
+    return {
+        "advice commitment of circuit 1": sh.n_adv * ps + 3,
+        "last z commitment": (N * (sh.n_adv + 2 * sh.n_lookups + sh.n_chunks) - 1) * ps + 3,
+        "h piece": (N * per_pts + 1) * ps + 5,
+        "shared fixed evaluation": ev0 + 32 * (N * n_aq) + 7,
+        "last sigma evaluation": ev0 + 32 * (z0 - 1) + 7,
+        "circuit-1 lookup evaluation": ev0 + 32 * (lk0 + 5 * sh.n_lookups) + 9,
+        "last opening": ev0 + 32 * n_ev + (n_open - 1) * ps + 11,
+        "length": ev0 + 32 * n_ev + n_open * ps,
+        "per circuit": per_pts * ps + 32 * (n_aq + 3 * sh.n_chunks - 1 + 5 * sh.n_lookups),
+    }
+
+
+def proof_size(sh, N, kind, scheme=None):
+    return proof_offsets(sh, N, kind, scheme)["length"]

@@ -1,12 +1,9 @@
 """Shared by the tests of one proof over N circuits (tests/test_multi_ref.py, tests/test_verify_multi_host.py,
-tests/test_gpu_prove_multi.py, tests/test_gpu_verify_multi.py): the oracle key and witnesses of a shape of tests/prover_shapes.py,
-the same on an engine, and the tampered variants of a proof."""
-import numpy as np
-
+tests/test_gpu_prove_multi.py, tests/test_gpu_verify_multi.py): the oracle key and witnesses of a shape of tests/prover_shapes.py
+without the instance column, the same on an engine (tests/public_cases.py's, at n_inst = 0), and the tampered variants of a proof."""
 import webauthn_halo2_amd as zk
 from zkoracle import plonk, prover
-from prover_shapes import SHAPES
-import multi_ref
+import public_cases
 
 PAIRINGS = [("evm", "gwc"), ("blake2b", "shplonk")]  # the reference's two: verify_evm and verify
 SEED = b"\x2a" * 32
@@ -14,8 +11,7 @@ PLACES = ("advice commitment of circuit 1", "h piece", "shared fixed evaluation"
 
 
 def params_of(name):
-    A, L, F, k, lb, idle = (tuple(SHAPES[name]) + (0,))[:6]
-    return zk.circuit.CircuitParams(degree=k, num_advice=A, num_lookup_advice=L, num_fixed=F, lookup_bits=lb, idle_gate_columns=idle)
+    return public_cases.params_of(name, 0)
 
 
 def witnesses(name, count):
@@ -36,28 +32,8 @@ def setup(name, n_witnesses):
 
 
 def engine_key(eng, name, asgs):
-    """(pk, advice sets) of the shape on `eng`: SRS of the shape's k, the key, every witness's columns resident."""
-    p = params_of(name)
-    eng.srs_setup(p.degree)
-    fixed = np.stack([asgs[0].to_limbs(c) for c in asgs[0].fixed])
-    pk = eng.keygen(p, fixed, asgs[0].copies)
-    sets = []
-    for asg in asgs:
-        polys = []
-        for col in asg.advice:
-            h = eng.poly(1 << p.degree)
-            eng.upload_canonical(h, asg.to_limbs(col))
-            polys.append(h)
-        sets.append(polys)
-    return pk, sets
+    return public_cases.engine_key(eng, name, asgs, 0)
 
 
 def tampered(proof, shape, N, kind, scheme):
-    """[(place, bytes)]: one flipped byte at each of PLACES."""
-    off = multi_ref.proof_offsets(shape, N, kind, scheme)
-    out = []
-    for place in PLACES:
-        b = bytearray(proof)
-        b[off[place]] ^= 0x10
-        out.append((place, bytes(b)))
-    return out
+    return public_cases.tampered(proof, shape, N, kind, scheme, PLACES)

@@ -1,4 +1,4 @@
-"""Shared by the tests of the batch and multi forms with public inputs (tests/test_multi_public_ref.py,
+"""Shared by the tests of the batch and multi forms with public inputs (tests/test_halo2_ref.py,
 tests/test_verify_public_forms_host.py, tests/golden/make_multi_public_proofs.py and the tests/test_gpu_*public* files of those
 forms): witnesses of ONE key whose instance lists have different lengths, and the lists under which a multi proof must not verify.
 
@@ -7,8 +7,8 @@ list has m < N_PUBLIC values has the other exposed outputs forced to zero (circu
 [v_0 .. v_{m-1}, 0, ..] satisfies the copy constraints; a list longer than N_PUBLIC is the full list with zeros appended - the same
 column, another transcript."""
 import webauthn_halo2_amd as zk
-from public_cases import params_of
-import public_ref
+from public_cases import engine_key, mont, params_of
+import halo2_ref
 
 N_PUBLIC = 9
 WITNESS_SEED = 0x5EED0A00
@@ -34,7 +34,7 @@ def wrong_multi_lists(lists):
     """[(what, lists)]: per-circuit instance lists under which a multi proof over `lists` must not verify (N >= 2; circuit 1's list
     has a value)."""
     changed = [list(l) for l in lists]
-    changed[1][len(changed[1]) // 2] = (changed[1][len(changed[1]) // 2] + 1) % public_ref.R
+    changed[1][len(changed[1]) // 2] = (changed[1][len(changed[1]) // 2] + 1) % halo2_ref.R
     swapped = [list(l) for l in lists]
     swapped[0], swapped[1] = swapped[1], swapped[0]
     dropped = [list(l) for l in lists]
@@ -51,20 +51,5 @@ def wrong_multi_lists(lists):
 def engine_lanes(eng, name, made, n_inst=1):
     """(pk, advice sets, Montgomery lists) of the lanes `made` (lanes() above) on `eng`: SRS of the shape's k, the key of lane 0's
     structure, every lane's columns resident."""
-    import numpy as np
-
-    from public_cases import mont
-
-    p = params_of(name, n_inst)
-    eng.srs_setup(p.degree)
-    first = made[0][0]
-    pk = eng.keygen(p, np.stack([first.to_limbs(c) for c in first.fixed]), first.copies)
-    sets = []
-    for asg, _ in made:
-        polys = []
-        for col in asg.advice:
-            h = eng.poly(1 << p.degree)
-            eng.upload_canonical(h, asg.to_limbs(col))
-            polys.append(h)
-        sets.append(polys)
+    pk, sets = engine_key(eng, name, [asg for asg, _ in made], n_inst)
     return pk, sets, [mont(vals) if vals else None for _, vals in made]

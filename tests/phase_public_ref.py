@@ -1,18 +1,17 @@
 """The phase-level forms with public inputs and N circuits as functions of explicit inputs (tests/test_phase_public_ref.py,
 tests/test_gpu_phase_public.py): step 3 (the permutation grand products, the instance column among their columns) and step 6 (the
-ONE quotient over N circuits) of tests/public_ref.py `create_proof` and tests/multi_public_ref.py `create_proof_multi`, lifted out
-of their transcript flow so that a test can hand them any beta, gamma, y, columns and instance lists - what a host on
-zk_permutation_product_public and zk_quotient_multi is free to do.  The same arrangement as tests/phase_ref.py for the forms
-without the column; the column itself, the permutation columns and the transforms are those references' own (public_ref.
-instance_column, the shape of public_ref.public_shape, zkoracle.prover's transforms).  Plain Python integers, canonical.
+ONE quotient over N circuits) of tests/halo2_ref.py `create_proof`, restated a second time outside its transcript flow so that a
+test can hand them any beta, gamma, y, columns and instance lists - what a host on zk_permutation_product_public and
+zk_quotient_multi is free to do.  The same arrangement as tests/phase_ref.py for the forms without the column; the column itself,
+the permutation columns and the transforms are that reference's own (halo2_ref.instance_column, the shape of
+halo2_ref.public_shape, zkoracle.prover's transforms).  Plain Python integers, canonical.
 
 Only the rows the device entry points promise are returned for z: rows 0 .. usable (usable = n - 7)."""
 from zkoracle.field import DELTA, R, ZETA, batch_inv, inv, omega
 from zkoracle.plonk import BLINDING_FACTORS, selector_value
 from zkoracle.prover import coeff_to_extended, extended_to_coeff, lagrange_to_coeff
 
-from multi_ref import quotient_terms
-from public_ref import instance_column
+from halo2_ref import instance_column, quotient_terms
 
 
 def _column(fixed, advice, inst, col):

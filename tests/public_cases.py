@@ -1,12 +1,13 @@
-"""Shared by the tests of public inputs (tests/test_public_ref.py, tests/test_public_host.py, tests/test_gpu_prove_public.py,
-tests/test_gpu_verify_public.py, tests/test_gpu_witness_check_public.py, tests/golden/make_public_proofs.py): the shapes of
-tests/prover_shapes.py with the instance column, their witnesses with n_public exposed gate outputs, the reference key
-(tests/public_ref.py) and the same on an engine, and the tampered variants of a proof."""
+"""Shared by the tests of public inputs (tests/test_halo2_ref.py, tests/test_public_host.py, tests/test_gpu_prove_public.py,
+tests/test_gpu_verify_public.py, tests/test_gpu_witness_check_public.py, tests/golden/make_public_proofs.py) and, through
+tests/multi_cases.py and tests/multi_public_cases.py, of N circuits: the shapes of tests/prover_shapes.py with the instance
+column, their witnesses with n_public exposed gate outputs, the reference key (tests/halo2_ref.py) and the same on an engine, and
+the tampered variants of a proof."""
 import numpy as np
 
 import webauthn_halo2_amd as zk
 from prover_shapes import SHAPES
-import public_ref
+import halo2_ref
 
 PAIRINGS = [("evm", "gwc"), ("blake2b", "shplonk")]  # the reference's two: verify_evm and verify
 COMBOS = [(k, s) for k in ("evm", "blake2b") for s in ("gwc", "shplonk")]
@@ -23,7 +24,7 @@ def params_of(name, n_inst=1):
 
 def shape_of(name, n_inst=1):
     A, L, F, k, lb, idle = (tuple(SHAPES[name]) + (0,))[:6]
-    return public_ref.public_shape(k, A, L, F, lb, idle, n_inst)
+    return halo2_ref.public_shape(k, A, L, F, lb, idle, n_inst)
 
 
 def witness(name, n_public, n_inst=1):
@@ -32,31 +33,35 @@ def witness(name, n_public, n_inst=1):
 
 
 def reference_key(name, asg, n_inst=1):
-    return public_ref.keygen(shape_of(name, n_inst), asg.fixed, asg.copies)
+    return halo2_ref.keygen(shape_of(name, n_inst), asg.fixed, asg.copies)
 
 
-def engine_key(eng, name, asg, n_inst=1):
-    """(pk, advice columns) of the shape on `eng`: SRS of the shape's k, the key, the witness's columns resident."""
+def engine_key(eng, name, asgs, n_inst=1):
+    """(pk, advice sets) of the shape on `eng`: SRS of the shape's k, the key of asgs[0]'s structure, every witness's columns
+    resident."""
     p = params_of(name, n_inst)
     eng.srs_setup(p.degree)
-    pk = eng.keygen(p, np.stack([asg.to_limbs(c) for c in asg.fixed]), asg.copies)
-    polys = []
-    for col in asg.advice:
-        h = eng.poly(1 << p.degree)
-        eng.upload_canonical(h, asg.to_limbs(col))
-        polys.append(h)
-    return pk, polys
+    pk = eng.keygen(p, np.stack([asgs[0].to_limbs(c) for c in asgs[0].fixed]), asgs[0].copies)
+    sets = []
+    for asg in asgs:
+        polys = []
+        for col in asg.advice:
+            h = eng.poly(1 << p.degree)
+            eng.upload_canonical(h, asg.to_limbs(col))
+            polys.append(h)
+        sets.append(polys)
+    return pk, sets
 
 
 def mont(vals):
     return zk.circuit.Assignment.to_mont_limbs(list(vals))
 
 
-def tampered(proof, shape, kind, scheme):
-    """[(place, bytes)]: one flipped byte at each of PLACES."""
-    off = public_ref.proof_offsets(shape, kind, scheme)
+def tampered(proof, shape, N, kind, scheme, places=PLACES):
+    """[(place, bytes)]: one flipped byte at each of `places` of a proof over N circuits."""
+    off = halo2_ref.proof_offsets(shape, N, kind, scheme)
     out = []
-    for place in PLACES:
+    for place in places:
         b = bytearray(proof)
         b[off[place]] ^= 0x10
         out.append((place, bytes(b)))
@@ -66,5 +71,5 @@ def tampered(proof, shape, kind, scheme):
 def wrong_lists(vals):
     """[(what, list)]: instance lists under which a proof over `vals` must not verify."""
     changed = list(vals)
-    changed[len(vals) // 2] = (changed[len(vals) // 2] + 1) % public_ref.R
+    changed[len(vals) // 2] = (changed[len(vals) // 2] + 1) % halo2_ref.R
     return [("one changed value", changed), ("a dropped value", list(vals[:-1])), ("an appended zero", list(vals) + [0])]

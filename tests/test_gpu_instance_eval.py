@@ -1,5 +1,5 @@
 """zk_instance_eval (csrc/verify.hip): inst(x) = sum_{i<m} v_i l_i(x) of many (list, point) pairs in one launch on the device,
-limb for limb what tests/public_ref.py's instance_eval computes - the value the host verifier (csrc/verifier.h) uses.
+limb for limb what tests/halo2_ref.py's instance_eval computes - the value the host verifier (csrc/verifier.h) uses.
 
 Sizes: k = 6, 10, 12; m = 0, 1, 2, 2^k and one below, at and one above every internal boundary of the kernel that fits the domain -
 the inversion group (IE_GROUP), a lane's contiguous range (IE_LANE), what one workgroup covers in a pass (IE_SPAN = 64 lanes x
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import webauthn_halo2_amd as zk
-import public_ref
+import halo2_ref
 from public_cases import mont
 from zkoracle.field import R, omega
 
@@ -43,7 +43,7 @@ def shape(k):
 def reference(k, vals, x):
     """(value, on_domain)"""
     try:
-        return public_ref.instance_eval(shape(k), list(vals), x), False
+        return halo2_ref.instance_eval(shape(k), list(vals), x), False
     except ValueError:
         return 0, True
 

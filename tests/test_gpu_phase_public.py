@@ -1,6 +1,6 @@
 """The phase-level forms with public inputs and N circuits (zk_permutation_product_public, zk_quotient_multi, zk_eval_batch) through
 Engine, against tests/phase_public_ref.py - the CPU restatement that tests/test_phase_public_ref.py ties to the whole proofs of
-public_ref and multi_public_ref - with beta, gamma and y of the test's own choosing.
+tests/halo2_ref.py - with beta, gamma and y of the test's own choosing.
 
   fallback    on a key without the column: permutation_product_public(instance None) is zk_permutation_product byte for byte,
               quotient_multi with one circuit is zk_quotient byte for byte, divide 0 and 1
@@ -69,7 +69,7 @@ def raises(code, fn, *args, **kw):
 def test_without_the_column_the_public_forms_are_the_plain_ones(name):
     eng = zk.Engine(0)
     asg = witness(name, 0, n_inst=0)
-    pk, adv = engine_key(eng, name, asg, n_inst=0)
+    pk, (adv,) = engine_key(eng, name, [asg], n_inst=0)
     sh = eng.pk_shape(pk)
     n = 1 << sh["k"]
     pr = random.Random(0x5EED0B01)
@@ -265,7 +265,7 @@ def test_refusals_leave_the_outputs_untouched():
     # -- a key WITHOUT the column takes no instance handle
     asg0 = witness("k19like", 0, n_inst=0)
     # (another SRS of the same k: the key above is stale from here on)
-    pk0, adv0 = engine_key(eng, "k19like", asg0, n_inst=0)
+    pk0, (adv0,) = engine_key(eng, "k19like", [asg0], n_inst=0)
     raises(ESTATE, pp, pk, adv, inst, zs)
     raises(ESTATE, qm, pk, A, I, Z, K, h)
     for z in zs:

@@ -1,6 +1,6 @@
 """zk_prove_batch_public (csrc/prover_lockstep.h): the lock-step batch with every proof's public inputs.  Proof j is zk_prove_public's
 with the same key, advice, list and seed on the same engine - every lane has its own witness seed and the lists have different
-lengths - and, at the shapes the plain-Python prover reaches, tests/public_ref.py's.  Shapes: k19like (n = 128), k18like (n = 64:
+lengths - and, at the shapes the plain-Python prover reaches, tests/halo2_ref.py's.  Shapes: k19like (n = 128), k18like (n = 64:
 fewer rows than a workgroup of the kernel that writes the columns), k17like (the column has a permutation chunk of its own), wide and
 k10batched (column-batched passes); B = 2, 3, 5; both reference pairings and one cross pairing; both quotient domains; the stream
 audit; a long list followed by a short one in the same lane (a stale tail would change the bytes); empty lists; a batch of one; a
@@ -13,7 +13,7 @@ import pytest
 import webauthn_halo2_amd as zk
 from webauthn_halo2_amd import engine as E
 from zkoracle.hashes import ChaCha20Rng
-import public_ref
+import halo2_ref
 from multi_public_cases import engine_lanes, lanes
 from public_cases import PAIRINGS, engine_key, mont, reference_key, shape_of, witness
 
@@ -54,7 +54,7 @@ def test_every_proof_is_zk_prove_public(name, B):
         for kind, scheme in (PAIRINGS if name in ("k19like", "k17like") else PAIRINGS[:1]):
             got = eng.prove_batch_public(pk, sets, lists, sd, KIND[kind], SCHEME[scheme])
             for j, (asg, vals) in enumerate(made):
-                assert got[j] == public_ref.create_proof(rpk, asg.advice, vals, ChaCha20Rng(sd[j]), kind, scheme), (kind, j)
+                assert got[j] == halo2_ref.create_proof(rpk, [asg.advice], [vals], ChaCha20Rng(sd[j]), kind, scheme), (kind, j)
     eng.close()
 
 
@@ -109,7 +109,7 @@ def test_a_key_without_the_column():
     eng = zk.Engine(0)
     name = "k17like"
     asg = witness(name, 0, n_inst=0)
-    pk, polys = engine_key(eng, name, asg, n_inst=0)
+    pk, (polys,) = engine_key(eng, name, [asg], n_inst=0)
     sd = seeds(3)
     for kind, _ in PAIRINGS:
         t = KIND[kind]
@@ -131,7 +131,7 @@ def test_refusals():
     sd = seeds(3)
     t = E.ZK_TRANSCRIPT_BLAKE2B
     want = eng.prove_batch_public(pk, sets, lists, sd, t)
-    modulus = np.array([[(public_ref.R >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]], dtype=np.uint64)
+    modulus = np.array([[(halo2_ref.R >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]], dtype=np.uint64)
     for bad in (mont([1] * (usable + 1)), np.concatenate([lists[1][:4], modulus, lists[1][5:]])):
         with pytest.raises(zk.ZkError) as e:
             eng.prove_batch_public(pk, sets, [lists[0], bad, lists[2]], sd, t)

@@ -1,7 +1,7 @@
 """zk_prove_multi (csrc/prover_lockstep.h): ONE proof over N circuits of one key — halo2's create_proof with several circuits.
 
 With one circuit the call is zk_prove, byte for byte, at every prover shape and all four transcript x scheme pairs.  With more it is
-compared byte for byte with tests/multi_ref.py, the plain-Python statement of the rule (tied to the pinned oracle at N = 1 by
+compared byte for byte with tests/halo2_ref.py, the plain-Python statement of the rule (tied to the pinned oracle at N = 1 by
 tests/test_multi_ref.py): a wrong chain weight of the accumulating quotient passes, a wrong RNG order or a wrong query order each
 change the bytes.  The accumulating quotient kernel is driven through its branches (lazy sums folded past 32 terms, lanes per row,
 whole domain and three cosets), the merged MSM passes through widths that fill, overflow and split unevenly; refusals leave the
@@ -14,7 +14,7 @@ import webauthn_halo2_amd as zk
 from webauthn_halo2_amd import engine as E
 from zkoracle.hashes import ChaCha20Rng
 from prover_shapes import SHAPES
-import multi_ref
+import halo2_ref
 from multi_cases import PAIRINGS, SEED, engine_key, oracle_key, params_of, witnesses
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +25,7 @@ ALL_PAIRS = [(k, s) for k in ("evm", "blake2b") for s in ("gwc", "shplonk")]
 
 
 def reference(opk, asgs, kind, scheme):
-    return multi_ref.create_proof_multi(opk, [a.advice for a in asgs], ChaCha20Rng(SEED), kind, scheme)
+    return halo2_ref.create_proof(opk, [a.advice for a in asgs], None, ChaCha20Rng(SEED), kind, scheme)
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -98,7 +98,7 @@ def test_batched_msm_passes(name, N):
         t, s = KIND[kind], SCHEME[scheme]
         proof = eng.prove_multi(pk, sets, SEED, t, s)
         assert eng.verify_multi(pk, N, proof, t, s)
-        assert multi_ref.verify_multi(opk.vk, proof, N, kind, scheme)
+        assert halo2_ref.verify(opk.vk, proof, [[]] * N, kind, scheme)
         assert not eng.verify_multi(pk, N - 1, proof, t, s)
         # every further circuit adds its own points and scalars, nothing else
         sh = opk.shape
@@ -124,7 +124,7 @@ def _default_width_proofs(name, N):
         for kind, scheme in PAIRINGS:
             proof = eng.prove_multi(pk, sets, SEED, KIND[kind], SCHEME[scheme])
             assert eng.verify_multi(pk, N, proof, KIND[kind], SCHEME[scheme]), (kind, scheme)
-            assert multi_ref.verify_multi(opk.vk, proof, N, kind, scheme), (kind, scheme)
+            assert halo2_ref.verify(opk.vk, proof, [[]] * N, kind, scheme), (kind, scheme)
             proofs[kind, scheme] = proof
         eng.close()
         _DEFAULT_WIDTH[name] = (asgs, proofs)

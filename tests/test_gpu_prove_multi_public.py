@@ -1,6 +1,6 @@
 """zk_prove_multi_public (csrc/prover_lockstep.h): ONE proof over N circuits with every circuit's public inputs, byte for byte what
-tests/multi_public_ref.py - the plain-Python statement of the rule, tied to public_ref and multi_ref by
-tests/test_multi_public_ref.py - makes: N = 2 and 3 at k19like (the column joins a permutation chunk), k17like (it has a chunk of its
+tests/halo2_ref.py - the plain-Python statement of the rule, tied to the pinned oracle and to recorded digests by
+tests/test_halo2_ref.py - makes: N = 2 and 3 at k19like (the column joins a permutation chunk), k17like (it has a chunk of its
 own) and wide, with lists of different lengths; the committed k = 10 fixture through the column-batched passes.  One circuit is
 zk_prove_public, a key without the column zk_prove_multi; the refusals leave the outputs untouched."""
 import ctypes
@@ -12,7 +12,7 @@ import pytest
 import webauthn_halo2_amd as zk
 from webauthn_halo2_amd import engine as E
 from zkoracle.hashes import ChaCha20Rng
-import multi_public_ref
+import halo2_ref
 from multi_public_cases import engine_lanes, lanes
 from public_cases import PAIRINGS, SEED, engine_key, mont, reference_key, shape_of, witness
 
@@ -39,7 +39,7 @@ def test_bytes_of_the_reference(name, N):
     for kind, scheme in (PAIRINGS if name == "k19like" else [PAIRINGS[N % 2]]):
         t, s = KIND[kind], SCHEME[scheme]
         got = eng.prove_multi_public(pk, sets, lists, SEED, t, s)
-        want = multi_public_ref.create_proof_multi(rpk, [a.advice for a, _ in made], [v for _, v in made], ChaCha20Rng(SEED), kind, scheme)
+        want = halo2_ref.create_proof(rpk, [a.advice for a, _ in made], [v for _, v in made], ChaCha20Rng(SEED), kind, scheme)
         assert got == want, (kind, scheme)
         assert len(got) == eng.proof_size_multi(pk, N, t, s)
         for domain in (1, 2):  # the accumulating pass reads circuit c's extended coset, or its three-coset copy
@@ -79,7 +79,7 @@ def test_one_circuit_and_a_key_without_the_column():
     eng.close()
     eng = zk.Engine(0)
     asg = witness(name, 0, n_inst=0)
-    pk, polys = engine_key(eng, name, asg, n_inst=0)
+    pk, (polys,) = engine_key(eng, name, [asg], n_inst=0)
     for kind, _ in PAIRINGS:
         t = KIND[kind]
         want = eng.prove_multi(pk, [polys, polys], SEED, t)

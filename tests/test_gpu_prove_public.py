@@ -1,8 +1,8 @@
 """zk_prove_public (csrc/prover.hip): create_proof with the circuit's public inputs - ONE instance column, absorbed into the
 transcript, copy-constrained, neither committed nor opened.
 
-The bytes are compared with tests/public_ref.py, the plain-Python statement of the rule (tied to the pinned oracle where they
-overlap by tests/test_public_ref.py): at the shape where the column joins a full permutation chunk (k19like), where it starts a
+The bytes are compared with tests/halo2_ref.py, the plain-Python statement of the rule (tied to the pinned oracle where they
+overlap by tests/test_halo2_ref.py): at the shape where the column joins a full permutation chunk (k19like), where it starts a
 chunk of its own (k17like), k18like, where it fills a free slot (wide) and - against the committed fixture - through the
 column-batched MSM passes and transforms (k10batched); with 0, 1, 9 and `usable` instance values; under both quotient domains;
 after the key went through its file forms; under the stream audit with the lone proof's side streams.  The entry points that carry
@@ -17,7 +17,7 @@ import pytest
 import webauthn_halo2_amd as zk
 from webauthn_halo2_amd import engine as E
 from zkoracle.hashes import ChaCha20Rng
-import public_ref
+import halo2_ref
 from public_cases import PAIRINGS, SEED, engine_key, mont, params_of, reference_key, shape_of, witness
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +38,7 @@ def made(name, n_public):
 @functools.lru_cache(maxsize=None)
 def reference(name, n_public, kind, scheme, extra_zeros=0):
     asg, rpk = made(name, n_public)
-    return public_ref.create_proof(rpk, asg.advice, asg.instance + [0] * extra_zeros, ChaCha20Rng(SEED), kind, scheme)
+    return halo2_ref.create_proof(rpk, [asg.advice], [asg.instance + [0] * extra_zeros], ChaCha20Rng(SEED), kind, scheme)
 
 
 def golden():
@@ -47,14 +47,14 @@ def golden():
 
 
 def canon(limbs):
-    return sum(int(limbs[i]) << (64 * i) for i in range(4)) * pow(1 << 256, -1, public_ref.R) % public_ref.R
+    return sum(int(limbs[i]) << (64 * i) for i in range(4)) * pow(1 << 256, -1, halo2_ref.R) % halo2_ref.R
 
 
 @pytest.mark.parametrize("name", ["k19like", "k17like", "k18like", "wide"])
 def test_bytes_of_the_reference(name):
     eng = zk.Engine(0)
     asg, rpk = made(name, N_PUBLIC)
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     sh = rpk.shape
     assert eng.pk_num_instance_columns(pk) == 1
     assert (eng.pk_shape(pk)["n_perm"], eng.pk_shape(pk)["n_chunks"]) == (len(sh.perm_cols), sh.n_chunks)
@@ -64,7 +64,7 @@ def test_bytes_of_the_reference(name):
         t, s = KIND[kind], SCHEME[scheme]
         got = eng.prove_public(pk, polys, mont(asg.instance), SEED, t, s)
         assert got == reference(name, N_PUBLIC, kind, scheme), (kind, scheme)
-        assert len(got) == eng.proof_size(pk, t, s) == public_ref.proof_size(sh, kind, scheme)
+        assert len(got) == eng.proof_size(pk, t, s) == halo2_ref.proof_size(sh, 1, kind, scheme)
     # the same bytes over the whole extended domain and over three of its cosets
     kind, scheme = PAIRINGS[0]
     for domain in (1, 2):
@@ -81,7 +81,7 @@ def test_instance_lengths(name, m):
     m = usable if m == "usable" else m
     asg, rpk = made(name, m)
     assert len(asg.instance) == m
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     kind, scheme = PAIRINGS[1 if name == "k19like" else 0]
     t = KIND[kind]
     got = eng.prove_public(pk, polys, mont(asg.instance), SEED, t)
@@ -104,7 +104,7 @@ def test_trailing_zeros_are_part_of_the_transcript():
     eng = zk.Engine(0)
     name = "k17like"
     asg, rpk = made(name, N_PUBLIC)
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     for kind, scheme in PAIRINGS:
         t = KIND[kind]
         v, vz = mont(asg.instance), mont(asg.instance + [0])
@@ -123,7 +123,7 @@ def test_batched_passes_against_the_fixture():
     eng = zk.Engine(0)
     asg = witness(g["shape"], g["n_public"])
     assert [hex(v) for v in asg.instance] == g["instances"]
-    pk, polys = engine_key(eng, g["shape"], asg)
+    pk, (polys,) = engine_key(eng, g["shape"], [asg])
     assert hex(canon(eng.vk_export(pk)[2])) == g["transcript_repr"]
     for kind, scheme in PAIRINGS:
         assert eng.prove_public(pk, polys, mont(asg.instance), SEED, KIND[kind]).hex() == g["proofs"][kind + "/" + scheme], kind
@@ -145,7 +145,7 @@ def test_a_key_without_the_column_is_what_it_was():
     eng = zk.Engine(0)
     name = "k17like"
     asg = witness(name, 0, n_inst=0)
-    pk, polys = engine_key(eng, name, asg, n_inst=0)
+    pk, (polys,) = engine_key(eng, name, [asg], n_inst=0)
     assert eng.pk_num_instance_columns(pk) == 0
     for kind, scheme in PAIRINGS:
         t = KIND[kind]
@@ -168,7 +168,7 @@ def test_entry_points_without_instances_refuse_the_key():
     eng = zk.Engine(0)
     name = "k17like"
     asg, rpk = made(name, N_PUBLIC)
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     t = E.ZK_TRANSCRIPT_EVM
     proof = eng.prove_public(pk, polys, mont(asg.instance), SEED, t)
     sh = eng.pk_shape(pk)
@@ -221,7 +221,7 @@ def test_the_key_through_its_files(name):
     shape has one permutation commitment too many."""
     eng = zk.Engine(0)
     asg, rpk = made(name, N_PUBLIC)
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     p = params_of(name)
     kind, scheme = PAIRINGS[0]
     t = KIND[kind]
@@ -262,7 +262,7 @@ def test_refusals_leave_the_outputs_untouched():
     eng = zk.Engine(0)
     name = "k19like"
     asg, rpk = made(name, N_PUBLIC)
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     size = eng.proof_size(pk)
     hs = (ctypes.c_uint64 * len(polys))(*[p.h for p in polys])
     inst = mont(asg.instance + [0] * (rpk.shape.usable_rows + 1 - N_PUBLIC))

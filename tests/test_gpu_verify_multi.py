@@ -1,5 +1,5 @@
 """zk_verify_multi (csrc/verifier.h with a circuit count, csrc/verify.hip): verify_proof of ONE proof over N circuits.  Proofs of
-zk_prove_multi and of tests/multi_ref.py are accepted; one flipped byte in a circuit's advice commitment, an h piece, a shared fixed
+zk_prove_multi and of tests/halo2_ref.py are accepted; one flipped byte in a circuit's advice commitment, an h piece, a shared fixed
 evaluation, a circuit's lookup evaluation or the last opening, another circuit count, or the single-circuit verifier each give the
 verdict 0 — a verdict, never an error — and a verifying-only key read from the key's own image says the same as the full key."""
 import pytest
@@ -7,7 +7,7 @@ import pytest
 import webauthn_halo2_amd as zk
 from webauthn_halo2_amd import engine as E
 from zkoracle.hashes import ChaCha20Rng
-import multi_ref
+import halo2_ref
 from multi_cases import PAIRINGS, SEED, engine_key, oracle_key, params_of, tampered, witnesses
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +33,7 @@ def test_verdicts(name, N):
             assert eng.verify_multi(pk, count, data, t, s) is want, (kind, label)
             assert eng.verify_multi(vk, count, data, t, s) is want, (kind, label, "verifying-only key")
         assert not eng.verify(pk, proof, t, s)  # the single-circuit verifier reads another layout
-        assert multi_ref.verify_multi(opk.vk, proof, N, kind, scheme)
+        assert halo2_ref.verify(opk.vk, proof, [[]] * N, kind, scheme)
     eng.close()
 
 
@@ -43,7 +43,7 @@ def test_reference_proofs_and_argument_errors():
     opk = oracle_key("k18like", asgs[0])
     pk, _ = engine_key(eng, "k18like", asgs[:1])
     for kind, scheme in PAIRINGS:
-        proof = multi_ref.create_proof_multi(opk, [a.advice for a in asgs], ChaCha20Rng(SEED), kind, scheme)
+        proof = halo2_ref.create_proof(opk, [a.advice for a in asgs], None, ChaCha20Rng(SEED), kind, scheme)
         assert eng.verify_multi(pk, 2, proof, KIND[kind], SCHEME[scheme])
         assert not eng.verify_multi(pk, 2, proof, KIND["blake2b" if kind == "evm" else "evm"], SCHEME[scheme])
     for bad_n in (0, E.ZK_PROVE_MULTI_MAX + 1):

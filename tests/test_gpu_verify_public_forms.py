@@ -3,7 +3,7 @@
 The batch form: 17 proofs of k17like with per-proof lists of 0, 1, 9 and `usable` values; its verdicts are zk_verify_public's one by
 one; three planted proofs - a wrong list, a tampered byte, a wrong length - are exactly the zeros; the same under
 zk_verify_instance_eval_mode 1 (host) and 2 (device); on a verifying-only key.  The multi form accepts zk_prove_multi_public's proofs
-and rejects what tests/multi_public_ref.py rejects.  An over-long list is an error for the whole call, not a verdict."""
+and rejects what tests/halo2_ref.py rejects.  An over-long list is an error for the whole call, not a verdict."""
 import json
 import os
 
@@ -45,7 +45,7 @@ def test_batch_verdicts_are_zk_verify_public_s(kind, scheme):
         assert got == [j != 6 for j in range(B)], what
     bad_proofs, use = list(proofs), list(lists)
     use[2] = m_or_none(wrong_lists(vals[2])[0][1])
-    bad_proofs[9] = tampered(proofs[9], shape_of(name), kind, scheme)[0][1]
+    bad_proofs[9] = tampered(proofs[9], shape_of(name), 1, kind, scheme)[0][1]
     bad_proofs[13] = proofs[13][:-32]
     want = [j not in (2, 9, 13) for j in range(B)]
     one_by_one = [eng.verify_public(pk, bad_proofs[j], use[j], t, s) for j in range(B)]
@@ -83,7 +83,7 @@ def test_multi_verdicts(name, lengths):
                 assert eng.verify_multi_public(key, proof, lists, t, s), (kind, mode)
             for what, wrong in wrong_multi_lists(vals):
                 assert not eng.verify_multi_public(pk, proof, [m_or_none(l) for l in wrong], t, s), (kind, mode, what)
-            for place, bad in tampered(proof, shape_of(name), kind, scheme):
+            for place, bad in tampered(proof, shape_of(name), len(lengths), kind, scheme):
                 assert not eng.verify_multi_public(pk, bad, lists, t, s), (kind, mode, place)
         with pytest.raises(zk.ZkError) as e:
             eng.verify_multi_public(pk, proof, [lists[0], mont([0] * (usable + 1))] + lists[2:], t, s)

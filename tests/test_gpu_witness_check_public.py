@@ -9,7 +9,7 @@ import pytest
 import webauthn_halo2_amd as zk
 from webauthn_halo2_amd import engine as E
 from public_cases import PAIRINGS, SEED, engine_key, mont, witness
-import public_ref
+import halo2_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +20,7 @@ N_PUBLIC = 9
 def test_one_changed_instance_value_is_one_copy_pair(name):
     eng = zk.Engine(0)
     asg = witness(name, N_PUBLIC)
-    pk, polys = engine_key(eng, name, asg)
+    pk, (polys,) = engine_key(eng, name, [asg])
     lay = asg.layout
     inst_col = len(lay.perm_cols) - 1
     assert lay.perm_cols[inst_col] == ("instance", 0) and eng.pk_shape(pk)["n_perm"] == inst_col + 1
@@ -32,7 +32,7 @@ def test_one_changed_instance_value_is_one_copy_pair(name):
     others = [c for c in asg.copies if cell in c and (inst_col, i) not in c]
     assert not others  # (a two-cell cycle: sigma swaps the two)
     bad = list(asg.instance)
-    bad[i] = (bad[i] + 1) % public_ref.R
+    bad[i] = (bad[i] + 1) % halo2_ref.R
     counts, failures = eng.witness_check_public(pk, polys, mont(bad))
     want = sorted([(E.ZK_FAIL_COPY, cell[0], cell[1], inst_col, i), (E.ZK_FAIL_COPY, inst_col, i, cell[0], cell[1])])
     assert counts == [2, 0, 0, 0, 2] and failures == want

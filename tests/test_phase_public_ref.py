@@ -1,30 +1,30 @@
-"""tests/phase_public_ref.py is tied to the whole proofs of the references it restates: fed what tests/public_ref.py `create_proof` and
-tests/multi_public_ref.py `create_proof_multi` commit to on their way (the blinded columns, a', s', zL) and the challenges they
-squeeze (beta, gamma, y), its functions give back the z those proofs commit to - on every row they promise - and their h pieces.
-The references are traced from outside (a recording committer and transcript in their namespace); they are not changed.  CPU only.
+"""tests/phase_public_ref.py is tied to the whole proofs of the reference it restates: fed what tests/halo2_ref.py `create_proof`
+commits to on its way (the blinded columns, a', s', zL) and the challenges it squeezes (beta, gamma, y), its functions give back the
+z those proofs commit to - on every row they promise - and their h pieces.  The reference is traced from outside (a recording
+committer and transcript in its namespace); it is not changed.  CPU only.
 
-  public_ref        k19like (the column joins a chunk) and k17like (it opens one), 9 public inputs
-  multi_public_ref  k19like N = 3 with lists of 9, 0 and 1 values; k17like N = 2 with 1 and 9
-  no column         N = 2 on k19like without the instance column: `instances` are ignored
-  divide            the undivided quotient times 1 / (X^n - 1) is the divided one; a wrong y moves every piece"""
+  one circuit  k19like (the column joins a chunk) and k17like (it opens one), 9 public inputs
+  N circuits   k19like N = 3 with lists of 9, 0 and 1 values; k17like N = 2 with 1 and 9
+  no column    N = 2 on k19like without the instance column: `instances` are ignored
+  divide       the undivided quotient times 1 / (X^n - 1) is the divided one; a wrong y moves every piece"""
 import os
 import sys
 
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import multi_public_ref  # noqa: E402
+import halo2_ref  # noqa: E402
 import phase_public_ref as PPR  # noqa: E402
-import public_ref  # noqa: E402
 from multi_public_cases import lanes  # noqa: E402
 from public_cases import SEED, reference_key, witness  # noqa: E402
 from zkoracle.field import R, ZETA, inv, omega  # noqa: E402
 from zkoracle.hashes import ChaCha20Rng  # noqa: E402
 
 
-def traced(monkeypatch, module, run):
-    """run() with `module`'s commitments and challenges recorded -> dict(lagrange=[columns], coeff=[polynomials], squeezed=[..])."""
+def traced(monkeypatch, run):
+    """run() with halo2_ref's commitments and challenges recorded -> dict(lagrange=[columns], coeff=[polynomials], squeezed=[..])."""
     rec = dict(lagrange=[], coeff=[], squeezed=[])
+    module = halo2_ref
     real_committer, real_commit_coeff, real_make = module.Committer, module.commit_coeff, module.make_transcript
 
     class Committer(real_committer):
@@ -89,23 +89,22 @@ def check(sh, pk, rec, lists):
 
 
 @pytest.mark.parametrize("name", ["k19like", "k17like"])
-def test_one_circuit_against_public_ref(monkeypatch, name):
+def test_one_circuit_against_the_whole_proof(monkeypatch, name):
     asg = witness(name, 9)
     pk = reference_key(name, asg)
     sh = pk.shape
-    assert sh.perm_cols[-1] == public_ref.INSTANCE and (len(sh.perm_cols) % sh.chunk_len == 1) == (name == "k17like")
+    assert sh.perm_cols[-1] == halo2_ref.INSTANCE and (len(sh.perm_cols) % sh.chunk_len == 1) == (name == "k17like")
     vals = list(asg.instance)
-    rec = traced(monkeypatch, public_ref, lambda: public_ref.create_proof(pk, asg.advice, vals, ChaCha20Rng(SEED), "evm"))
+    rec = traced(monkeypatch, lambda: halo2_ref.create_proof(pk, [asg.advice], [vals], ChaCha20Rng(SEED), "evm"))
     check(sh, pk, rec, [vals])
 
 
 @pytest.mark.parametrize("name,lengths", [("k19like", (9, 0, 1)), ("k17like", (1, 9))], ids=["k19like-9-0-1", "k17like-1-9"])
-def test_n_circuits_against_multi_public_ref(monkeypatch, name, lengths):
+def test_n_circuits_against_the_whole_proof(monkeypatch, name, lengths):
     made = lanes(name, lengths)
     pk = reference_key(name, made[0][0])
     lists = [vals for _, vals in made]
-    rec = traced(monkeypatch, multi_public_ref,
-                 lambda: multi_public_ref.create_proof_multi(pk, [a.advice for a, _ in made], lists, ChaCha20Rng(SEED), "blake2b"))
+    rec = traced(monkeypatch, lambda: halo2_ref.create_proof(pk, [a.advice for a, _ in made], lists, ChaCha20Rng(SEED), "blake2b"))
     sh = pk.shape
     circuits, beta, gamma, y, hv = check(sh, pk, rec, lists)
     if name != "k19like":
@@ -128,8 +127,7 @@ def test_without_the_column_instances_are_ignored(monkeypatch):
     name = "k19like"
     asgs = [witness(name, 0, n_inst=0), witness(name, 0, n_inst=0)]
     pk = reference_key(name, asgs[0], n_inst=0)
-    rec = traced(monkeypatch, multi_public_ref,
-                 lambda: multi_public_ref.create_proof_multi(pk, [a.advice for a in asgs], [[], []], ChaCha20Rng(SEED), "evm"))
+    rec = traced(monkeypatch, lambda: halo2_ref.create_proof(pk, [a.advice for a in asgs], [[], []], ChaCha20Rng(SEED), "evm"))
     check(pk.shape, pk, rec, [[], []])
-    with pytest.raises(public_ref.InstanceTooLarge):
+    with pytest.raises(halo2_ref.InstanceTooLarge):
         PPR.permutation_products_public(pk.shape, pk.fixed, pk.sigma, asgs[0].advice, [1], 2, 3)

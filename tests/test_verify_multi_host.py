@@ -1,6 +1,6 @@
 """csrc/verifier.h with a circuit count, on the host (tests/verify_multi_host_check.cpp, built here with hipcc; no GPU): proofs of
-tests/multi_ref.py over two and three circuits — intact, with one flipped byte at five places, and read as proofs of another
-circuit count — get the verdicts of multi_ref.verify_multi, in all four transcript x scheme combinations; with one circuit the
+tests/halo2_ref.py over two and three circuits — intact, with one flipped byte at five places, and read as proofs of another
+circuit count — get the verdicts of halo2_ref.verify, in all four transcript x scheme combinations; with one circuit the
 verdicts are those of the single-circuit layout."""
 import os
 import shutil
@@ -10,7 +10,7 @@ import pytest
 
 from zkoracle import srs
 from zkoracle.hashes import ChaCha20Rng
-import multi_ref
+import halo2_ref
 import verify_cases as vc
 from multi_cases import SEED, setup, tampered
 
@@ -46,9 +46,9 @@ def test_same_verdicts_as_the_reference(exe, name, N):
     pk, asgs = setup(name, N)
     vk = pk.vk
     for kind, scheme in vc.COMBOS:
-        proof = multi_ref.create_proof_multi(pk, [a.advice for a in asgs], ChaCha20Rng(SEED), kind, scheme)
+        proof = halo2_ref.create_proof(pk, [a.advice for a in asgs], None, ChaCha20Rng(SEED), kind, scheme)
         cases = [proof] + [b for _, b in tampered(proof, vk.shape, N, kind, scheme)] + [proof[:-32], proof + bytes(32)]
-        want = [multi_ref.verify_multi(vk, c, N, kind, scheme) for c in cases]
+        want = [halo2_ref.verify(vk, c, [[]] * N, kind, scheme) for c in cases]
         assert want == [True] + [False] * (len(cases) - 1)
         assert run_job(exe, N, vk, kind, scheme, cases) == want, (kind, scheme)
         for other in (N - 1, N + 1):  # a proof of another circuit count has another length

@@ -1,7 +1,7 @@
 """csrc/verifier.h with one instance list per circuit, on the host (tests/verify_public_forms_host_check.cpp, built here with hipcc;
-no GPU): proofs of tests/multi_public_ref.py over two and three circuits get that reference's verdicts - intact, under every wrong
+no GPU): proofs of tests/halo2_ref.py over two and three circuits get that reference's verdicts - intact, under every wrong
 set of lists (one changed value in circuit 1's list only, the lists swapped, a dropped value, an appended zero, one circuit fewer
-and one more) and with the flipped bytes of public_cases.PLACES - and with one circuit the verdicts of public_ref.  For every
+and one more) and with the flipped bytes of public_cases.PLACES - and likewise with one circuit.  For every
 proof the program also prepares the term lists a second time from inst(x) values computed outside verifier::prepare_lists and
 fails unless verdict, challenges and term lists are the same."""
 import os
@@ -12,8 +12,7 @@ import pytest
 
 from zkoracle import srs
 from zkoracle.hashes import ChaCha20Rng
-import multi_public_ref
-import public_ref
+import halo2_ref
 from multi_public_cases import lanes, wrong_multi_lists
 from public_cases import COMBOS, PAIRINGS, SEED, reference_key, tampered
 
@@ -55,20 +54,20 @@ def test_same_verdicts_as_the_reference(exe, tmp_path, name, lengths):
     vk = pk.vk
     lists = [vals for _, vals in made]
     for kind, scheme in (COMBOS if lengths == (9, 9) else PAIRINGS):
-        proof = multi_public_ref.create_proof_multi(pk, [a.advice for a, _ in made], lists, ChaCha20Rng(SEED), kind, scheme)
-        cases = [proof] + [b for _, b in tampered(proof, vk.shape, kind, scheme)] + [proof[:-32], proof + bytes(32)]
-        want = [multi_public_ref.verify_multi(vk, c, lists, kind, scheme) for c in cases]
+        proof = halo2_ref.create_proof(pk, [a.advice for a, _ in made], lists, ChaCha20Rng(SEED), kind, scheme)
+        cases = [proof] + [b for _, b in tampered(proof, vk.shape, len(lists), kind, scheme)] + [proof[:-32], proof + bytes(32)]
+        want = [halo2_ref.verify(vk, c, lists, kind, scheme) for c in cases]
         assert want == [True] + [False] * (len(cases) - 1)
         assert verdicts(exe, tmp_path, vk, kind, scheme, lists, cases) == want, (kind, scheme)
         for what, wrong in wrong_multi_lists(lists):
-            assert not multi_public_ref.verify_multi(vk, proof, wrong, kind, scheme), what
+            assert not halo2_ref.verify(vk, proof, wrong, kind, scheme), what
             assert verdicts(exe, tmp_path, vk, kind, scheme, wrong, [proof]) == [False], (kind, scheme, what)
 
 
-def test_one_circuit_is_public_ref(exe, tmp_path):
+def test_one_circuit_has_the_single_proof_layout(exe, tmp_path):
     (asg, vals), = lanes("k17like", [9])
     pk = reference_key("k17like", asg)
     for kind, scheme in PAIRINGS:
-        proof = public_ref.create_proof(pk, asg.advice, vals, ChaCha20Rng(SEED), kind, scheme)
+        proof = halo2_ref.create_proof(pk, [asg.advice], [vals], ChaCha20Rng(SEED), kind, scheme)
         assert verdicts(exe, tmp_path, pk.vk, kind, scheme, [vals], [proof, proof[:-1] + bytes([proof[-1] ^ 4])]) == [True, False]
         assert verdicts(exe, tmp_path, pk.vk, kind, scheme, [vals + [0]], [proof]) == [False]

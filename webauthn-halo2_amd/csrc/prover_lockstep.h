@@ -24,7 +24,7 @@
 // four-column k = 17 shape with GWC, one inverse coset transform of h instead of N, and one pairing for the verifier.
 //
 // The rule [RECALLED] (halo2_proofs plonk/prover.rs `create_proof`, plonk/verifier.rs `verify_proof`; restated in plain Python
-// by tests/multi_ref.py, against which the bytes are compared).  c = 0 .. N - 1 in the caller's order, T = quotient_terms(..),
+// by tests/halo2_ref.py, against which the bytes are compared).  c = 0 .. N - 1 in the caller's order, T = quotient_terms(..),
 // bf = BLINDING_FACTORS:
 //   transcript   transcript_repr (N is not hashed); for c: circuit c's advice commitments; theta; for c, per lookup: a', s';
 //                beta, gamma; for c: z of every chunk; for c: zL of every lookup; ONE random-polynomial commitment; y; the h
@@ -41,7 +41,7 @@
 //                lookup opens (per lookup zL@0, a'@0, s'@0, a'@-1, zL@1); after all circuits: fixed, sigma, h, random.  GWC groups
 //                this list by rotation in order of first appearance, SHPLONK by rotation set: Prover::gwc_stage1 / shplonk_stage1/2
 //                as they stand, on the longer list (Prover::build_evals / queries_from_evals state both orders, for 1 and for N)
-// With public inputs (zk_prove_multi_public; restated by tests/multi_public_ref.py) the rule gains: behind transcript_repr, for c:
+// With public inputs (zk_prove_multi_public; restated by the same tests/halo2_ref.py) the rule gains: behind transcript_repr, for c:
 // every value of circuit c's instance list as common_scalar (absorbed, not written; neither N nor the lengths are hashed) — ALL
 // circuits' instances before any advice commitment, halo2's loop over `instances` at the top of create_proof.  The columns draw
 // nothing; circuit c's grand product reads c's column and quotient pass c its coset forms; nothing of them is committed or opened.

@@ -51,7 +51,7 @@ struct Query {
 };
 
 // One proof over nc circuits of one key [RECALLED: halo2's create_proof / verify_proof over `circuits: &[C]`; restated by
-// tests/multi_ref.py]: every per-circuit group of a phase is written for circuit 0, then circuit 1, ...; what belongs to the key
+// tests/halo2_ref.py]: every per-circuit group of a phase is written for circuit 0, then circuit 1, ...; what belongs to the key
 // or to the proof (fixed / sigma evaluations, random polynomial, h pieces, the opening) is written once.  The per-circuit
 // groups below hold circuit 0's index; circuit c's is that plus c times the group's stride (`*_of`).  nc = 1: a proof of zk_prove.
 // point indices in transcript order

@@ -25,6 +25,7 @@ def windowed(engine):
 
     yield select
     engine.set_option(E.ZK_OPT_MSM_WINDOW, 0)
+    engine.set_option(E.ZK_OPT_MSM_T1, 0)
     engine.srs_setup(10)  # tables of the default plan for whoever comes next
 
 
@@ -59,12 +60,17 @@ def test_wide_commit_matches_tau_oracle(windowed, bits, k):
         p.free()
 
 
-@pytest.mark.parametrize("bits", [16, 17])
+@pytest.mark.parametrize("t1", [0, 1])
+@pytest.mark.parametrize("bits", [15, 16, 17])
 @pytest.mark.parametrize("with_identity", [False, True])
-def test_wide_commit_over_degenerate_srs(windowed, with_identity, bits):
+def test_wide_commit_over_degenerate_srs(windowed, with_identity, bits, t1):
     """Equal points with equal scalars (doublings inside a segment), P / -P (cancellation), an SRS with the identity:
-    the unchecked accumulation + redo kernel and the checked one, on the wide path's column regions."""
+    the unchecked accumulation + redo kernel and the checked one, on the wide path's column regions.  ZK_OPT_MSM_T1 = 1: the
+    pass's tail starts with the per-bucket kernel, the redo's tail runs by parts alone whatever the option says."""
+    from webauthn_halo2_amd import engine as E
+
     eng = windowed(bits)
+    eng.set_option(E.ZK_OPT_MSM_T1, t1)
     k = 10
     n = 1 << k
     rng = random.Random(4321)

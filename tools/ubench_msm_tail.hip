@@ -13,7 +13,7 @@ using namespace zk;
 #define CHK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 int main() {
-    const uint32_t k = 19, n = 1u << k, c = 13, nwin = msm_num_windows(c);
+    const uint32_t k = 19, n = 1u << k, c = 13, nwin = nwin_for(c);
     std::vector<uint32_t> hs((size_t)n * 8), hb((size_t)n * 16);
     srand(11);
     for (auto& w : hs) w = ((uint32_t)rand() << 16) ^ (uint32_t)rand();
@@ -37,8 +37,9 @@ int main() {
     CHK(hipHostMalloc(&hsum, 4096 * sizeof(G1X)));
     const Fr* list[1] = {dscal};
     for (int rep = 0; rep < 3; rep++) {
-        uint32_t nw, cc;
-        CHK(msm_run(ws, list, 1, dbases, n, st, hsum, &nw, &cc, nullptr, dtable, n));
+        const MsmPassArgs args = {list, 1, n, dbases, dtable, n, st, nullptr, nullptr, nullptr, true, hsum};
+        MsmPass pass;
+        CHK(msm_run(ws, args, &pass));
         CHK(hipStreamSynchronize(st));
         static unsigned long long tr[3][8192];
         CHK(hipMemcpyFromSymbol(tr, HIP_SYMBOL(zk_wg_trace), sizeof(tr)));

@@ -118,13 +118,9 @@ struct zk_ctx : SrsView {
         hipEvent_t head_done = nullptr, tail_done = nullptr;
         hipEvent_t t_head[2] = {nullptr, nullptr};  // timing: the pass as enqueued on the main stream
         hipEvent_t t_acc[4] = {nullptr, nullptr, nullptr, nullptr};  // timing: accumulate kernel [0, 1]; reduction tail [2, 3] (wide path)
-        size_t n = 0;
-        const G1Affine* table = nullptr;  // the window table of the MSM in flight (fixed-base mode)
         G1X* host_buf = nullptr;  // pinned
         bool busy = false;
-        uint32_t nwin = 0, cw = 0;
-        uint32_t batch = 1;       // columns of the MSM in flight (fixed-base mode), results collected together
-        bool fixed = false;       // the MSM in flight runs over the resident SRS's window tables
+        MsmPass pass{};           // the MSM in flight, as msm_run handed it back: what ctx_msm_end_batch collects
     } lanes[MSM_LANES];
     // scratch
     Fr* scratch = nullptr;

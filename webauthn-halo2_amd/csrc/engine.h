@@ -59,42 +59,41 @@ hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hi
 struct MsmWorkspace;  // opaque, sized for a maximum n and a maximum number of columns per launch
 MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, hipError_t* err, uint32_t max_batch = 1);
 void msm_workspace_destroy(MsmWorkspace* ws);
-uint32_t msm_num_windows(uint32_t c);
 size_t msm_ws_max_n(const MsmWorkspace* ws);
 uint32_t msm_ws_max_batch(const MsmWorkspace* ws);
 uint32_t msm_ws_window(const MsmWorkspace* ws);
 void msm_ws_set_t1_mode(MsmWorkspace* ws, uint32_t mode);  // ZK_OPT_MSM_T1: 1 one lane per bucket, 0 / 2 parts + segmented tree (default)
-bool msm_ws_last_pass_wide(const MsmWorkspace* ws);
-// table[w * n + i] = 2^(c w) * bases[i] (affine), w < msm_num_windows(c)
-// (the wide path's tables — 15 / 16-bit windows, msm_table_is_internal — hold the points in the accumulation's internal form,
-// x * 2^261: they are read by the fixed-base MSM only)
+// table[w * n + i] = 2^(c w) * bases[i] (affine), w < nwin_for(c); the wide path's tables (15 .. 17-bit windows: msm_table_is_internal)
+// hold the points in the accumulation's internal form, x * 2^261: they are read by the fixed-base MSM only
 hipError_t msm_build_table(const G1Affine* bases, uint32_t n, uint32_t c, G1Affine* table, hipStream_t st);
 bool msm_table_is_internal(uint32_t c, size_t n);
-// Launches the whole device pipeline on `st`; the bit sums (XYZZ) are copied to `host_window_sums`
-// asynchronously.  `table` != nullptr selects the fixed-base mode: `batch` scalar vectors (columns) against
-// the same bases in ONE pass, one bucket set per column; *nwin_out = batch independent results, each finished
-// with msm_finish_host(sums + q * stride, 1, c).  Without a table batch must be 1 and *nwin_out windows need
-// the host Horner: msm_finish_host(sums, *nwin_out, c).  A workspace of 15 / 16-bit windows whose table indexes fit 24 bits runs the
-// fixed-base mode on the "wide path" (msm.hip: dense entry lists, restartable lanes, row / column tail): results through
-// msm_ws_finish_fixed, msm_ws_sums_per_result sums each.
-hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t batch, const G1Affine* bases, size_t n,
-                   hipStream_t st, G1X* host_window_sums, uint32_t* nwin_out, uint32_t* c_out,
-                   hipEvent_t* accum_events = nullptr, const G1Affine* table = nullptr, uint32_t table_stride = 0,
-                   hipStream_t tail_st = nullptr, hipEvent_t head_done = nullptr, bool bases_may_be_identity = true);
-// whether any of the n points is the identity (synchronises `st`; d_word / h_word: one device word and one pinned host word of
-// scratch): a basis without one takes the unchecked accumulation loop
+// whether any of the n points is the identity (synchronises `st`; scratch: a device word, a pinned host word): if none, the unchecked loop
 hipError_t msm_bases_have_identity(const G1Affine* bases, uint32_t n, hipStream_t st, uint32_t* d_word, uint32_t* h_word, bool* out);
-// G1X entries per result in host_window_sums (fixed-base mode)
-uint32_t msm_sums_per_result(uint32_t c);
-// fixed-base mode, by workspace (the wide path of 15 / 16-bit windows hands over 16 sums per column)
-uint32_t msm_ws_sums_per_result(const MsmWorkspace* ws);
-G1Jac msm_ws_finish_fixed(const MsmWorkspace* ws, const G1X* sums);
-// wide path: lanes of the unchecked accumulation that must be redone with the checked loop (0 unless the basis is degenerate),
-// as reported with the pass's sums, and that redo + the tail again (results into host_window_sums once `st` has drained)
-uint32_t msm_wide_redo_count(const MsmWorkspace* ws, const G1X* host_window_sums, uint32_t batch);
-hipError_t msm_wide_redo(MsmWorkspace* ws, uint32_t batch, size_t n, hipStream_t st, G1X* host_window_sums, const G1Affine* table);
-// Host-side finish: Horner over windows -> Jacobian (Montgomery).
-G1Jac msm_finish_host(const G1X* window_sums, uint32_t nwin, uint32_t c);
+// One pass: `batch` columns of n scalars over a window table (fixed-base mode: ONE pass, a bucket set and a result per column), or, batch = 1, over `bases`
+struct MsmPassArgs {
+    const Fr* const* columns;
+    uint32_t batch;
+    size_t n;
+    const G1Affine *bases, *table;  // arbitrary bases, or table[w * table_stride + i] = 2^(c w) P_i
+    uint32_t table_stride;
+    hipStream_t head, tail;      // sort head + accumulation | the reduction tail, behind head_done (tail == head, or none: in order)
+    hipEvent_t head_done;
+    hipEvent_t* events;          // optional timing: [0, 1] around the accumulation, [2, 3] around the wide path's tail
+    bool bases_may_be_identity;  // false: the unchecked accumulation loop
+    G1X* host_sums;              // pinned, device-visible: the bit sums (XYZZ) arrive here once `tail` has drained
+};
+// What the pass was, for msm_collect (the wide path: fixed-base mode, 15 .. 17-bit windows, table indexes within 26 bits; 20 sums per column)
+struct MsmPass {
+    enum Plan : uint32_t { GENERIC, FIXED, WIDE } plan;  // arbitrary bases / the standard plan over window tables / the wide path
+    uint32_t batch, sums_per_result, c;  // results (one per column; one over all windows for arbitrary bases), G1X each, window bits
+    size_t n;
+    bool redo_word;  // behind the sums: the lanes the wide path's unchecked accumulation (n > 0) wants redone with the checked loop
+    const G1Affine* table;
+};
+hipError_t msm_run(MsmWorkspace* ws, const MsmPassArgs& a, MsmPass* pass);
+// Once `tail` has drained: the results (Jacobian, Montgomery), Horner over the sums; a non-zero redo word (a degenerate basis only)
+// first runs those lanes and the tail again on `tail` and waits for it (*redone)
+hipError_t msm_collect(MsmWorkspace* ws, const MsmPass& pass, hipStream_t tail, G1X* host_sums, G1Jac* out, bool* redone);
 
 // ---- host helpers (ctx.hip) --------------------------------------------------
 G1Affine g1_jac_to_affine_host(const G1Jac& p);

@@ -6,10 +6,10 @@
 // Any correct algorithm yields the same group element, so the result is
 // bit-identical to the reference's after affine normalisation.
 //
-// Layout of the source (round 6; one translation unit — the parts are textual includes that share the constants and the
-// workspace record defined here):
-//   msm.hip             constants, the workspace, msm_run / msm_run_wide (the launch sequences), the host's finish (Horner over
-//                       the bit sums)
+// Layout of the source (round 6; one translation unit — the parts are textual includes that share the constants defined here):
+//   msm.hip             constants; behind the kernels the host: the workspace (the wide geometry made once), msm_run (the standard
+//                       plan's launch sequence) / msm_run_wide (head + accumulation) / wide_tail (T1 .. T3, for the pass and for the
+//                       redo), msm_collect (redo where the pass's word asks for it, Horner over the bit sums per result)
 //   msm_plan.h          the choice of the plan as host code without HIP types: window by size, wide / fused / swept path, which
 //                       sort and scatter, bit-sum split, columns per pass (walked by tests/msm_plan_check.cpp)
 //   msm_wide.hip.h      THE path of every proof of the reference's configurations (2^16 .. 2^21 points over the resident SRS):
@@ -83,36 +83,47 @@ struct MsmBatch {
     const Fr* s[MSM_MAX_BATCH];
 };
 
+// the plan rules (nwin_for, msm_wide_shape, msm_auto_window .., sort2_applies, bitsum_split, msm_max_pass): msm_plan.h, host only
+
+// the kernels, by plan (one translation unit: the parts share the constants above)
+#include "msm_legacy.hip.h"  // 13-bit fused plan (n < 2^16), 15-bit swept sort (n >= 2^22), arbitrary bases
+#include "msm_wide.hip.h"    // 15 .. 17-bit windows, one bucket set per column: every proof of the reference's configurations
+#include "msm_tables.hip.h"  // window tables
+
+// ------------------------------------------------------------------ host ---
+
 struct MsmWorkspace {
+    // ---- every plan
     size_t max_n;
     uint32_t max_batch;         // columns per fixed-base launch this workspace is sized for
     uint32_t c, nwin, nb;       // window bits, windows, buckets per window
-    uint32_t parts_fixed, parts_generic;
-    size_t slot_elems;          // elements of slot_pt
-    int16_t* digits;            // [nwin][max_n]  (|digit| <= 2^(c-1) <= 8192)
-    uint32_t* totals;           // [nwin*nb + 1]
-    uint32_t* bucket_start;     // [nwin*nb + 1]
-    uint32_t* blockbase;        // [nblk][nb]
-    uint32_t* counts;           // [4]
+    bool wide;                  // a fixed-base pass whose table stride is max_n takes the wide path (msm_wide_shape)
+    // the buffers the standard plan and the wide path share (a workspace runs one pass at a time; the standard plan leaves the
+    // counters used: w_clean)
+    uint32_t* totals;           // [nwin*nb + 1]; the wide path's w_tot[0]
+    uint32_t* cursor;           // [max_batch * nb] per-bucket write cursors of the second level; the wide path's w_cur[0]
+    uint32_t* counts;           // [4 * (MSM_MAX_BATCH + 1)]
     uint32_t* entries;          // [max_n * nwin + padding]: +-base index, bucket implied by position
     // two-level sort (fixed-base mode): entries first grouped by coarse bin (bucket / 64) in `inter`, then by bucket
     uint32_t* inter;            // [max_batch][max_n * nwin]
+    size_t inter_stride;        // entries per column in `inter`
     uint32_t* coarse;           // per column: COARSE_WORDS (coarse-bin starts, chunk prefix, append cursors), then [blocks][CBINS_MAX] reserved bases
     uint32_t coarse_stride;     // words per column in `coarse`
-    uint32_t* cursor;           // [max_batch * nb] per-bucket write cursors of the second level
-    size_t inter_stride;        // entries per column in `inter`
     uint32_t* redo;             // [entries / SEG0] segments the unchecked accumulation hands to the checked one
     G1X29S* slot_pt;            // [entries / SEG0]  partial sums stay in the accumulation's internal form (ec29.hip.h)
+    size_t slot_elems;          // elements of slot_pt
+    // ---- the standard plan only (msm_legacy.hip.h)
+    uint32_t parts_fixed, parts_generic;
+    int16_t* digits;            // [nwin][max_n]  (|digit| <= 2^(c-1) <= 8192)
+    uint32_t* bucket_start;     // [nwin*nb + 1]
+    uint32_t* blockbase;        // [nblk][nb]
     G1X29S* partial;            // [entries / PAD]
-    G1X29S* part;                  // [nbt * parts]
+    G1X29S* part;               // [nbt * parts]
     G1X* bit_sum;               // [nwin * c]
-    // wide path (15 / 16-bit windows, fixed-base mode): per-column regions
-    bool wide;
-    bool w_redo_valid;          // the last pass on this workspace ran the wide path's unchecked accumulation over n > 0 scalars: the word
-                                // behind its sums in the host buffer is that pass's redo count (msm_wide_redo_count); any other pass —
-                                // the standard plan on a wide workspace, an empty one — leaves no such word
+    // ---- the wide path only (msm_wide.hip.h; 15 .. 17-bit windows, fixed-base mode): per-column regions
+    WideGeo geo;                // entry layout, coarse bins, the recoding bias: fixed by (c, max_n)
+    uint32_t rows, row_bits;    // the bucket matrix [rows = nb / 256][256]; rows = 2^row_bits
     uint32_t w_t1_mode;         // T1 of the wide path (ZK_OPT_MSM_T1): 1 one lane per bucket, otherwise parts + segmented tree
-    bool w_last_wide;           // the last pass on this workspace took the wide path (its tail's timing events were recorded)
     bool w_clean;               // the pass counters (totals, cursors, counts) are zero: the previous wide pass left them so
     // per-bucket totals and level-2 cursors exist twice: pass i counts in set i & 1 while its first kernel — 131 K lanes with
     // to spare (the fine histogram: two thousand workgroups) — zeroes the other set for pass i + 1 (in the 16 waves of the last
@@ -121,7 +132,6 @@ struct MsmWorkspace {
     uint32_t* w_cur[2];
     uint32_t w_par;
     uint32_t w_used_cols[2];    // columns of a set that hold counts of its last pass (what the next H1 has to zero)
-    uint32_t w_ib, w_fb;        // entry layout: table index bits, fine key bits (msm_wide_shape)
     size_t w_ent_stride;        // entries per column region (multiple of 64)
     uint32_t w_lane_stride;     // accumulation lanes per column region
     uint32_t w_slot_stride;     // slots per column region: lanes + buckets
@@ -131,24 +141,13 @@ struct MsmWorkspace {
     uint32_t* w_pstart;         // [max_batch][nb] first part of every bucket
     uint32_t* w_pbucket;        // [max_batch][w_part_stride] bucket of every part
     G1X29S* w_part;             // [max_batch][w_part_stride]
-    G1X29S* w_rc;               // [max_batch][nb / 256 + 256] row and column sums of the bucket matrix
+    G1X29S* w_rc;               // [max_batch][rows + 256] row and column sums of the bucket matrix
 };
 
-// the plan rules (nwin_for, msm_wide_shape, msm_auto_window .., sort2_applies, bitsum_split, msm_max_pass): msm_plan.h, host only
-
-uint32_t msm_num_windows(uint32_t c) { return nwin_for(c); }
 size_t msm_ws_max_n(const MsmWorkspace* ws) { return ws->max_n; }
 uint32_t msm_ws_max_batch(const MsmWorkspace* ws) { return ws->max_batch; }
 uint32_t msm_ws_window(const MsmWorkspace* ws) { return ws->c; }
 void msm_ws_set_t1_mode(MsmWorkspace* ws, uint32_t mode) { ws->w_t1_mode = mode; }
-bool msm_ws_last_pass_wide(const MsmWorkspace* ws) { return ws->w_last_wide; }
-
-// the kernels, by plan (one translation unit: the parts share the constants and the workspace record above)
-#include "msm_legacy.hip.h"  // 13-bit fused plan (n < 2^16), 15-bit swept sort (n >= 2^22), arbitrary bases
-#include "msm_wide.hip.h"    // 15 .. 17-bit windows, one bucket set per column: every proof of the reference's configurations
-#include "msm_tables.hip.h"  // window tables
-
-// ------------------------------------------------------------------ host ---
 
 #define MSM_TRY(x)                     \
     do {                               \
@@ -209,9 +208,21 @@ MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, hipError_t* err, ui
     MSM_TRY(hipMalloc(&ws->partial, (threads / GA + 2) * sizeof(G1X29S)));
     MSM_TRY(hipMalloc(&ws->part, part_n * sizeof(G1X29S)));
     MSM_TRY(hipMalloc(&ws->bit_sum, slices * c * BITSUM_MAX_SPLIT * sizeof(G1X)));
-    ws->wide = msm_wide_shape(c, max_n, &ws->w_ib, &ws->w_fb);
+    WideGeo& g = ws->geo;
+    ws->wide = msm_wide_shape(c, max_n, &g.ib, &g.fb);
     ws->w_clean = false;
     if (ws->wide) {
+        // the geometry of every pass of this workspace, made once
+        g.c = c;
+        g.nwin = ws->nwin;
+        g.nb = ws->nb;
+        g.bins = ws->nb >> g.fb;
+        for (uint32_t w = 0; w < ws->nwin; w++) {  // the recoding bias: s + K < 2^254 + 2^(nwin c - 1) (1 + 2^-c + ..) < 2^256
+            const uint32_t bit = c - 1 + w * c;
+            g.K[bit >> 5] |= 1u << (bit & 31);
+        }
+        ws->rows = ws->nb >> 8;
+        while ((1u << ws->row_bits) < ws->rows) ws->row_bits++;
         ws->w_ent_stride = (max_n * ws->nwin + 63) & ~(size_t)63;
         if (ws->w_ent_stride * max_batch > ent) {  // cannot happen: the dense list is padded to 64 per bucket
             if (err) *err = hipErrorInvalidValue;
@@ -220,7 +231,7 @@ MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, hipError_t* err, ui
         }
         ws->w_lane_stride = (uint32_t)(ws->w_ent_stride / WL) + 64;
         ws->w_slot_stride = ws->w_lane_stride + ws->nb + 64;
-        ws->w_part_stride = ((ws->w_lane_stride + 2 * ws->nb) / WCAP_MIN + ws->nb + 2 * (ws->nb >> ws->w_fb) + 127) & ~63u;
+        ws->w_part_stride = ((ws->w_lane_stride + 2 * ws->nb) / WCAP_MIN + ws->nb + 2 * g.bins + 127) & ~63u;
         if ((size_t)max_batch * ws->w_slot_stride > threads) {  // cannot happen: sized for 16-entry segments
             if (err) *err = hipErrorInvalidValue;
             msm_workspace_destroy(ws);
@@ -235,7 +246,7 @@ MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, hipError_t* err, ui
         MSM_TRY(hipMalloc(&ws->w_pstart, (size_t)max_batch * ws->nb * 4));
         MSM_TRY(hipMalloc(&ws->w_pbucket, (size_t)max_batch * ws->w_part_stride * 4));
         MSM_TRY(hipMalloc(&ws->w_part, (size_t)max_batch * ws->w_part_stride * sizeof(G1X29S)));
-        MSM_TRY(hipMalloc(&ws->w_rc, (size_t)max_batch * ((ws->nb >> 8) + 256) * sizeof(G1X29S)));
+        MSM_TRY(hipMalloc(&ws->w_rc, (size_t)max_batch * (ws->rows + 256) * sizeof(G1X29S)));
     }
     return ws;
 }
@@ -256,10 +267,8 @@ void msm_workspace_destroy(MsmWorkspace* ws) {
     hipFree(ws->partial);
     hipFree(ws->part);
     hipFree(ws->bit_sum);
-    if (ws->wide) {
-        hipFree(ws->w_tot[1]);
-        hipFree(ws->w_cur[1]);
-    }
+    hipFree(ws->w_tot[1]);  // ([0]: totals, cursor)
+    hipFree(ws->w_cur[1]);
     hipFree(ws->w_lane_b);
     hipFree(ws->w_bstart);
     hipFree(ws->w_pstart);
@@ -269,36 +278,85 @@ void msm_workspace_destroy(MsmWorkspace* ws) {
     delete ws;
 }
 
-// The wide path's pipeline (see "wide path" above): `batch` columns against the resident basis whose window table — in the
-// internal form, msm_build_table(.., internal = true) — is `table`.
-static hipError_t msm_run_wide(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t batch, size_t n, hipStream_t st,
-                               G1X* host_window_sums, uint32_t* nwin_out, uint32_t* c_out, hipEvent_t* accum_events,
-                               const G1Affine* table, uint32_t table_stride, hipStream_t tail_st, hipEvent_t head_done,
-                               bool bases_may_be_identity) {
-    const uint32_t c = ws->c, nwin = ws->nwin, nb = ws->nb;
-    const uint32_t rows = nb >> 8;
-    const uint32_t WCAP = wcap_for(batch);
-    uint32_t row_bits = 0;
-    while ((1u << row_bits) < rows) row_bits++;
-    *nwin_out = batch;
-    *c_out = c;
+static MsmBatch msm_columns(const MsmPassArgs& a) {
+    MsmBatch mb;
+    memset(&mb, 0, sizeof(mb));
+    for (uint32_t q = 0; q < a.batch; q++) mb.s[q] = a.columns[q];
+    return mb;
+}
+
+// the head's hand-off: the tail goes on a.tail behind a.head_done where that is another stream than the head's
+static hipError_t msm_tail_stream(const MsmPassArgs& a, hipStream_t* ts) {
+    *ts = a.head;
+    if (!a.tail || a.tail == a.head) return hipSuccess;
     hipError_t e;
-    WideGeo g;
-    memset(&g, 0, sizeof(g));
-    g.c = c;
-    g.nwin = nwin;
-    g.nb = nb;
-    g.ib = ws->w_ib;
-    g.fb = ws->w_fb;
-    g.bins = nb >> g.fb;
-    for (uint32_t w = 0; w < nwin; w++) {  // the recoding bias: s + K < 2^254 + 2^(nwin c - 1) (1 + 2^-c + ..) < 2^256
-        const uint32_t bit = c - 1 + w * c;
-        g.K[bit >> 5] |= 1u << (bit & 31);
+    if ((e = hipEventRecord(a.head_done, a.head)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(a.tail, a.head_done, 0)) != hipSuccess) return e;
+    *ts = a.tail;
+    return hipSuccess;
+}
+
+// ---- the wide path's pipeline (msm_wide.hip.h).  The geometry is the workspace's; what depends on the pass:
+// accumulation lanes of one column at most
+static uint32_t wide_lanes(const MsmWorkspace* ws, size_t n) { return (uint32_t)((n * ws->nwin + WL - 1) / WL); }
+// chunks of one column's binned list at most (msm_wfinehist / msm_wscatter2: one workgroup each)
+static uint32_t wide_max_chunks(const MsmWorkspace* ws, size_t n) { return (uint32_t)(((uint64_t)n * ws->nwin + SUB - 1) / SUB) + ws->geo.bins; }
+// parts of one column at most: every bin's region is its slots / WCAP + a part per bucket + slack (msm_wscatter1_kernel);
+// WCAP = wcap_for(batch)
+static uint32_t wide_max_parts(const MsmWorkspace* ws, size_t n, uint32_t WCAP) {
+    return (wide_lanes(ws, n) + 2 * ws->nb) / WCAP + ws->nb + 2 * ws->geo.bins + 64;
+}
+
+// H1 + S1 at C-bit windows: the coarse histogram and the first scatter
+template <uint32_t C>
+static void wide_head(const MsmWorkspace* ws, const MsmPassArgs& a, uint32_t WCAP) {
+    const uint32_t n32 = (uint32_t)a.n;
+    const dim3 gh((n32 + FCHUNK - 1) / FCHUNK, a.batch);
+    const MsmBatch mb = msm_columns(a);
+    hipLaunchKernelGGL(msm_whist_kernel<C>, gh, dim3(256), 0, a.head, mb, n32, ws->geo, ws->coarse, ws->coarse_stride, ws->counts);
+    hipLaunchKernelGGL(msm_wscatter1_kernel<C>, gh, dim3(256), 0, a.head, mb, n32, ws->geo, a.table_stride, ws->coarse, ws->coarse_stride,
+                       ws->inter, ws->inter_stride, ws->counts, WCAP);
+}
+
+// The reduction tail of `batch` columns of n scalars on `ts`, over the counter set `totals` the pass counted in: T1 per part, with
+// `per_bucket` behind the per-bucket kernel (ZK_OPT_MSM_T1 = 1: fewer instructions, a longer chain — measured: no gain,
+// msm_wide.hip.h), T2, T3.  T3 writes its sums (and the redo count) STRAIGHT into the caller's pinned host buffer: 17 x 128 bytes
+// per column over the bus instead of a copy kernel at the end of every pass's chain (host_sums must be device-visible pinned
+// memory: the engine's lanes allocate it with hipHostMalloc).  The caller asks hipGetLastError.
+static hipError_t wide_tail(MsmWorkspace* ws, uint32_t batch, size_t n, hipStream_t ts, uint32_t* totals, bool per_bucket, G1X* host_sums) {
+    const uint32_t nb = ws->nb, WCAP = wcap_for(batch);
+    if (n > 0) {
+        uint32_t lmin = 0;
+        if (per_bucket) {
+            lmin = ZK_T1B_LMAX;
+            hipLaunchKernelGGL(msm_wbucket_kernel, dim3(nb / 64, batch), dim3(64), 0, ts, ws->slot_pt, ws->w_slot_stride, totals, ws->w_bstart,
+                               ws->w_pstart, ws->w_part_stride, nb, ws->w_part, WCAP, lmin);
+        }
+        hipLaunchKernelGGL(msm_wparts_kernel, dim3((wide_max_parts(ws, n, WCAP) + 63) / 64, batch), dim3(64), 0, ts, ws->slot_pt,
+                           ws->w_slot_stride, totals, ws->w_bstart, ws->w_pstart, ws->w_pbucket, ws->w_part_stride, nb, ws->counts, ws->w_part,
+                           WCAP, lmin);
     }
+    hipLaunchKernelGGL(msm_wrowcol_kernel, dim3(ws->rows + 256, batch), dim3(64), 0, ts, ws->w_part, ws->w_part_stride, totals, ws->w_bstart,
+                       ws->w_pstart, nb, ws->w_rc, WCAP);
+    G1X* out_dev = nullptr;
+    const hipError_t e = hipHostGetDevicePointer((void**)&out_dev, host_sums, 0);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(msm_wbits_kernel, dim3(9 + ws->row_bits, batch), dim3(64), 0, ts, ws->w_rc, nb, out_dev, ws->counts);
+    return hipSuccess;
+}
+
+// `a.batch` columns against the resident basis whose window table — in the internal form, msm_build_table(.., internal = true)
+// — is a.table
+static hipError_t msm_run_wide(MsmWorkspace* ws, const MsmPassArgs& a, MsmPass* pass) {
+    const uint32_t c = ws->c, nb = ws->nb, batch = a.batch, WCAP = wcap_for(batch);
+    const size_t n = a.n;
+    const WideGeo& g = ws->geo;
+    hipStream_t st = a.head;
+    hipError_t e;
 #ifdef ZK_MSM_POISON  // debug: a slot / part / row-column sum read without having been written by THIS pass shows
     hipMemsetAsync(ws->slot_pt, 0xA5, ws->slot_elems * sizeof(G1X29S), st);
     hipMemsetAsync(ws->w_part, 0xA5, (size_t)ws->max_batch * ws->w_part_stride * sizeof(G1X29S), st);
-    hipMemsetAsync(ws->w_rc, 0xA5, (size_t)ws->max_batch * ((ws->nb >> 8) + 256) * sizeof(G1X29S), st);
+    hipMemsetAsync(ws->w_rc, 0xA5, (size_t)ws->max_batch * (ws->rows + 256) * sizeof(G1X29S), st);
 #endif
     if (!ws->w_clean) {
         // first pass on this workspace (or the previous one did not finish): every later pass finds the counters zeroed by
@@ -316,143 +374,83 @@ static hipError_t msm_run_wide(MsmWorkspace* ws, const Fr* const* scalars_list, 
     uint32_t* const cursor = ws->w_cur[ws->w_par];
     uint32_t* const next_totals = ws->w_tot[ws->w_par ^ 1];
     uint32_t* const next_cursor = ws->w_cur[ws->w_par ^ 1];
-    const uint32_t n32 = (uint32_t)n;
-    const uint32_t lanes = (uint32_t)(((size_t)n * nwin + WL - 1) / WL);  // accumulation lanes of one column at most
     if (n > 0) {
-        const uint32_t nblk = (n32 + FCHUNK - 1) / FCHUNK;
-        MsmBatch mb;
-        memset(&mb, 0, sizeof(mb));
-        for (uint32_t q = 0; q < batch; q++) mb.s[q] = scalars_list[q];
-        const dim3 gh(nblk, batch);
-        if (c == 17) {
-            hipLaunchKernelGGL(msm_whist_kernel<17>, gh, dim3(256), 0, st, mb, n32, g, ws->coarse, ws->coarse_stride, ws->counts);
-            hipLaunchKernelGGL(msm_wscatter1_kernel<17>, gh, dim3(256), 0, st, mb, n32, g, table_stride, ws->coarse, ws->coarse_stride,
-                               ws->inter, ws->inter_stride, ws->counts, WCAP);
-        } else if (c == 16) {
-            hipLaunchKernelGGL(msm_whist_kernel<16>, gh, dim3(256), 0, st, mb, n32, g, ws->coarse, ws->coarse_stride, ws->counts);
-            hipLaunchKernelGGL(msm_wscatter1_kernel<16>, gh, dim3(256), 0, st, mb, n32, g, table_stride, ws->coarse, ws->coarse_stride,
-                               ws->inter, ws->inter_stride, ws->counts, WCAP);
+        if (c == 17)
+            wide_head<17>(ws, a, WCAP);
+        else if (c == 16)
+            wide_head<16>(ws, a, WCAP);
+        else
+            wide_head<15>(ws, a, WCAP);
+        const dim3 gc(wide_max_chunks(ws, n) + 1, batch), gl((wide_lanes(ws, n) + 63) / 64, batch);
+        hipLaunchKernelGGL(msm_wfinehist_kernel, gc, dim3(256), 0, st, ws->inter, ws->inter_stride, ws->coarse, ws->coarse_stride, g, totals,
+                           next_totals, next_cursor, ws->w_used_cols[ws->w_par ^ 1]);
+        hipLaunchKernelGGL(msm_wscatter2_kernel, gc, dim3(256), 0, st, ws->inter, ws->inter_stride, ws->coarse, ws->coarse_stride, g, totals,
+                           ws->w_bstart, cursor, ws->entries, ws->w_ent_stride, ws->w_lane_b, ws->w_lane_stride, ws->w_pstart, ws->w_pbucket,
+                           ws->w_part_stride, WCAP);
+        if (a.events) hipEventRecord(a.events[0], st);
+        if (a.bases_may_be_identity) {
+            hipLaunchKernelGGL(msm_wacc_kernel, gl, dim3(64), 0, st, ws->entries, ws->w_ent_stride, a.table, ws->counts, ws->w_lane_b,
+                               ws->w_lane_stride, ws->w_bstart, nb, ws->slot_pt, ws->w_slot_stride, g.ib);
         } else {
-            hipLaunchKernelGGL(msm_whist_kernel<15>, gh, dim3(256), 0, st, mb, n32, g, ws->coarse, ws->coarse_stride, ws->counts);
-            hipLaunchKernelGGL(msm_wscatter1_kernel<15>, gh, dim3(256), 0, st, mb, n32, g, table_stride, ws->coarse, ws->coarse_stride,
-                               ws->inter, ws->inter_stride, ws->counts, WCAP);
+            hipLaunchKernelGGL(msm_wacc_fast_kernel, gl, dim3(64), 0, st, ws->entries, ws->w_ent_stride, a.table, ws->counts, ws->w_lane_b,
+                               ws->w_lane_stride, ws->w_bstart, nb, ws->slot_pt, ws->w_slot_stride, ws->redo, g.ib);
         }
-        const uint32_t max_chunks = (uint32_t)(((uint64_t)n32 * nwin + SUB - 1) / SUB) + g.bins;
-        hipLaunchKernelGGL(msm_wfinehist_kernel, dim3(max_chunks + 1, batch), dim3(256), 0, st, ws->inter, ws->inter_stride, ws->coarse,
-                           ws->coarse_stride, g, totals, next_totals, next_cursor, ws->w_used_cols[ws->w_par ^ 1]);
-        hipLaunchKernelGGL(msm_wscatter2_kernel, dim3(max_chunks + 1, batch), dim3(256), 0, st, ws->inter, ws->inter_stride, ws->coarse,
-                           ws->coarse_stride, g, totals, ws->w_bstart, cursor, ws->entries, ws->w_ent_stride, ws->w_lane_b, ws->w_lane_stride,
-                           ws->w_pstart, ws->w_pbucket, ws->w_part_stride, WCAP);
-        if (accum_events) hipEventRecord(accum_events[0], st);
-        if (bases_may_be_identity) {
-            hipLaunchKernelGGL(msm_wacc_kernel, dim3((lanes + 63) / 64, batch), dim3(64), 0, st, ws->entries, ws->w_ent_stride, table, ws->counts,
-                               ws->w_lane_b, ws->w_lane_stride, ws->w_bstart, nb, ws->slot_pt, ws->w_slot_stride, g.ib);
-        } else {
-            hipLaunchKernelGGL(msm_wacc_fast_kernel, dim3((lanes + 63) / 64, batch), dim3(64), 0, st, ws->entries, ws->w_ent_stride, table,
-                               ws->counts, ws->w_lane_b, ws->w_lane_stride, ws->w_bstart, nb, ws->slot_pt, ws->w_slot_stride, ws->redo, g.ib);
-        }
-        if (accum_events) hipEventRecord(accum_events[1], st);
+        if (a.events) hipEventRecord(a.events[1], st);
     }
-    hipStream_t ts = st;
-    if (tail_st && tail_st != st) {
-        if ((e = hipEventRecord(head_done, st)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(tail_st, head_done, 0)) != hipSuccess) return e;
-        ts = tail_st;
-    }
-    if (accum_events && accum_events[2]) hipEventRecord(accum_events[2], ts);  // the reduction tail (T1 .. T3) alone
-    if (n > 0) {
-        // parts of one column at most: every bin's region is its slots / WCAP + a part per bucket + slack (msm_wscatter1_kernel)
-        const uint32_t max_parts = (lanes + 2 * nb) / WCAP + nb + 2 * g.bins + 64;
-        // T1 per part (default) or per bucket (ZK_OPT_MSM_T1 = 1: fewer instructions, a longer chain — measured: no gain, msm_wide.hip.h)
-        const bool per_bucket = ws->w_t1_mode == 1;
-        uint32_t lmin = 0;
-        if (per_bucket) {
-            lmin = ZK_T1B_LMAX;
-            hipLaunchKernelGGL(msm_wbucket_kernel, dim3(nb / 64, batch), dim3(64), 0, ts, ws->slot_pt, ws->w_slot_stride, totals, ws->w_bstart,
-                               ws->w_pstart, ws->w_part_stride, nb, ws->w_part, WCAP, lmin);
-        }
-        hipLaunchKernelGGL(msm_wparts_kernel, dim3((max_parts + 63) / 64, batch), dim3(64), 0, ts, ws->slot_pt, ws->w_slot_stride, totals,
-                           ws->w_bstart, ws->w_pstart, ws->w_pbucket, ws->w_part_stride, nb, ws->counts, ws->w_part, WCAP, lmin);
-    }
-    hipLaunchKernelGGL(msm_wrowcol_kernel, dim3(rows + 256, batch), dim3(64), 0, ts, ws->w_part, ws->w_part_stride, totals, ws->w_bstart,
-                       ws->w_pstart, nb, ws->w_rc, WCAP);
-    // T3 writes its sums (and the redo count) STRAIGHT into the caller's pinned host buffer: 17 x 128 bytes per column over the
-    // bus instead of a copy kernel at the end of every pass's chain (host_window_sums must be device-visible pinned memory: the
-    // engine's lanes allocate it with hipHostMalloc)
-    G1X* out_dev = nullptr;
-    if ((e = hipHostGetDevicePointer((void**)&out_dev, host_window_sums, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(msm_wbits_kernel, dim3(9 + row_bits, batch), dim3(64), 0, ts, ws->w_rc, nb, out_dev, ws->counts);
-    if (accum_events && accum_events[3]) hipEventRecord(accum_events[3], ts);
+    hipStream_t ts;
+    if ((e = msm_tail_stream(a, &ts)) != hipSuccess) return e;
+    if (a.events && a.events[2]) hipEventRecord(a.events[2], ts);  // the reduction tail (T1 .. T3) alone
+    if ((e = wide_tail(ws, batch, n, ts, totals, ws->w_t1_mode == 1, a.host_sums)) != hipSuccess) return e;
+    if (a.events && a.events[3]) hipEventRecord(a.events[3], ts);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     ws->w_clean = true;
-    ws->w_redo_valid = n > 0 && !bases_may_be_identity;  // (the checked loop lists nothing; an empty pass never reset counts[1])
     if (n > 0) {  // (an empty pass neither counts nor zeroes anything)
         ws->w_used_cols[ws->w_par] = batch;
         ws->w_used_cols[ws->w_par ^ 1] = 0;
         ws->w_par ^= 1;  // the next pass counts in the set this one has zeroed
     }
+    // the unchecked accumulation's count of lanes to redo follows the sums (the checked loop lists nothing; an empty pass never
+    // reset counts[1])
+    *pass = MsmPass{MsmPass::WIDE, batch, WIDE_SUMS, c, n, n > 0 && !a.bases_may_be_identity, a.table};
     return hipSuccess;
 }
 
 // The unchecked accumulation of the wide path lists the lanes whose sums show an exceptional step; the count travels to the host
-// with the pass's sums (msm_wbits_kernel).  Non-zero — a degenerate basis only — and the host calls this: the listed lanes again
-// with the checked loop, then the tail again, on `st`; the pass's workspace is intact until the lane's next pass.
-uint32_t msm_wide_redo_count(const MsmWorkspace* ws, const G1X* host_window_sums, uint32_t batch) {
-    if (!ws->wide || !ws->w_redo_valid) return 0;
-    uint32_t v;
-    memcpy(&v, host_window_sums + (size_t)batch * WIDE_SUMS, 4);
-    return v;
-}
-
-hipError_t msm_wide_redo(MsmWorkspace* ws, uint32_t batch, size_t n, hipStream_t st, G1X* host_window_sums, const G1Affine* table) {
-    if (!ws->wide || n == 0 || batch == 0 || batch > ws->max_batch) return hipErrorInvalidValue;
-    const uint32_t nb = ws->nb, rows = nb >> 8, nwin = ws->nwin, WCAP = wcap_for(batch);
-    uint32_t row_bits = 0;
-    while ((1u << row_bits) < rows) row_bits++;
-    const uint32_t lanes = (uint32_t)(((size_t)n * nwin + WL - 1) / WL);
-    const uint32_t bins = nb >> ws->w_fb;
-    uint32_t* const totals = ws->w_tot[ws->w_par ^ 1];  // the set the pass counted in (the parity has moved on)
-    hipLaunchKernelGGL(msm_wacc_redo_kernel, dim3(256), dim3(64), 0, st, ws->entries, ws->w_ent_stride, table, ws->counts, ws->w_lane_b,
-                       ws->w_lane_stride, ws->w_bstart, nb, ws->slot_pt, ws->w_slot_stride, ws->redo, ws->w_ib);
+// with the pass's sums (msm_wbits_kernel).  Non-zero — a degenerate basis only — and msm_collect calls this: the listed lanes again
+// with the checked loop, then the tail again — by parts, whatever the pass's T1 was — on `st`; the pass's workspace is intact
+// until the lane's next pass.
+static hipError_t msm_wide_redo(MsmWorkspace* ws, const MsmPass& p, hipStream_t st, G1X* host_sums) {
+    hipLaunchKernelGGL(msm_wacc_redo_kernel, dim3(256), dim3(64), 0, st, ws->entries, ws->w_ent_stride, p.table, ws->counts, ws->w_lane_b,
+                       ws->w_lane_stride, ws->w_bstart, ws->nb, ws->slot_pt, ws->w_slot_stride, ws->redo, ws->geo.ib);
     hipError_t e = hipMemsetAsync(ws->counts + 1, 0, 4, st);  // the second tail reports none
     if (e != hipSuccess) return e;
-    const uint32_t max_parts = (lanes + 2 * nb) / WCAP + nb + 2 * bins + 64;
-    hipLaunchKernelGGL(msm_wparts_kernel, dim3((max_parts + 63) / 64, batch), dim3(64), 0, st, ws->slot_pt, ws->w_slot_stride, totals,
-                       ws->w_bstart, ws->w_pstart, ws->w_pbucket, ws->w_part_stride, nb, ws->counts, ws->w_part, WCAP, 0u);
-    hipLaunchKernelGGL(msm_wrowcol_kernel, dim3(rows + 256, batch), dim3(64), 0, st, ws->w_part, ws->w_part_stride, totals, ws->w_bstart,
-                       ws->w_pstart, nb, ws->w_rc, WCAP);
-    G1X* out_dev = nullptr;
-    if ((e = hipHostGetDevicePointer((void**)&out_dev, host_window_sums, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(msm_wbits_kernel, dim3(9 + row_bits, batch), dim3(64), 0, st, ws->w_rc, nb, out_dev, ws->counts);
+    // the set the pass counted in (the parity has moved on)
+    if ((e = wide_tail(ws, p.batch, p.n, st, ws->w_tot[ws->w_par ^ 1], false, host_sums)) != hipSuccess) return e;
     return hipGetLastError();
 }
 
-// `table` != nullptr selects the fixed-base mode: table[w * table_stride + i] = 2^(c w) P_i.
-// The "head" (recode .. accumulate) runs on `st`; the latency-bound "tail" (gather, bit sums,
-// D2H) runs on `tail_st` after `head_done`, so that the caller can put the next MSM's head (or
-// any other kernels) on `st` right away.  tail_st == st gives the plain sequential order.
-hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t batch, const G1Affine* bases, size_t n,
-                   hipStream_t st, G1X* host_window_sums, uint32_t* nwin_out, uint32_t* c_out, hipEvent_t* accum_events,
-                   const G1Affine* table, uint32_t table_stride, hipStream_t tail_st, hipEvent_t head_done,
-                   bool bases_may_be_identity) {
+// One pass: a.table != nullptr selects the fixed-base mode: table[w * table_stride + i] = 2^(c w) P_i.
+// The "head" (recode .. accumulate) runs on a.head; the latency-bound "tail" (gather, bit sums,
+// D2H) runs on a.tail after a.head_done, so that the caller can put the next MSM's head (or
+// any other kernels) on a.head right away.  a.tail == a.head (or none) gives the plain sequential order.
+hipError_t msm_run(MsmWorkspace* ws, const MsmPassArgs& a, MsmPass* pass) {
+    const size_t n = a.n;
+    const uint32_t batch = a.batch;
     if (n > ws->max_n || batch == 0 || batch > ws->max_batch) return hipErrorInvalidValue;
     const uint32_t c = ws->c, nwin = ws->nwin, nb = ws->nb;
-    const bool fixed = table != nullptr;
-    ws->w_redo_valid = false;
-    ws->w_last_wide = fixed && ws->wide && table_stride == ws->max_n;
-    if (fixed && ws->wide && table_stride == ws->max_n)
-        return msm_run_wide(ws, scalars_list, batch, n, st, host_window_sums, nwin_out, c_out, accum_events, table, table_stride, tail_st,
-                            head_done, bases_may_be_identity);
+    const bool fixed = a.table != nullptr;
+    if (fixed && ws->wide && a.table_stride == ws->max_n) return msm_run_wide(ws, a, pass);
     if (c > 15) return hipErrorInvalidValue;  // 16 / 17-bit digits exist on the wide path only
     ws->w_clean = false;                       // this plan shares totals / cursors / counts with the wide path and leaves them used
     const bool fused = msm_fused(fixed, nb);  // one-kernel digits + histogram; 15-bit windows take the swept sort
     if (!fused && batch != 1) return hipErrorInvalidValue;  // columns are batched on the fused fixed-base path only
-    const Fr* scalars = scalars_list[0];
+    hipStream_t st = a.head;
+    const G1Affine* const points = fixed ? a.table : a.bases;
     const uint32_t slices = fixed ? batch : nwin;
     const uint32_t nbt = slices * nb;
     const uint32_t parts = fixed ? ws->parts_fixed : ws->parts_generic;
-    *nwin_out = slices;
-    *c_out = c;
+    const bool sort2 = sort2_applies(fused, n, nb, nwin, a.table_stride);
+    const size_t worst = (size_t)(fixed ? batch : 1) * n * nwin + (size_t)nbt * (PAD - 1);  // worst-case padded entry count
     hipError_t e;
     {
         // the bucket parts need no reset: the bit sums read only the parts the gather wrote (msm_bitsum_kernel used_parts);
@@ -464,7 +462,6 @@ hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t bat
         uint32_t m = nbt + 1;
         if (clear_parts > m) m = clear_parts;
         if (batch * CBINS_MAX > m) m = batch * CBINS_MAX;
-        const bool sort2 = sort2_applies(fused, n, nb, nwin, table_stride);
         hipLaunchKernelGGL(msm_clear_kernel, dim3((m + 255) / 256), dim3(256), 0, st, ws->part, clear_parts, ws->totals, nbt + 1,
                            ws->counts, ws->cursor, sort2 ? nbt : 0u, ws->coarse, ws->coarse_stride, sort2 ? batch : 0u);
     }
@@ -472,73 +469,60 @@ hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t bat
         const uint32_t n32 = (uint32_t)n;
         const uint32_t stride = (uint32_t)ws->max_n;
         const uint32_t nchunks = (n32 + CHUNK - 1) / CHUNK;
-        const bool sort2 = sort2_applies(fused, n, nb, nwin, table_stride);
+        const uint32_t nblk = (n32 + FCHUNK - 1) / FCHUNK;
         if (sort2) {
             // two-level counting sort with coalesced stores (see msm_scatter1_kernel)
-            const uint32_t nblk = (n32 + FCHUNK - 1) / FCHUNK;
-            MsmBatch mb;
-            memset(&mb, 0, sizeof(mb));
-            for (uint32_t q = 0; q < batch; q++) mb.s[q] = scalars_list[q];
-            hipLaunchKernelGGL(msm_recode_hist2_kernel, dim3(nblk, batch), dim3(256), (nb + 256 * 9) * 4, st, mb, n32, stride, c, nwin, nb,
-                               ws->digits, ws->totals, ws->coarse, ws->coarse_stride);
+            hipLaunchKernelGGL(msm_recode_hist2_kernel, dim3(nblk, batch), dim3(256), (nb + 256 * 9) * 4, st, msm_columns(a), n32, stride, c,
+                               nwin, nb, ws->digits, ws->totals, ws->coarse, ws->coarse_stride);
             hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, ws->totals, ws->bucket_start, nbt, ws->counts);
             hipLaunchKernelGGL(msm_scan_coarse_kernel, dim3(batch), dim3(CBINS_MAX), 0, st, ws->totals, nb, ws->coarse, ws->coarse_stride, nb >> 6, 6u);
-            hipLaunchKernelGGL(msm_scatter1_kernel, dim3(nblk, batch), dim3(256), 0, st, ws->digits, n32, stride, nwin, nb, table_stride,
+            hipLaunchKernelGGL(msm_scatter1_kernel, dim3(nblk, batch), dim3(256), 0, st, ws->digits, n32, stride, nwin, nb, a.table_stride,
                                ws->coarse, ws->coarse_stride, ws->inter, ws->inter_stride, 6u);
             const uint32_t max_chunks = (uint32_t)(((uint64_t)n32 * nwin + SUB - 1) / SUB) + (nb >> 6);
             hipLaunchKernelGGL(msm_scatter2_kernel, dim3(max_chunks, batch), dim3(256), 0, st, ws->inter, ws->inter_stride, ws->coarse,
                                ws->coarse_stride, nb, ws->totals, ws->bucket_start, ws->cursor, ws->entries, 6u, PAD, (size_t)0, (const uint8_t*)nullptr);
         } else if (fused) {
-            const uint32_t nblk = (n32 + FCHUNK - 1) / FCHUNK;
-            MsmBatch mb;
-            memset(&mb, 0, sizeof(mb));
-            for (uint32_t q = 0; q < batch; q++) mb.s[q] = scalars_list[q];
-            hipLaunchKernelGGL(msm_recode_hist_kernel, dim3(nblk, batch), dim3(256), (nb + 256 * 9) * 4, st, mb, n32, stride, c,
+            hipLaunchKernelGGL(msm_recode_hist_kernel, dim3(nblk, batch), dim3(256), (nb + 256 * 9) * 4, st, msm_columns(a), n32, stride, c,
                                nwin, nb, ws->digits, ws->totals, ws->blockbase);
             hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, ws->totals, ws->bucket_start, nbt, ws->counts);
             // long columns: one scatter launch per column (msm_plan.h msm_scatter_per_launch)
             const uint32_t per_launch = msm_scatter_per_launch(n32, batch);
             for (uint32_t q = 0; q < batch; q += per_launch)
                 hipLaunchKernelGGL(msm_scatter_fixed_kernel, dim3(nblk, per_launch), dim3(SCAT_T), nb * 4, st,
-                                   ws->digits + (size_t)q * nwin * stride, n32, stride, nwin, nb, table_stride,
+                                   ws->digits + (size_t)q * nwin * stride, n32, stride, nwin, nb, a.table_stride,
                                    ws->totals + (size_t)q * nb, ws->bucket_start + (size_t)q * nb,
                                    ws->blockbase + (size_t)q * nblk * nb, ws->entries);
         } else {
-            hipLaunchKernelGGL(msm_recode_kernel, dim3((n32 + 255) / 256), dim3(256), 0, st, scalars, n32, stride, c, nwin,
+            const uint32_t sort_lds = (nb < SORT_LDS_BUCKETS ? nb : SORT_LDS_BUCKETS) * 4;
+            hipLaunchKernelGGL(msm_recode_kernel, dim3((n32 + 255) / 256), dim3(256), 0, st, a.columns[0], n32, stride, c, nwin,
                                ws->digits);
-            hipLaunchKernelGGL(msm_sort_kernel<false>, dim3(nchunks * nwin), dim3(256), (nb < SORT_LDS_BUCKETS ? nb : SORT_LDS_BUCKETS) * 4, st, ws->digits, n32, stride,
-                               nchunks, nb, fixed ? 1u : 0u, table_stride, ws->totals, ws->bucket_start, ws->blockbase,
+            hipLaunchKernelGGL(msm_sort_kernel<false>, dim3(nchunks * nwin), dim3(256), sort_lds, st, ws->digits, n32, stride,
+                               nchunks, nb, fixed ? 1u : 0u, a.table_stride, ws->totals, ws->bucket_start, ws->blockbase,
                                (uint32_t*)nullptr);
             hipLaunchKernelGGL(msm_scan_kernel, dim3(1), dim3(1024), 0, st, ws->totals, ws->bucket_start, nbt, ws->counts);
-            hipLaunchKernelGGL(msm_sort_kernel<true>, dim3(nchunks * nwin), dim3(256), (nb < SORT_LDS_BUCKETS ? nb : SORT_LDS_BUCKETS) * 4, st, ws->digits, n32, stride,
-                               nchunks, nb, fixed ? 1u : 0u, table_stride, ws->totals, ws->bucket_start, ws->blockbase,
+            hipLaunchKernelGGL(msm_sort_kernel<true>, dim3(nchunks * nwin), dim3(256), sort_lds, st, ws->digits, n32, stride,
+                               nchunks, nb, fixed ? 1u : 0u, a.table_stride, ws->totals, ws->bucket_start, ws->blockbase,
                                ws->entries);
             hipLaunchKernelGGL(msm_pad_kernel, dim3((nbt + 255) / 256), dim3(256), 0, st, ws->totals, ws->bucket_start, nbt,
                                ws->entries);
         }
-        const size_t worst = (size_t)(fixed ? batch : 1) * n * nwin + (size_t)nbt * (PAD - 1);  // worst-case padded entry count
         const size_t threads = (worst + SEG0 - 1) / SEG0;
-        if (accum_events) hipEventRecord(accum_events[0], st);
-        if (bases_may_be_identity) {
-            hipLaunchKernelGGL(msm_accumulate_kernel, dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st, ws->entries,
-                               fixed ? table : bases, ws->counts, ws->slot_pt);
+        if (a.events) hipEventRecord(a.events[0], st);
+        if (a.bases_may_be_identity) {
+            hipLaunchKernelGGL(msm_accumulate_kernel, dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st, ws->entries, points,
+                               ws->counts, ws->slot_pt);
         } else {
-            hipLaunchKernelGGL(msm_accumulate_fast_kernel, dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st, ws->entries,
-                               fixed ? table : bases, ws->counts, ws->redo, ws->slot_pt);
-        }
-        if (accum_events) hipEventRecord(accum_events[1], st);  // the dominant kernel alone (bench.py's roofline)
-        if (!bases_may_be_identity)
-            hipLaunchKernelGGL(msm_accumulate_redo_kernel, dim3(1024), dim3(64), 0, st, ws->entries, fixed ? table : bases,
+            hipLaunchKernelGGL(msm_accumulate_fast_kernel, dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st, ws->entries, points,
                                ws->counts, ws->redo, ws->slot_pt);
+        }
+        if (a.events) hipEventRecord(a.events[1], st);  // the dominant kernel alone (bench.py's roofline)
+        if (!a.bases_may_be_identity)
+            hipLaunchKernelGGL(msm_accumulate_redo_kernel, dim3(1024), dim3(64), 0, st, ws->entries, points, ws->counts, ws->redo,
+                               ws->slot_pt);
     }
-    hipStream_t ts = st;
-    if (tail_st && tail_st != st) {
-        if ((e = hipEventRecord(head_done, st)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(tail_st, head_done, 0)) != hipSuccess) return e;
-        ts = tail_st;
-    }
+    hipStream_t ts;
+    if ((e = msm_tail_stream(a, &ts)) != hipSuccess) return e;
     if (n > 0) {
-        const size_t worst = (size_t)(fixed ? batch : 1) * n * nwin + (size_t)nbt * (PAD - 1);
         const size_t lanes1 = (worst + PAD - 1) / PAD;
         hipLaunchKernelGGL(msm_gather1_kernel, dim3((uint32_t)((lanes1 + 63) / 64)), dim3(64), 0, ts, ws->slot_pt, ws->counts,
                            ws->partial);
@@ -550,36 +534,29 @@ hipError_t msm_run(MsmWorkspace* ws, const Fr* const* scalars_list, uint32_t bat
             hipLaunchKernelGGL(msm_gather_kernel<4>, dim3((ngroups * 4 + 255) / 256), dim3(256), 0, ts, ws->bucket_start,
                                ws->partial, parts, ngroups, ws->part);
     }
-    const uint32_t bt = bitsum_threads(nb), bs = bitsum_split(nb);
-    if (bt == 512)
-        hipLaunchKernelGGL(msm_bitsum_kernel<512>, dim3(slices * c * bs), dim3(512), 0, ts, ws->part, parts, nb, c, bs, ws->bucket_start,
-                           ws->bit_sum);
-    else if (bt == 256)
-        hipLaunchKernelGGL(msm_bitsum_kernel<256>, dim3(slices * c * bs), dim3(256), 0, ts, ws->part, parts, nb, c, bs, ws->bucket_start,
-                           ws->bit_sum);
-    else if (bt == 128)
-        hipLaunchKernelGGL(msm_bitsum_kernel<128>, dim3(slices * c * bs), dim3(128), 0, ts, ws->part, parts, nb, c, bs, ws->bucket_start,
-                           ws->bit_sum);
-    else
-        hipLaunchKernelGGL(msm_bitsum_kernel<64>, dim3(slices * c * bs), dim3(64), 0, ts, ws->part, parts, nb, c, bs, ws->bucket_start,
-                           ws->bit_sum);
+    // bit_sum[(w * c + t) * split + q]: partials of G_{w,t}; one wave per workgroup (msm_plan.h bitsum_threads)
+    const uint32_t bs = bitsum_split(nb);
+    hipLaunchKernelGGL(msm_bitsum_kernel<64>, dim3(slices * c * bs), dim3(64), 0, ts, ws->part, parts, nb, c, bs, ws->bucket_start,
+                       ws->bit_sum);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    return hipMemcpyAsync(host_window_sums, ws->bit_sum, (size_t)slices * c * bs * sizeof(G1X),
-                          hipMemcpyDeviceToHost, ts);
+    // fixed-base mode: a result per column from its c bit positions; arbitrary bases: one result from all windows' positions
+    *pass = MsmPass{fixed ? MsmPass::FIXED : MsmPass::GENERIC, batch, (fixed ? 1u : nwin) * c * bs, c, n, false, a.table};
+    return hipMemcpyAsync(a.host_sums, ws->bit_sum, (size_t)slices * c * bs * sizeof(G1X), hipMemcpyDeviceToHost, ts);
 }
 
-// bit_sums[(w * c + t) * split + q]: partials of G_{w,t}, split = bitsum_split(2^(c-1));
-// result = sum_w 2^(c w) sum_t 2^t G_{w,t}  (Horner over all bit positions)
-uint32_t msm_sums_per_result(uint32_t c) { return c * bitsum_split(1u << (c - 1)); }
+// The host's finish of one result.  Standard plan: sum over the bit positions pos of 2^pos G_pos (Horner), G_pos in `split`
+// partials (bitsum_split) ...
+static G1Jac msm_horner(const G1X* bit_sums, uint32_t positions, uint32_t split) {
+    G1X acc = G1X::identity();
+    for (int q = (int)positions - 1; q >= 0; q--) {
+        if (!acc.is_identity()) acc = g1x_dbl(acc);
+        for (uint32_t k = 0; k < split; k++) g1x_add(acc, bit_sums[(size_t)q * split + k]);
+    }
+    return g1x_to_jac(acc);
+}
 
-uint32_t msm_ws_sums_per_result(const MsmWorkspace* ws) { return ws->wide ? WIDE_SUMS : msm_sums_per_result(ws->c); }
-
-// fixed-base mode: one column's result from its bit sums
-G1Jac msm_ws_finish_fixed(const MsmWorkspace* ws, const G1X* sums) {
-    if (!ws->wide) return msm_finish_host(sums, 1, ws->c);
-    // sum_{t < 9} 2^t S_t (columns of the bucket matrix, weight l + 1) + sum_u 2^(8 + u) S_{9 + u} (rows, weight 256 h)
-    uint32_t row_bits = 0;
-    while ((1u << row_bits) < (ws->nb >> 8)) row_bits++;
+// ... wide path: sum_{t < 9} 2^t S_t (columns of the bucket matrix, weight l + 1) + sum_u 2^(8 + u) S_{9 + u} (rows, weight 256 h)
+static G1Jac msm_horner_wide(const G1X* sums, uint32_t row_bits) {
     G1X acc = G1X::identity();
     for (int pos = (int)(8 + row_bits) - 1; pos >= 0; pos--) {
         if (!acc.is_identity()) acc = g1x_dbl(acc);
@@ -589,14 +566,25 @@ G1Jac msm_ws_finish_fixed(const MsmWorkspace* ws, const G1X* sums) {
     return g1x_to_jac(acc);
 }
 
-G1Jac msm_finish_host(const G1X* bit_sums, uint32_t nwin, uint32_t c) {
-    const uint32_t split = bitsum_split(1u << (c - 1));
-    G1X acc = G1X::identity();
-    for (int q = (int)(nwin * c) - 1; q >= 0; q--) {
-        if (!acc.is_identity()) acc = g1x_dbl(acc);
-        for (uint32_t k = 0; k < split; k++) g1x_add(acc, bit_sums[(size_t)q * split + k]);
+hipError_t msm_collect(MsmWorkspace* ws, const MsmPass& p, hipStream_t tail, G1X* host_sums, G1Jac* out, bool* redone) {
+    *redone = false;
+    if (p.redo_word) {
+        uint32_t listed;
+        memcpy(&listed, host_sums + (size_t)p.batch * p.sums_per_result, 4);
+        if (listed) {
+            // a degenerate basis (equal or opposite points): the unchecked accumulation reported lanes to redo with the checked loop
+            hipError_t e = msm_wide_redo(ws, p, tail, host_sums);
+            if (e == hipSuccess) e = hipStreamSynchronize(tail);
+            if (e != hipSuccess) return e;
+            *redone = true;
+        }
     }
-    return g1x_to_jac(acc);
+    const uint32_t split = bitsum_split(1u << (p.c - 1));
+    for (uint32_t q = 0; q < p.batch; q++) {
+        const G1X* sums = host_sums + (size_t)q * p.sums_per_result;
+        out[q] = p.plan == MsmPass::WIDE ? msm_horner_wide(sums, ws->row_bits) : msm_horner(sums, p.sums_per_result / split, split);
+    }
+    return hipSuccess;
 }
 
 }  // namespace zk

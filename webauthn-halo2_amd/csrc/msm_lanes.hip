@@ -112,8 +112,8 @@ int ctx_msm_begin_batch(zk_ctx* c, int lane, const Fr* const* d_scalars, uint32_
     c->stream_counts[L.tail == c->stream ? 0 : 1]++;  // zk_ctx_stream_info
     HIPCHK(c, aud_record(c, L.t_head[0], hs));
     msm_ws_set_t1_mode(ws, c->opt_msm_t1);
-    HIPCHK(c, msm_run(ws, d_scalars, batch, d_bases, n, hs, L.host_buf, &L.nwin, &L.cw, L.t_acc, table, stride, L.tail,
-                      L.head_done, !table || ident));
+    const MsmPassArgs pass = {d_scalars, batch, n, d_bases, table, stride, hs, L.tail, L.head_done, L.t_acc, !table || ident, L.host_buf};
+    HIPCHK(c, msm_run(ws, pass, &L.pass));
     if (c->audit.on) {
         // the ledger's twin of what msm_run enqueued: head + accumulation on hs (reads the columns, fills the lane's workspace),
         // the head_done hand-off, the tail on L.tail (reads the workspace, writes the lane's pinned result buffer)
@@ -130,10 +130,6 @@ int ctx_msm_begin_batch(zk_ctx* c, int lane, const Fr* const* d_scalars, uint32_
     HIPCHK(c, aud_record(c, L.tail_done, L.tail));
     HIPCHK(c, aud_record(c, L.t_head[1], hs));
     c->msm_launches++;
-    L.n = n;
-    L.batch = batch;
-    L.table = table;
-    L.fixed = table != nullptr;
     L.busy = true;
     return ZK_OK;
 }
@@ -148,35 +144,29 @@ int ctx_msm_end_batch(zk_ctx* c, int lane, G1Jac* out) {
     L.busy = false;
     HIPCHK(c, aud_esync(c, L.tail_done));
     c->audit.host_read(L.host_buf, "MSM pass: the host collects the sums");
-    if (L.fixed && L.n > 0 && msm_wide_redo_count(L.ws_run, L.host_buf, L.batch)) {
-        // a degenerate basis (equal or opposite points): the unchecked accumulation reported lanes to redo with the checked loop
-        HIPCHK(c, msm_wide_redo(L.ws_run, L.batch, L.n, L.tail, L.host_buf, L.table));
+    const MsmPass& P = L.pass;
+    bool redone;
+    HIPCHK(c, msm_collect(L.ws_run, P, L.tail, L.host_buf, out, &redone));
+    if (redone) {  // the ledger's twin of what msm_collect did over a degenerate basis
         c->audit.op(L.tail, {L.ws_run}, {L.ws_run, L.host_buf}, "MSM pass: checked redo + tail");
-        HIPCHK(c, aud_sync(c, L.tail));
-    }
-    if (L.fixed) {
-        // fixed-base mode: one independent result per column
-        const uint32_t per = msm_ws_sums_per_result(L.ws_run);
-        for (uint32_t q = 0; q < L.batch; q++) out[q] = msm_ws_finish_fixed(L.ws_run, L.host_buf + (size_t)q * per);
-    } else {
-        out[0] = msm_finish_host(L.host_buf, L.nwin, L.cw);  // generic mode: Horner over the windows
+        c->audit.host_stream(L.tail);
     }
     // timers: head (recode .. accumulate, on the context stream) and the accumulate kernel alone
     // (the head ends with the accumulate kernel: t_acc[1] — always complete once the tail is; an event recorded behind the tail's
     // own on the same stream, as round 4 did, is often not: with the tails on the main stream most passes went uncounted)
     float ms = 0.f;
     c->acc_n[ZK_T_MSM]++;
-    if (L.n > 0 && hipEventElapsedTime(&ms, L.t_head[0], L.t_acc[1]) == hipSuccess) {
+    if (P.n > 0 && hipEventElapsedTime(&ms, L.t_head[0], L.t_acc[1]) == hipSuccess) {
         c->acc_ms[ZK_T_MSM] += ms;
         c->last_plain_ms[ZK_T_MSM] = ms;
     }
-    if (L.n > 0 && hipEventElapsedTime(&ms, L.t_acc[0], L.t_acc[1]) == hipSuccess) {
+    if (P.n > 0 && hipEventElapsedTime(&ms, L.t_acc[0], L.t_acc[1]) == hipSuccess) {
         c->acc_ms[ZK_T_MSM_ACCUM] += ms;
         c->acc_n[ZK_T_MSM_ACCUM]++;
-        c->acc_n[ZK_T_MSM_COLUMNS] += L.batch;
+        c->acc_n[ZK_T_MSM_COLUMNS] += P.batch;
         c->last_plain_ms[ZK_T_MSM_ACCUM] = ms;
     }
-    if (L.n > 0 && L.fixed && msm_ws_last_pass_wide(L.ws_run) && hipEventElapsedTime(&ms, L.t_acc[2], L.t_acc[3]) == hipSuccess) {
+    if (P.n > 0 && P.plan == MsmPass::WIDE && hipEventElapsedTime(&ms, L.t_acc[2], L.t_acc[3]) == hipSuccess) {
         c->acc_ms[ZK_T_MSM_TAIL] += ms;
         c->acc_n[ZK_T_MSM_TAIL]++;
         c->last_plain_ms[ZK_T_MSM_TAIL] = ms;
@@ -193,7 +183,7 @@ void ctx_msm_drain(zk_ctx* c) {
 }
 
 int ctx_msm_end(zk_ctx* c, int lane, G1Jac* out) {
-    if (lane >= 0 && lane < zk_ctx::MSM_LANES && c->lanes[lane].busy && c->lanes[lane].batch != 1) return ZK_EINVAL;
+    if (lane >= 0 && lane < zk_ctx::MSM_LANES && c->lanes[lane].busy && c->lanes[lane].pass.batch != 1) return ZK_EINVAL;
     return ctx_msm_end_batch(c, lane, out);
 }
 

@@ -2,7 +2,7 @@
 // (part of msm.hip's translation unit, inside namespace zk).  Kernels: the head (msm_whist, msm_wscatter1, msm_wfinehist,
 // msm_wscatter2: digits recomputed from the scalars, two-level counting sort into a dense entry list), the accumulation
 // (msm_wacc_fast / msm_wacc / msm_wacc_redo: restartable lanes of 16 entries, one partial sum per lane and bucket) and the
-// reduction tail (T1 msm_wparts / msm_wbucket, T2 msm_wrowcol, T3 msm_wbits).  Host side: msm_run_wide in msm.hip.
+// reduction tail (T1 msm_wparts / msm_wbucket, T2 msm_wrowcol, T3 msm_wbits).  Host side in msm.hip: msm_run_wide, wide_tail.
 // ================================================================== wide path ==
 // Windows of 15 / 16 bits (fixed-base mode): 17 / 16 bucket additions per scalar instead of 20 at 13 bits, paid for with
 // 16384 / 32768 buckets per column.  What changes against the 13-bit plan above:

@@ -9,7 +9,7 @@ int srs_build_tables(zk_ctx* c, uint32_t k) {
     if (k < 10) return ZK_OK;
     const uint32_t n = 1u << k;
     const uint32_t cw = msm_auto_window(n, c->opt_msm_window);
-    const size_t cnt = (size_t)msm_num_windows(cw) * n;
+    const size_t cnt = (size_t)nwin_for(cw) * n;
     if (hipMalloc(&c->srs->g_table, cnt * sizeof(G1Affine)) != hipSuccess ||
         hipMalloc(&c->srs->g_lagrange_table, cnt * sizeof(G1Affine)) != hipSuccess)
         return ZK_ENOMEM;
@@ -195,6 +195,6 @@ ZK_API(zk_srs_msm_plan, (const zk_ctx* c, uint32_t* window_bits, uint32_t* windo
     if (!c || !window_bits || !windows) return ZK_EINVAL;
     if (c->srs_k < 0) return ZK_ESTATE;
     *window_bits = c->table_c;  // 0: no window-multiple tables (k < 10), zk_commit takes the generic path
-    *windows = c->table_c ? msm_num_windows(c->table_c) : 0;
+    *windows = c->table_c ? nwin_for(c->table_c) : 0;
     return ZK_OK;
 }

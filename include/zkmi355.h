@@ -735,6 +735,40 @@ int zk_instance_eval(zk_ctx* ctx, uint32_t k, size_t count, const uint64_t* cons
 int zk_es256_verify(zk_ctx* ctx, size_t count, const uint8_t* sigs /* count x 160 */, uint8_t* verdicts /* count: 1 = valid */,
                     uint8_t* reasons /* count, may be NULL */);
 
+/* ---- KZG pairing checks on the device ----------------------------------------------------------------------------------
+ * `count` checks e(a_i, s_g2) = e(b_i, g2) in one launch, one per lane, against ONE (g2, s_g2) pair: the caller's (16-word
+ * Montgomery images as zk_srs_set_g2 takes them), or with both NULL the resident SRS's.  a_i, b_i are affine Montgomery points of
+ * G1, (0, 0) the identity.  The walk through the Miller loop of the two G2 points is done once per pair on the host (the resident
+ * pair's is kept with the SRS and dropped with it) and the lanes evaluate its lines at their points; the final exponentiation
+ * uses no table.  verdicts[i] = 1 where the check holds; reasons (may be NULL) names the FIRST failing test:
+ *   ZK_PAIRING_RANGE      a coordinate of a_i or b_i not below p
+ *   ZK_PAIRING_OFF_CURVE  a_i or b_i neither on y^2 = x^3 + 3 nor the identity (0, 0)
+ *   ZK_PAIRING_MISMATCH   e(a_i, s_g2) != e(b_i, g2)
+ * A pair with the identity on the G1 side contributes 1: (O, O) holds, (O, b) and (a, O) do not.  A bad pair is a verdict, never
+ * an error.  Needs no key; with its own G2 points it needs no SRS.
+ * ZK_EINVAL: ctx, a, b or verdicts NULL, count == 0 or > ZK_PAIRING_BATCH_MAX, exactly one of g2 / s_g2 NULL, a given G2 point
+ * with a coordinate not below p, off the twist, outside the order-r subgroup, or the identity.  ZK_ESTATE: both NULL and no SRS
+ * or no G2 half resident.  Outputs are untouched on every error. */
+#define ZK_PAIRING_VALID 0
+#define ZK_PAIRING_RANGE 1
+#define ZK_PAIRING_OFF_CURVE 2
+#define ZK_PAIRING_MISMATCH 3
+#define ZK_PAIRING_BATCH_MAX 4096
+int zk_pairing_check_batch(zk_ctx* ctx, size_t count, const uint64_t* a /* count x 8 */, const uint64_t* b /* count x 8 */,
+                           const uint64_t g2[16], const uint64_t s_g2[16], uint8_t* verdicts /* count: 1 = holds */,
+                           uint8_t* reasons /* count, may be NULL */);
+/* How zk_verify_batch / zk_verify_batch_public settle a set of two or more proofs whose folded check fails.  HOST: the set is
+ * halved and each half folded and paired again (up to 2 B - 1 host pairings when every proof fails).  DEVICE: the first fold is
+ * still one host check — an all-good batch costs what it always did —, and when it fails every proof of the set goes through one
+ * launch of the device pairing, whose verdicts are final.  Sets of one (zk_verify, zk_verify_public, zk_verify_multi*) stay on the
+ * host.  AUTO is the host.  Verdicts are the same in every mode.  ZK_EINVAL outside 0..2. */
+#define ZK_VERIFY_PAIRING_AUTO 0
+#define ZK_VERIFY_PAIRING_HOST 1
+#define ZK_VERIFY_PAIRING_DEVICE 2
+int zk_verify_pairing_mode(zk_ctx* ctx, int mode);
+/* out[0]: host pairing checks, out[1]: device-checked pairs, of the zk_verify* calls of this context since zk_ctx_create */
+int zk_verify_pairing_stats(zk_ctx* ctx, uint64_t out[2]);
+
 /* ---- timing of the last call of each kind, measured with HIP events on the
  *      context stream (ms); used by bench.py for the roofline figures ---------- */
 #define ZK_T_MSM 0

@@ -38,6 +38,20 @@ struct SrsBlock {
     }
 };
 
+// The prepared lines of the resident (g2, s_g2) pair on the device (pairing.hip: a PairingTable's bytes), made by the first
+// device pairing check against the resident pair and immutable from then on.  It travels with the SRS view, so contexts that
+// share a block share it; whatever replaces the block or the pair lets go of it (srs_new_block, zk_srs_set_g2).  `key` is the
+// pair it was made from (g2_raw || s_g2_raw): a table is only ever used against the pair that made it.
+struct PairLinesDev {
+    int device = -1;
+    void* d = nullptr;
+    uint8_t key[256] = {0};
+    ~PairLinesDev() {
+        if (device >= 0) hipSetDevice(device);
+        if (d) hipFree(d);
+    }
+};
+
 // The SRS as one context sees it.  zk_ctx_create_shared hands the whole view to the child and srs_install keeps it aside as one
 // value: a member added here travels with both.  (The pointers alias the members of `srs`, the owner.)
 struct SrsView {
@@ -53,6 +67,7 @@ struct SrsView {
     // computes with it, it only travels through the SRS file (zk_srs_write / zk_srs_read)
     bool g2_valid = false;
     uint8_t g2_raw[128] = {0}, s_g2_raw[128] = {0};
+    std::shared_ptr<PairLinesDev> pair_lines;  // the device pairing's table of that pair, or empty
 };
 
 struct zk_ctx : SrsView {
@@ -72,7 +87,9 @@ struct zk_ctx : SrsView {
     std::map<uint32_t, Fr*> coset3_pre;    // k -> [2][2^k]: the twists (zeta w_4n^j)^m, j = 1, 2, of the three-coset transforms (poly.hip)
     std::map<uint32_t, Coset3Consts> coset3_consts;  // k -> the constants of the 3 x 3 solve
     uint32_t opt_verify_inst_eval = 0;     // zk_verify_instance_eval_mode: where zk_verify_batch_public / zk_verify_multi_public evaluate inst(x): 0 auto (host: not measured), 1 host, 2 device
-    uint32_t opt_quotient_domain = 0;      // ZK_OPT_QUOTIENT_DOMAIN: 0 auto (three cosets from k = 16), 1 always the whole extended domain, 2 three cosets wherever h has three pieces
+    uint32_t opt_verify_pairing = 0;       // zk_verify_pairing_mode: how a failing fold of two or more proofs is settled: 0 auto (host), 1 host (bisection), 2 device (one launch)
+    uint64_t verify_pairing_stats[2] = {0, 0};  // zk_verify_pairing_stats: host pairing checks, device-checked pairs of the zk_verify* calls
+    uint32_t opt_quotient_domain = 0;     // ZK_OPT_QUOTIENT_DOMAIN: 0 auto (three cosets from k = 16), 1 always the whole extended domain, 2 three cosets wherever h has three pieces
     uint64_t srs_gen = 0;  // bumped by every zk_srs_setup / zk_srs_load / zk_srs_read: keys remember the SRS they were made under
     // tuning options (zk_ctx_set_option); 0 = built-in choice
     uint32_t opt_msm_window = 0, opt_msm_batch = 0, opt_ntt_max_r = 0, opt_gp_batch_invert = 0;
@@ -131,6 +148,7 @@ struct zk_ctx : SrsView {
     Fr* small = nullptr;  // 2048 + 8 elements for reductions
     struct VerifyWs* vws = nullptr;  // zk_verify_batch's device buffers (verify.hip), grow-only
     struct Es256Ws* es256 = nullptr;  // zk_es256_verify's comb table of G and staging buffers (es256.hip), made on first use
+    struct PairingWs* pairing = nullptr;  // the device pairing's staging buffers and the table of a caller's own pair (pairing.hip), made on first use
     Fr* host_small = nullptr;  // pinned, 8 elements
     void* eval_batch_host = nullptr;  // pinned: zk_eval_batch's items and results (prover_phases.hip), made on first use
     // polys
@@ -288,3 +306,7 @@ int ctx_g1_to_lagrange(zk_ctx* c, const G1Affine* d_in, uint32_t k, G1Affine* d_
 void srs_set_g2_from_secret(zk_ctx* c, const Fr& s_mont);
 void verify_ws_destroy(struct VerifyWs* w);
 void es256_ws_destroy(struct Es256Ws* w);
+void pairing_ws_destroy(struct PairingWs* w);
+// reasons[i] (ZK_PAIRING_*) of e(a_i, s_g2) = e(b_i, g2) for `count` host pairs against the RESIDENT pair, one check per lane in
+// one launch (pairing.hip).  Caller holds the context lock, device bound, g2_valid
+int pairing_check_resident(zk_ctx* c, size_t count, const G1Affine* a, const G1Affine* b, uint8_t* reasons);

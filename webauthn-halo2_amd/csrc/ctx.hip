@@ -293,6 +293,7 @@ void zk_ctx_destroy(zk_ctx* c) {
     if (c->small) hipFree(c->small);
     verify_ws_destroy(c->vws);
     es256_ws_destroy(c->es256);
+    pairing_ws_destroy(c->pairing);
     for (int i = 0; i < ZK_T_COUNT; i++)
         for (int j = 0; j < 2; j++)
             if (c->ev[i][j]) hipEventDestroy(c->ev[i][j]);

@@ -1,12 +1,19 @@
-// pairing.h — BN254 G2 and the optimal-ate pairing on the host (the KZG check of zk_verify / zk_verify_batch).
+// pairing.h — BN254 G2 and the optimal-ate pairing: the KZG check of zk_verify / zk_verify_batch on the host, and the one copy
+// of the per-check arithmetic that the device form (pairing.hip: zk_pairing_check_batch, one check per lane) compiles too.
 //
 // Fq2 = Fq[u] / (u^2 + 1), Fq6 = Fq2[v] / (v^3 - xi), Fq12 = Fq6[w] / (w^2 - v), xi = 9 + u: halo2curves bn256's tower.
 // G2 is the D-type twist y^2 = x^3 + 3 / xi over Fq2, untwisted by (x, y) -> (x w^2, y w^3).  The Miller loop runs over
 // the bits of 6u + 2 (u = 4965661367192848881) in affine coordinates, followed by the two Frobenius lines of the optimal
-// ate pairing; the final exponentiation is the easy part (p^6 - 1)(p^2 + 1) and the hard part (p^4 - p^2 + 1) / r taken as
-// one multi-exponentiation of f, f^p, f^p^2, f^p^3 by the base-p digits of that exponent.  A verifier computes two Miller
-// loops per check, so this stays host code (field.hip.h's 64-bit host products): nothing here runs enough pairings to
-// pay for a device form.  The same Fq2 / G2 helpers serve the SRS file's G2 half (serde.hip).
+// ate pairing; the final exponentiation is the easy part (p^6 - 1)(p^2 + 1) and the hard part (p^4 - p^2 + 1) / r.
+// Host and device: the tower, the Frobenius map (its constants are an argument: the device reads them as data), the line
+// evaluation, the Miller loop over PREPARED lines (pairing_prepare walks T once per G2 point on the host and keeps every
+// step's slope and constant, so the evaluation inverts nothing and does not depend on G2 arithmetic), and a final
+// exponentiation without a table (final_exponentiation_chain: three powers by u and the Frobenius maps).  Host only: G2
+// arithmetic, the table of constants, multi_miller_loop and final_exponentiation — the latter takes the hard part as one
+// multi-exponentiation of f, f^p, f^p^2, f^p^3 by the base-p digits of the exponent through a 16-entry Fq12 table, which a
+// lane could only keep in scratch.  The same Fq2 / G2 helpers serve the SRS file's G2 half (serde.hip).
+// On the device the Fq2 / Fq6 / Fq12 products are calls, not copies per use (ZK_PAIR_MULFN): inlined, a check is about
+// 33 000 field-product sites and many times the instruction cache.
 #pragma once
 #include <string.h>
 
@@ -16,38 +23,66 @@
 #include "field.hip.h"
 #include "hostutil.h"
 
+#ifndef ZK_PAIRING_VALID  // (include/zkmi355.h defines the same four: this header also stands alone)
+#define ZK_PAIRING_VALID 0
+#define ZK_PAIRING_RANGE 1
+#define ZK_PAIRING_OFF_CURVE 2
+#define ZK_PAIRING_MISMATCH 3
+#endif
+
+#define ZK_PAIR_FN __host__ __device__ inline
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ZK_PAIR_MULFN __host__ __device__ __noinline__ inline
+#else
+#define ZK_PAIR_MULFN __host__ __device__ inline
+#endif
+
 namespace zk {
 
-inline Fq fq_small(uint32_t x) {
+ZK_PAIR_FN Fq fq_small(uint32_t x) {
     Fq t = Fq::zero();
     t.v[0] = x;
     return fe_to_mont(t);
+}
+ZK_PAIR_FN bool fq_is_canonical(const Fq& a) {  // the image is below p
+    for (int i = 7; i >= 0; i--)
+        if (a.v[i] != FqParams::P[i]) return a.v[i] < FqParams::P[i];
+    return false;
+}
+// the inverse; one value whichever way it is found (the host's binary Euclid, the device's Fermat power)
+ZK_PAIR_FN Fq fq_inv_any(const Fq& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fe_inv(a);
+#else
+    return fe_inv_fast(a);
+#endif
 }
 
 // ---- Fq2 and the twist y^2 = x^3 + 3 / (9 + u) ---------------------------------------------------------------------
 struct Fq2 {
     Fq c0, c1;
 };
-inline Fq2 f2_add(const Fq2& a, const Fq2& b) { return {fe_add(a.c0, b.c0), fe_add(a.c1, b.c1)}; }
-inline Fq2 f2_sub(const Fq2& a, const Fq2& b) { return {fe_sub(a.c0, b.c0), fe_sub(a.c1, b.c1)}; }
-inline Fq2 f2_neg(const Fq2& a) { return {fe_neg(a.c0), fe_neg(a.c1)}; }
-inline Fq2 f2_mul(const Fq2& a, const Fq2& b) {
-    return {fe_sub(fe_mul(a.c0, b.c0), fe_mul(a.c1, b.c1)), fe_add(fe_mul(a.c0, b.c1), fe_mul(a.c1, b.c0))};
+ZK_PAIR_FN Fq2 f2_add(const Fq2& a, const Fq2& b) { return {fe_add(a.c0, b.c0), fe_add(a.c1, b.c1)}; }
+ZK_PAIR_FN Fq2 f2_sub(const Fq2& a, const Fq2& b) { return {fe_sub(a.c0, b.c0), fe_sub(a.c1, b.c1)}; }
+ZK_PAIR_FN Fq2 f2_neg(const Fq2& a) { return {fe_neg(a.c0), fe_neg(a.c1)}; }
+ZK_PAIR_MULFN Fq2 f2_mul(const Fq2& a, const Fq2& b) {  // Karatsuba over u^2 = -1
+    const Fq t0 = fe_mul(a.c0, b.c0), t1 = fe_mul(a.c1, b.c1);
+    return {fe_sub(t0, t1), fe_sub(fe_sub(fe_mul(fe_add(a.c0, a.c1), fe_add(b.c0, b.c1)), t0), t1)};
 }
-inline Fq2 f2_mul_fq(const Fq2& a, const Fq& s) { return {fe_mul(a.c0, s), fe_mul(a.c1, s)}; }
-inline Fq2 f2_conj(const Fq2& a) { return {a.c0, fe_neg(a.c1)}; }
-inline Fq2 f2_inv(const Fq2& a) {
-    const Fq d = fe_inv_fast(fe_add(fe_sqr(a.c0), fe_sqr(a.c1)));
+ZK_PAIR_FN Fq2 f2_mul_fq(const Fq2& a, const Fq& s) { return {fe_mul(a.c0, s), fe_mul(a.c1, s)}; }
+ZK_PAIR_FN Fq2 f2_conj(const Fq2& a) { return {a.c0, fe_neg(a.c1)}; }
+ZK_PAIR_FN Fq2 f2_inv(const Fq2& a) {
+    const Fq d = fq_inv_any(fe_add(fe_sqr(a.c0), fe_sqr(a.c1)));
     return {fe_mul(a.c0, d), fe_neg(fe_mul(a.c1, d))};
 }
-inline bool f2_is_zero(const Fq2& a) { return a.c0.is_zero() && a.c1.is_zero(); }
-inline bool f2_eq(const Fq2& a, const Fq2& b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-inline Fq2 f2_small(uint32_t a, uint32_t b) { return {fq_small(a), fq_small(b)}; }
-inline Fq2 f2_one() { return {Fq::one(), Fq::zero()}; }
-inline Fq2 f2_zero() { return {Fq::zero(), Fq::zero()}; }
-inline Fq2 f2_mul_xi(const Fq2& a) {  // a (9 + u)
-    const Fq n9 = fq_small(9);
-    return {fe_sub(fe_mul(a.c0, n9), a.c1), fe_add(a.c0, fe_mul(a.c1, n9))};
+ZK_PAIR_FN bool f2_is_zero(const Fq2& a) { return a.c0.is_zero() && a.c1.is_zero(); }
+ZK_PAIR_FN bool f2_eq(const Fq2& a, const Fq2& b) { return a.c0 == b.c0 && a.c1 == b.c1; }
+ZK_PAIR_FN Fq2 f2_small(uint32_t a, uint32_t b) { return {fq_small(a), fq_small(b)}; }
+ZK_PAIR_FN Fq2 f2_one() { return {Fq::one(), Fq::zero()}; }
+ZK_PAIR_FN Fq2 f2_zero() { return {Fq::zero(), Fq::zero()}; }
+ZK_PAIR_FN Fq2 f2_mul_xi(const Fq2& a) {  // a (9 + u) = (9 a0 - a1) + (a0 + 9 a1) u, 9 x = 8 x + x
+    const Fq n0 = fe_add(fe_dbl(fe_dbl(fe_dbl(a.c0))), a.c0), n1 = fe_add(fe_dbl(fe_dbl(fe_dbl(a.c1))), a.c1);
+    return {fe_sub(n0, a.c1), fe_add(a.c0, n1)};
 }
 inline Fq2 f2_twist_b() { return f2_mul(f2_small(3, 0), f2_inv(f2_small(9, 1))); }
 // a^e, e as 8 little-endian 32-bit words
@@ -102,6 +137,17 @@ inline G2A g2_generator() {  // the BN254 G2 generator (reference proving-server
     return G2A{{fq_from_hex_words(X0), fq_from_hex_words(X1)}, {fq_from_hex_words(Y0), fq_from_hex_words(Y1)}, false};
 }
 inline bool g2_on_curve(const G2A& p) { return f2_eq(f2_mul(p.y, p.y), f2_add(f2_mul(f2_mul(p.x, p.x), p.x), f2_twist_b())); }
+// a point of G2 other than the identity: coordinates reduced, on the twist, and of order r (the twist has a cofactor)
+inline bool g2_is_proper(const G2A& q) {
+    if (q.inf || !fq_is_canonical(q.x.c0) || !fq_is_canonical(q.x.c1) || !fq_is_canonical(q.y.c0) || !fq_is_canonical(q.y.c1)) return false;
+    if (!g2_on_curve(q)) return false;
+    G2A acc{q.x, q.y, true};
+    for (int i = 255; i >= 0; i--) {  // [r] q
+        acc = g2_add(acc, acc);
+        if ((FrParams::P[i >> 5] >> (i & 31)) & 1) acc = g2_add(acc, q);
+    }
+    return acc.inf;
+}
 
 // raw image: x.c0 || x.c1 || y.c0 || y.c1 Montgomery; identity = all zero
 inline void g2_to_raw(const G2A& p, uint8_t raw[128]) {
@@ -128,20 +174,28 @@ inline G2A g2_from_raw(const uint8_t raw[128]) {
 struct Fq6 {
     Fq2 c0, c1, c2;
 };
-inline Fq6 f6_zero() { return {f2_zero(), f2_zero(), f2_zero()}; }
-inline Fq6 f6_one() { return {f2_one(), f2_zero(), f2_zero()}; }
-inline Fq6 f6_add(const Fq6& a, const Fq6& b) { return {f2_add(a.c0, b.c0), f2_add(a.c1, b.c1), f2_add(a.c2, b.c2)}; }
-inline Fq6 f6_sub(const Fq6& a, const Fq6& b) { return {f2_sub(a.c0, b.c0), f2_sub(a.c1, b.c1), f2_sub(a.c2, b.c2)}; }
-inline Fq6 f6_neg(const Fq6& a) { return {f2_neg(a.c0), f2_neg(a.c1), f2_neg(a.c2)}; }
-inline Fq6 f6_mul(const Fq6& a, const Fq6& b) {  // Karatsuba over v^3 = xi
+ZK_PAIR_FN Fq6 f6_zero() { return {f2_zero(), f2_zero(), f2_zero()}; }
+ZK_PAIR_FN Fq6 f6_one() { return {f2_one(), f2_zero(), f2_zero()}; }
+ZK_PAIR_FN Fq6 f6_add(const Fq6& a, const Fq6& b) { return {f2_add(a.c0, b.c0), f2_add(a.c1, b.c1), f2_add(a.c2, b.c2)}; }
+ZK_PAIR_FN Fq6 f6_sub(const Fq6& a, const Fq6& b) { return {f2_sub(a.c0, b.c0), f2_sub(a.c1, b.c1), f2_sub(a.c2, b.c2)}; }
+ZK_PAIR_FN Fq6 f6_neg(const Fq6& a) { return {f2_neg(a.c0), f2_neg(a.c1), f2_neg(a.c2)}; }
+ZK_PAIR_MULFN Fq6 f6_mul(const Fq6& a, const Fq6& b) {  // Karatsuba over v^3 = xi
     const Fq2 t0 = f2_mul(a.c0, b.c0), t1 = f2_mul(a.c1, b.c1), t2 = f2_mul(a.c2, b.c2);
     const Fq2 c0 = f2_add(t0, f2_mul_xi(f2_sub(f2_sub(f2_mul(f2_add(a.c1, a.c2), f2_add(b.c1, b.c2)), t1), t2)));
     const Fq2 c1 = f2_add(f2_sub(f2_sub(f2_mul(f2_add(a.c0, a.c1), f2_add(b.c0, b.c1)), t0), t1), f2_mul_xi(t2));
     const Fq2 c2 = f2_add(f2_sub(f2_sub(f2_mul(f2_add(a.c0, a.c2), f2_add(b.c0, b.c2)), t0), t2), t1);
     return {c0, c1, c2};
 }
-inline Fq6 f6_mul_v(const Fq6& a) { return {f2_mul_xi(a.c2), a.c0, a.c1}; }
-inline Fq6 f6_inv(const Fq6& a) {
+// a (b0 + b1 v): the shape of a line's w-half
+ZK_PAIR_MULFN Fq6 f6_mul_01(const Fq6& a, const Fq2& b0, const Fq2& b1) {
+    const Fq2 t0 = f2_mul(a.c0, b0), t1 = f2_mul(a.c1, b1);
+    const Fq2 c0 = f2_add(t0, f2_mul_xi(f2_mul(a.c2, b1)));
+    const Fq2 c1 = f2_sub(f2_sub(f2_mul(f2_add(a.c0, a.c1), f2_add(b0, b1)), t0), t1);
+    const Fq2 c2 = f2_add(t1, f2_mul(a.c2, b0));
+    return {c0, c1, c2};
+}
+ZK_PAIR_FN Fq6 f6_mul_v(const Fq6& a) { return {f2_mul_xi(a.c2), a.c0, a.c1}; }
+ZK_PAIR_FN Fq6 f6_inv(const Fq6& a) {
     const Fq2 A = f2_sub(f2_mul(a.c0, a.c0), f2_mul_xi(f2_mul(a.c1, a.c2)));
     const Fq2 B = f2_sub(f2_mul_xi(f2_mul(a.c2, a.c2)), f2_mul(a.c0, a.c1));
     const Fq2 C = f2_sub(f2_mul(a.c1, a.c1), f2_mul(a.c0, a.c2));
@@ -153,18 +207,23 @@ inline Fq6 f6_inv(const Fq6& a) {
 struct Fq12 {
     Fq6 c0, c1;  // c0 + c1 w
 };
-inline Fq12 f12_one() { return {f6_one(), f6_zero()}; }
-inline bool f12_is_one(const Fq12& a) {
-    const Fq12 o = f12_one();
-    return memcmp(&a, &o, sizeof(Fq12)) == 0;
+ZK_PAIR_FN Fq12 f12_one() { return {f6_one(), f6_zero()}; }
+ZK_PAIR_FN bool f12_is_one(const Fq12& a) {
+    const Fq2 z = f2_zero();
+    return f2_eq(a.c0.c0, f2_one()) && f2_eq(a.c0.c1, z) && f2_eq(a.c0.c2, z) && f2_eq(a.c1.c0, z) && f2_eq(a.c1.c1, z) && f2_eq(a.c1.c2, z);
 }
-inline Fq12 f12_mul(const Fq12& a, const Fq12& b) {
+ZK_PAIR_MULFN Fq12 f12_mul(const Fq12& a, const Fq12& b) {
     const Fq6 t0 = f6_mul(a.c0, b.c0), t1 = f6_mul(a.c1, b.c1);
     return {f6_add(t0, f6_mul_v(t1)), f6_sub(f6_sub(f6_mul(f6_add(a.c0, a.c1), f6_add(b.c0, b.c1)), t0), t1)};
 }
-inline Fq12 f12_sqr(const Fq12& a) { return f12_mul(a, a); }
-inline Fq12 f12_conj(const Fq12& a) { return {a.c0, f6_neg(a.c1)}; }
-inline Fq12 f12_inv(const Fq12& a) {  // (c0 - c1 w) / (c0^2 - v c1^2)
+// (c0 + c1 w)^2 = (c0 + c1)(c0 + v c1) - c0 c1 - v c0 c1 + 2 c0 c1 w
+ZK_PAIR_MULFN Fq12 f12_sqr(const Fq12& a) {
+    const Fq6 m = f6_mul(a.c0, a.c1);
+    const Fq6 s = f6_mul(f6_add(a.c0, a.c1), f6_add(a.c0, f6_mul_v(a.c1)));
+    return {f6_sub(f6_sub(s, m), f6_mul_v(m)), f6_add(m, m)};
+}
+ZK_PAIR_FN Fq12 f12_conj(const Fq12& a) { return {a.c0, f6_neg(a.c1)}; }
+ZK_PAIR_FN Fq12 f12_inv(const Fq12& a) {  // (c0 - c1 w) / (c0^2 - v c1^2)
     const Fq6 d = f6_inv(f6_sub(f6_mul(a.c0, a.c0), f6_mul_v(f6_mul(a.c1, a.c1))));
     return {f6_mul(a.c0, d), f6_neg(f6_mul(a.c1, d))};
 }
@@ -195,8 +254,8 @@ struct PairingConsts {
     }
 };
 
-inline Fq12 f12_frobenius(const Fq12& a) {
-    const Fq2* g = PairingConsts::get().gamma;
+// a^p with the six gamma[i] given (the device has them in memory)
+ZK_PAIR_MULFN Fq12 f12_frobenius_with(const Fq12& a, const Fq2* g) {
     // w-power of each coefficient: c0.c0 w^0, c1.c0 w^1, c0.c1 w^2, c1.c1 w^3, c0.c2 w^4, c1.c2 w^5
     Fq12 r;
     r.c0.c0 = f2_conj(a.c0.c0);
@@ -207,42 +266,64 @@ inline Fq12 f12_frobenius(const Fq12& a) {
     r.c1.c2 = f2_mul(f2_conj(a.c1.c2), g[5]);
     return r;
 }
+inline Fq12 f12_frobenius(const Fq12& a) { return f12_frobenius_with(a, PairingConsts::get().gamma); }
 
 // ---- Miller loop ---------------------------------------------------------------------------------------------------
-// the line through T (twist, affine) with slope lam, untwisted and evaluated at P: yP - lam xP w + (lam xT - yT) w^3
-inline Fq12 pairing_line(const Fq2& lam, const Fq2& xT, const Fq2& yT, const G1Affine& P) {
+constexpr uint64_t SIX_U_PLUS_2_LO = 0x9d797039be763ba8ULL;  // 6u + 2 is 65 bits: 2^64 + this (the top bit: T starts at Q)
+constexpr uint64_t BN_U = 4965661367192848881ULL;            // 63 bits
+// the steps of T through one Miller loop: a doubling per low bit of 6u + 2, an addition per set one, the two Frobenius lines
+constexpr int PAIRING_STEPS = 64 + __builtin_popcountll(SIX_U_PLUS_2_LO) + 2;
+
+// one step's line through T with slope lam: all of it that does not depend on the G1 point
+struct PairingLine {
+    Fq2 lam, c;  // c = lam xT - yT
+};
+// that line untwisted and evaluated at P: yP - lam xP w + c w^3
+ZK_PAIR_FN Fq12 pairing_line_at(const PairingLine& s, const G1Affine& P) {
     Fq12 l;
     l.c0 = f6_zero();
     l.c1 = f6_zero();
     l.c0.c0 = Fq2{P.y, Fq::zero()};
-    l.c1.c0 = f2_neg(f2_mul_fq(lam, P.x));
-    l.c1.c1 = f2_sub(f2_mul(lam, xT), yT);
+    l.c1.c0 = f2_neg(f2_mul_fq(s.lam, P.x));
+    l.c1.c1 = s.c;
     return l;
 }
-// T <- T + Q (Q != -T) or 2T (Q == T), returning the line's factor at P
-inline Fq12 pairing_step(G2A& T, const G2A& Q, const G1Affine& P) {
+// f times that line, with the line's zero coefficients left out of the products
+ZK_PAIR_MULFN Fq12 f12_mul_line(const Fq12& f, const PairingLine& s, const G1Affine& P) {
+    const Fq2 b = f2_neg(f2_mul_fq(s.lam, P.x));
+    const Fq6 t0 = {f2_mul_fq(f.c0.c0, P.y), f2_mul_fq(f.c0.c1, P.y), f2_mul_fq(f.c0.c2, P.y)};
+    const Fq6 t1 = f6_mul_01(f.c1, b, s.c);
+    const Fq6 m = f6_mul_01(f6_add(f.c0, f.c1), Fq2{fe_add(P.y, b.c0), b.c1}, s.c);
+    return {f6_add(t0, f6_mul_v(t1)), f6_sub(f6_sub(m, t0), t1)};
+}
+// the line through T (twist, affine) with slope lam, untwisted and evaluated at P: yP - lam xP w + (lam xT - yT) w^3
+inline Fq12 pairing_line(const Fq2& lam, const Fq2& xT, const Fq2& yT, const G1Affine& P) {
+    return pairing_line_at(PairingLine{lam, f2_sub(f2_mul(lam, xT), yT)}, P);
+}
+// T <- T + Q (Q != -T) or 2T (Q == T), returning the step's line
+inline PairingLine pairing_step_line(G2A& T, const G2A& Q) {
     Fq2 lam;
     if (f2_eq(T.x, Q.x)) lam = f2_mul(f2_mul(f2_small(3, 0), f2_mul(T.x, T.x)), f2_inv(f2_add(T.y, T.y)));
     else lam = f2_mul(f2_sub(Q.y, T.y), f2_inv(f2_sub(Q.x, T.x)));
-    const Fq12 l = pairing_line(lam, T.x, T.y, P);
+    const PairingLine s{lam, f2_sub(f2_mul(lam, T.x), T.y)};
     G2A r;
     r.inf = false;
     r.x = f2_sub(f2_sub(f2_mul(lam, lam), T.x), Q.x);
     r.y = f2_sub(f2_mul(lam, f2_sub(T.x, r.x)), T.y);
     T = r;
-    return l;
+    return s;
 }
+// the same, returning the line's factor at P
+inline Fq12 pairing_step(G2A& T, const G2A& Q, const G1Affine& P) { return pairing_line_at(pairing_step_line(T, Q), P); }
 
 // prod_i ML(P_i, Q_i); pairs with an identity on either side contribute 1
 inline Fq12 multi_miller_loop(const G1Affine* P, const G2A* Q, int n) {
-    static const uint64_t SIX_U_PLUS_2_HI = 1, SIX_U_PLUS_2_LO = 0x9d797039be763ba8ULL;  // 6u + 2, 65 bits
     std::vector<int> idx;
     for (int i = 0; i < n; i++)
         if (!affine_is_identity(P[i]) && !Q[i].inf) idx.push_back(i);
     std::vector<G2A> T;
     for (int i : idx) T.push_back(Q[i]);
     Fq12 f = f12_one();
-    (void)SIX_U_PLUS_2_HI;  // the top bit: T starts at Q
     for (int b = 63; b >= 0; b--) {
         f = f12_sqr(f);
         for (size_t j = 0; j < idx.size(); j++) f = f12_mul(f, pairing_step(T[j], T[j], P[idx[j]]));
@@ -258,6 +339,93 @@ inline Fq12 multi_miller_loop(const G1Affine* P, const G2A* Q, int n) {
         f = f12_mul(f, pairing_step(T[j], nq2, P[idx[j]]));
     }
     return f;
+}
+
+// ---- prepared lines: the Miller loop with its G2 side done once -------------------------------------------------------
+// the PAIRING_STEPS lines of q's walk (q not the identity), in the order multi_miller_loop takes them
+inline void pairing_prepare(const G2A& q, PairingLine* out) {
+    const PairingConsts& k = PairingConsts::get();
+    G2A T = q;
+    int n = 0;
+    for (int b = 63; b >= 0; b--) {
+        out[n++] = pairing_step_line(T, T);
+        if ((SIX_U_PLUS_2_LO >> b) & 1) out[n++] = pairing_step_line(T, q);
+    }
+    const G2A q1{f2_mul(f2_conj(q.x), k.gamma[2]), f2_mul(f2_conj(q.y), k.gamma[3]), false};
+    const G2A nq2{f2_mul(q.x, k.gamma2_x), f2_neg(f2_mul(q.y, k.gamma2_y)), false};
+    out[n++] = pairing_step_line(T, q1);
+    out[n++] = pairing_step_line(T, nq2);
+}
+
+// everything a check against one (g2, s_g2) pair reads: the Frobenius constants and both walks.  Plain data: the device form
+// is this struct's bytes
+struct PairingTable {
+    Fq2 gamma[6];
+    uint32_t inf[8];  // [0]: s_g2 is the identity, [1]: g2 is (pairs with them contribute 1); the rest pads to 16 bytes
+    PairingLine line[2][PAIRING_STEPS];  // [0]: s_g2's walk, [1]: g2's
+};
+inline void pairing_table_make(const G2A& g2, const G2A& s_g2, PairingTable* t) {
+    memset((void*)t, 0, sizeof(*t));
+    for (int i = 0; i < 6; i++) t->gamma[i] = PairingConsts::get().gamma[i];
+    t->inf[0] = s_g2.inf;
+    t->inf[1] = g2.inf;
+    if (!s_g2.inf) pairing_prepare(s_g2, t->line[0]);
+    if (!g2.inf) pairing_prepare(g2, t->line[1]);
+}
+
+// ML(P0, Q0) ML(P1, Q1) over the two prepared walks; an identity on either side of a pair leaves the pair out.  Fixed trip
+// counts: the bits are those of the constant 6u + 2
+ZK_PAIR_FN Fq12 miller_loop_lines(const G1Affine& P0, const G1Affine& P1, const PairingTable& t) {
+    const bool use0 = !affine_is_identity(P0) && !t.inf[0], use1 = !affine_is_identity(P1) && !t.inf[1];
+    Fq12 f = f12_one();
+    int n = 0;
+#pragma unroll 1
+    for (int b = 63; b >= -2; b--) {
+        if (b >= 0) f = f12_sqr(f);
+        // a doubling step, then an addition step where the bit is set; b = -1, -2: the Frobenius lines
+        const int steps = (b >= 0 && ((SIX_U_PLUS_2_LO >> b) & 1)) ? 2 : 1;
+#pragma unroll 1
+        for (int s = 0; s < steps; s++, n++) {
+            if (use0) f = f12_mul_line(f, t.line[0][n], P0);
+            if (use1) f = f12_mul_line(f, t.line[1][n], P1);
+        }
+    }
+    return f;
+}
+
+// f^u, u = BN_U, by squarings and products (f anywhere in Fq12)
+ZK_PAIR_FN Fq12 f12_pow_u(const Fq12& f) {
+    Fq12 acc = f;
+#pragma unroll 1
+    for (int i = 61; i >= 0; i--) {
+        acc = f12_sqr(acc);
+        if ((BN_U >> i) & 1) acc = f12_mul(acc, f);
+    }
+    return acc;
+}
+
+// f^((p^12 - 1) / r) without a table: the easy part as below, then the hard part (p^4 - p^2 + 1) / r itself by the chain of
+// Devegili, Scott and Dahab: with a = t^u, b = a^u, c = b^u, the product y0 y1^2 y2^6 y3^12 y4^18 y5^30 y6^36 of
+// y0 = t^p t^p^2 t^p^3, y1 = 1/t, y2 = b^p^2, y3 = 1/a^p, y4 = 1/(a b^p), y5 = 1/b, y6 = 1/(c c^p).  After the easy part t lies
+// in the cyclotomic subgroup, where 1/x is the conjugate.  (tests/test_pairing_lines.py adds the exponents up as integers.)
+ZK_PAIR_FN Fq12 final_exponentiation_chain(const Fq12& f, const Fq2* gamma) {
+    Fq12 t = f12_mul(f12_conj(f), f12_inv(f));                                      // ^(p^6 - 1)
+    t = f12_mul(f12_frobenius_with(f12_frobenius_with(t, gamma), gamma), t);        // ^(p^2 + 1)
+    const Fq12 fp = f12_frobenius_with(t, gamma), fp2 = f12_frobenius_with(fp, gamma);
+    const Fq12 y0 = f12_mul(f12_mul(fp, fp2), f12_frobenius_with(fp2, gamma));
+    const Fq12 fu = f12_pow_u(t), fu2 = f12_pow_u(fu), fu3 = f12_pow_u(fu2);
+    const Fq12 fu2p = f12_frobenius_with(fu2, gamma);
+    const Fq12 y2 = f12_frobenius_with(fu2p, gamma);
+    const Fq12 y3 = f12_conj(f12_frobenius_with(fu, gamma));
+    const Fq12 y4 = f12_conj(f12_mul(fu, fu2p));
+    const Fq12 y5 = f12_conj(fu2);
+    Fq12 y6 = f12_conj(f12_mul(fu3, f12_frobenius_with(fu3, gamma)));
+    y6 = f12_mul(f12_mul(f12_sqr(y6), y4), y5);
+    Fq12 t1 = f12_mul(f12_mul(y3, y5), y6);
+    y6 = f12_mul(y6, y2);
+    t1 = f12_sqr(f12_mul(f12_sqr(t1), y6));
+    const Fq12 t0 = f12_sqr(f12_mul(t1, f12_conj(t)));
+    return f12_mul(t0, f12_mul(t1, y0));
 }
 
 // f^((p^12 - 1) / r)
@@ -301,6 +469,19 @@ inline bool pairing_check(const G1Affine& a, const G1Affine& b, const G2A& g2, c
     if (!affine_is_identity(b)) P[1].y = fe_neg(b.y);
     const G2A Q[2] = {s_g2, g2};
     return f12_is_one(final_exponentiation(multi_miller_loop(P, Q, 2)));
+}
+
+// the same check of one (a, b) against a prepared pair, as a lane of pairing_check_kernel runs it: the ZK_PAIRING_* reason.
+// a and b are validated first (both coordinates below p, then on y^2 = x^3 + 3 or the identity (0, 0))
+ZK_PAIR_FN uint8_t pairing_check_lines(const G1Affine& a, const G1Affine& b, const PairingTable& t) {
+    if (!fq_is_canonical(a.x) || !fq_is_canonical(a.y) || !fq_is_canonical(b.x) || !fq_is_canonical(b.y)) return ZK_PAIRING_RANGE;
+    const Fq three = fq_small(3);
+    if (!affine_is_identity(a) && fe_sqr(a.y) != fe_add(fe_mul(fe_sqr(a.x), a.x), three)) return ZK_PAIRING_OFF_CURVE;
+    if (!affine_is_identity(b) && fe_sqr(b.y) != fe_add(fe_mul(fe_sqr(b.x), b.x), three)) return ZK_PAIRING_OFF_CURVE;
+    G1Affine nb = b;
+    nb.y = fe_neg(b.y);  // (the identity stays (0, 0))
+    const Fq12 f = final_exponentiation_chain(miller_loop_lines(a, nb, t), t.gamma);
+    return f12_is_one(f) ? ZK_PAIRING_VALID : ZK_PAIRING_MISMATCH;
 }
 
 }  // namespace zk

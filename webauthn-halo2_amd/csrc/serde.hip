@@ -168,6 +168,7 @@ ZK_API(zk_srs_set_g2, (zk_ctx* c, const uint64_t g2[16], const uint64_t s_g2[16]
     memcpy(c->g2_raw, a, 128);
     memcpy(c->s_g2_raw, b, 128);
     c->g2_valid = true;
+    c->pair_lines.reset();  // the device pairing's table of the previous pair
     return ZK_OK;
 }
 

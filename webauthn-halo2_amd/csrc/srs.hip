@@ -32,6 +32,7 @@ int srs_build_tables(zk_ctx* c, uint32_t k) {
 // a fresh, empty block for this context (the previous one is released: freed unless another context still shares it)
 static void srs_new_block(zk_ctx* c) {
     c->g2_valid = false;
+    c->pair_lines.reset();  // the device pairing's table of the old pair (srs_install puts it back with the old view on failure)
     c->srs_gen++;  // proving keys made under the previous SRS are refused from now on (ZK_ESTATE)
     c->srs = std::make_shared<SrsBlock>();
     c->srs->device = c->device;

@@ -19,11 +19,6 @@ inline void secure_zero(void* p, size_t n) {
     while (n--) *v++ = 0;
 }
 
-inline bool fq_is_canonical(const Fq& a) {  // the image is below p
-    for (int i = 7; i >= 0; i--)
-        if (a.v[i] != FqParams::P[i]) return a.v[i] < FqParams::P[i];
-    return false;
-}
 inline G1Affine g1_from_words(const uint64_t w[8]) {
     G1Affine p;
     memcpy(p.x.v, w, 32);
@@ -39,17 +34,7 @@ inline bool g1_is_proper(const G1Affine& p) {
     if (!fq_is_canonical(p.x) || !fq_is_canonical(p.y) || affine_is_identity(p)) return false;
     return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
 }
-// a point of G2 other than the identity: coordinates reduced, on the twist, and of order r (the twist has a cofactor)
-inline bool g2_is_proper(const G2A& q) {
-    if (q.inf || !fq_is_canonical(q.x.c0) || !fq_is_canonical(q.x.c1) || !fq_is_canonical(q.y.c0) || !fq_is_canonical(q.y.c1)) return false;
-    if (!g2_on_curve(q)) return false;
-    G2A acc{q.x, q.y, true};
-    for (int i = 255; i >= 0; i--) {  // [r] q
-        acc = g2_add(acc, acc);
-        if ((FrParams::P[i >> 5] >> (i & 31)) & 1) acc = g2_add(acc, q);
-    }
-    return acc.inf;
-}
+// (g2_is_proper, the same for G2 with the subgroup test, is pairing.h's: zk_pairing_check_batch applies it too)
 
 inline G1Affine g1_generator_host() {
     G1Affine g;

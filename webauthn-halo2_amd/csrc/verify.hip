@@ -12,7 +12,9 @@
 //      doubling chain over the scalars' bits, then a tree sum through LDS);
 //   4. fold: A = sum rho_j A_j, B = sum rho_j B_j with 128-bit rho_j drawn from a hash of the key's transcript_repr and
 //      every proof's bytes (the same kernel over the accumulators), ONE host pairing (pairing.h); if it fails, the set is
-//      halved and each half folded and paired again, down to single proofs, so every verdict is the proof's own.
+//      halved and each half folded and paired again, down to single proofs, so every verdict is the proof's own.  Under
+//      zk_verify_pairing_mode 2 a failing fold of two or more proofs is settled by ONE launch of the device pairing instead
+//      (pairing.hip: every (A_j, B_j) of the set, one check per lane); auto is the host.
 // zk_verify is the batch of one: the same path, without a fold.
 // Public inputs: every proof (zk_verify_batch_public) or circuit (zk_verify_multi_public) has its instance list; step 2 absorbs them
 // and needs inst(x) per list — on the host inside verifier.h, or (zk_verify_instance_eval_mode 2) every transcript runs to x, ONE
@@ -490,10 +492,12 @@ int fold(Job& J, const std::vector<uint32_t>& S, G1Affine* A, G1Affine* B) {
     return ZK_OK;
 }
 
-// exact verdicts for the proofs S (positions into J.live): one fold + pairing, halves on failure
+// exact verdicts for the proofs S (positions into J.live): one fold + pairing; on failure halves (host), or under
+// ZK_VERIFY_PAIRING_DEVICE every proof of S in one launch of the device pairing (pairing.hip), whose verdicts are final
 int settle(Job& J, const std::vector<uint32_t>& S, uint8_t* verdicts) {
     if (S.empty()) return ZK_OK;
     bool ok;
+    J.c->verify_pairing_stats[0]++;
     if (S.size() == 1) {
         ok = pairing_check(J.acc[2 * S[0]], J.acc[2 * S[0] + 1], J.g2, J.s_g2);
     } else {
@@ -506,6 +510,18 @@ int settle(Job& J, const std::vector<uint32_t>& S, uint8_t* verdicts) {
         return ZK_OK;
     }
     if (S.size() == 1) return ZK_OK;
+    if (J.c->opt_verify_pairing == ZK_VERIFY_PAIRING_DEVICE) {
+        std::vector<G1Affine> a(S.size()), b(S.size());
+        for (size_t t = 0; t < S.size(); t++) {
+            a[t] = J.acc[2 * S[t]];
+            b[t] = J.acc[2 * S[t] + 1];
+        }
+        std::vector<uint8_t> reasons(S.size());
+        if (int rc = pairing_check_resident(J.c, S.size(), a.data(), b.data(), reasons.data())) return rc;
+        J.c->verify_pairing_stats[1] += S.size();
+        for (size_t t = 0; t < S.size(); t++) verdicts[J.live[S[t]]] = reasons[t] == ZK_PAIRING_VALID ? 1 : 0;
+        return ZK_OK;
+    }
     const size_t h = S.size() / 2;
     if (int rc = settle(J, std::vector<uint32_t>(S.begin(), S.begin() + h), verdicts)) return rc;
     return settle(J, std::vector<uint32_t>(S.begin() + h, S.end()), verdicts);
@@ -812,6 +828,23 @@ ZK_API(zk_verify_instance_eval_mode, (zk_ctx* c, int mode), (c, mode)) {
     if (!c || mode < 0 || mode > 2) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     c->opt_verify_inst_eval = (uint32_t)mode;
+    return ZK_OK;
+}
+
+// how settle() finds the verdicts of a set of two or more proofs whose fold fails; auto is the host (the device route has not
+// been measured against it)
+ZK_API(zk_verify_pairing_mode, (zk_ctx* c, int mode), (c, mode)) {
+    if (!c || mode < ZK_VERIFY_PAIRING_AUTO || mode > ZK_VERIFY_PAIRING_DEVICE) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->opt_verify_pairing = (uint32_t)mode;
+    return ZK_OK;
+}
+
+ZK_API(zk_verify_pairing_stats, (zk_ctx* c, uint64_t out[2]), (c, out)) {
+    if (!c || !out) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    out[0] = c->verify_pairing_stats[0];
+    out[1] = c->verify_pairing_stats[1];
     return ZK_OK;
 }
 

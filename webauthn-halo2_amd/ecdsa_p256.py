@@ -799,6 +799,26 @@ def generate_proof_evm_synthetic(pubkey_x, pubkey_y, r, s, msg_hash, proving_key
 
 # ---- verify / verify_evm (ecdsa_p256.rs:429-469) -----------------------------------------------------------------------------
 
+# How a verifying context settles a batch whose folded pairing check fails (zk_verify_pairing_mode): by halving on the host, or by
+# one launch of the device pairing over the whole set (csrc/pairing.hip).  A process-wide setting like the signature check's,
+# applied to every context _resident_vk hands out; "auto" is the host (tools/verify_bad_rate.py measures both).  Same verdicts.
+_VERIFY_PAIRING = "auto"
+_VERIFY_PAIRING_MODES = {"auto": 0, "host": 1, "device": 2}
+
+
+def set_verify_pairing(mode: str):
+    """Where verify_batch (and proving_server.verify_batch behind it) finds the verdicts of a batch with failing proofs: "host"
+    (bisection, up to 2 B - 1 host pairings), "device" (one launch) or "auto" (the host).  The verdicts are the same."""
+    global _VERIFY_PAIRING
+    if mode not in _VERIFY_PAIRING_MODES:
+        raise ValueError('verify pairing: "host", "device" or "auto"')
+    _VERIFY_PAIRING = mode
+
+
+def verify_pairing() -> str:
+    return _VERIFY_PAIRING
+
+
 def _resident_vk(degree, verifying_key_path, device, public=False):
     """(engine, verifying-only key) for the file: VerifyingKey::read::<_, ECDSACircuit<Fr>> (ecdsa_p256.rs:431-435) once per file
     version, cached with the device's resident state (the key is a few kB: commitments and transcript_repr).  public: the file is
@@ -819,6 +839,7 @@ def _resident_vk(degree, verifying_key_path, device, public=False):
                 data = f.read()
             p = _config_for(degree)
             vks[tag] = eng.vk_read(dataclasses.replace(p, num_instance_columns=1) if public else p, data)
+        eng.verify_pairing_mode(_VERIFY_PAIRING_MODES[_VERIFY_PAIRING])
         return eng, vks[tag]
 
 

@@ -29,6 +29,9 @@ ZK_VERIFY_BATCH_MAX = 1024
 ZK_PROVE_MULTI_MAX = 16
 ZK_ES256_VALID, ZK_ES256_RANGE, ZK_ES256_OFF_CURVE, ZK_ES256_MISMATCH = 0, 1, 2, 3
 ZK_ES256_BATCH_MAX = 16384
+ZK_PAIRING_VALID, ZK_PAIRING_RANGE, ZK_PAIRING_OFF_CURVE, ZK_PAIRING_MISMATCH = 0, 1, 2, 3
+ZK_PAIRING_BATCH_MAX = 4096
+ZK_VERIFY_PAIRING_AUTO, ZK_VERIFY_PAIRING_HOST, ZK_VERIFY_PAIRING_DEVICE = 0, 1, 2
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 ZK_SRS_CONTRIB_SAME_SECRET, ZK_SRS_CONTRIB_LINKS, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT = 1, 2, 4, 8
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
@@ -278,6 +281,9 @@ def load_library():
         "zk_pk_check": ([vp, ctypes.c_uint64, ctypes.POINTER(u32), ctypes.POINTER(PkFindingC), sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_stream_placement": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(PlacementC)], ctypes.c_int),
         "zk_ctx_stream_info": ([vp, ctypes.POINTER(CtxStreamsC)], ctypes.c_int),
+        "zk_pairing_check_batch": ([vp, sz, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_verify_pairing_mode": ([vp, ctypes.c_int], ctypes.c_int),
+        "zk_verify_pairing_stats": ([vp, u64p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name, None)
@@ -285,7 +291,8 @@ def load_library():
             if name in ("zk_witness_check", "zk_pk_check", "zk_stream_placement", "zk_ctx_stream_info", "zk_proof_size_multi",
                         "zk_prove_multi", "zk_verify_multi", "zk_prove_public", "zk_verify_public", "zk_witness_check_public",
                         "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
-                        "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify") and os.environ.get("ZKMI355_LIB"):
+                        "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify",
+                        "zk_pairing_check_batch", "zk_verify_pairing_mode", "zk_verify_pairing_stats") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -936,6 +943,32 @@ class Engine:
         reasons = (ctypes.c_uint8 * max(count, 1))()
         self._chk(self.L.zk_es256_verify(self.ctx, count, sigs, verdicts, reasons), "zk_es256_verify")
         return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+
+    def pairing_check_batch(self, a, b, g2=None, s_g2=None):
+        """zk_pairing_check_batch: e(a_i, s_g2) = e(b_i, g2) for every pair in one launch, one check per lane.  a, b: (count, 8)
+        uint64 affine Montgomery points ((0, 0): the identity); g2, s_g2: 16-word Montgomery images as set_g2 takes them, or both
+        None for the resident SRS's pair.  -> ([bool verdicts], [ZK_PAIRING_* reasons]); a bad pair is a verdict, not an error."""
+        a, b = _arr(a, 8), _arr(b, 8)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("one b per a")
+        count = a.shape[0]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        gp = [ctypes.cast(None, u64p) if g is None else _p(np.ascontiguousarray(g, dtype=np.uint64).reshape(16)) for g in (g2, s_g2)]
+        verdicts = (ctypes.c_uint8 * max(count, 1))()
+        reasons = (ctypes.c_uint8 * max(count, 1))()
+        self._chk(self.L.zk_pairing_check_batch(self.ctx, count, _p(a), _p(b), gp[0], gp[1], verdicts, reasons), "zk_pairing_check_batch")
+        return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+
+    def verify_pairing_mode(self, mode):
+        """zk_verify_pairing_mode: how verify_batch / verify_batch_public settle a failing fold of two or more proofs - 0 auto (the
+        host), 1 host (bisection), 2 device (one launch of the device pairing over the whole set).  Same verdicts."""
+        self._chk(self.L.zk_verify_pairing_mode(self.ctx, mode), "zk_verify_pairing_mode")
+
+    def verify_pairing_stats(self):
+        """zk_verify_pairing_stats -> (host pairing checks, device-checked pairs) of this engine's verify calls since it was made"""
+        out = (ctypes.c_uint64 * 2)()
+        self._chk(self.L.zk_verify_pairing_stats(self.ctx, out), "zk_verify_pairing_stats")
+        return int(out[0]), int(out[1])
 
     def proof_size_multi(self, pk, n_circuits, transcript=ZK_TRANSCRIPT_BLAKE2B, scheme=ZK_SCHEME_DEFAULT):
         ln = ctypes.c_size_t()

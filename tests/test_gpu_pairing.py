@@ -2,7 +2,9 @@
 (tests/pairing_cases.py: e([x] G1, [t] G2) = e([y] G1, G2) exactly when x t = y mod r).  Counts around the wave size with holding
 and non-holding pairs in every wave; one holding pair at lanes 0, 63 and 64; the reasons of improper G1 points and the identity
 cases; reasons = NULL; every argument error with untouched outputs; the resident SRS's pair and its cached table across
-zk_srs_update and zk_srs_downsize; one call under ZK_OPT_STREAM_AUDIT.  No launch is larger than 130 pairs.
+zk_srs_update and zk_srs_downsize; one call under ZK_OPT_STREAM_AUDIT; one call of ZK_PAIRING_BATCH_MAX pairs (every other launch
+is 130 pairs at the most); contexts that share an SRS, across zk_srs_set_g2 and the parent's end.  The values behind the verdicts
+are tests/test_gpu_pairing_device.py's.
 """
 import ctypes
 import random
@@ -180,3 +182,54 @@ def test_under_the_stream_audit(pool):
         assert checks > 0 and violations == 0, msg
     finally:
         e.close()
+
+
+def test_one_call_at_the_batch_maximum(eng, pool):
+    """ZK_PAIRING_BATCH_MAX pairs in one call: 64 one-wave workgroups and their scratch, which no smaller launch reaches.  The pool
+    tiled by a stride coprime to its length, so the points cost nothing new and every wave holds both verdicts; then one pair on
+    the same engine, through the staging buffers the large call left behind."""
+    n, stride = E.ZK_PAIRING_BATCH_MAX, 37
+    assert n == 4096 and np.gcd(stride, 130) == 1
+    idx = [(5 + stride * i) % 130 for i in range(n)]
+    assert len(set(idx[:130])) == 130
+    want = [pool["want"][j] for j in idx]
+    assert all(set(want[w:w + 64]) == {True, False} for w in range(0, n, 64))
+    verdicts, reasons = eng.pairing_check_batch(pool["a"][idx], pool["b"][idx], G2W, pool["s_g2"])
+    assert verdicts == want
+    assert reasons == [pc.VALID if w else pc.MISMATCH for w in want]
+    for j in (idx[0], pool["want"].index(False)):
+        verdicts, reasons = eng.pairing_check_batch(pool["a"][j:j + 1], pool["b"][j:j + 1], G2W, pool["s_g2"])
+        assert verdicts == [pool["want"][j]] and reasons == [pc.VALID if pool["want"][j] else pc.MISMATCH]
+
+
+def test_contexts_that_share_an_srs():
+    """Engine(0, share_with=parent): a child made after the parent's first resident-pair check gets the parent's table with the
+    view and keeps it when the parent is closed; one made before makes its own; zk_srs_set_g2 on the parent moves the parent
+    alone."""
+    parent = zk.Engine(0)
+    early = late = None
+    try:
+        parent.srs_setup(5, b"\x44" * 32)
+        g = parent.srs_export(0, 0, 2)
+        a, b, want = np.stack([g[0], g[0], g[1]]), np.stack([g[1], g[0], g[0]]), [True, False, False]  # e(g0, s_g2) = e(g1, g2) alone holds
+        early = zk.Engine(0, share_with=parent)  # (the parent has no table yet)
+        assert parent.pairing_check_batch(a, b) == (want, [pc.VALID, pc.MISMATCH, pc.MISMATCH])
+        late = zk.Engine(0, share_with=parent)
+        assert late.pairing_check_batch(a, b)[0] == want
+        assert early.pairing_check_batch(a, b)[0] == want
+        assert early.pairing_check_batch(a, b)[0] == want  # (its own cached table)
+        # the parent moves to the pair of another secret: [T] G1 holds there, the resident g[1] stops holding; the children stay
+        parent.srs_set_g2(G2W, pc.g2_to_words(pc.g2(T)))
+        a2, b2 = np.stack([g[0], g[0]]), np.stack([g[1], pc.g1_words([pc.g1(T)])[0]])
+        assert parent.pairing_check_batch(a2, b2)[0] == [False, True]
+        assert late.pairing_check_batch(a2, b2)[0] == [True, False]
+        assert early.pairing_check_batch(a2, b2)[0] == [True, False]
+        assert parent.pairing_check_batch(a, b)[0] == [False, False, False]
+        parent.close()
+        assert late.pairing_check_batch(a, b)[0] == want  # the table lives on with the view that holds it
+        assert late.pairing_check_batch(a2, b2)[0] == [True, False]
+        assert early.pairing_check_batch(a, b)[0] == want
+    finally:
+        for e in (late, early, parent):
+            if e is not None:
+                e.close()

@@ -240,3 +240,110 @@ def test_activity_hold_option_same_bytes():
         assert engs[3].timer_stats(E.ZK_T_MSM_TAIL_MAIN)[1] == on_main, value
     for e in engs[::-1]:
         e.close()
+
+
+# ---- the lone proof is the driver (csrc/prover_lockstep.h) at one lane: what one lane keeps of its own
+_KINDS = {"blake2b": E.ZK_TRANSCRIPT_BLAKE2B, "evm": E.ZK_TRANSCRIPT_EVM}  # (Blake2b + SHPLONK, EVM + GWC: the schemes' passes differ)
+_LONE_SEED = bytes([77]) * 32
+_lone_ref = {}
+
+
+def _resident(eng, p, asgs):
+    """A key of the shape and the witnesses' advice columns, resident on `eng`."""
+    pk = eng.keygen(p, np.stack([asgs[0].to_limbs(c) for c in asgs[0].fixed]), asgs[0].copies)
+    sets = []
+    for asg in asgs:
+        hs = []
+        for col in asg.advice:
+            h = eng.poly(1 << p.degree)
+            eng.upload_canonical(h, asg.to_limbs(col))
+            hs.append(h)
+        sets.append(hs)
+    return pk, sets
+
+
+def _msm_passes(eng):
+    counts = eng.stream_info()["counts"]
+    return counts[0] + counts[1]
+
+
+def _lone_reference(name):
+    """Once per shape, on a context with no option set: two witnesses, the bytes of zk_prove (witness 0), of zk_prove_batch over
+    both and of zk_prove_multi over both per transcript, and the MSM passes one zk_prove makes.  Shared by the tests below."""
+    if name not in _lone_ref:
+        from prover_shapes import SHAPES
+
+        A, L, F, k, lb = SHAPES[name]
+        p = zk.circuit.CircuitParams(degree=k, num_advice=A, num_lookup_advice=L, num_fixed=F, lookup_bits=lb)
+        asgs = [zk.circuit.synthesize(p, 0x5EED0019 + 5 * i) for i in range(2)]
+        eng = zk.Engine(0)
+        eng.srs_setup(k)
+        pk, sets = _resident(eng, p, asgs)
+        seeds = [_LONE_SEED, bytes([78]) * 32]
+        ref = {"p": p, "asgs": asgs, "seeds": seeds, "prove": {}, "batch": {}, "multi": {}, "passes": {}}
+        for kind, tk in _KINDS.items():
+            eng.prove(pk, sets[0], _LONE_SEED, tk)  # (the first proof of a key makes its workspaces)
+            before = _msm_passes(eng)
+            ref["prove"][kind] = eng.prove(pk, sets[0], _LONE_SEED, tk)
+            ref["passes"][kind] = _msm_passes(eng) - before
+            assert ref["passes"][kind] > 0
+            ref["batch"][kind] = eng.prove_batch(pk, sets, seeds, tk)
+            ref["multi"][kind] = eng.prove_multi(pk, sets, _LONE_SEED, tk)
+            assert ref["batch"][kind][0] == ref["prove"][kind]
+        assert eng.stream_info()["counts"][2:] == [0, 0]  # (k = 10: no proof of this context took a side stream)
+        eng.close()
+        _lone_ref[name] = ref
+    return _lone_ref[name]
+
+
+@pytest.mark.parametrize("name", ["k10single", "k10batched"])
+@pytest.mark.parametrize("cols", [1, 3, 16])
+def test_lone_proof_pass_width_is_its_own(cols, name):
+    """ZK_OPT_BATCH_PASS_COLUMNS and the column floor that a batch leaves on the context's MSM workspaces belong to the lock-step
+    entry: under either, zk_prove gives the bytes of a context with no option set and makes the same number of MSM passes."""
+    ref = _lone_reference(name)
+    eng = zk.Engine(0)
+    eng.set_option(E.ZK_OPT_BATCH_PASS_COLUMNS, cols)
+    eng.srs_setup(ref["p"].degree)
+    pk, sets = _resident(eng, ref["p"], ref["asgs"][:1])
+    for kind, tk in _KINDS.items():
+        eng.prove(pk, sets[0], _LONE_SEED, tk)
+        for after_batch in (False, True):
+            before = _msm_passes(eng)
+            got = eng.prove(pk, sets[0], _LONE_SEED, tk)
+            passes = _msm_passes(eng) - before
+            print(name, cols, kind, "after a batch of four" if after_batch else "fresh", "MSM passes", passes, "default", ref["passes"][kind])
+            assert got == ref["prove"][kind], (cols, kind, after_batch)
+            assert passes == ref["passes"][kind], (cols, kind, after_batch)
+            if not after_batch:  # one batch of four: the workspaces' column floor rises to its pass width
+                batch = eng.prove_batch(pk, [sets[0]] * 4, [_LONE_SEED] * 4, tk)
+                assert batch == [ref["prove"][kind]] * 4
+    eng.close()
+
+
+@pytest.mark.parametrize("name", ["k10single", "k10batched"])
+def test_side_streams_are_taken_by_one_lane_only(name):
+    """ZK_OPT_XFORM_STREAM = ZK_OPT_MSM_STREAM = 1: a lone proof — zk_prove, or zk_prove_batch of one, which forwards — takes the
+    transform stream and the MSM stream (zk_ctx_stream_info counts[2], counts[3]: one each per proof); the lanes of a batch of two
+    and of one proof over two circuits stay on the main stream.  The bytes are those of a context with no option set."""
+    ref = _lone_reference(name)
+    eng = zk.Engine(0)
+    eng.set_option(E.ZK_OPT_XFORM_STREAM, 1)
+    eng.set_option(E.ZK_OPT_MSM_STREAM, 1)
+    eng.srs_setup(ref["p"].degree)
+    pk, sets = _resident(eng, ref["p"], ref["asgs"])
+    side = lambda: eng.stream_info()["counts"][2:]
+    assert side() == [0, 0]
+    taken = 0
+    for kind, tk in _KINDS.items():
+        assert eng.prove(pk, sets[0], _LONE_SEED, tk) == ref["prove"][kind]
+        taken += 1
+        assert side() == [taken, taken], kind
+        assert eng.prove_batch(pk, sets[:1], ref["seeds"][:1], tk) == [ref["prove"][kind]]
+        taken += 1
+        assert side() == [taken, taken], kind
+        assert eng.prove_batch(pk, sets, ref["seeds"], tk) == ref["batch"][kind]
+        assert side() == [taken, taken], kind
+        assert eng.prove_multi(pk, sets, _LONE_SEED, tk) == ref["multi"][kind]
+        assert side() == [taken, taken], kind
+    eng.close()

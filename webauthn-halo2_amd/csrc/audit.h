@@ -14,8 +14,8 @@
 // Granularity: a buffer is identified by its base pointer as the engine passes it around (a zk_poly's vector, a workspace
 // member, an MSM lane's workspace, the NTT scratch, a pinned result buffer); sub-ranges of one vector are the same buffer.
 // Coverage: the engine-level operators (MSM passes with their head / tail streams, NTT batches, evaluations, the quotient), the
-// steps every prover takes (csrc/prover_steps.h: the single prover, the lock-step prover and the phase-level entry points name
-// the same buffers at the same steps) and the single prover's own launches (csrc/prover.hip).  Cost when off: one predictable
+// steps every prover takes (csrc/prover_steps.h: the whole-proof driver — one lane or several — and the phase-level entry points
+// name the same buffers at the same steps) and a lane's own launches (csrc/prover.hip).  Cost when off: one predictable
 // branch per enqueue.
 #pragma once
 #include <hip/hip_runtime.h>

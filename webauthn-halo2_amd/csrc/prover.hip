@@ -1,7 +1,7 @@
-// prover.hip — create_proof on the device-resident engine: the single prover (Prover::run), the lock-step prover of several
-// proofs or of one proof over several circuits (prover_lockstep.h) and their entry points.  Keygen and the key's workspace are prover_key.hip, the phase-level entry
-// points prover_phases.hip; the steps the three share are prover_steps.h — the two drivers here hold the scheduling only: which
-// step, in which order, on which lane, and when a lane is collected.
+// prover.hip — create_proof on the device-resident engine: a lane's state and its multi-open stages (Prover), the one driver of
+// a proof alone, of several proofs and of one proof over several circuits (prover_lockstep.h) and their entry points.  Keygen and the
+// key's workspace are prover_key.hip, the phase-level entry points prover_phases.hip; the steps they share are prover_steps.h — the
+// driver holds the scheduling only: which step, in which order, on which lane, and when a lane is collected.
 //
 // Host orchestration (C++) of the kernels in msm.hip / ntt.hip / quotient.hip /
 // prover_kernels.hip / poly.hip, mirroring halo2_proofs `plonk::create_proof` as the reference calls it:
@@ -90,6 +90,8 @@ Fr vanishing_eval(const std::vector<Fr>& pts, const Fr& x) {
     return acc;
 }
 
+// One lane of a proof run (prover_lockstep.h): its transcript, RNG stream and row stager, what begin() decides for the proof
+// (xside / cosets3 / loaded), the helpers over its workspace and the multi-open stages.  The schedule is the driver's.
 struct Prover {
     zk_ctx* c;
     zk_pk_rec* pk;
@@ -117,7 +119,7 @@ struct Prover {
     bool absorb_instance = true;
     bool batch_member = false;  // one of the proofs of a lock-step batch (prover_lockstep.h): transforms stay on the main stream
 
-    Prover(const Prover&) = delete;  // (cq is bound to this object)
+    Prover(const Prover&) = delete;  // (`rows` may point into this object)
     Prover(zk_ctx* c_, zk_pk_rec* pk_, const uint8_t seed[32], Transcript* t)
         : c(c_), pk(pk_), lay(pk_->lay), st(c_->stream), rng(seed), tr(t), n(pk_->lay.n), N(4 * pk_->lay.n) {
         own_rows.host = pk_->rows_host;
@@ -131,7 +133,7 @@ struct Prover {
 
     // ---- device helpers
     // Blinding rows are staged on the host and written by rows_flush() — one upload and one launch for all
-    // the columns of a phase — before the first kernel that reads those columns (the commitment queue and
+    // the columns of a phase — before the first kernel that reads those columns (the driver's commitment queue and
     // transforms() flush; other readers call rows_flush() themselves).
     // ---- stream audit (audit.h, ZK_OPT_STREAM_AUDIT): every enqueue of this prover names the buffers it reads and writes
     void A(std::initializer_list<const void*> r, std::initializer_list<const void*> w, const char* site) {
@@ -174,15 +176,6 @@ struct Prover {
             rows->block = 0;
         }
     }
-    // commitments in flight over MSM lanes (prover_steps.h): every column of this prover goes to its own transcript
-    using CQ = Commits<Prover>;
-    CQ cq{*this};
-    // one commitment on lane 0, written to the transcript at once
-    void commit_write(const Fr* poly, int basis) {
-        CQ::Fifo f{{0}, {}, nullptr};
-        cq.begin(f, {CommitCol{poly, tr}}, basis);
-        cq.drain(f);
-    }
     std::vector<Fr> draw(uint32_t count) {
         std::vector<Fr> v(count);
         for (auto& x : v) x = rng.next_fr();
@@ -207,7 +200,7 @@ struct Prover {
     // the columns' coset forms are [3][n] coset-major, made by n-point transforms.  Decided once per proof (begin())
     bool cosets3 = false;
     // three or more contexts busy on the device (the regime in which reduction tails run on the main stream): decided once per
-    // proof (begin()); multi-column commitments are then not split into two passes (Commits::flush)
+    // proof (begin()); a lone proof's multi-column commitments are then not split into two passes (LockstepRun::batcher)
     bool loaded = false;
     // (audit self-test, ZK_OPT_STREAM_AUDIT = 2: round 5's faulty form on purpose — the stream chosen per CALL, alternating, and no
     // join before a main-stream transform: the ledger must then refuse every proof whose transforms come in more than one call)
@@ -316,7 +309,7 @@ struct Prover {
     };
 
     // ---- the opened values and the query order of a proof over one or more circuits of this key (`circuits`: this prover's own
-    // workspace first; the lone prover and every proof of a lock-step batch have the one, prover_lockstep.h's one-proof mode B).
+    // workspace first; a lone proof and every proof of a lock-step batch have the one, prover_lockstep.h's one-proof mode B).
     // The verifier (verifier.h) reads both orders; they are stated here and nowhere else.
     // Every opened value in transcript order — for c: advice; fixed; random; sigma; for c: z; for c: lookups — then h(x) (not
     // written); where the groups start
@@ -417,8 +410,8 @@ struct Prover {
         launch_lincomb(a, st);
     }
 
-    // ------------------------------------------------------------------ run ---
-    // domain constants, and the transcript's first word
+    // ---------------------------------------------------------------- begin ---
+    // the proof's once-only decisions, domain constants, and the transcript's first word
     int begin() {
         xside = !batch_member && (c->opt_xform_stream == 1 || (c->opt_xform_stream == 0 && lay.k >= 18 && ctx_activity_touch(c) <= 1));
         // the MSM passes of a lone proof on the context's MSM stream (ctx.h): same rule, same once-per-proof decision; measured
@@ -431,7 +424,7 @@ struct Prover {
         // auto: columns of 2^16 rows or more (measured, tools/r6_cosets3_ab.sh: k = 18 / 17 / 16 - 1 / - 3 / - 3 %, k = 17 EVM over four
         // pipelines 196 -> 203 proofs/s; the many-column rows lose — three vectors per column fill the transforms' launches three
         // times as fast: k = 13 / 12 / 11 + 5 / + 5 / + 12 %)
-        // (the members of a lock-step batch get the key's coset-major copies from the batch driver: prover_lockstep.h)
+        // (the members of a lock-step batch read the key's coset-major copies, made by lane 0's begin(): pk_ensure_cosets3)
         {
             const uint32_t above = c->opt_tail_main_above ? c->opt_tail_main_above : 2u;
             loaded = c->opt_tail_stream == 2 || (c->opt_tail_stream == 0 && (uint32_t)ctx_activity_touch(c) > above);
@@ -446,231 +439,8 @@ struct Prover {
             for (const Fr& v : *instance) tr->common_scalar(v);  // (the count is not hashed)
         return ZK_OK;
     }
-    // the instance column's forms go with the first advice transforms: its values are uploaded on the main stream before the first
-    // flush of blinding rows, which is what a transform on the side stream waits for
-    void with_instance(std::vector<Forms>& fm) const {
-        if (pk->inst_val) fm.push_back(Forms{pk->inst_val, pk->inst_poly, pk->inst_coset});
-    }
-
-    int run(const Fr* const* advice_dev, int scheme) {
-        if (begin()) return rc;
-        const uint32_t bf = BLINDING_FACTORS, usable = lay.usable;
-
-        // Commitments are computed as early as their inputs exist (none of a', s', the random
-        // polynomial needs a challenge) and collected in transcript order; RNG draws keep
-        // halo2's order (the random polynomial's block range is reserved up front).
-        // -- 1. advice
-        // (many columns: one launch copies them all — the argument staging is reused by the later batched launches, each
-        // preceded by a stream-ordered upload, so the host must not overwrite it before the upload has been consumed)
-        if (pk->inst_val) {
-            static const std::vector<Fr> none;
-            if (int r = pk_instance_upload(c, st, pk, instance ? *instance : none)) return r;
-        }
-        const bool many = advice_staged(lay);
-        if (many) {
-            if (int r = advice_columns_staged(c, st, pk, advice_dev)) return r;
-            if (aud_sync(c, st) != hipSuccess) return ZK_EHIP;
-        }
-        for (uint32_t j = 0; j < lay.n_adv; j++) {
-            if (!many)
-                if (int r = advice_column(c, st, pk, advice_dev, j)) return r;
-            set_rows(pk->adv_val[j], usable, draw(bf + 1));
-        }
-        draw(lay.n_adv);  // advice blinds (unused by KZG, still drawn)
-        // few advice columns (k=19: one): pipeline them with the lookup commitments; many: plain order
-        const bool pipe = lay.n_adv == 1 && lay.n_lookups == 1;
-        // The coefficient and extended-coset forms the quotient needs are produced right behind each
-        // commitment's head: they need no challenge, and they keep the main stream busy while the MSM tails
-        // (and the host's transcript work) would otherwise leave it idle.
-        const uint32_t max_batch = ctx_msm_max_batch(c);
-        bool adv_transformed = false;
-        CQ::Fifo af{{0}, {}, nullptr};  // the pipelined advice pass: in flight on lane 0 until theta is needed
-        if (pipe) {
-            cq.begin(af, {CommitCol{pk->adv_val[0], tr}}, ZK_BASIS_LAGRANGE);
-            if (xform_side()) {  // a lone proof: the advice column's forms are made under its own MSM pass
-                std::vector<Forms> fm{Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]}};
-                with_instance(fm);
-                transforms(fm);
-                adv_transformed = true;
-            }
-        } else {
-            // several advice columns: whole batches of columns per MSM pass, up to MSM_LANES passes in flight,
-            // each followed by its columns' transforms; collected in column order
-            CQ::Fifo f{{0, 1, 2}, {}, nullptr};
-            for (uint32_t j0 = 0; j0 < lay.n_adv && ok(); j0 += max_batch) {
-                const uint32_t j1 = std::min(lay.n_adv, j0 + max_batch);
-                std::vector<CommitCol> cols;
-                std::vector<Forms> fm;
-                for (uint32_t j = j0; j < j1; j++) {
-                    cols.push_back(CommitCol{pk->adv_val[j], tr});
-                    fm.push_back(Forms{pk->adv_val[j], pk->adv_poly[j], pk->adv_coset[j]});
-                }
-                if (j0 == 0) with_instance(fm);
-                cq.begin(f, cols, ZK_BASIS_LAGRANGE);
-                transforms(fm);
-            }
-            cq.drain(f);
-        }
-        if (!ok()) return rc;
-
-        // -- 2. lookups: permuted input / table (single-expression lookups: theta-compression is the identity)
-        bool theta_done = false;
-        auto squeeze_theta = [&]() {
-            if (!theta_done) {
-                if (pipe) cq.drain(af);
-                tr->squeeze();
-                theta_done = true;
-            }
-        };
-        // a', s' of every lookup: batches of columns per MSM pass; their transforms (and, in the pipelined
-        // case, the advice column's) follow the MSM heads so that they cover the tails
-        CQ::Fifo lf{pipe ? std::vector<int>{1, 2} : std::vector<int>{0, 1, 2}, {}, nullptr};
-        CQ::Batcher lb{&lf, ZK_BASIS_LAGRANGE, max_batch, loaded, {}};
-        std::vector<uint32_t> due;
-        auto lookup_transforms = [&](bool with_advice) {
-            std::vector<Forms> fm;
-            if (with_advice) {
-                fm.push_back(Forms{pk->adv_val[0], pk->adv_poly[0], pk->adv_coset[0]});
-                with_instance(fm);
-            }
-            for (uint32_t l : due) {
-                fm.push_back(Forms{pk->lk_ap[l], pk->lk_ap_poly[l], pk->lk_ap_coset[l]});
-                fm.push_back(Forms{pk->lk_sp[l], pk->lk_sp_poly[l], pk->lk_sp_coset[l]});
-            }
-            transforms(fm);
-            due.clear();
-        };
-        if (!pipe) squeeze_theta();  // the advice commitments are all written: theta precedes the first a'
-        {
-            std::vector<LkItem> items;
-            for (uint32_t l = 0; l < lay.n_lookups; l++) items.push_back(LkItem{pk, pk->adv_val.data(), l, pk->lk_ap[l], pk->lk_sp[l]});
-            if (int r = lookup_permute(c, st, lay, items, pk->lks)) return r;
-        }
-        for (uint32_t l = 0; l < lay.n_lookups && ok(); l++) {
-            set_rows(pk->lk_ap[l], usable, draw(bf + 1));
-            set_rows(pk->lk_sp[l], usable, draw(bf + 1));
-            draw(2);
-            cq.add(lb, pk->lk_ap[l], tr);
-            cq.add(lb, pk->lk_sp[l], tr);
-            due.push_back(l);
-            if (lb.pend.empty()) lookup_transforms(false);
-        }
-        cq.flush(lb);
-        lookup_transforms(pipe && !adv_transformed);
-        {
-            // one check for all lookups (the flag accumulates): an input outside the table is halo2's
-            // ConstraintSystemFailure; nothing has been written for the lookups yet
-            bool bad = false;
-            if (int r = lookup_permute_failed(c, st, pk->lks, &bad)) return r;
-            if (bad) {
-                ctx_msm_drain(c);
-                return ZK_EWITNESS;
-            }
-        }
-        squeeze_theta();
-        cq.drain(lf);
-        if (!ok()) return rc;
-        const Fr beta = tr->squeeze();
-        const Fr gamma = tr->squeeze();
-
-        // -- 5 (early). vanishing argument: the random polynomial does not depend on any challenge.
-        // Its n draws come after the grand products' draws in halo2's order: reserve that block range.
-        CQ::Fifo rf{{0}, {}, nullptr};
-        {
-            const uint64_t skip = (uint64_t)lay.n_chunks * (bf + 1) + (uint64_t)lay.n_lookups * (bf + 1);
-            ChaChaKey key;
-            memcpy(key.w, rng.key, 32);
-            A({}, {pk->random_poly}, "random polynomial");
-            launch_chacha_fr(key, rng.block + skip, pk->random_poly, n, st);
-            cq.begin(rf, {CommitCol{pk->random_poly, tr}}, ZK_BASIS_MONOMIAL);
-        }
-
-        // -- 3. permutation grand products.  All z columns (permutation chunks, then lookups) are committed in
-        // batches on lanes 1 and 2; their transforms follow each batch's MSM head.
-        CQ::Fifo zf{{1, 2}, {}, nullptr};
-        CQ::Batcher zb{&zf, ZK_BASIS_LAGRANGE, max_batch, loaded, {}};
-        std::vector<Forms> zdue;
-        auto z_transforms = [&]() {
-            transforms(zdue);
-            zdue.clear();
-        };
-        {
-            // numerators / denominators of every product, then all scans in one batch (the argument staging of the
-            // many-column shapes may still be in use: the host waits before it rewrites it)
-            const uint32_t nprod = lay.n_chunks + lay.n_lookups;
-            std::vector<Fr*> zs(pk->z_val);
-            zs.insert(zs.end(), pk->lk_z.begin(), pk->lk_z.end());
-            if (lay.n_chunks > BATCH_ARGS_MIN && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
-            if (int r = perm_numden_enqueue(c, st, pk, pk->adv_val.data(), tw, beta, gamma, true)) return r;
-            if (lay.n_lookups > BATCH_ARGS_MIN && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
-            if (int r = lk_numden_enqueue(c, st, pk, pk->adv_val.data(), pk->lk_ap.data(), pk->lk_sp.data(), beta, gamma, lay.n_chunks, true, false))
-                return r;
-            if (int r = grand_products(c, st, lay, {GpGroup{pk, zs.data(), nprod, lay.n_chunks}}, GpScratch{pk->d_gp_items, pk->gp_scal, pk->gp_host}))
-                return r;
-            // blinding rows and commitments, in halo2's order (chunks, then lookups)
-            for (uint32_t p = 0; p < nprod && ok(); p++) {
-                set_rows(zs[p], n - bf, draw(bf));
-                draw(1);
-                cq.add(zb, zs[p], tr);
-                if (p < lay.n_chunks) zdue.push_back(Forms{pk->z_val[p], pk->z_poly[p], pk->z_coset[p]});
-                else zdue.push_back(Forms{pk->lk_z[p - lay.n_chunks], pk->lk_z_poly[p - lay.n_chunks], pk->lk_z_coset[p - lay.n_chunks]});
-                if (zb.pend.empty()) z_transforms();
-            }
-        }
-        cq.flush(zb);
-        z_transforms();
-        cq.drain(zf);
-        if (!ok()) return rc;
-
-        // -- 5. collect the random polynomial's commitment (its draws happen here in stream order)
-        rng.block += n;
-        draw(1);
-        cq.drain(rf);
-        if (!ok()) return rc;
-        const Fr y = tr->squeeze();
-
-        // -- 6. quotient (every coefficient / coset form was produced behind its commitment above)
-        if (int r = quotient(beta, gamma, y)) return r;
-        draw(lay.n_h);  // h-piece blinds
-        {
-            // the h pieces are contiguous n-coefficient slices of the quotient: one MSM pass for all of them
-            CQ::Fifo hf{{0, 1, 2}, {}, nullptr};
-            CQ::Batcher hb{&hf, ZK_BASIS_MONOMIAL, max_batch, loaded, {}};
-            for (uint32_t i = 0; i < lay.n_h && ok(); i++) cq.add(hb, pk->h_ext + (size_t)i * n, tr);
-            cq.flush(hb);
-            cq.drain(hf);
-        }
-        if (!ok()) return rc;
-        const Fr x = tr->squeeze();
-        HT("x squeezed");
-
-        // -- 7. evaluations: every opened value in ONE batched launch, then written in transcript order
-        combine_h(x);
-        std::vector<Q> ev;  // transcript order, then h(x) (not written)
-        EvIdx ix;
-        build_evals({pk}, ev, ix);
-        if (ev.size() > pk->max_evals) return ZK_ESTATE;
-        for (size_t i = 0; i < ev.size(); i++) {
-            pk->h_evargs[i].poly = ev[i].poly;
-            pk->h_evargs[i].x = xrot(x, ev[i].rot);
-        }
-        if (int r = evaluate_enqueue(c, st, EvalBufs{pk->h_evargs, pk->d_evargs, pk->ev_scratch, pk->ev_out, pk->tail_host}, (uint32_t)ev.size(), n))
-            return r;
-        for (size_t i = 0; i < ev.size(); i++) ev[i].eval = pk->tail_host[i];
-        HT("evals on host");
-        for (size_t i = 0; i < ix.n_written; i++) tr->write_scalar(ev[i].eval);
-        const std::vector<Q> queries = queries_from_evals(ev, ix);
-        if (!ok()) return rc;
-
-        // -- 8. multi-open
-        pk->lc_used = 0;
-        HT("queries built");
-        return scheme == ZK_SCHEME_GWC ? open_gwc(queries, x, max_batch) : open_shplonk(queries, x);
-    }
-
     // ---- multi-open, in stages: each stage ends with polynomials launched whose commitments the transcript needs next, so
-    // that a lock-step prover of several proofs (prover_lockstep.h) can put the same commitment of all its proofs into ONE MSM
-    // pass; open_gwc / open_shplonk below run the stages of one proof back to back.
+    // that the driver (prover_lockstep.h) can put the same commitment of all its proofs into ONE MSM pass.
 
     // GWC (ProverGWC, halo2_proofs poly/kzg/multiopen/gwc): one witness polynomial per rotation.
     // Stage 1 (squeezes v): every set's (sum v^i p_i - sum v^i e_i) / (X - point), all in one batched division; the witness
@@ -712,17 +482,6 @@ struct Prover {
         }
         launch_kate_division_batch(wbuf, wbuf, pts, (uint32_t)set_idx, n, pk->kd_scratch, st);
         for (size_t i = 0; i < set_idx; i++) wit.push_back(wbuf[i]);
-        return rc;
-    }
-    int open_gwc(const std::vector<Q>& queries, const Fr& x, uint32_t max_batch) {
-        std::vector<const Fr*> wit;
-        if (int r = gwc_stage1(queries, x, wit)) return r;
-        // the witness polynomials need no challenge in between: all of them go through one MSM pass
-        CQ::Fifo wf{{0, 1, 2}, {}, nullptr};
-        CQ::Batcher wb{&wf, ZK_BASIS_MONOMIAL, max_batch, loaded, {}};
-        for (const Fr* w : wit) cq.add(wb, w, tr);
-        cq.flush(wb);
-        cq.drain(wf);
         return rc;
     }
 
@@ -915,16 +674,6 @@ struct Prover {
         *out = pk->t_b;
         return rc;
     }
-    int open_shplonk(const std::vector<Q>& queries, const Fr& x) {
-        Shplonk S;
-        if (int r = shplonk_stage1(queries, x, S)) return r;
-        commit_write(S.hx, ZK_BASIS_MONOMIAL);
-        if (!ok()) return rc;
-        const Fr* last = nullptr;
-        if (int r = shplonk_stage2(S, &last)) return r;
-        commit_write(last, ZK_BASIS_MONOMIAL);
-        return rc;
-    }
 };
 
 #include "prover_lockstep.h"
@@ -1013,7 +762,22 @@ static int resolve_advice(zk_ctx* c, const Layout& lay, const zk_poly* advice, s
     return ZK_OK;
 }
 
-// create_proof for one circuit.  `with_instances`: zk_prove_public — the caller's instance values (none on a key without the
+// the run of an admitted call (prover_lockstep.h) over its lanes' provers — one: a lone proof — under the stream audit's verdict
+static int run_lanes(zk_ctx* c, zk_pk_rec* pk, const std::vector<Prover*>& P, bool one_proof, uint32_t pass_cap, const Fr* const* adv, int scheme) {
+    const uint64_t aud0 = c->audit.violations;
+    c->audit.base_of.clear();  // (allocations may have changed hands since the last proof)
+    int rc;
+    {
+        LockstepRun run(c, pk, P, one_proof, pass_cap);
+        ProveQuiesce quiesce(c);  // (made after the provers: it settles the streams while their host buffers are alive)
+        rc = run.run(adv, scheme);
+    }
+    if ((rc = aud_verdict(c, aud0, rc))) return rc;
+    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+    return ZK_OK;
+}
+
+// create_proof for one circuit: the driver at one lane.  `with_instances`: zk_prove_public — the caller's instance values (none on a key without the
 // column: zk_prove's bytes); otherwise zk_prove, which a key WITH the column refuses (halo2's InvalidInstances)
 static int prove_one(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice, bool with_instances, const uint64_t* instance_mont,
                      size_t n_instance, const uint8_t rng_seed[32], int transcript, int scheme, uint8_t* proof_out, size_t proof_cap,
@@ -1035,16 +799,10 @@ static int prove_one(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n_advice,
     EvmTranscript evm;
     Blake2bTranscript b2;
     Transcript* tr = transcript == ZK_TRANSCRIPT_EVM ? (Transcript*)&evm : (Transcript*)&b2;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();  // (allocations may have changed hands since the last proof)
+    // the one lane: a prover on the key's own workspace, the pass width the context's own
     Prover p(c, pk, rng_seed, tr);
     if (lay.n_inst) p.instance = &lists[0];
-    {
-        ProveQuiesce quiesce(c);  // (declared after the prover: it settles the streams while the prover's host buffers are alive)
-        rc = p.run(adv.data(), scheme);
-    }
-    if ((rc = aud_verdict(c, aud0, rc))) return rc;
-    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
+    if ((rc = run_lanes(c, pk, {&p}, false, ctx_msm_max_batch(c), adv.data(), scheme))) return rc;
     *proof_len = tr->out.size();
     if (!proof_out || proof_cap < tr->out.size()) return proof_out ? ZK_EINVAL : ZK_OK;
     memcpy(proof_out, tr->out.data(), tr->out.size());
@@ -1072,7 +830,7 @@ static int prove_one_of_lists(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t 
                            proof_cap, proof_len);
 }
 
-// ---- the lock-step entry (prover_lockstep.h): what zk_prove_batch and zk_prove_multi do alike once a call is admitted.  Lane q —
+// ---- the lock-step entry (prover_lockstep.h) for two or more lanes: what zk_prove_batch and zk_prove_multi do alike once a call is admitted.  Lane q —
 // proof q, or circuit q of the one proof — gets a prover on the key's own workspace (q = 0) or on member q - 1, with the
 // caller's transcript and seed for it and, on a key with the column, list q.  The callers keep what is their own: whose
 // transcripts and seeds these are, and the copy of the output
@@ -1103,16 +861,7 @@ static int prove_lockstep(zk_ctx* c, zk_pk_rec* pk, bool one_proof, const std::v
         if (lay.n_inst) provers.back()->instance = &lists[q];
         P.push_back(provers.back().get());
     }
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();  // (allocations may have changed hands since the last proof)
-    {
-        LockstepRun run(c, pk, P, one_proof, cap);
-        ProveQuiesce quiesce(c);  // (declared after the provers: it settles the streams while their host buffers are alive)
-        rc = run.run(adv.data(), scheme);
-    }
-    if ((rc = aud_verdict(c, aud0, rc))) return rc;
-    if (hipGetLastError() != hipSuccess) return ZK_EHIP;
-    return ZK_OK;
+    return run_lanes(c, pk, P, one_proof, cap, adv.data(), scheme);
 }
 
 // create_proof for `batch` independent proofs of one key in lock-step.  `with_instances`: zk_prove_batch_public —

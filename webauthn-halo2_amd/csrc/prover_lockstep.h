@@ -1,6 +1,7 @@
-// prover_lockstep.h — create_proof for several circuits of ONE key in lock-step on one context: B independent proofs
-// (zk_prove_batch), or ONE proof over B circuits (zk_prove_multi).  One schedule, one driver; the mode is fixed at construction.
-// Included by prover.hip after `struct Prover`; not a translation unit of its own.
+// prover_lockstep.h — create_proof, the ONE driver: B lanes of ONE key in lock-step on one context.  One lane is zk_prove /
+// zk_prove_public; several are B independent proofs (zk_prove_batch) or ONE proof over B circuits (zk_prove_multi).  One schedule;
+// the lane count and the mode are fixed at construction.  Included by prover.hip after `struct Prover`; not a translation unit of
+// its own.
 //
 // Why lock-step: a proof alone is a chain of ~150 launches, most of them small (sort heads, reduction tails, scans, staging); several
 // independent pipelines overlap those chains, but each still pays them per proof.  The B proofs of a batch — the reference's
@@ -9,9 +10,10 @@
 // B x columns, one reduction tail), the same transform through ONE launch per NTT pass (blockIdx.y), all lookups through
 // one set of permutation launches, all grand products through one scan, all opened values through one evaluation launch.  What
 // stays per lane is chip-filling anyway (quotient, linear combinations, Kate divisions) or host work (transcripts, RNG).
-// The steps themselves are the single prover's (prover_steps.h): this driver holds the schedule — the per-lane steps looped, the
-// shared ones given every lane's workspace at once — and the phase order is Prover::run's.  Lane q works in the key's member record
-// q - 1 (zk_pk_rec::members; lane 0 in the key's own workspace: ~1.4 GiB each at k = 19, allocated on first use and kept).
+// The steps themselves are prover_steps.h's and Prover's (prover.hip): this driver holds the schedule — which step, in which order,
+// on which MSM lane, when a lane is collected and when the host waits; the per-lane steps looped, the shared ones given every
+// lane's workspace at once.  Lane 0 works in the key's own workspace, lane q > 0 in the key's member record q - 1
+// (zk_pk_rec::members: ~1.4 GiB each at k = 19, allocated on first use and kept).
 //
 // B proofs: every proof keeps its own transcript, its own ChaCha20 stream and its own workspace; the bytes of proof j are those of
 // zk_prove with the same key, advice and seed (tests/test_gpu_prove_batch.py).  With public inputs (zk_prove_batch_public) every
@@ -33,7 +35,7 @@
 //                then the multi-open
 //   RNG          ONE ChaCha20 stream: for c: (bf + 1) rows per advice column, then n_adv blinds; for c, per lookup: (bf + 1) rows
 //                for a', (bf + 1) for s', 2 blinds; for c, per chunk: bf rows, 1 blind; for c, per lookup: bf rows, 1 blind; n draws
-//                for the random polynomial, 1 blind; n_h blinds.  N = 1: Prover::run's order
+//                for the random polynomial, 1 blind; n_h blinds
 //   quotient     the y-Horner chain runs on across the circuits: term j of circuit c has weight y^(N T - 1 - (c T + j)), so
 //                h = sum_c y^(T (N - 1 - c)) h_c with h_c what quotient_row makes of circuit c's columns.  The division by X^n - 1
 //                is linear and is applied per pass; the number of h pieces is that of one circuit
@@ -41,6 +43,7 @@
 //                lookup opens (per lookup zL@0, a'@0, s'@0, a'@-1, zL@1); after all circuits: fixed, sigma, h, random.  GWC groups
 //                this list by rotation in order of first appearance, SHPLONK by rotation set: Prover::gwc_stage1 / shplonk_stage1/2
 //                as they stand, on the longer list (Prover::build_evals / queries_from_evals state both orders, for 1 and for N)
+// This is the one statement of the order: a lone proof is N = 1.
 // With public inputs (zk_prove_multi_public; restated by the same tests/halo2_ref.py) the rule gains: behind transcript_repr, for c:
 // every value of circuit c's instance list as common_scalar (absorbed, not written; neither N nor the lengths are hashed) — ALL
 // circuits' instances before any advice commitment, halo2's loop over `instances` at the top of create_proof.  The columns draw
@@ -52,6 +55,35 @@
 // owner through tr_of / draw / squeeze; phases 1 - 3 loop over the lanes alike.  What only one mode has (the instances absorbed
 // by the driver, the quotient accumulated over the circuits, the limit of the evaluation list, the lane of the SHPLONK
 // commitments) is a branch on `one`, each with its reason.
+//
+// Where ONE lane differs from several — a lone proof has the context to itself, a member of a batch shares it — is a branch on
+// `lone`, each with its reason: the shared buffers (LaneBufs), the instance upload, the side streams (Prover::batch_member, and
+// with it the early advice transforms and the quotient), the split of wide passes, and two places where the host waits.  The
+// pass width is the caller's (prove_one: the context's own; prove_lockstep: the lock-step rule).
+
+// the buffers of the launches that all lanes share: one lane has the key's own, several the key's BatchBufs (sized for `cap`
+// proofs; null on a key that has never seen a batch)
+struct LaneBufs {
+    LookupScratch lks;
+    GpScratch gp;
+    EvalBufs ev;
+    size_t max_evals;  // what `ev` holds
+    LaneBufs(const zk_pk_rec* pk, bool lone, bool one_proof) {
+        if (lone) {
+            lks = pk->lks;
+            gp = GpScratch{pk->d_gp_items, pk->gp_scal, pk->gp_host};
+            ev = EvalBufs{pk->h_evargs, pk->d_evargs, pk->ev_scratch, pk->ev_out, pk->tail_host};
+            max_evals = pk->max_evals;
+        } else {
+            const BatchBufs& bb = *pk->bb;
+            lks = bb.lks;
+            gp = GpScratch{bb.d_gp_items, bb.gp_scal, bb.gp_host};
+            ev = EvalBufs{bb.h_evargs, bb.d_evargs, bb.ev_scratch, bb.ev_out, bb.tail_host};
+            // (cap x one proof's openings: B proofs share them, the one proof has them all)
+            max_evals = one_proof ? (size_t)bb.cap * pk->max_evals : pk->max_evals;
+        }
+    }
+};
 
 struct LockstepRun {
     zk_ctx* c;
@@ -60,18 +92,19 @@ struct LockstepRun {
     hipStream_t st;
     uint32_t n, N, B;  // rows; extended rows; lanes: the proofs, or the circuits of the one proof
     std::vector<Prover*> P;
-    const bool one;  // ONE proof over the B circuits (P[0] holds its transcript and RNG); otherwise B proofs
-    BatchBufs& bb;
+    const bool one;   // ONE proof over the B circuits (P[0] holds its transcript and RNG); otherwise B proofs
+    const bool lone;  // one lane: the lone proof
+    LaneBufs bufs;
     uint32_t pass_cap;  // columns per MSM pass
     int rc = ZK_OK;
 
     LockstepRun(const LockstepRun&) = delete;  // (cq is bound to this object)
-    LockstepRun(zk_ctx* c_, zk_pk_rec* pk_, std::vector<Prover*>& provers, bool one_proof, uint32_t cap)
+    LockstepRun(zk_ctx* c_, zk_pk_rec* pk_, const std::vector<Prover*>& provers, bool one_proof, uint32_t cap)
         : c(c_), pk0(pk_), lay(pk_->lay), st(c_->stream), n(pk_->lay.n), N(4 * pk_->lay.n), B((uint32_t)provers.size()), P(provers),
-          one(one_proof), bb(*pk_->bb), pass_cap(cap) {
+          one(one_proof), lone(provers.size() == 1), bufs(pk_, lone, one_proof), pass_cap(cap) {
         for (Prover* p : P) {
             p->rows = &P[0]->own_rows;  // one row stager for all lanes: one upload + one launch per phase
-            p->batch_member = true;
+            p->batch_member = !lone;    // (a lone proof may take the side streams: Prover::begin)
         }
     }
 
@@ -104,27 +137,115 @@ struct LockstepRun {
         return ch;
     }
 
-    // ---- merged commitments (prover_steps.h): columns of several lanes in one MSM pass; every point goes to its owner's
-    // transcript, in the order the columns were given (per proof that is the transcript's order).  Passes of four or more columns
-    // are always split over two lanes (Commits::Batcher: never `loaded`)
-    using CQ = Commits<LockstepRun>;
-    CQ cq{*this};
-    using Fifo = CQ::Fifo;
-    using Batcher = CQ::Batcher;
+    // ---- commitments in flight over MSM lanes, collected — written to their transcripts — in the order they were begun: columns
+    // of several lanes in one MSM pass; every point goes to its owner's transcript, in the order the columns were given (per
+    // proof that is the transcript's order).  The staged blinding rows of the columns about to be read go up first
+    struct Commits {
+        LockstepRun& d;
+        struct Pass {
+            int lane;
+            std::vector<Transcript*> to;
+        };
+        // a set of lanes used in turn; a one-lane queue is a commitment begun on a fixed lane and collected later (drain)
+        struct Fifo {
+            std::vector<int> lanes;
+            std::deque<Pass> busy;
+            // run before a pass of this queue is collected: what the transcripts must hold first (the lookup passes of a pipelined
+            // proof may fill their lanes while the advice pass is still in flight on its own)
+            std::function<void()> before_collect;
+        };
+        // gathers columns into passes of at most `cap`; flush() begins what is pending.  A pass of four or more columns goes as two
+        // passes on two lanes — the first half's reduction tail runs under the second half's head — unless `loaded`: that pays only
+        // while the tails have a stream of their own (a lone proof, two pipelines); under load — tails on the main stream — a second
+        // pass is just a second head and tail (k = 17 EVM over four pipelines: 232.9 -> 236.9 proofs/s unsplit)
+        struct Batcher {
+            Fifo* f;
+            int basis;
+            uint32_t cap;
+            bool loaded;
+            std::vector<CommitCol> pend;
+        };
+
+        void begin(Fifo& f, const std::vector<CommitCol>& cols, int basis) {
+            if (!d.ok() || cols.empty()) return;
+            if (f.busy.size() == f.lanes.size()) {
+                if (f.before_collect) f.before_collect();
+                end_write(f.busy.front());
+                f.busy.pop_front();
+            }
+            int lane = -1;
+            for (int l : f.lanes) {
+                bool used = false;
+                for (const Pass& ps : f.busy) used = used || ps.lane == l;
+                if (!used) lane = l;
+            }
+            d.rows_flush();
+            if (!d.ok()) return;
+            std::vector<const Fr*> polys;
+            Pass ps{lane, {}};
+            for (const CommitCol& cl : cols) {
+                polys.push_back(cl.poly);
+                ps.to.push_back(cl.to);
+            }
+            int r = ctx_msm_begin_batch(d.c, lane, polys.data(), (uint32_t)polys.size(), ctx_basis(d.c, basis), d.n);
+            if (r) return d.fail(r);
+            f.busy.push_back(ps);
+        }
+        // collects a pass: its commitments are written to their transcripts in the order the columns were given
+        void end_write(const Pass& ps) {
+            if (!d.ok()) return;
+            G1Jac js[MSM_MAX_BATCH];
+            int r = ctx_msm_end_batch(d.c, ps.lane, js);
+            if (r) return d.fail(r);
+            G1Affine af[MSM_MAX_BATCH];
+            const uint32_t cnt = (uint32_t)ps.to.size();
+            jac_batch_to_affine(js, cnt, af);
+            for (uint32_t q = 0; q < cnt && d.ok(); q++)
+                if (!ps.to[q]->write_point(af[q])) d.fail(ZK_EINVAL);  // identity: halo2 refuses to write it
+        }
+        void drain(Fifo& f) {
+            if (f.before_collect && !f.busy.empty()) f.before_collect();
+            while (!f.busy.empty()) {
+                end_write(f.busy.front());
+                f.busy.pop_front();
+            }
+        }
+        void add(Batcher& b, const Fr* poly, Transcript* to) {
+            b.pend.push_back(CommitCol{poly, to});
+            if (b.pend.size() >= b.cap) flush(b);
+        }
+        void flush(Batcher& b) {
+            if (b.pend.size() >= 4 && b.f->lanes.size() >= 2 && !b.loaded) {
+                const size_t h = (b.pend.size() + 1) / 2;
+                begin(*b.f, std::vector<CommitCol>(b.pend.begin(), b.pend.begin() + h), b.basis);
+                begin(*b.f, std::vector<CommitCol>(b.pend.begin() + h, b.pend.end()), b.basis);
+            } else {
+                begin(*b.f, b.pend, b.basis);
+            }
+            b.pend.clear();
+        }
+    };
+    Commits cq{*this};
+    using Fifo = Commits::Fifo;
+    using Batcher = Commits::Batcher;
     using Col = CommitCol;
     void rows_flush() { P[0]->rows_flush(); }  // (the one row stager of all lanes)
-    Batcher batcher(Fifo& f, int basis) { return Batcher{&f, basis, pass_cap, false, {}}; }
+    // `lone`: wide passes stay whole in the regime the proof's begin() found (Prover::loaded: three or more contexts busy); the
+    // passes of several lanes are always split over two lanes
+    Batcher batcher(Fifo& f, int basis) { return Batcher{&f, basis, pass_cap, lone && P[0]->loaded, {}}; }
     void add(Batcher& b, const Fr* poly, uint32_t lane) { cq.add(b, poly, tr_of(lane)); }
     void transforms(const std::vector<Prover::Forms>& cols) {
         if (!ok()) return;
         P[0]->transforms(cols);  // (flushes the shared row stager first)
     }
 
-    // the instance columns of every lane (a key with the column): ONE staged upload and ONE launch, where the lone prover has its
-    // memset + copy; every lane's list is its prover's (none: the empty column)
+    // the instance columns of every lane (a key with the column); every lane's list is its prover's (none: the empty column)
     int instance_columns() {
         if (!pk0->inst_val) return ZK_OK;
         static const std::vector<Fr> none;
+        // `lone`: memset + copy into the key's own column; several lanes: ONE staged upload and ONE launch, whose staging is the
+        // BatchBufs' — which a lone proof's key need not have
+        if (lone) return pk_instance_upload(c, st, pk0, P[0]->instance ? *P[0]->instance : none);
         std::vector<zk_pk_rec*> ws;
         std::vector<const std::vector<Fr>*> lists;
         for (Prover* p : P) {
@@ -133,12 +254,18 @@ struct LockstepRun {
         }
         return pk_instance_upload_lanes(c, st, pk0, ws, lists);
     }
-    // the columns' coefficient and coset forms ride with the lanes' first advice forms (Prover::with_instance's place)
+    // the columns' coefficient and coset forms ride with the lanes' first advice forms: a column's values are uploaded on the main
+    // stream before the first flush of blinding rows, which is what a transform on the side stream waits for
     void with_instances(std::vector<Prover::Forms>& fm) {
-        for (Prover* p : P) p->with_instance(fm);
+        for (Prover* p : P)
+            if (p->pk->inst_val) fm.push_back(Prover::Forms{p->pk->inst_val, p->pk->inst_poly, p->pk->inst_coset});
     }
 
     // ------------------------------------------------------------------ run ---
+    // Commitments are computed as early as their inputs exist (none of a', s', the random polynomial needs a challenge) and
+    // collected in transcript order; RNG draws keep halo2's order (the random polynomial's block range is reserved up front).  The
+    // coefficient and extended-coset forms the quotient needs are produced right behind each commitment's head: they need no
+    // challenge, and they keep the main stream busy while the MSM tails (and the host's transcript work) would leave it idle.
     int run(const Fr* const* advice /* B x n_adv, lane-major */, int scheme) {
         using Forms = Prover::Forms;
         const uint32_t bf = BLINDING_FACTORS, usable = lay.usable, np = proofs();
@@ -154,20 +281,23 @@ struct LockstepRun {
             for (Prover* p : P)
                 if (p->instance)
                     for (const Fr& v : *p->instance) P[0]->tr->common_scalar(v);  // (neither N nor the lengths are hashed)
-        // the three-coset route (poly.hip): one key, one context, one option — every begin() took the same decision; the members
-        // read the key's coset-major copies through their own records
+        // the three-coset route (poly.hip): one key, one context, one option — every begin() took the same decision; lane 0's made
+        // the key's coset-major copies, which the members read through their own records (pk_ensure_cosets3)
         const bool c3 = P[0]->cosets3;
-        if (c3 && (rc = pk_ensure_cosets3(c, pk0))) return rc;
         if (int r = instance_columns()) return r;
 
         // -- 1. advice of every lane
+        // (many columns: one launch copies a lane's — every lane stages into its own workspace's argument block.  That staging is
+        // reused by the later batched launches, each preceded by a stream-ordered upload, so the host must not overwrite it
+        // before the upload has been consumed: `lone` waits right behind its staging, several lanes once behind the last lane's rows)
         const bool many = advice_staged(lay);
         for (uint32_t q = 0; q < B; q++) {
             zk_pk_rec* pk = P[q]->pk;
             const Fr* const* adv = advice + (size_t)q * lay.n_adv;
-            // (many columns: every lane stages into its own workspace's argument block)
-            if (many)
+            if (many) {
                 if (int r = advice_columns_staged(c, st, pk, adv)) return r;
+                if (lone && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
+            }
             for (uint32_t j = 0; j < lay.n_adv; j++) {
                 if (!many)
                     if (int r = advice_column(c, st, pk, adv, j)) return r;
@@ -175,22 +305,34 @@ struct LockstepRun {
             }
             draw(q, lay.n_adv);  // advice blinds (unused by KZG, still drawn)
         }
-        if (many && aud_sync(c, st) != hipSuccess) return ZK_EHIP;  // the argument staging is reused below
+        if (many && !lone && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
         // one advice column and one lookup per lane (k = 19): the advice pass of all lanes stays in flight on lane 0
-        // while the lookup columns are made and committed; otherwise plain order, as Prover::run
+        // while the lookup columns are made and committed; otherwise plain order
         const bool pipe = lay.n_adv == 1 && lay.n_lookups == 1 && B <= pass_cap;
+        bool adv_transformed = false;
         Fifo af{{0}, {}, nullptr};
         if (pipe) {
             std::vector<Col> cols;
             for (uint32_t q = 0; q < B; q++) cols.push_back(Col{P[q]->pk->adv_val[0], tr_of(q)});
             cq.begin(af, cols, ZK_BASIS_LAGRANGE);
+            if (P[0]->xform_side()) {  // a lone proof on the transform stream: the advice column's forms are made under its own MSM pass
+                std::vector<Forms> fm;
+                for (uint32_t q = 0; q < B; q++) fm.push_back(Forms{P[q]->pk->adv_val[0], P[q]->pk->adv_poly[0], P[q]->pk->adv_coset[0]});
+                with_instances(fm);
+                transforms(fm);
+                adv_transformed = true;
+            }
         } else {
+            // several advice columns: whole batches of columns per MSM pass, up to MSM_LANES passes in flight, each followed by its
+            // columns' transforms; collected in column order
             Fifo f{{0, 1, 2}, {}, nullptr};
             std::vector<Col> cols;
             std::vector<Forms> fm;
-            with_instances(fm);  // (with the first pass's transforms)
+            bool first = true;
             auto go = [&]() {
                 cq.begin(f, cols, ZK_BASIS_LAGRANGE);
+                if (first) with_instances(fm);  // (with the first pass's transforms, behind its advice forms)
+                first = false;
                 transforms(fm);
                 cols.clear();
                 fm.clear();
@@ -217,6 +359,8 @@ struct LockstepRun {
                 theta_done = true;
             }
         };
+        // a', s' of every lookup: batches of columns per MSM pass; their transforms (and, in the pipelined case, the advice
+        // columns' where they have not gone out yet) follow the MSM heads so that they cover the tails
         // (no a' / s' commitment reaches a transcript before the proof's advice commitments and theta)
         Fifo lf{pipe ? std::vector<int>{1, 2} : std::vector<int>{0, 1, 2}, {}, squeeze_theta};
         Batcher lb = batcher(lf, ZK_BASIS_LAGRANGE);
@@ -229,7 +373,7 @@ struct LockstepRun {
                     zk_pk_rec* pk = P[q]->pk;
                     items.push_back(LkItem{pk, pk->adv_val.data(), l, pk->lk_ap[l], pk->lk_sp[l]});
                 }
-            if (int r = lookup_permute(c, st, lay, items, bb.lks)) return r;
+            if (int r = lookup_permute(c, st, lay, items, bufs.lks)) return r;
         }
         for (uint32_t q = 0; q < B && ok(); q++) {
             zk_pk_rec* pk = P[q]->pk;
@@ -248,9 +392,12 @@ struct LockstepRun {
             }
         }
         cq.flush(lb);
-        if (pipe) {
-            for (uint32_t q = 0; q < B; q++) due.push_back(Forms{P[q]->pk->adv_val[0], P[q]->pk->adv_poly[0], P[q]->pk->adv_coset[0]});
-            with_instances(due);
+        if (pipe && !adv_transformed) {
+            // (the advice columns' forms ahead of the lookups' in the one call, for every lane count)
+            std::vector<Forms> fm;
+            for (uint32_t q = 0; q < B; q++) fm.push_back(Forms{P[q]->pk->adv_val[0], P[q]->pk->adv_poly[0], P[q]->pk->adv_coset[0]});
+            with_instances(fm);
+            due.insert(due.begin(), fm.begin(), fm.end());
         }
         transforms(due);
         due.clear();
@@ -258,7 +405,7 @@ struct LockstepRun {
             // one check for all lookups of all lanes (the flag accumulates): an input outside the table is halo2's
             // ConstraintSystemFailure; nothing has been written for the lookups yet.  The call fails as a whole.
             bool bad = false;
-            if (int r = lookup_permute_failed(c, st, bb.lks, &bad)) return r;
+            if (int r = lookup_permute_failed(c, st, bufs.lks, &bad)) return r;
             if (bad) {
                 ctx_msm_drain(c);
                 return ZK_EWITNESS;
@@ -271,7 +418,7 @@ struct LockstepRun {
         const std::vector<Fr> gamma = squeeze();
 
         // -- 5 (early). the random polynomial of every proof — B, or the ONE: no challenge needed; its n draws come after the
-        // grand products' draws of all the proof's circuits, each proof's from its own key
+        // grand products' draws of all the proof's circuits, each proof's from its own key: that block range is reserved
         const uint32_t nprod = lay.n_chunks + lay.n_lookups;
         Fifo rf{{0}, {}, nullptr};
         // (more proofs than a pass takes: the random polynomials are committed after the grand products.  One proof: always early)
@@ -289,19 +436,23 @@ struct LockstepRun {
             if (rand_early) cq.begin(rf, cols, ZK_BASIS_MONOMIAL);
         }
 
-        // -- 3. grand products of every lane: numerators / denominators per lane, then ALL scans in one batch
+        // -- 3. grand products of every lane: numerators / denominators per lane, then ALL scans in one batch; the z columns
+        // (permutation chunks, lookups) are committed in batches on lanes 1 and 2, their transforms behind each batch's MSM head
         Fifo zf{{1, 2}, {}, nullptr};
         Batcher zb = batcher(zf, ZK_BASIS_LAGRANGE);
         std::vector<Forms> zdue;
         {
             std::vector<Fr*> zs;
             std::vector<GpGroup> groups;
+            // The argument staging of the many-column shapes may still be in use: the host waits before it rewrites it.  Several
+            // lanes, each with a staging of its own: once before the first lane's, and per lane between the two where both stage.
+            // `lone`: as late as it may — before the chunks' only if they stage, before the lookups' if those do
             const bool many_chunks = lay.n_chunks > BATCH_ARGS_MIN, many_lookups = lay.n_lookups > BATCH_ARGS_MIN;
-            if ((many_chunks || many_lookups) && aud_sync(c, st) != hipSuccess) return ZK_EHIP;  // the argument staging may still be in use
+            if ((many_chunks || (many_lookups && !lone)) && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
             for (uint32_t q = 0; q < B; q++) {
                 zk_pk_rec* pk = P[q]->pk;
                 if (int r = perm_numden_enqueue(c, st, pk, pk->adv_val.data(), P[q]->tw, beta[q], gamma[q], true)) return r;
-                if (many_chunks && many_lookups && aud_sync(c, st) != hipSuccess) return ZK_EHIP;  // the staging is rewritten below
+                if (many_lookups && (many_chunks || lone) && aud_sync(c, st) != hipSuccess) return ZK_EHIP;
                 if (int r = lk_numden_enqueue(c, st, pk, pk->adv_val.data(), pk->lk_ap.data(), pk->lk_sp.data(), beta[q], gamma[q], lay.n_chunks, true,
                                               false))
                     return r;
@@ -310,7 +461,7 @@ struct LockstepRun {
             }
             // (a lane's first product starts a new chain)
             for (uint32_t q = 0; q < B; q++) groups.push_back(GpGroup{P[q]->pk, zs.data() + (size_t)q * nprod, nprod, lay.n_chunks});
-            if (int r = grand_products(c, st, lay, groups, GpScratch{bb.d_gp_items, bb.gp_scal, bb.gp_host})) return r;
+            if (int r = grand_products(c, st, lay, groups, bufs.gp)) return r;
             // blinding rows and commitments, per proof in halo2's order: the permutation products of every circuit of the proof, then
             // its lookup products — B proofs: per proof chunks, then lookups; one proof: part-major over the circuits.  This fixes
             // the RNG order, the transcript order and how zdue groups the transforms
@@ -356,8 +507,12 @@ struct LockstepRun {
         if (!ok()) return rc;
         const std::vector<Fr> y = squeeze();
 
-        // -- 6. quotients into every proof's h_ext (P[p]->pk), then their inverse coset transforms
-        if (one) {
+        // -- 6. quotients into every proof's h_ext (P[p]->pk), then their inverse coset transforms (every coefficient / coset
+        // form was produced behind its commitment above)
+        if (lone) {
+            // Prover::quotient: the transforms on the side stream are joined first; one launch, one inverse transform
+            if (int r = P[0]->quotient(beta[0], gamma[0], y[0])) return r;
+        } else if (one) {
             // B passes into circuit 0's h_ext (the y-Horner chain runs on across the circuits: pass q carries y^(T (B - 1 - q));
             // circuit 0 stores, the others accumulate), then ONE inverse transform
             const uint32_t T = quotient_terms(lay.n_gate, lay.n_chunks, lay.n_lookups);
@@ -399,31 +554,32 @@ struct LockstepRun {
         }
         if (!ok()) return rc;
         const std::vector<Fr> x = squeeze();
+        HT("x squeezed");
 
-        // -- 7. evaluations: every opened value of every proof in ONE launch.  A proof's list is Prover::build_evals' over its
-        // circuits: B proofs, each its own; one proof, the concatenated one with fixed, sigma, random and h ONCE
+        // -- 7. evaluations: every opened value of every proof in ONE launch, then written in transcript order.  A proof's list
+        // is Prover::build_evals' over its circuits: B proofs, each its own; one proof, the concatenated one with fixed, sigma,
+        // random and h ONCE
         std::vector<std::vector<Prover::Q>> ev(np), queries(np);
         std::vector<Prover::EvIdx> ix(np);
         {
-            // (the shared buffers hold cap x one proof's openings: B proofs share them, the one proof has them all)
-            const size_t max_evals = one ? (size_t)bb.cap * pk0->max_evals : pk0->max_evals;
             size_t total = 0;
             for (uint32_t p = 0; p < np; p++) {
                 P[p]->combine_h(x[p]);
                 std::vector<const zk_pk_rec*> circuits;
                 for (uint32_t q = p; q < lanes_end(p); q++) circuits.push_back(P[q]->pk);
                 P[p]->build_evals(circuits, ev[p], ix[p]);
-                if (ev[p].size() > max_evals) return ZK_ESTATE;
+                if (ev[p].size() > bufs.max_evals) return ZK_ESTATE;
                 for (size_t i = 0; i < ev[p].size(); i++) {
-                    bb.h_evargs[total + i].poly = ev[p][i].poly;
-                    bb.h_evargs[total + i].x = P[p]->xrot(x[p], ev[p][i].rot);
+                    bufs.ev.h_items[total + i].poly = ev[p][i].poly;
+                    bufs.ev.h_items[total + i].x = P[p]->xrot(x[p], ev[p][i].rot);
                 }
                 total += ev[p].size();
             }
-            if (int r = evaluate_enqueue(c, st, EvalBufs{bb.h_evargs, bb.d_evargs, bb.ev_scratch, bb.ev_out, bb.tail_host}, (uint32_t)total, n)) return r;
+            if (int r = evaluate_enqueue(c, st, bufs.ev, (uint32_t)total, n)) return r;
+            HT("evals on host");
             size_t pos = 0;
             for (uint32_t p = 0; p < np; p++) {
-                for (size_t i = 0; i < ev[p].size(); i++) ev[p][i].eval = bb.tail_host[pos + i];
+                for (size_t i = 0; i < ev[p].size(); i++) ev[p][i].eval = bufs.ev.host[pos + i];
                 pos += ev[p].size();
                 for (size_t i = 0; i < ix[p].n_written; i++) P[p]->tr->write_scalar(ev[p][i].eval);
                 queries[p] = P[p]->queries_from_evals(ev[p], ix[p]);
@@ -431,9 +587,11 @@ struct LockstepRun {
             }
         }
         if (!ok()) return rc;
+        HT("queries built");
 
         // -- 8. multi-open: the stages of every proof, from its prover's workspace, the commitments between them merged
         if (scheme == ZK_SCHEME_GWC) {
+            // the witness polynomials need no challenge in between: all of them go through one MSM pass
             Fifo wf{{0, 1, 2}, {}, nullptr};
             Batcher wb = batcher(wf, ZK_BASIS_MONOMIAL);
             for (uint32_t p = 0; p < np && ok(); p++) {
@@ -446,8 +604,9 @@ struct LockstepRun {
             return ok() ? ZK_OK : rc;
         }
         std::vector<Prover::Shplonk> S(np);
-        // (a queue takes the LAST of its free lanes: the one proof's single commitments stay on lane 0, as Prover::commit_write's)
-        Fifo of{one ? std::vector<int>{0} : std::vector<int>{0, 1, 2}, {}, nullptr};
+        // (a queue takes the LAST of its free lanes: the single commitments of one proof — the lone one, or the one over B
+        // circuits — stay on lane 0)
+        Fifo of{np == 1 ? std::vector<int>{0} : std::vector<int>{0, 1, 2}, {}, nullptr};
         {
             Batcher ob = batcher(of, ZK_BASIS_MONOMIAL);
             for (uint32_t p = 0; p < np && ok(); p++) {

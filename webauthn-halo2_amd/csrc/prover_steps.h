@@ -1,8 +1,8 @@
-// prover_steps.h — the steps of create_proof that more than one driver takes: ONE definition each, called by the single prover
-// (prover.hip Prover::run), the lock-step prover (prover_lockstep.h LockstepRun::run) and the phase-level entry points
-// (prover_phases.hip).  A step enqueues on the stream it is given and names its buffers to the stream audit (audit.h) when that is
-// on; WHICH step runs, in which order, on which lane, and when the host waits is the drivers' business — no step synchronises
-// except where its result is read by the host (the grand products' scan totals, the lookup error flag, the evaluations).
+// prover_steps.h — the steps of create_proof: ONE definition each, called by the whole-proof driver (prover_lockstep.h
+// LockstepRun::run: one lane or several) and the phase-level entry points (prover_phases.hip).  A step enqueues on the stream it is
+// given and names its buffers to the stream audit (audit.h) when that is on; WHICH step runs, in which order, on which lane, and
+// when the host waits is the callers' business — no step synchronises except where its result is read by the host (the grand
+// products' scan totals, the lookup error flag, the evaluations).
 #pragma once
 #include <algorithm>
 #include <deque>
@@ -366,98 +366,9 @@ inline void lincomb_enqueue(hipStream_t st, Fr* out, uint32_t n, const std::vect
 }
 
 // ------------------------------------------------------------- commitments ---
-// a column to commit, and the transcript that receives its point
+// a column to commit, and the transcript that receives its point (the queue of commitments in flight over the MSM lanes is the
+// driver's: prover_lockstep.h LockstepRun::Commits — one proof: every column carries the proof's transcript; several: each its owner's)
 struct CommitCol {
     const Fr* poly;
     Transcript* to;
-};
-// Commitments in flight over MSM lanes, collected — written to their transcripts — in the order they were begun.  D is the driver
-// that owns the error state and the staged blinding rows: d.ok(), d.fail(code), d.rows_flush() (the rows of the columns about to
-// be read go up first), d.c, d.n.  One proof: every column carries the proof's transcript; a lock-step batch: each its owner's.
-template <class D>
-struct Commits {
-    D& d;  // (a driver holds its queue as a member bound to itself: drivers are not copyable)
-    struct Pass {
-        int lane;
-        std::vector<Transcript*> to;
-    };
-    // a set of lanes used in turn; a one-lane queue is a commitment begun on a fixed lane and collected later (drain)
-    struct Fifo {
-        std::vector<int> lanes;
-        std::deque<Pass> busy;
-        // run before a pass of this queue is collected: what the transcripts must hold first (the lookup passes of a pipelined
-        // proof may fill their lanes while the advice pass is still in flight on its own)
-        std::function<void()> before_collect;
-    };
-    // gathers columns into passes of at most `cap`; flush() begins what is pending.  A pass of four or more columns goes as two
-    // passes on two lanes — the first half's reduction tail runs under the second half's head — unless `loaded`: that pays only
-    // while the tails have a stream of their own (a lone proof, two pipelines); under load — tails on the main stream — a second
-    // pass is just a second head and tail (k = 17 EVM over four pipelines: 232.9 -> 236.9 proofs/s unsplit).  The single prover
-    // passes its own flag (Prover::loaded), the lock-step prover false
-    struct Batcher {
-        Fifo* f;
-        int basis;
-        uint32_t cap;
-        bool loaded;
-        std::vector<CommitCol> pend;
-    };
-
-    void begin(Fifo& f, const std::vector<CommitCol>& cols, int basis) {
-        if (!d.ok() || cols.empty()) return;
-        if (f.busy.size() == f.lanes.size()) {
-            if (f.before_collect) f.before_collect();
-            end_write(f.busy.front());
-            f.busy.pop_front();
-        }
-        int lane = -1;
-        for (int l : f.lanes) {
-            bool used = false;
-            for (const Pass& ps : f.busy) used = used || ps.lane == l;
-            if (!used) lane = l;
-        }
-        d.rows_flush();
-        if (!d.ok()) return;
-        std::vector<const Fr*> polys;
-        Pass ps{lane, {}};
-        for (const CommitCol& cl : cols) {
-            polys.push_back(cl.poly);
-            ps.to.push_back(cl.to);
-        }
-        int r = ctx_msm_begin_batch(d.c, lane, polys.data(), (uint32_t)polys.size(), ctx_basis(d.c, basis), d.n);
-        if (r) return d.fail(r);
-        f.busy.push_back(ps);
-    }
-    // collects a pass: its commitments are written to their transcripts in the order the columns were given
-    void end_write(const Pass& ps) {
-        if (!d.ok()) return;
-        G1Jac js[MSM_MAX_BATCH];
-        int r = ctx_msm_end_batch(d.c, ps.lane, js);
-        if (r) return d.fail(r);
-        G1Affine af[MSM_MAX_BATCH];
-        const uint32_t cnt = (uint32_t)ps.to.size();
-        jac_batch_to_affine(js, cnt, af);
-        for (uint32_t q = 0; q < cnt && d.ok(); q++)
-            if (!ps.to[q]->write_point(af[q])) d.fail(ZK_EINVAL);  // identity: halo2 refuses to write it
-    }
-    void drain(Fifo& f) {
-        if (f.before_collect && !f.busy.empty()) f.before_collect();
-        while (!f.busy.empty()) {
-            end_write(f.busy.front());
-            f.busy.pop_front();
-        }
-    }
-    void add(Batcher& b, const Fr* poly, Transcript* to) {
-        b.pend.push_back(CommitCol{poly, to});
-        if (b.pend.size() >= b.cap) flush(b);
-    }
-    void flush(Batcher& b) {
-        if (b.pend.size() >= 4 && b.f->lanes.size() >= 2 && !b.loaded) {
-            const size_t h = (b.pend.size() + 1) / 2;
-            begin(*b.f, std::vector<CommitCol>(b.pend.begin(), b.pend.begin() + h), b.basis);
-            begin(*b.f, std::vector<CommitCol>(b.pend.begin() + h, b.pend.end()), b.basis);
-        } else {
-            begin(*b.f, b.pend, b.basis);
-        }
-        b.pend.clear();
-    }
 };

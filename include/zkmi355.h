@@ -700,6 +700,26 @@ int zk_verify_batch_public(zk_ctx* ctx, zk_pk pk, size_t batch, int transcript, 
                            const size_t* n_instances, const uint8_t* const* proofs, const size_t* lens, uint8_t* verdicts);
 int zk_verify_multi_public(zk_ctx* ctx, zk_pk pk, size_t n_circuits, int transcript, int scheme, const uint64_t* const* instances_mont,
                            const size_t* n_instances, const uint8_t* proof, size_t len, int* ok);
+
+/* The EVM verifier of ONE kind of proof, as the text of a Yul program (the reference's /generate_evm_verifier; csrc/evm_codegen.h):
+ * proofs of `pk` (full or verifying-only: the same bytes) over n_circuits circuits with n_instances[c] public inputs in circuit c
+ * (NULL: none anywhere), made with the EVM transcript and `scheme` (ZK_SCHEME_DEFAULT is GWC), checked against the g2 / s_g2 of the
+ * context's resident SRS.  The program takes the calldata [every instance, circuit-major, as a 32-byte big-endian word][the proof],
+ * of one exact length, and reverts unless the proof verifies: it accepts exactly what zk_verify / zk_verify_public / zk_verify_multi /
+ * zk_verify_multi_public accept for the same lists.  The text is a function of the arguments alone (no time stamp, no address).
+ * out == NULL: only *len is set, like zk_vk_write; cap < *len: ZK_EINVAL with *len set.  ZK_EINVAL also: NULL ctx / len, n_circuits
+ * == 0 or > ZK_PROVE_MULTI_MAX, a non-zero count on a key without the instance column, a count above n - 7, an unknown scheme, a
+ * bad handle.  ZK_ESTATE as zk_verify (no SRS or no G2 half; a full key whose SRS was replaced).  `out` is untouched on every error.
+ * Host work only: nothing is launched.  The text has not been compiled by solc nor run on an EVM by anyone: the suite runs it in
+ * an interpreter of the Yul subset it uses. */
+typedef struct {
+    uint32_t calldata_bytes, memory_bytes, modexp, ecadd, ecmul, pairing, keccak_calls, keccak_bytes;
+} zk_evm_cost;
+int zk_evm_verifier(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const size_t* n_instances /* n_circuits, NULL = none */, int scheme,
+                    char* out, size_t cap, size_t* len);
+/* what that program costs, counted where it is generated: calldata length, the top of the memory it touches, its calls of
+ * precompiles 5 / 6 / 7 / 8 and its keccak256 calls with the bytes they hash.  Errors as zk_evm_verifier (out untouched). */
+int zk_evm_verifier_cost(zk_ctx* ctx, zk_pk pk, size_t n_circuits, const size_t* n_instances, int scheme, zk_evm_cost* out);
 /* where zk_verify_batch_public / zk_verify_multi_public evaluate inst(x): mode 0 auto, 1 on the host (verifier.h, one batch inversion
  * per list), 2 on the device (zk_instance_eval's kernel: one launch for every list of the call).  Same verdicts.  Auto is the host:
  * the two have NOT been measured against each other (tools/verify_public_rate.py is the tool).  zk_verify_public always evaluates

@@ -139,6 +139,35 @@ inline std::vector<int> gwc_rotations(const std::vector<Query>& qs) {
     return rots;
 }
 
+// SHPLONK: the commitments by rotation set.  Commitments with their rotations in order of first appearance; the sets (each sorted)
+// in order of first appearance, each with its commitments in that order; all_rots: the distinct rotations by first appearance
+struct RSet {
+    std::vector<int> rots;  // sorted
+    std::vector<uint32_t> keys;
+};
+inline std::vector<RSet> shplonk_sets(const std::vector<Query>& qs, std::vector<int>* all_rots) {
+    struct ComRots {
+        uint32_t key;
+        std::vector<int> rots;
+    };
+    std::vector<ComRots> cr;
+    all_rots->clear();
+    for (const Query& q : qs) {
+        if (std::find(all_rots->begin(), all_rots->end(), q.rot) == all_rots->end()) all_rots->push_back(q.rot);
+        auto it = std::find_if(cr.begin(), cr.end(), [&](const ComRots& c2) { return c2.key == q.key; });
+        if (it == cr.end()) cr.push_back({q.key, {q.rot}});
+        else if (std::find(it->rots.begin(), it->rots.end(), q.rot) == it->rots.end()) it->rots.push_back(q.rot);
+    }
+    std::vector<RSet> rs;
+    for (ComRots& c2 : cr) {
+        std::sort(c2.rots.begin(), c2.rots.end());
+        auto it = std::find_if(rs.begin(), rs.end(), [&](const RSet& r) { return r.rots == c2.rots; });
+        if (it == rs.end()) rs.push_back({c2.rots, {c2.key}});
+        else it->keys.push_back(c2.key);
+    }
+    return rs;
+}
+
 inline ProofLayout proof_layout(const Layout& lay, bool evm, bool shplonk, uint32_t nc = 1) {
     ProofLayout pl;
     pl.nc = nc;
@@ -429,30 +458,8 @@ inline bool prepare_lists(const Layout& lay, const Fr& transcript_repr, const Pr
         }
         B.push_back({fe_neg(eval_multi), pl.base_g0()});
     } else {
-        // commitments with their rotation sets, by first appearance; rotation sets keyed by the set, by first appearance
-        struct ComRots {
-            uint32_t key;
-            std::vector<int> rots;
-        };
-        std::vector<ComRots> cr;
         std::vector<int> all_rots;
-        for (const Query& q : qs) {
-            if (std::find(all_rots.begin(), all_rots.end(), q.rot) == all_rots.end()) all_rots.push_back(q.rot);
-            auto it = std::find_if(cr.begin(), cr.end(), [&](const ComRots& c2) { return c2.key == q.key; });
-            if (it == cr.end()) cr.push_back({q.key, {q.rot}});
-            else if (std::find(it->rots.begin(), it->rots.end(), q.rot) == it->rots.end()) it->rots.push_back(q.rot);
-        }
-        struct RSet {
-            std::vector<int> rots;  // sorted
-            std::vector<uint32_t> keys;
-        };
-        std::vector<RSet> rs;
-        for (ComRots& c2 : cr) {
-            std::sort(c2.rots.begin(), c2.rots.end());
-            auto it = std::find_if(rs.begin(), rs.end(), [&](const RSet& r) { return r.rots == c2.rots; });
-            if (it == rs.end()) rs.push_back({c2.rots, {c2.key}});
-            else it->keys.push_back(c2.key);
-        }
+        const std::vector<RSet> rs = shplonk_sets(qs, &all_rots);
         auto eval_of = [&](uint32_t key, int rot) {
             Fr e = Fr::zero();
             for (const Query& q : qs)

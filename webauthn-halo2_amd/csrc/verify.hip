@@ -16,6 +16,7 @@
 //      zk_verify_pairing_mode 2 a failing fold of two or more proofs is settled by ONE launch of the device pairing instead
 //      (pairing.hip: every (A_j, B_j) of the set, one check per lane); auto is the host.
 // zk_verify is the batch of one: the same path, without a fold.
+// zk_evm_verifier / zk_evm_verifier_cost: the same rule emitted as a Yul program for one kind of proof (evm_codegen.h; host only).
 // Public inputs: every proof (zk_verify_batch_public) or circuit (zk_verify_multi_public) has its instance list; step 2 absorbs them
 // and needs inst(x) per list — on the host inside verifier.h, or (zk_verify_instance_eval_mode 2) every transcript runs to x, ONE
 // launch of instance_eval_kernel evaluates every list of the call, and the term lists take those values.  zk_instance_eval is
@@ -25,6 +26,7 @@
 #include <algorithm>
 #include <thread>
 
+#include "evm_codegen.h"
 #include "pairing.h"
 #include "pk.h"
 #include "verifier.h"
@@ -435,6 +437,57 @@ ZK_API(zk_vk_from_parts, (zk_ctx* c, const zk_circuit_params* params, const uint
             if (!affine_is_identity(p) && fe_sqr(p.y) != fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3))) return ZK_EINVAL;
         }
     return pk_make_verify_only(c, lay, fixed, perm, transcript_repr, out);
+}
+
+// the description of the program of zk_evm_verifier: the key's shape, commitments and transcript_repr, the resident SRS's G2 half
+static int evm_description(zk_ctx* c, zk_pk h, size_t n_circuits, const size_t* n_instances, int scheme, zk::evmgen::Desc* d) {
+    if (n_circuits == 0 || n_circuits > ZK_PROVE_MULTI_MAX) return ZK_EINVAL;
+    if (int r = resolve_scheme(ZK_TRANSCRIPT_EVM, &scheme)) return r;
+    auto it = c->pks.find(h);
+    if (it == c->pks.end()) return ZK_EINVAL;
+    const zk_pk_rec* pk = it->second;
+    const Layout& lay = pk->lay;
+    d->n_instances.assign(n_circuits, 0);
+    for (size_t i = 0; n_instances && i < n_circuits; i++) {
+        if (n_instances[i] > lay.usable || (n_instances[i] && !lay.n_inst)) return ZK_EINVAL;  // halo2's InstanceTooLarge
+        d->n_instances[i] = (uint32_t)n_instances[i];
+    }
+    if (!pk->verify_only && pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // as zk_verify
+    if (c->srs_k < 0 || !c->g2_valid) return ZK_ESTATE;
+    d->params = zk_circuit_params{lay.k, lay.A, lay.L, lay.F, lay.lookup_bits, lay.idle, lay.n_inst};
+    d->fixed = pk->fixed_commit;
+    d->perm = pk->perm_commit;
+    d->transcript_repr = pk->transcript_repr;
+    d->g2 = g2_from_raw(c->g2_raw);
+    d->s_g2 = g2_from_raw(c->s_g2_raw);
+    d->n_circuits = (uint32_t)n_circuits;
+    d->shplonk = scheme == ZK_SCHEME_SHPLONK;
+    return ZK_OK;
+}
+
+ZK_API(zk_evm_verifier, (zk_ctx* c, zk_pk h, size_t n_circuits, const size_t* n_instances, int scheme, char* out, size_t cap, size_t* len), (c, h, n_circuits, n_instances, scheme, out, cap, len)) {
+    if (!c || !len) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    zk::evmgen::Desc d;
+    if (int r = evm_description(c, h, n_circuits, n_instances, scheme, &d)) return r;
+    std::string text;
+    if (!zk::evmgen::generate(d, &text, nullptr)) return ZK_EINVAL;
+    *len = text.size();
+    if (!out) return ZK_OK;
+    if (cap < text.size()) return ZK_EINVAL;
+    memcpy(out, text.data(), text.size());
+    return ZK_OK;
+}
+
+ZK_API(zk_evm_verifier_cost, (zk_ctx* c, zk_pk h, size_t n_circuits, const size_t* n_instances, int scheme, zk_evm_cost* out), (c, h, n_circuits, n_instances, scheme, out)) {
+    if (!c || !out) return ZK_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    zk::evmgen::Desc d;
+    if (int r = evm_description(c, h, n_circuits, n_instances, scheme, &d)) return r;
+    zk_evm_cost cost;
+    if (!zk::evmgen::generate(d, nullptr, &cost)) return ZK_EINVAL;
+    *out = cost;
+    return ZK_OK;
 }
 
 namespace {

@@ -45,7 +45,7 @@ import time
 import numpy as np
 
 from . import circuit
-from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_SRS_CONTRIB_LINKS,
+from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_SRS_CONTRIB_LINKS,
                      ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT, ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
                      ZK_ES256_BATCH_MAX, ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
 
@@ -885,3 +885,17 @@ def verify_multi(degree: int, proof: bytes, verifying_key_path: str, n: int, evm
     if len(instances) != n:
         raise ValueError("one instance list per circuit")
     return eng.verify_multi_public(vk, bytes(proof), [_mont_limbs(l) for l in instances], t, s)
+
+
+def generate_verifier(verifying_key_path: str, degree: int, n: int = 1, public: bool = False, scheme=None, device: int = 0) -> str:
+    """`generate_verifier` (ecdsa_p256.rs:275-327), the Yul half: the text of the EVM verifier of the proofs of the key in the file
+    under gen_srs(degree) - of ONE proof over n circuits (n = 1: generate_proof_evm's; above: create_proof_multi_from_advice's with
+    the EVM transcript), with the nine values of public_inputs per circuit when public (the key of a circuit with public inputs).
+    scheme: ZK_SCHEME_GWC (None: the EVM transcript's default, GWC) or ZK_SCHEME_SHPLONK.  The program's calldata is
+    encode_calldata's: every circuit's instance words in circuit order, then the proof.  The reference then compiles the text with
+    solc, runs the bytecode on revm against a valid proof and rewrites the text as Solidity; the engine carries no solc and stops
+    at the text - nobody has compiled it or run it on an EVM (the suite runs it in an interpreter of the Yul subset it uses)."""
+    eng, vk = _resident_vk(degree, verifying_key_path, device, public)
+    p = _config_for(degree)
+    counts = [3 * p.num_limbs] * n if public else None
+    return eng.evm_verifier(vk, n, counts, ZK_SCHEME_DEFAULT if scheme is None else scheme)

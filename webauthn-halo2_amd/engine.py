@@ -148,6 +148,11 @@ def lib_path():
     return os.environ.get("ZKMI355_LIB") or os.path.join(_HERE, "libzkmi355.so")
 
 
+class EvmCostC(ctypes.Structure):  # zk_evm_cost
+    _fields_ = [(n, ctypes.c_uint32) for n in ("calldata_bytes", "memory_bytes", "modexp", "ecadd", "ecmul", "pairing", "keccak_calls",
+                                               "keccak_bytes")]
+
+
 def load_library():
     """Load libzkmi355.so; raises if it has not been built (./build.sh)."""
     global _LIB
@@ -284,6 +289,8 @@ def load_library():
         "zk_pairing_check_batch": ([vp, sz, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "zk_verify_pairing_mode": ([vp, ctypes.c_int], ctypes.c_int),
         "zk_verify_pairing_stats": ([vp, u64p], ctypes.c_int),
+        "zk_evm_verifier": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
+        "zk_evm_verifier_cost": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(sz), ctypes.c_int, ctypes.POINTER(EvmCostC)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name, None)
@@ -292,7 +299,8 @@ def load_library():
                         "zk_prove_multi", "zk_verify_multi", "zk_prove_public", "zk_verify_public", "zk_witness_check_public",
                         "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
                         "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify",
-                        "zk_pairing_check_batch", "zk_verify_pairing_mode", "zk_verify_pairing_stats") and os.environ.get("ZKMI355_LIB"):
+                        "zk_pairing_check_batch", "zk_verify_pairing_mode", "zk_verify_pairing_stats", "zk_evm_verifier",
+                        "zk_evm_verifier_cost") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -1057,6 +1065,33 @@ class Engine:
         ok = ctypes.c_int(0)
         self._chk(self.L.zk_verify(self.ctx, pk, transcript, scheme, proof, len(proof), ctypes.byref(ok)), "zk_verify")
         return bool(ok.value)
+
+    @staticmethod
+    def _evm_counts(n_circuits, n_instances):
+        if n_instances is None:
+            return None
+        if len(n_instances) != n_circuits:
+            raise ValueError("one instance count per circuit")
+        return (ctypes.c_size_t * max(n_circuits, 1))(*[int(m) for m in n_instances])
+
+    def evm_verifier(self, pk, n_circuits=1, n_instances=None, scheme=ZK_SCHEME_DEFAULT) -> str:
+        """zk_evm_verifier: the text of the Yul program that verifies, on the EVM, ONE proof of `pk` (full or verifying-only) over
+        n_circuits circuits with n_instances[c] public inputs in circuit c (None: none), made with the EVM transcript and `scheme`
+        (default GWC) under the resident SRS.  Its calldata is ecdsa_p256.encode_calldata's: all instances, then the proof."""
+        counts = self._evm_counts(n_circuits, n_instances)
+        ln = ctypes.c_size_t()
+        self._chk(self.L.zk_evm_verifier(self.ctx, pk, n_circuits, counts, scheme, None, 0, ctypes.byref(ln)), "zk_evm_verifier")
+        buf = ctypes.create_string_buffer(ln.value)
+        self._chk(self.L.zk_evm_verifier(self.ctx, pk, n_circuits, counts, scheme, buf, len(buf), ctypes.byref(ln)), "zk_evm_verifier")
+        return buf.raw[:ln.value].decode("ascii")
+
+    def evm_verifier_cost(self, pk, n_circuits=1, n_instances=None, scheme=ZK_SCHEME_DEFAULT) -> dict:
+        """zk_evm_verifier_cost: that program's calldata length, memory top, precompile calls (modexp, ecadd, ecmul, pairing) and
+        keccak256 calls / hashed bytes, counted where it is generated."""
+        out = EvmCostC()
+        self._chk(self.L.zk_evm_verifier_cost(self.ctx, pk, n_circuits, self._evm_counts(n_circuits, n_instances), scheme, ctypes.byref(out)),
+                  "zk_evm_verifier_cost")
+        return {n: int(getattr(out, n)) for n, _ in EvmCostC._fields_}
 
     def verify_batch(self, pk, proofs, transcript, scheme=ZK_SCHEME_DEFAULT):
         """zk_verify_batch: one verdict per proof, each what verify() says of it (batches above ZK_VERIFY_BATCH_MAX are split)."""

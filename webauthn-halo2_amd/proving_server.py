@@ -12,6 +12,9 @@ be replayed against the engine):
     struct VerifyRequestBody { verifying_key_path: String, proof: String }      main.rs:409-413
     POST /verify     -> verify(DEGREE, hex::decode(proof)?, path) ? "verified" : "rejected"      main.rs:415-425
     POST /verify_evm -> verify_evm(DEGREE, hex::decode(proof)?, path) ? "verified" : "rejected"  main.rs:427-439
+    struct GenerateEVMVerifierRequestBody { verifying_key_path, valid_proof_hex, deploy_code_path, sol_code_path, yul_code_path }
+    POST /generate_evm_verifier -> the Yul text of generate_verifier(path, DEGREE, ..), written to yul_code_path   main.rs:376-409
+                                   (the Solidity rewrite and the deployment bytecode need solc: not made here)
     const DEGREE: u32 = 17                                             main.rs:17
 
 The five byte arrays are LITTLE-endian, as the web client builds them (web-demo/src/pages/index.tsx:285-293:
@@ -276,3 +279,30 @@ def verify_multi(body, evm=True, device=0, degree=DEGREE, public=0) -> str:
         return "rejected"  # (a generated verifier contract reverts on a non-canonical instance word)
     lists = [words[c * public:(c + 1) * public] for c in range(n)]
     return "verified" if ecdsa_p256.verify_multi(degree, proof, path, n, evm, device, lists) else "rejected"
+
+
+def generate_evm_verifier(body, device=0, degree=DEGREE, public=0, n=1) -> str:
+    """POST /generate_evm_verifier: GenerateEVMVerifierRequestBody (JSON string / dict) -> the Yul text of the EVM verifier of the
+    proofs of the verifying key in `verifying_key_path` (ecdsa_p256.generate_verifier), written to `yul_code_path` and returned.
+    public: the key is that of the circuit with public inputs (setup(public=True)) - every circuit carries its nine instance words;
+    n: the program verifies ONE proof over n requests (prove_multi's).  The reference also compiles the text with solc into
+    deployment bytecode (`deploy_code_path`), runs it on revm against `valid_proof_hex` and rewrites the text as Solidity
+    (`sol_code_path`); the engine carries no solc, so a non-empty `sol_code_path` or `deploy_code_path` is a ValueError, and
+    `valid_proof_hex` is not read."""
+    if isinstance(body, (str, bytes, bytearray)):
+        body = json.loads(body)
+    if not isinstance(body, dict):
+        raise ValueError("request body must be a JSON object")
+    path, yul_path = body.get("verifying_key_path"), body.get("yul_code_path")
+    if not isinstance(path, str):
+        raise ValueError("verifying_key_path: expected a string")
+    if not isinstance(yul_path, str) or not yul_path:
+        raise ValueError("yul_code_path: expected a file name")
+    for f in ("sol_code_path", "deploy_code_path"):
+        if body.get(f):
+            raise ValueError(f"{f}: the Solidity rewrite and the deployment bytecode need solc, which the engine does not carry; "
+                             "leave it empty and compile the Yul text elsewhere")
+    text = ecdsa_p256.generate_verifier(path, degree, n, bool(public), None, device)
+    with open(yul_path, "w") as f:
+        f.write(text)
+    return text

@@ -262,6 +262,14 @@ int zk_srs_update(zk_ctx* ctx, const uint8_t seed[32], zk_srs_contribution* out)
 #define ZK_SRS_CONTRIB_NONTRIVIAL  4u /* all points on their curves; s_g1 neither the identity nor the generator */
 #define ZK_SRS_CONTRIB_RESIDENT    8u /* after_g1 is g[1] of the context's resident SRS (clear if it has none) */
 int zk_srs_contribution_check(zk_ctx* ctx, const zk_srs_contribution* c, uint32_t* flags);
+/* a chain of receipts in one launch on the device, one receipt per lane: flags[i] is what zk_srs_contribution_check gives for
+ * c[i] (RESIDENT included; clear everywhere without a resident SRS, which the call does not need), plus CHAINED, which the host
+ * adds.  Each lane tests its four points and walks its own s_g2 once through the Miller loop for both equations (csrc/pairing.h
+ * contribution_check_lanes).  A bad receipt is a verdict, never an error.
+ * ZK_EINVAL: NULL arguments, count == 0 or > ZK_SRS_CONTRIB_BATCH_MAX.  flags is untouched on every error. */
+#define ZK_SRS_CONTRIB_CHAINED 16u /* i == 0, or before_g1 equals receipt i-1's after_g1 byte for byte */
+#define ZK_SRS_CONTRIB_BATCH_MAX 4096
+int zk_srs_contribution_check_batch(zk_ctx* ctx, size_t count, const zk_srs_contribution* c, uint32_t* flags /* count */);
 
 /* ---- resident polynomials -------------------------------------------------- */
 int zk_poly_alloc(zk_ctx* ctx, size_t n, zk_poly* out);
@@ -777,6 +785,18 @@ int zk_es256_verify(zk_ctx* ctx, size_t count, const uint8_t* sigs /* count x 16
 int zk_pairing_check_batch(zk_ctx* ctx, size_t count, const uint64_t* a /* count x 8 */, const uint64_t* b /* count x 8 */,
                            const uint64_t g2[16], const uint64_t s_g2[16], uint8_t* verdicts /* count: 1 = holds */,
                            uint8_t* reasons /* count, may be NULL */);
+/* The same check with a G2 point PER ITEM: `count` checks e(a_i, q_i) = e(b_i, g2) in one launch, one per lane.  q_i are 16-word
+ * images like g2's; g2 is the caller's, or with NULL the resident SRS's.  No walk of q_i can be prepared, so the lane tests its q_i
+ * ([r] q_i in Jacobian coordinates) and walks it through the Miller loop itself, inverting nothing; g2's lines come from a
+ * prepared table as above.  Reasons are zk_pairing_check_batch's in its order, the G1 tests first, then
+ *   ZK_PAIRING_G2         q_i not a proper G2 point (range, off the twist, outside the subgroup, identity)
+ * and ZK_PAIRING_MISMATCH last.  A bad item is a verdict, never an error.
+ * ZK_EINVAL: ctx, a, b, q or verdicts NULL, count == 0 or > ZK_PAIRING_BATCH_MAX, a given g2 that is not a proper G2 point.
+ * ZK_ESTATE: g2 NULL and no SRS or no G2 half resident.  Outputs are untouched on every error. */
+#define ZK_PAIRING_G2 4            /* q_i not a proper G2 point (range, off the twist, outside the subgroup, identity) */
+int zk_pairing_check_each(zk_ctx* ctx, size_t count, const uint64_t* a /* count x 8 */, const uint64_t* b /* count x 8 */,
+                          const uint64_t* q /* count x 16 */, const uint64_t g2[16] /* NULL: the resident SRS's */,
+                          uint8_t* verdicts /* count: 1 = holds */, uint8_t* reasons /* count, may be NULL */);
 /* How zk_verify_batch / zk_verify_batch_public settle a set of two or more proofs whose folded check fails.  HOST: the set is
  * halved and each half folded and paired again (up to 2 B - 1 host pairings when every proof fails).  DEVICE: the first fold is
  * still one host check — an all-good batch costs what it always did —, and when it fails every proof of the set goes through one

@@ -8,9 +8,11 @@
 // Host and device: the tower, the Frobenius map (its constants are an argument: the device reads them as data), the line
 // evaluation, the Miller loop over PREPARED lines (pairing_prepare walks T once per G2 point on the host and keeps every
 // step's slope and constant, so the evaluation inverts nothing and does not depend on G2 arithmetic), and a final
-// exponentiation without a table (final_exponentiation_chain: three powers by u and the Frobenius maps).  Host only: G2
-// arithmetic, the table of constants, multi_miller_loop and final_exponentiation — the latter takes the hard part as one
-// multi-exponentiation of f, f^p, f^p^2, f^p^3 by the base-p digits of the exponent through a 16-entry Fq12 table, which a
+// exponentiation without a table (final_exponentiation_chain: three powers by u and the Frobenius maps); and, for a check that
+// brings its own G2 point (zk_pairing_check_each, zk_srs_contribution_check_batch), inversion-free G2 arithmetic in Jacobian
+// coordinates, the subgroup test on it and a Miller loop that walks that point while it evaluates (miller_loop_walk).  Host
+// only: affine G2 arithmetic, the table of constants, multi_miller_loop and final_exponentiation — the latter takes the hard part as
+// one multi-exponentiation of f, f^p, f^p^2, f^p^3 by the base-p digits of the exponent through a 16-entry Fq12 table, which a
 // lane could only keep in scratch.  The same Fq2 / G2 helpers serve the SRS file's G2 half (serde.hip).
 // On the device the Fq2 / Fq6 / Fq12 products are calls, not copies per use (ZK_PAIR_MULFN): inlined, a check is about
 // 33 000 field-product sites and many times the instruction cache.
@@ -28,6 +30,14 @@
 #define ZK_PAIRING_RANGE 1
 #define ZK_PAIRING_OFF_CURVE 2
 #define ZK_PAIRING_MISMATCH 3
+#endif
+#ifndef ZK_PAIRING_G2
+#define ZK_PAIRING_G2 4
+#endif
+#ifndef ZK_SRS_CONTRIB_SAME_SECRET
+#define ZK_SRS_CONTRIB_SAME_SECRET 1u
+#define ZK_SRS_CONTRIB_LINKS 2u
+#define ZK_SRS_CONTRIB_NONTRIVIAL 4u
 #endif
 
 #define ZK_PAIR_FN __host__ __device__ inline
@@ -482,6 +492,180 @@ ZK_PAIR_FN uint8_t pairing_check_lines(const G1Affine& a, const G1Affine& b, con
     nb.y = fe_neg(b.y);  // (the identity stays (0, 0))
     const Fq12 f = final_exponentiation_chain(miller_loop_lines(a, nb, t), t.gamma);
     return f12_is_one(f) ? ZK_PAIRING_VALID : ZK_PAIRING_MISMATCH;
+}
+
+// a point of G1 other than the identity: both coordinates reduced, y^2 = x^3 + 3 (G1 has cofactor 1)
+ZK_PAIR_FN bool g1_is_proper(const G1Affine& p) {
+    if (!fq_is_canonical(p.x) || !fq_is_canonical(p.y) || affine_is_identity(p)) return false;
+    return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
+}
+
+// ---- G2 on a lane: a G2 point per check -------------------------------------------------------------------------------------
+// A lane that brings its own G2 point walks it through the Miller loop itself, so the walk may not invert: T is kept in Jacobian
+// coordinates (x / z^2, y / z^3; z = 0 the identity) and a step hands out its line times a factor of Fq2 — the final
+// exponentiation sends every element of a proper subfield to 1, so what is pinned is the value after final_exponentiation_chain.
+struct G2J {
+    Fq2 x, y, z;
+};
+// a step's line before it meets a G1 point P: a yP + b xP w + c w^3, pairing_line_at's line times 2 yT z^3 (a doubling) or z3 (an addition)
+struct PairingLineJ {
+    Fq2 a, b, c;
+};
+ZK_PAIR_FN bool g2j_is_identity(const G2J& t) { return f2_is_zero(t.z); }
+// T <- 2 T with the tangent's line.  (x, y, z) -> (m^2 - 2 s, m (s - x3) - 8 y^4, 2 y z), m = 3 x^2, s = 4 x y^2; the slope is m / z3.
+// The identity stays the identity (z3 = 0); the twist has odd order, so no other point doubles to it
+ZK_PAIR_MULFN PairingLineJ g2j_double_line(G2J& T) {
+    const Fq2 xx = f2_mul(T.x, T.x), yy = f2_mul(T.y, T.y), zz = f2_mul(T.z, T.z);
+    const Fq2 m = f2_add(f2_add(xx, xx), xx);
+    Fq2 s = f2_mul(T.x, yy), y4 = f2_mul(yy, yy);
+    s = f2_add(s, s);
+    s = f2_add(s, s);
+    y4 = f2_add(y4, y4);
+    y4 = f2_add(y4, y4);
+    y4 = f2_add(y4, y4);
+    const Fq2 z3 = f2_mul(f2_add(T.y, T.y), T.z);
+    PairingLineJ l;
+    l.a = f2_mul(z3, zz);
+    l.b = f2_neg(f2_mul(m, zz));
+    l.c = f2_sub(f2_mul(m, T.x), f2_add(yy, yy));
+    const Fq2 x3 = f2_sub(f2_mul(m, m), f2_add(s, s));
+    T.y = f2_sub(f2_mul(m, f2_sub(s, x3)), y4);
+    T.x = x3;
+    T.z = z3;
+    return l;
+}
+// T <- T + Q with the line through both, Q = (qx, qy) affine, T neither the identity nor +-Q.  With h = qx z^2 - x and
+// r = qy z^3 - y: (r^2 - h^3 - 2 x h^2, r (x h^2 - x3) - y h^3, z h); the slope is r / z3
+ZK_PAIR_MULFN PairingLineJ g2j_add_line(G2J& T, const Fq2& qx, const Fq2& qy) {
+    const Fq2 zz = f2_mul(T.z, T.z);
+    const Fq2 h = f2_sub(f2_mul(qx, zz), T.x), r = f2_sub(f2_mul(qy, f2_mul(T.z, zz)), T.y);
+    const Fq2 hh = f2_mul(h, h);
+    const Fq2 hhh = f2_mul(h, hh), v = f2_mul(T.x, hh);
+    const Fq2 z3 = f2_mul(T.z, h);
+    PairingLineJ l;
+    l.a = z3;
+    l.b = f2_neg(r);
+    l.c = f2_sub(f2_mul(r, qx), f2_mul(z3, qy));
+    const Fq2 x3 = f2_sub(f2_sub(f2_mul(r, r), hhh), f2_add(v, v));
+    T.y = f2_sub(f2_mul(r, f2_sub(v, x3)), f2_mul(T.y, hhh));
+    T.x = x3;
+    T.z = z3;
+    return l;
+}
+// T <- T + Q for any T and any affine Q on the twist: the cases the Miller loop of a proper point never meets
+ZK_PAIR_FN void g2j_add_any(G2J& T, const Fq2& qx, const Fq2& qy) {
+    if (g2j_is_identity(T)) {
+        T = G2J{qx, qy, f2_one()};
+        return;
+    }
+    const Fq2 zz = f2_mul(T.z, T.z);
+    if (f2_eq(f2_mul(qx, zz), T.x)) {
+        if (f2_eq(f2_mul(qy, f2_mul(T.z, zz)), T.y)) (void)g2j_double_line(T);
+        else T.z = f2_zero();
+        return;
+    }
+    (void)g2j_add_line(T, qx, qy);
+}
+// g2_is_proper's verdict for every input, as a lane finds it: coordinates reduced, on the twist, [r] q the identity, q not.
+// The twist equation is taken times xi, (y^2 - x^3) xi = 3, and [r] q runs in Jacobian coordinates from the top bit of r (bit 253)
+// down: nothing is inverted, and the trip count is that of the constant r
+ZK_PAIR_FN bool g2_is_proper_lane(const G2A& q) {
+    if (q.inf || !fq_is_canonical(q.x.c0) || !fq_is_canonical(q.x.c1) || !fq_is_canonical(q.y.c0) || !fq_is_canonical(q.y.c1)) return false;
+    if (!f2_eq(f2_mul_xi(f2_sub(f2_mul(q.y, q.y), f2_mul(f2_mul(q.x, q.x), q.x))), f2_small(3, 0))) return false;
+    uint32_t e[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) e[i] = FrParams::P[i];
+    G2J acc{q.x, q.y, f2_one()};
+#pragma unroll 1
+    for (int i = 252; i >= 0; i--) {
+        (void)g2j_double_line(acc);
+        if ((e[i >> 5] >> (i & 31)) & 1) g2j_add_any(acc, q.x, q.y);
+    }
+    return g2j_is_identity(acc);
+}
+
+// f times the line l0 + l1 w + l3 w^3 with all three coefficients in Fq2 (f12_mul_line's shape, its Fq coefficient widened)
+ZK_PAIR_MULFN Fq12 f12_mul_line3(const Fq12& f, const Fq2& l0, const Fq2& l1, const Fq2& l3) {
+    const Fq6 t0 = {f2_mul(f.c0.c0, l0), f2_mul(f.c0.c1, l0), f2_mul(f.c0.c2, l0)};
+    const Fq6 t1 = f6_mul_01(f.c1, l1, l3);
+    const Fq6 m = f6_mul_01(f6_add(f.c0, f.c1), f2_add(l0, l1), l3);
+    return {f6_add(t0, f6_mul_v(t1)), f6_sub(f6_sub(m, t0), t1)};
+}
+
+// f[k] = ML(Pw[k], q) ML(Pf[k], g2), k < N, over ONE walk of q (a proper point): every line of the walk is evaluated at each
+// Pw[k] into its own accumulator, and g2's lines come from the prepared walk t.line[1].  An identity on either side of a pair
+// leaves the pair out.  Fixed trip counts, as in miller_loop_lines
+template <int N>
+ZK_PAIR_FN void miller_loop_walk(const G2A& q, const G1Affine* Pw, const G1Affine* Pf, const PairingTable& t, Fq12* f) {
+    bool usew[N], usef[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        usew[k] = !affine_is_identity(Pw[k]);
+        usef[k] = !affine_is_identity(Pf[k]) && !t.inf[1];
+        f[k] = f12_one();
+    }
+    // pi(q) and -pi^2(q), the ends of the two Frobenius lines
+    const Fq2 q1x = f2_mul(f2_conj(q.x), t.gamma[2]), q1y = f2_mul(f2_conj(q.y), t.gamma[3]);
+    const Fq2 nq2x = f2_mul(q.x, f2_mul(f2_conj(t.gamma[2]), t.gamma[2])), nq2y = f2_neg(f2_mul(q.y, f2_mul(f2_conj(t.gamma[3]), t.gamma[3])));
+    G2J T{q.x, q.y, f2_one()};
+    int n = 0;
+#pragma unroll 1
+    for (int b = 63; b >= -2; b--) {
+        if (b >= 0) {
+#pragma unroll
+            for (int k = 0; k < N; k++) f[k] = f12_sqr(f[k]);
+        }
+        const int steps = (b >= 0 && ((SIX_U_PLUS_2_LO >> b) & 1)) ? 2 : 1;
+#pragma unroll 1
+        for (int s = 0; s < steps; s++, n++) {
+            PairingLineJ l;
+            if (b >= 0 && s == 0) l = g2j_double_line(T);
+            else if (b >= 0) l = g2j_add_line(T, q.x, q.y);
+            else if (b == -1) l = g2j_add_line(T, q1x, q1y);
+            else l = g2j_add_line(T, nq2x, nq2y);
+#pragma unroll
+            for (int k = 0; k < N; k++) {
+                if (usew[k]) f[k] = f12_mul_line3(f[k], f2_mul_fq(l.a, Pw[k].y), f2_mul_fq(l.b, Pw[k].x), l.c);
+                if (usef[k]) f[k] = f12_mul_line(f[k], t.line[1][n], Pf[k]);
+            }
+        }
+    }
+}
+
+// e(a, q) = e(b, g2) with the lane's own q, as a lane of pairing_check_each_kernel runs it: pairing_check_lines' reasons in its
+// order, then ZK_PAIRING_G2 for a q that is not a proper point (such a lane returns before it walks).  t: a table whose line[1]
+// is g2's walk
+ZK_PAIR_FN uint8_t pairing_check_walk(const G1Affine& a, const G1Affine& b, const G2A& q, const PairingTable& t) {
+    if (!fq_is_canonical(a.x) || !fq_is_canonical(a.y) || !fq_is_canonical(b.x) || !fq_is_canonical(b.y)) return ZK_PAIRING_RANGE;
+    if (!affine_is_identity(a) && !g1_is_proper(a)) return ZK_PAIRING_OFF_CURVE;
+    if (!affine_is_identity(b) && !g1_is_proper(b)) return ZK_PAIRING_OFF_CURVE;
+    if (!g2_is_proper_lane(q)) return ZK_PAIRING_G2;
+    G1Affine nb = b;
+    nb.y = fe_neg(b.y);
+    Fq12 f;
+    miller_loop_walk<1>(q, &a, &nb, t, &f);
+    return f12_is_one(final_exponentiation_chain(f, t.gamma)) ? ZK_PAIRING_VALID : ZK_PAIRING_MISMATCH;
+}
+
+// The receipt rule of a ceremony contribution (srs_update.h srs_contribution_flags) as a lane of contribution_check_kernel runs
+// it: ZK_SRS_CONTRIB_SAME_SECRET | LINKS | NONTRIVIAL, and no bit for a receipt with an improper point.  Both equations,
+// e(G1, s_g2) = e(s_g1, G2) and e(before, s_g2) = e(after, G2), share s_g2: one walk, two accumulators, two final
+// exponentiations.  t: a table whose line[1] is the walk of the G2 generator
+ZK_PAIR_FN uint32_t contribution_check_lanes(const G1Affine& before, const G1Affine& after, const G1Affine& s_g1, const G2A& s_g2, const PairingTable& t) {
+    if (!g1_is_proper(before) || !g1_is_proper(after) || !g1_is_proper(s_g1) || !g2_is_proper_lane(s_g2)) return 0;
+    G1Affine Pw[2], Pf[2] = {s_g1, after};
+    Pw[0].x = Fq::one();
+    Pw[0].y = fe_add(Fq::one(), Fq::one());
+    Pw[1] = before;
+    uint32_t flags = (s_g1.x == Pw[0].x && s_g1.y == Pw[0].y) ? 0 : ZK_SRS_CONTRIB_NONTRIVIAL;
+    Pf[0].y = fe_neg(Pf[0].y);
+    Pf[1].y = fe_neg(Pf[1].y);
+    Fq12 f[2];
+    miller_loop_walk<2>(s_g2, Pw, Pf, t, f);
+#pragma unroll 1
+    for (int k = 0; k < 2; k++)
+        if (f12_is_one(final_exponentiation_chain(f[k], t.gamma))) flags |= k ? ZK_SRS_CONTRIB_LINKS : ZK_SRS_CONTRIB_SAME_SECRET;
+    return flags;
 }
 
 }  // namespace zk

@@ -13,23 +13,20 @@
 // trip count, no lane waits for another, and lanes beyond `count` return before touching memory.
 // The resident SRS's table is kept with the SRS view (ctx.h PairLinesDev) and dropped with the block or the pair; a caller's own
 // pair gets a table per call.
+// The checks with a G2 point per lane (zk_pairing_check_each, zk_srs_contribution_check_batch) are pairing_each.hip's; they share
+// the staging buffers and the two table helpers below (pairing_ws.h).
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "ctx.h"
+#include "pairing_ws.h"
 #include "srs_update.h"
-
-// the context's staging buffers (grow-only) and the table of a caller's own pair
-struct PairingWs {
-    void *a = nullptr, *b = nullptr, *out = nullptr, *own = nullptr;
-    size_t c_a = 0, c_b = 0, c_out = 0, c_own = 0;
-};
 
 void pairing_ws_destroy(PairingWs* w) {
     if (!w) return;
-    for (void* p : {w->a, w->b, w->out, w->own})
+    for (void* p : {w->a, w->b, w->out, w->own, w->q, w->gen})
         if (p) hipFree(p);
     delete w;
 }
@@ -44,6 +41,8 @@ __global__ __launch_bounds__(PAIRING_WG) void pairing_check_kernel(const G1Affin
     if (i >= count) return;  // the tail lanes of the last wave touch no memory
     reasons[i] = pairing_check_lines(affine_load(a + i), affine_load(b + i), *table);
 }
+
+}  // namespace
 
 int pw_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
     if (*cap >= bytes) return ZK_OK;
@@ -66,7 +65,7 @@ int pairing_ws(zk_ctx* c, PairingWs** out) {
 }
 
 // the table of (g2, s_g2) into the device buffer d (sizeof(PairingTable) bytes), waited for: the host copy goes out of scope
-int table_upload(zk_ctx* c, const G2A& g2, const G2A& s_g2, void* d) {
+int pairing_table_upload(zk_ctx* c, const G2A& g2, const G2A& s_g2, void* d) {
     std::vector<PairingTable> t(1);
     pairing_table_make(g2, s_g2, t.data());
     if (c->audit.on) c->audit.op(c->stream, {}, {d}, "pairing: prepared lines upload");
@@ -74,6 +73,8 @@ int table_upload(zk_ctx* c, const G2A& g2, const G2A& s_g2, void* d) {
     HIPCHK(c, aud_sync(c, c->stream));
     return ZK_OK;
 }
+
+namespace {
 
 // `count` host pairs against the table at d_table, one launch; reasons: a host array of `count`
 int pairing_launch(zk_ctx* c, PairingWs* w, size_t count, const G1Affine* a, const G1Affine* b, const void* d_table, uint8_t* reasons) {
@@ -94,8 +95,10 @@ int pairing_launch(zk_ctx* c, PairingWs* w, size_t count, const G1Affine* a, con
     return ZK_OK;
 }
 
+}  // namespace
+
 // the resident pair's table, made on first use
-int resident_table(zk_ctx* c, const void** out) {
+int pairing_resident_table(zk_ctx* c, const void** out) {
     uint8_t key[256];
     memcpy(key, c->g2_raw, 128);
     memcpy(key + 128, c->s_g2_raw, 128);
@@ -106,20 +109,18 @@ int resident_table(zk_ctx* c, const void** out) {
     std::shared_ptr<PairLinesDev> t = std::make_shared<PairLinesDev>();
     t->device = c->device;
     if (hipMalloc(&t->d, sizeof(PairingTable)) != hipSuccess) return ZK_ENOMEM;
-    if (int rc = table_upload(c, g2_from_raw(c->g2_raw), g2_from_raw(c->s_g2_raw), t->d)) return rc;
+    if (int rc = pairing_table_upload(c, g2_from_raw(c->g2_raw), g2_from_raw(c->s_g2_raw), t->d)) return rc;
     memcpy(t->key, key, 256);
     c->pair_lines = t;
     *out = t->d;
     return ZK_OK;
 }
 
-}  // namespace
-
 int pairing_check_resident(zk_ctx* c, size_t count, const G1Affine* a, const G1Affine* b, uint8_t* reasons) {
     PairingWs* w;
     const void* table;
     int rc;
-    if ((rc = pairing_ws(c, &w)) || (rc = resident_table(c, &table))) return rc;
+    if ((rc = pairing_ws(c, &w)) || (rc = pairing_resident_table(c, &table))) return rc;
     return pairing_launch(c, w, count, a, b, table, reasons);
 }
 
@@ -142,7 +143,7 @@ ZK_API(zk_pairing_check_batch, (zk_ctx* c, size_t count, const uint64_t* a, cons
     std::vector<uint8_t> res(count);
     const G1Affine *pa = reinterpret_cast<const G1Affine*>(a), *pb = reinterpret_cast<const G1Affine*>(b);
     if (g2) {
-        if ((rc = pw_grow(c, &w->own, &w->c_own, sizeof(PairingTable))) || (rc = table_upload(c, own[0], own[1], w->own)) ||
+        if ((rc = pw_grow(c, &w->own, &w->c_own, sizeof(PairingTable))) || (rc = pairing_table_upload(c, own[0], own[1], w->own)) ||
             (rc = pairing_launch(c, w, count, pa, pb, w->own, res.data())))
             return rc;
     } else if ((rc = pairing_check_resident(c, count, pa, pb, res.data()))) {

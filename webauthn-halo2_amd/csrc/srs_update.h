@@ -29,12 +29,8 @@ inline void g1_to_words(const G1Affine& p, uint64_t w[8]) {
     memcpy(w, p.x.v, 32);
     memcpy(w + 4, p.y.v, 32);
 }
-// a point of G1 other than the identity: both coordinates reduced, y^2 = x^3 + 3 (G1 has cofactor 1)
-inline bool g1_is_proper(const G1Affine& p) {
-    if (!fq_is_canonical(p.x) || !fq_is_canonical(p.y) || affine_is_identity(p)) return false;
-    return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
-}
-// (g2_is_proper, the same for G2 with the subgroup test, is pairing.h's: zk_pairing_check_batch applies it too)
+// (g1_is_proper, and g2_is_proper, the same for G2 with the subgroup test, are pairing.h's: the device form of the receipt rule,
+// contribution_check_lanes, and zk_pairing_check_batch apply them too)
 
 inline G1Affine g1_generator_host() {
     G1Affine g;

@@ -46,7 +46,8 @@ import numpy as np
 
 from . import circuit
 from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEME_SHPLONK, ZK_SERDE_RAW_BYTES, ZK_SRS_CONTRIB_LINKS,
-                     ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT, ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
+                     ZK_SRS_CONTRIB_BATCH_MAX, ZK_SRS_CONTRIB_CHAINED, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT,
+                     ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
                      ZK_ES256_BATCH_MAX, ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
@@ -220,6 +221,35 @@ def _gen_srs_locked(degree, device):
 _RECEIPT_POINTS = (("before_g1", 8), ("after_g1", 8), ("s_g1", 8), ("s_g2", 16))
 _CONTRIB_CHAIN = ZK_SRS_CONTRIB_SAME_SECRET | ZK_SRS_CONTRIB_LINKS | ZK_SRS_CONTRIB_NONTRIVIAL
 
+# Where check_contributions checks a chain's receipts: one host check per receipt (zk_srs_contribution_check), or the chain in
+# launches of up to ZK_SRS_CONTRIB_BATCH_MAX receipts, one per lane (zk_srs_contribution_check_batch).  A process-wide setting like
+# set_verify_pairing's.  "auto" is the host for chains shorter than _CONTRIBUTION_AUTO_DEVICE_FROM receipts and the device from there
+# on: the smallest count of tools/contribution_chain_rate.py's table (docs/experiments.md, 2026-10-20) at which the device median lies
+# below the host median by more than either cell's min-to-median spread; at 1 and 8 receipts the host is ahead.  Same verdicts.
+_CONTRIBUTION_CHECK = "auto"
+_CONTRIBUTION_CHECK_MODES = ("auto", "host", "device")
+_CONTRIBUTION_AUTO_DEVICE_FROM = 64
+
+
+def set_contribution_check(mode: str):
+    """Where check_contributions checks the receipts of a chain: "host" (one check per receipt), "device" (the chain in launches
+    of up to 4096 receipts) or "auto" (the host below 64 receipts, the device from 64 on).  The verdict is the same."""
+    global _CONTRIBUTION_CHECK
+    if mode not in _CONTRIBUTION_CHECK_MODES:
+        raise ValueError('contribution check: "host", "device" or "auto"')
+    _CONTRIBUTION_CHECK = mode
+
+
+def contribution_check() -> str:
+    return _CONTRIBUTION_CHECK
+
+
+def _contribution_route(n_receipts: int) -> str:
+    """"host" or "device": where a chain of n_receipts is checked under the current setting"""
+    if _CONTRIBUTION_CHECK != "auto":
+        return _CONTRIBUTION_CHECK
+    return "device" if n_receipts >= _CONTRIBUTION_AUTO_DEVICE_FROM else "host"
+
 
 def _sha256_file(path):
     h = hashlib.sha256()
@@ -300,7 +330,8 @@ def check_contributions(params_path, receipts, device: int = 0) -> bool:
     """Checks a params file against the chain of receipts that led to it (oldest first): every receipt shows
     SAME_SECRET | LINKS | NONTRIVIAL, each before_g1 is the previous receipt's after_g1, the last after_g1 is g[1] of the file
     (RESIDENT), and the file passes the structure check (srs_check == 7).  Then the file's secret is the chain's starting one
-    times every contributor's.  False for an empty chain or a file that cannot be read as RawBytes params."""
+    times every contributor's.  False for an empty chain or a file that cannot be read as RawBytes params.  The receipts are
+    checked one by one on the host or in launches of up to 4096 on the device (set_contribution_check); the verdict is the same."""
     from .engine import ZkError
 
     receipts = list(receipts)
@@ -320,10 +351,19 @@ def check_contributions(params_path, receipts, device: int = 0) -> bool:
                 eng.srs_read(f.read())
             except ZkError:
                 return False
-        for i, pts in enumerate(points):
-            want = _CONTRIB_CHAIN | (ZK_SRS_CONTRIB_RESIDENT if i == len(points) - 1 else 0)
-            if eng.srs_contribution_check(pts) & want != want:
-                return False
+        if _contribution_route(len(points)) == "device":
+            for at in range(0, len(points), ZK_SRS_CONTRIB_BATCH_MAX):
+                chunk = points[at:at + ZK_SRS_CONTRIB_BATCH_MAX]
+                for i, flags in enumerate(eng.srs_contribution_check_batch(chunk), at):
+                    # (a chunk's first receipt is CHAINED by rule: the links across chunks are the byte comparison above)
+                    want = _CONTRIB_CHAIN | ZK_SRS_CONTRIB_CHAINED | (ZK_SRS_CONTRIB_RESIDENT if i == len(points) - 1 else 0)
+                    if flags & want != want:
+                        return False
+        else:
+            for i, pts in enumerate(points):
+                want = _CONTRIB_CHAIN | (ZK_SRS_CONTRIB_RESIDENT if i == len(points) - 1 else 0)
+                if eng.srs_contribution_check(pts) & want != want:
+                    return False
         return eng.srs_check(os.urandom(32)) == 7  # fresh weights: a file cannot be made to fit a known check
     finally:
         eng.close()

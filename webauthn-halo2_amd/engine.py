@@ -30,10 +30,13 @@ ZK_PROVE_MULTI_MAX = 16
 ZK_ES256_VALID, ZK_ES256_RANGE, ZK_ES256_OFF_CURVE, ZK_ES256_MISMATCH = 0, 1, 2, 3
 ZK_ES256_BATCH_MAX = 16384
 ZK_PAIRING_VALID, ZK_PAIRING_RANGE, ZK_PAIRING_OFF_CURVE, ZK_PAIRING_MISMATCH = 0, 1, 2, 3
+ZK_PAIRING_G2 = 4
 ZK_PAIRING_BATCH_MAX = 4096
 ZK_VERIFY_PAIRING_AUTO, ZK_VERIFY_PAIRING_HOST, ZK_VERIFY_PAIRING_DEVICE = 0, 1, 2
 ZK_SRS_CHECK_POWERS, ZK_SRS_CHECK_LAGRANGE, ZK_SRS_CHECK_GENERATORS = 1, 2, 4
 ZK_SRS_CONTRIB_SAME_SECRET, ZK_SRS_CONTRIB_LINKS, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT = 1, 2, 4, 8
+ZK_SRS_CONTRIB_CHAINED = 16
+ZK_SRS_CONTRIB_BATCH_MAX = 4096
 ZK_FAIL_GATE, ZK_FAIL_GATE_BLINDED, ZK_FAIL_LOOKUP, ZK_FAIL_COPY = 1, 2, 3, 4
 ZK_PK_FIXED_POLY, ZK_PK_SIGMA_POLY = 0, 1
 (ZK_PK_PART_FIXED_COMMIT, ZK_PK_PART_SIGMA_COMMIT, ZK_PK_PART_FIXED_POLY, ZK_PK_PART_SIGMA_POLY, ZK_PK_PART_FIXED_COSET,
@@ -287,6 +290,8 @@ def load_library():
         "zk_stream_placement": ([ctypes.c_int, ctypes.c_int, ctypes.POINTER(PlacementC)], ctypes.c_int),
         "zk_ctx_stream_info": ([vp, ctypes.POINTER(CtxStreamsC)], ctypes.c_int),
         "zk_pairing_check_batch": ([vp, sz, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_pairing_check_each": ([vp, sz, u64p, u64p, u64p, u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_srs_contribution_check_batch": ([vp, sz, ctypes.POINTER(SrsContributionC), ctypes.POINTER(u32)], ctypes.c_int),
         "zk_verify_pairing_mode": ([vp, ctypes.c_int], ctypes.c_int),
         "zk_verify_pairing_stats": ([vp, u64p], ctypes.c_int),
         "zk_evm_verifier": ([vp, ctypes.c_uint64, sz, ctypes.POINTER(sz), ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(sz)], ctypes.c_int),
@@ -300,7 +305,7 @@ def load_library():
                         "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
                         "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify",
                         "zk_pairing_check_batch", "zk_verify_pairing_mode", "zk_verify_pairing_stats", "zk_evm_verifier",
-                        "zk_evm_verifier_cost") and os.environ.get("ZKMI355_LIB"):
+                        "zk_evm_verifier_cost", "zk_pairing_check_each", "zk_srs_contribution_check_batch") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -488,6 +493,23 @@ class Engine:
         flags = ctypes.c_uint32()
         self._chk(self.L.zk_srs_contribution_check(self.ctx, ctypes.byref(c), ctypes.byref(flags)), "zk_srs_contribution_check")
         return flags.value
+
+    def srs_contribution_check_batch(self, contributions):
+        """zk_srs_contribution_check_batch: the flag word of every receipt of a chain (oldest first) in one launch, one receipt per
+        lane: srs_contribution_check's bits, plus ZK_SRS_CONTRIB_CHAINED where a receipt's before_g1 is the previous one's after_g1
+        (always set for the first).  1 .. ZK_SRS_CONTRIB_BATCH_MAX receipts; needs no SRS.  -> [flag words]"""
+        contributions = list(contributions)
+        count = len(contributions)
+        cs = (SrsContributionC * max(count, 1))()
+        for c, contribution in zip(cs, contributions):
+            for f in self.CONTRIBUTION_FIELDS:
+                a = np.ascontiguousarray(contribution[f], dtype=np.uint64).reshape(-1)
+                if a.size != len(getattr(c, f)):
+                    raise ValueError("contribution field %s has the wrong length" % f)
+                ctypes.memmove(getattr(c, f), a.ctypes.data, a.nbytes)
+        flags = (ctypes.c_uint32 * max(count, 1))()
+        self._chk(self.L.zk_srs_contribution_check_batch(self.ctx, count, cs, flags), "zk_srs_contribution_check_batch")
+        return [int(flags[j]) for j in range(count)]
 
     def vk_write(self, pk, fmt=ZK_SERDE_RAW_BYTES):
         return self._write(self.L.zk_vk_write, "zk_vk_write", pk, fmt)
@@ -965,6 +987,21 @@ class Engine:
         verdicts = (ctypes.c_uint8 * max(count, 1))()
         reasons = (ctypes.c_uint8 * max(count, 1))()
         self._chk(self.L.zk_pairing_check_batch(self.ctx, count, _p(a), _p(b), gp[0], gp[1], verdicts, reasons), "zk_pairing_check_batch")
+        return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+
+    def pairing_check_each(self, a, b, q, g2=None):
+        """zk_pairing_check_each: e(a_i, q_i) = e(b_i, g2) with a G2 point per item, one check per lane; every lane tests and walks
+        its own q_i.  a, b: (count, 8) uint64 affine Montgomery points; q: (count, 16) Montgomery images as set_g2 takes them; g2: one
+        such image, or None for the resident SRS's.  -> ([bool verdicts], [ZK_PAIRING_* reasons]; ZK_PAIRING_G2: q_i not a proper
+        point); a bad item is a verdict, not an error."""
+        a, b, q = _arr(a, 8), _arr(b, 8), _arr(q, 16)
+        if a.shape[0] != b.shape[0] or a.shape[0] != q.shape[0]:
+            raise ValueError("one b and one q per a")
+        count = a.shape[0]
+        gp = ctypes.cast(None, ctypes.POINTER(ctypes.c_uint64)) if g2 is None else _p(np.ascontiguousarray(g2, dtype=np.uint64).reshape(16))
+        verdicts = (ctypes.c_uint8 * max(count, 1))()
+        reasons = (ctypes.c_uint8 * max(count, 1))()
+        self._chk(self.L.zk_pairing_check_each(self.ctx, count, _p(a), _p(b), _p(q), gp, verdicts, reasons), "zk_pairing_check_each")
         return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
 
     def verify_pairing_mode(self, mode):

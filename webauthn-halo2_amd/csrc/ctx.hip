@@ -194,7 +194,7 @@ ZK_API(zk_ctx_create, (int device_id, zk_ctx** out), (device_id, out)) {
     if (hipSetDevice(device_id) != hipSuccess ||
         ((c->stream_slot = pool_take_slot(device_id, &c->stream)) < 0 && hipStreamCreate(&c->stream) != hipSuccess) ||
         hipHostMalloc(&c->host_small, 8 * sizeof(Fr)) != hipSuccess ||
-        hipMalloc(&c->small, (2048 + 8) * sizeof(Fr)) != hipSuccess) {
+        hipMalloc(&c->small, EVAL_SMALL_ELEMS * sizeof(Fr)) != hipSuccess) {  // (2048 + 8: poly_plan.h)
         zk_ctx_destroy(c);
         return ZK_EHIP;
     }

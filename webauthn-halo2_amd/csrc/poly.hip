@@ -55,17 +55,10 @@ __global__ __launch_bounds__(256) void poly_sum_kernel(const Fr* __restrict__ in
     if (threadIdx.x == 0) fe_store(out, sh[0]);
 }
 
-// scratch: at least eval_blocks(n) + 1 elements; result in scratch[eval_blocks(n)]
-uint32_t eval_blocks(uint32_t n) {
-    uint32_t b = (n + 256 * 16 - 1) / (256 * 16);
-    if (b < 1) b = 1;
-    if (b > 1024) b = 1024;
-    return b;
-}
-
+// scratch: at least eval_blocks(n) + 1 elements; result in scratch[eval_blocks(n)]  (the shapes: poly_plan.h)
 void launch_eval(const Fr* c, uint32_t n, const Fr& x, Fr* scratch, hipStream_t st) {
     const uint32_t blocks = eval_blocks(n);
-    const uint32_t S = blocks * 256;
+    const uint32_t S = eval_stride(n);
     Fr y = Fr::one(), base = x;
     for (uint32_t e = S; e; e >>= 1) {
         if (e & 1) y = fe_mul(y, base);
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void poly_eval_batch_kernel(const EvalItem* __
     }
     sh[threadIdx.x] = acc;
     __syncthreads();
-    const uint32_t live = min(256u, n - min(n, blockIdx.x * 256 * M));  // lanes holding coefficients (a short last workgroup)
+    const uint32_t live = eval_batch_live(n, M, blockIdx.x);  // lanes holding coefficients (a short last workgroup)
 #pragma unroll 1
     for (int l = 7; l >= 0; l--) {
         const uint32_t s = 1u << l;
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(256) void poly_sum_batch_kernel(const EvalItem* __r
 void launch_eval_batch(EvalItem* h_items, EvalItem* d_items, uint32_t count, uint32_t n, Fr* scratch, Fr* out,
                        hipStream_t st) {
     const uint32_t blocks = eval_blocks(n);
-    const uint32_t M = (n + blocks * 256 - 1) / (blocks * 256);  // coefficients per lane (16 up to 2^22)
+    const uint32_t M = eval_batch_per_lane(n);  // coefficients per lane (16 up to 2^22)
     // a proof opens at a handful of points (x, w x, w^-1 x, ..): the powers are computed once per distinct point
     uint32_t distinct[16], nd = 0;
     for (uint32_t e = 0; e < count; e++) {

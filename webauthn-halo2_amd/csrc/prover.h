@@ -2,6 +2,7 @@
 // prover.hip, prover_key.hip, prover_phases.hip).  Not part of the public C-ABI.
 #pragma once
 #include "engine.h"
+#include "poly_plan.h"
 
 namespace zk {
 
@@ -166,7 +167,7 @@ struct InstEntry {
     uint32_t off, len;  // in elements of the staged values; len <= n
 };
 void launch_instance_columns(const InstEntry* d_entries, const Fr* d_vals, uint32_t lanes, uint32_t n, hipStream_t st);
-static constexpr uint32_t KD_MAX_BATCH = 6;  // divisions per launch (SHPLONK / GWC have at most six rotation sets)
+// (KD_MAX_BATCH, the divisions per launch, and the shapes of a division: poly_plan.h)
 uint32_t kate_division_scratch(uint32_t n);  // elements of scratch per division
 void launch_kate_division(const Fr* p, Fr* q, uint32_t n, const Fr& z, Fr* scratch, hipStream_t st);
 void launch_kate_division_batch(const Fr* const* p, Fr* const* q, const Fr* z, uint32_t count, uint32_t n, Fr* scratch,
@@ -188,7 +189,7 @@ struct EvalItem {
 };
 void launch_eval_batch(EvalItem* h_items, EvalItem* d_items, uint32_t count, uint32_t n, Fr* scratch, Fr* out,
                        hipStream_t st);
-uint32_t eval_blocks(uint32_t n);
+// (eval_blocks and the other shape rules of the two evaluations: poly_plan.h)
 // pairs per launch of zk_eval_batch (its staging is sized for them; more pairs take further launches inside the call)
 #define EVAL_BATCH_PAIRS 64
 void launch_eval(const Fr* c, uint32_t n, const Fr& x, Fr* scratch, hipStream_t st);

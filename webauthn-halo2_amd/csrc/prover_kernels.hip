@@ -816,21 +816,8 @@ void launch_instance_columns(const InstEntry* d_entries, const Fr* d_vals, uint3
 // over chunks carry_t = c_{t+1} + z^L carry_{t+1}, (3) replay each chunk from its carry.
 // Up to KD_MAX_BATCH independent divisions per launch (blockIdx.y): SHPLONK divides every rotation
 // set's polynomial by that set's next point in the same step.  q may be p (in place).
-#ifndef ZK_KD_L
-#define ZK_KD_L 8
-#endif
-// shortest chunk (power of two): 8: 4x the lanes of 32 (a 2^19 division is 65 536 Horner chains of 8 instead of 16 384 of 32:
-// -0.1 ms per k=19 proof, -0.3 ms at k=15..17)
-static constexpr uint32_t KD_L_MIN = ZK_KD_L;
-static constexpr uint32_t KD_BLK = 256;
-static constexpr uint32_t KD_TOP = 1024;  // most blocks of a division: every block sums the aggregates above it directly
-// chunk length of an n-coefficient division: the shortest that keeps the number of blocks within KD_TOP (8 up to 2^21,
-// 16 at 2^22, ...)
-__host__ __device__ inline uint32_t kd_len(uint32_t n) {
-    uint32_t L = KD_L_MIN;
-    while (((n + L - 1) / L + KD_BLK - 1) / KD_BLK > KD_TOP) L <<= 1;
-    return L;
-}
+// The chunk length, the chunk and block counts and the scratch layout: poly_plan.h (kd_len, kd_chunks, kd_blocks,
+// kd_scratch_elems), walked on the host by tests/poly_plan_check.cpp.
 
 struct KdPtrs {
     const Fr* p[KD_MAX_BATCH];
@@ -844,11 +831,7 @@ struct KdTop {
     Fr top[KD_MAX_BATCH][10];  // (Z^256)^(2^j): exponents below KD_TOP = 2^10
 };
 
-// per-division scratch: (m unused) | suf[m] | agg[nblk] | tpow[nblk] | zpow[256]
-__host__ __device__ inline uint32_t kd_scratch_elems(uint32_t n) {
-    const uint32_t L = kd_len(n), m = (n + L - 1) / L, nblk = (m + KD_BLK - 1) / KD_BLK;
-    return 2 * m + 2 * nblk + 256;
-}
+// per-division scratch: (m unused) | suf[m] | agg[nblk] | tpow[nblk] | zpow[256]  (kd_scratch_elems, poly_plan.h)
 uint32_t kate_division_scratch(uint32_t n) { return kd_scratch_elems(n); }
 
 // Carries between chunks: K_t = sum_{s > t} c_s Z^(s-t-1), Z = z^KD_L.  Two-level suffix scan with KNOWN multipliers (powers
@@ -862,7 +845,7 @@ uint32_t kate_division_scratch(uint32_t n) { return kd_scratch_elems(n); }
 __global__ __launch_bounds__(KD_BLK) void kd_scan_kernel(KdPtrs a, KdStep pw, KdTop tw, uint32_t n, Fr* __restrict__ scratch) {
     __shared__ Fr sh[KD_BLK];
     const uint32_t KD_L = kd_len(n);
-    const uint32_t m = (n + KD_L - 1) / KD_L, nblk = (m + KD_BLK - 1) / KD_BLK;
+    const uint32_t m = kd_chunks(n, KD_L), nblk = kd_blocks(m);
     Fr* suf = scratch + (size_t)blockIdx.y * kd_scratch_elems(n) + m;
     Fr* agg = suf + m;
     Fr* tpow = agg + nblk;
@@ -916,7 +899,7 @@ __global__ __launch_bounds__(KD_BLK) void kd_scan_kernel(KdPtrs a, KdStep pw, Kd
 __global__ __launch_bounds__(KD_BLK) void kd_apply_kernel(KdPtrs a, uint32_t n, Fr* __restrict__ scratch) {
     __shared__ Fr sh[KD_BLK];
     const uint32_t KD_L = kd_len(n);
-    const uint32_t m = (n + KD_L - 1) / KD_L, nblk = (m + KD_BLK - 1) / KD_BLK;
+    const uint32_t m = kd_chunks(n, KD_L), nblk = kd_blocks(m);
     const Fr* suf = scratch + (size_t)blockIdx.y * kd_scratch_elems(n) + m;
     const Fr* agg = suf + m;
     const Fr* tpow = agg + nblk;
@@ -955,8 +938,7 @@ __global__ __launch_bounds__(KD_BLK) void kd_apply_kernel(KdPtrs a, uint32_t n, 
 void launch_kate_division_batch(const Fr* const* p, Fr* const* q, const Fr* z, uint32_t count, uint32_t n, Fr* scratch,
                                 hipStream_t st) {
     const uint32_t KD_L = kd_len(n);
-    const uint32_t m = (n + KD_L - 1) / KD_L;
-    const uint32_t nblk = (m + KD_BLK - 1) / KD_BLK;
+    const uint32_t nblk = kd_blocks(kd_chunks(n, KD_L));
     KdPtrs pt;
     KdStep stp;
     KdTop tp;
@@ -980,7 +962,7 @@ void launch_kate_division_batch(const Fr* const* p, Fr* const* q, const Fr* z, u
             cur = fe_sqr(cur);
         }
     }
-    hipLaunchKernelGGL(kd_scan_kernel, dim3(nblk + 1 + (nblk + KD_BLK - 1) / KD_BLK, count), dim3(KD_BLK), 0, st, pt, stp, tp, n, scratch);
+    hipLaunchKernelGGL(kd_scan_kernel, dim3(kd_scan_grid(nblk), count), dim3(KD_BLK), 0, st, pt, stp, tp, n, scratch);
     hipLaunchKernelGGL(kd_apply_kernel, dim3(nblk, count), dim3(KD_BLK), 0, st, pt, n, scratch);
 }
 

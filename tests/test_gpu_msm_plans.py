@@ -1,4 +1,4 @@
-"""GPU parity for the STANDARD MSM plan (msm_legacy.hip.h, msm.hip msm_run) at every window, pass width and column length:
+"""GPU parity for the STANDARD MSM plan (msm_standard.hip.h, msm.hip msm_run_standard) at every window, pass width and column length:
 the plan of every SRS below 2^16 and from 2^22, of every zk_msm_bn254 call, and of any size under ZK_OPT_MSM_WINDOW = 9 .. 14.
 Every expected value is exact — the tau-oracle of the seed-generated SRS, the C Pippenger for loaded bases — and compared after
 affine normalisation.  The grid is data (tests/msm_cases.py; tests/test_msm_cases.py checks which branch each case reaches);

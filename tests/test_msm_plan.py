@@ -1,6 +1,8 @@
 """The MSM plan rules (csrc/msm_plan.h) on the host: tests/msm_plan_check.cpp, built with the host compiler under ASan + UBSan,
 walks both modes over every log n, ZK_OPT_MSM_WINDOW value and pass width, asserts the kernels' invariants and the documented
-defaults, and prints one line per combination; the lines equal the Python restatement of tests/msm_cases.py.  No GPU."""
+defaults, and prints one line per combination; the lines equal the Python restatement of tests/msm_cases.py.  It then walks
+every workspace get_msm_ws can make and asserts that no launcher of msm.hip reaches beyond a buffer of its plan's layout (`ws `
+lines).  No GPU."""
 import os
 import shutil
 import subprocess
@@ -63,3 +65,21 @@ def test_widest_pass_is_one_where_msm_run_refuses_more(plan_output):
         elif f["req"] != "0":
             assert f["pass"] == f["req"], ln
     assert seen == 5 * len(MC.PLAN_WIDTHS) * 4  # lg 22 .. 26 x overrides {0, 15, 16, 17}
+
+
+def test_every_workspace_holds_its_own_plan_only_and_prints_its_size(plan_output):
+    """One `ws ` line per (mode, log n, ZK_OPT_MSM_WINDOW, pass width in {default, 1, 3, 8, 256}); the bounds themselves are the
+    program's assertions (test_msm_plan_invariants_and_documented_defaults).  Here: wide exactly where the fixed-base plan line says
+    so, never for arbitrary bases — 15 bits over 2^21 points included — and a k = 19 workspace of two columns well under the 1.1 GiB
+    it took when it carried both plans' buffers."""
+    ws = [dict(t.split("=") for t in ln.split()[2:]) | {"mode": ln.split()[1]} for ln in plan_output.stdout.splitlines() if ln.startswith("ws ")]
+    assert len(ws) == len(MC.PLAN_LOG_N) * (len(MC.PLAN_OVERRIDES) * 5 + 1)
+    for w in ws:
+        if w["mode"] == "generic":
+            assert w["plan"] == "generic" and w["cols"] == "1", w
+        else:
+            assert (w["plan"] == "wide") == MC.plan("fixed", 1 << int(w["lg"]), int(w["ov"]))["wide"], w
+        assert int(w["largest"].split(":")[1]) <= int(w["bytes"]) and w["largest"].split(":")[0] in ("slot_pt", "w_part", "entries", "digits", "inter", "part", "counts"), w
+    assert [w["c"] for w in ws if w["mode"] == "generic" and w["lg"] == "21"] == ["15"]
+    k19 = [w for w in ws if w["mode"] == "fixed" and (w["lg"], w["ov"], w["req"]) == ("19", "0", "0")]
+    assert len(k19) == 1 and k19[0]["cols"] == "2" and int(k19[0]["bytes"]) < 512 << 20

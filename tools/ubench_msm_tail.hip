@@ -31,7 +31,7 @@ int main() {
     CHK(hipStreamCreate(&st));
     CHK(msm_build_table(dbases, n, c, dtable, st));
     hipError_t err;
-    MsmWorkspace* ws = msm_workspace_create(n, c, &err, 1);
+    MsmWorkspace* ws = msm_workspace_create(n, c, true, &err, 1);
     CHK(err);
     G1X* hsum;
     CHK(hipHostMalloc(&hsum, 4096 * sizeof(G1X)));

@@ -56,8 +56,9 @@ void launch_srs_fixed_base(const Fr* scalars, uint32_t n, const G1Affine* table,
 hipError_t launch_g1_validate(const G1Affine* d, uint32_t n, uint32_t* d_err, hipStream_t st);  // *d_err |= 1: a coordinate not below p, a point off the curve
 
 // ---- MSM (msm.hip) ---------------------------------------------------------
-struct MsmWorkspace;  // opaque, sized for a maximum n and a maximum number of columns per launch
-MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, hipError_t* err, uint32_t max_batch = 1);
+struct MsmWorkspace;  // opaque, sized for a maximum n and a maximum number of columns per launch, and made for one plan (msm_plan.h
+// msm_ws_plan): `fixed` = the fixed-base mode over a resident table of max_n points, otherwise arbitrary bases
+MsmWorkspace* msm_workspace_create(size_t max_n, uint32_t c, bool fixed, hipError_t* err, uint32_t max_batch = 1);
 void msm_workspace_destroy(MsmWorkspace* ws);
 size_t msm_ws_max_n(const MsmWorkspace* ws);
 uint32_t msm_ws_max_batch(const MsmWorkspace* ws);

@@ -58,11 +58,11 @@ static int get_msm_ws(zk_ctx* c, int lane, size_t n, uint32_t table_window, MsmW
     }
     if (!slot) {
         hipError_t e;
-        slot = msm_workspace_create(want, cw, &e, cols);
+        slot = msm_workspace_create(want, cw, table_window != 0, &e, cols);
         if (!slot && e != hipErrorInvalidValue && !c->poly_spare.empty()) {
             ctx_release_spares(c);
             (void)hipGetLastError();
-            slot = msm_workspace_create(want, cw, &e, cols);
+            slot = msm_workspace_create(want, cw, table_window != 0, &e, cols);
         }
         if (!slot) {
             c->last_hip = (int)e;

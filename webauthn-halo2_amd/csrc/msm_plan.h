@@ -1,10 +1,12 @@
-// msm_plan.h — the plan rules of the MSM (msm.hip, msm_legacy.hip.h, msm_lanes.hip): which window a size takes, which path serves
-// it (wide / fused / swept), which sort and scatter the fused plan runs, how its bit sums are split and how many columns one pass
-// may hold.  Host only, no HIP types: tests/msm_plan_check.cpp walks every (mode, log n, ZK_OPT_MSM_WINDOW, pass width) through
-// it without a GPU, and tests/msm_cases.py restates it in Python.
+// msm_plan.h — the plan rules of the MSM (msm.hip, msm_standard.hip.h, msm_lanes.hip): which window a size takes, which path
+// serves it (wide / fused / swept), which sort and scatter the fused plan runs, how its bit sums are split, how many columns one
+// pass may hold — and the workspace of a plan: its buffers with their sizes, and how far the launchers of msm.hip reach into them.
+// Host only, no HIP types: tests/msm_plan_check.cpp walks every (mode, log n, ZK_OPT_MSM_WINDOW, pass width) through it without
+// a GPU, and tests/msm_cases.py restates the rules in Python.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <initializer_list>
 
 namespace zk {
 
@@ -81,7 +83,7 @@ inline size_t msm_ws_len(size_t n) {
 // the LDS budget (15-bit windows off the wide path) take the swept sort, one column per pass
 inline bool msm_fused(bool fixed, uint32_t nb) { return fixed && nb <= SORT_LDS_BUCKETS; }
 
-// ---- two-level counting sort (msm_legacy.hip.h, ZK_SORT2)
+// ---- two-level counting sort (msm_standard.hip.h, ZK_SORT2)
 #ifndef ZK_SORT2
 #define ZK_SORT2 1
 #endif
@@ -135,6 +137,140 @@ inline uint32_t msm_max_pass(uint32_t c, size_t table_stride, uint32_t want) {
     if (want > MSM_MAX_BATCH) want = MSM_MAX_BATCH;
     const bool wide = msm_wide_applies(c, table_stride) && table_stride == msm_ws_len(table_stride);
     return wide || msm_fused(true, 1u << (c - 1)) ? want : 1;
+}
+
+// ---- the geometry the kernels and the workspace share (#ifndef: build-time tuning knobs, tools/ab_variants.sh)
+#ifndef ZK_SEG0
+#define ZK_SEG0 16
+#endif
+#ifndef ZK_GA
+#define ZK_GA 4
+#endif
+#ifndef ZK_FCHUNK
+#define ZK_FCHUNK 1024
+#endif
+#ifndef ZK_SORT_SUB
+#define ZK_SORT_SUB 4096
+#endif
+#ifndef ZK_WL
+#define ZK_WL 16
+#endif
+#ifndef ZK_WCUR_STRIDE
+#define ZK_WCUR_STRIDE 32
+#endif
+static constexpr uint32_t CHUNK = 16384;              // scalars per histogram / scatter workgroup of the swept sort
+static constexpr uint32_t FCHUNK = ZK_FCHUNK;         // scalars per workgroup (x nwin entries) of the fused heads
+static constexpr uint32_t SEG0 = ZK_SEG0;             // entries per accumulate lane
+static constexpr uint32_t GA = ZK_GA;                 // slots per first-level gather lane
+static constexpr uint32_t PAD = SEG0 * GA;            // bucket ranges are padded to multiples of PAD entries
+static constexpr uint32_t SUB = ZK_SORT_SUB;          // entries sorted in LDS at a time
+static constexpr uint32_t COARSE_WORDS = 5 * (CBINS_MAX + 1);  // two-level sort: words of a column's header in `coarse`; [blocks][CBINS_MAX] follow
+static constexpr uint32_t WL = ZK_WL;                 // wide path: entries per accumulation lane (measured: msm_wide.hip.h)
+static constexpr uint32_t WCB = 512;                  // ... coarse bins at most (65 536 buckets / 128, or 32 768 / 64)
+static constexpr uint32_t WCUR = ZK_WCUR_STRIDE;      // ... words between two append cursors (one per 128-byte line: msm_wide.hip.h)
+static constexpr uint32_t WCUR0 = 5 * (WCB + 1);      // ... first cursor
+static constexpr uint32_t WHDR = WCUR0 + WCB * WCUR;  // ... words of a column's header; the workgroups' reserved bases [blocks][WCB] follow
+static constexpr uint32_t WCAP_MIN = 2;               // ... slots per part at least: sizes the part lists
+static constexpr uint32_t MSM_PARTS_FIXED = 8, MSM_PARTS_GENERIC = 1;  // parts per bucket of the second-level gather
+
+// ---- what the launchers of msm.hip index at most in one pass.  Standard plan, `batch` columns of n scalars (arbitrary bases: 1):
+struct MsmStdPass {
+    uint32_t slices, nbt, parts, ngroups;  // bucket sets (one per column; per window for arbitrary bases), buckets, parts per bucket, gather groups
+    size_t worst, threads, lanes1;         // padded entries, accumulation segments, first-level gather lanes
+};
+inline MsmStdPass msm_std_pass(bool fixed, uint32_t c, size_t n, uint32_t batch) {
+    MsmStdPass p;
+    p.slices = fixed ? batch : nwin_for(c);
+    p.nbt = p.slices << (c - 1);
+    p.parts = fixed ? MSM_PARTS_FIXED : MSM_PARTS_GENERIC;
+    p.ngroups = p.nbt * p.parts;
+    p.worst = (size_t)batch * n * nwin_for(c) + (size_t)p.nbt * (PAD - 1);
+    p.threads = (p.worst + SEG0 - 1) / SEG0;
+    p.lanes1 = (p.worst + PAD - 1) / PAD;
+    return p;
+}
+// Wide path: every column owns a region of the entry / lane / slot / part lists, strides fixed by (c, max_n) ...
+struct MsmWideDims {
+    uint32_t bins, rows;     // coarse bins; the bucket matrix is [rows = nb / 256][256]
+    size_t ent_stride;       // entries per column region (multiple of 64)
+    uint32_t lane_stride, slot_stride, part_stride;  // accumulation lanes, slots (lanes + buckets), parts per column region
+};
+inline MsmWideDims msm_wide_dims(uint32_t c, size_t max_n) {
+    MsmWideDims d = {};
+    uint32_t ib = 0, fb = 0;
+    if (!msm_wide_shape(c, max_n, &ib, &fb)) return d;
+    const uint32_t nb = 1u << (c - 1);
+    d.bins = nb >> fb;
+    d.rows = nb >> 8;
+    d.ent_stride = (max_n * nwin_for(c) + 63) & ~(size_t)63;
+    d.lane_stride = (uint32_t)(d.ent_stride / WL) + 64;
+    d.slot_stride = d.lane_stride + nb + 64;
+    d.part_stride = ((d.lane_stride + 2 * nb) / WCAP_MIN + nb + 2 * d.bins + 127) & ~63u;
+    return d;
+}
+// ... and per pass of n scalars: accumulation lanes of one column at most; chunks of its binned list (msm_wfinehist /
+// msm_wscatter2: one workgroup each); parts: every bin's region is its slots / WCAP + a part per bucket + slack (msm_wscatter1_kernel)
+inline uint32_t wide_lanes(uint32_t nwin, size_t n) { return (uint32_t)((n * nwin + WL - 1) / WL); }
+inline uint32_t wide_max_chunks(uint32_t nwin, uint32_t bins, size_t n) { return (uint32_t)(((uint64_t)n * nwin + SUB - 1) / SUB) + bins; }
+inline uint32_t wide_max_parts(uint32_t nwin, uint32_t nb, uint32_t bins, size_t n, uint32_t WCAP) {
+    return (wide_lanes(nwin, n) + 2 * nb) / WCAP + nb + 2 * bins + 64;
+}
+
+// ---- the workspace of a plan (msm_workspace_create): fixed when it is made.  A fixed-base workspace over a resident table of
+// max_n points runs wide where msm_wide_shape holds; arbitrary bases never do.
+enum MsmPlan : uint32_t { MSM_PLAN_WIDE, MSM_PLAN_FIXED, MSM_PLAN_GENERIC };
+inline MsmPlan msm_ws_plan(bool fixed, uint32_t c, size_t max_n) {
+    return !fixed ? MSM_PLAN_GENERIC : msm_wide_applies(c, max_n) ? MSM_PLAN_WIDE : MSM_PLAN_FIXED;
+}
+enum MsmBuf : uint32_t {
+    WS_COUNTS, WS_ENTRIES, WS_REDO, WS_SLOT_PT, WS_INTER, WS_COARSE,  // every plan (the last two: no arbitrary bases)
+    WS_TOTALS, WS_CURSOR, WS_DIGITS, WS_BUCKET_START, WS_BLOCKBASE, WS_PARTIAL, WS_PART, WS_BIT_SUM,  // the standard plan's
+    WS_W_TOT0, WS_W_TOT1, WS_W_CUR0, WS_W_CUR1, WS_W_LANE_B, WS_W_BSTART, WS_W_PSTART, WS_W_PBUCKET, WS_W_PART, WS_W_RC,  // the wide path's
+    WS_NBUF
+};
+struct MsmWsLayout {
+    struct { size_t count, elem; } buf[WS_NBUF];  // elements and bytes per element; 0: the plan has no such buffer
+    uint32_t coarse_stride;                       // words per column in WS_COARSE: the wide header covers the two-level sort's (256 bins)
+};
+// pt29 / ptx: sizeof(G1X29S) / sizeof(G1X).  Bucket sets are max_batch (fixed base) or nwin (arbitrary bases).  The wide path's
+// entries, redo list and slots are its own column regions, not the standard plan's padded list.
+inline MsmWsLayout msm_ws_layout(MsmPlan plan, uint32_t c, size_t max_n, uint32_t max_batch, size_t pt29, size_t ptx) {
+    MsmWsLayout L = {};
+    const auto set = [&L](MsmBuf id, size_t count, size_t elem) { L.buf[id].count = count, L.buf[id].elem = elem; };
+    const size_t cols = max_batch, nwin = nwin_for(c), nb = (size_t)1 << (c - 1), nblk = (max_n + FCHUNK - 1) / FCHUNK;
+    L.coarse_stride = (uint32_t)(WHDR + nblk * WCB);
+    set(WS_COUNTS, 4 * (MSM_MAX_BATCH + 1), 4);
+    if (plan != MSM_PLAN_GENERIC) {
+        set(WS_INTER, cols * max_n * nwin, 4);
+        set(WS_COARSE, cols * L.coarse_stride, 4);
+    }
+    if (plan == MSM_PLAN_WIDE) {
+        const MsmWideDims d = msm_wide_dims(c, max_n);
+        set(WS_ENTRIES, cols * d.ent_stride, 4);
+        set(WS_REDO, cols * d.lane_stride, 4);
+        set(WS_SLOT_PT, cols * d.slot_stride, pt29);
+        for (MsmBuf id : {WS_W_TOT0, WS_W_TOT1, WS_W_CUR0, WS_W_CUR1, WS_W_BSTART, WS_W_PSTART}) set(id, cols * nb, 4);
+        set(WS_W_LANE_B, cols * d.lane_stride, 4);
+        set(WS_W_PBUCKET, cols * d.part_stride, 4);
+        set(WS_W_PART, cols * d.part_stride, pt29);
+        set(WS_W_RC, cols * (d.rows + 256), pt29);
+        return L;
+    }
+    const bool fixed = plan == MSM_PLAN_FIXED;
+    const MsmStdPass p = msm_std_pass(fixed, c, max_n, max_batch);  // the widest, longest pass
+    const size_t swept_blocks = (max_n + CHUNK - 1) / CHUNK * nwin, fused_blocks = fixed ? cols * nblk : 0;
+    set(WS_ENTRIES, p.worst, 4);
+    set(WS_REDO, p.threads + 1, 4);
+    set(WS_SLOT_PT, p.threads + 1, pt29);
+    set(WS_TOTALS, (size_t)p.nbt + 1, 4);
+    set(WS_BUCKET_START, (size_t)p.nbt + 1, 4);
+    if (fixed) set(WS_CURSOR, cols * nb, 4);
+    set(WS_DIGITS, cols * max_n * nwin, 2);
+    set(WS_BLOCKBASE, (swept_blocks > fused_blocks ? swept_blocks : fused_blocks) * nb, 4);
+    set(WS_PARTIAL, (p.threads + 1) / GA + 2, pt29);
+    set(WS_PART, p.ngroups, pt29);
+    set(WS_BIT_SUM, (size_t)p.slices * c * BITSUM_MAX_SPLIT, ptx);
+    return L;
 }
 
 }  // namespace zk

@@ -1,4 +1,4 @@
-// msm_legacy.hip.h — the window plans of the SMALL and the VERY LARGE fixed-base MSMs and of arbitrary bases (part of msm.hip's
+// msm_standard.hip.h — the window plans of the SMALL and the VERY LARGE fixed-base MSMs and of arbitrary bases (part of msm.hip's
 // translation unit, inside namespace zk): signed-digit recoding into int16 planes, the one-pass and the two-level counting
 // sort, the padded 16-entry accumulation segments, the two-level gather and the bit sums.  Who takes it: n < 2^16 over the
 // resident SRS (lg n - 5 window bits: a bucket set of its own per column is too much tail for so few points — tools/bench_rows.py:
@@ -97,10 +97,7 @@ __global__ __launch_bounds__(256) void msm_sort_kernel(const int16_t* __restrict
 // ---- fixed-base mode: every window feeds ONE bucket set, so a workgroup owns a chunk of scalars with
 // ALL their windows: digit extraction and the LDS histogram are one kernel, and the scatter re-reads the
 // digits it wrote (5 launches per MSM head instead of 10).
-#ifndef ZK_FCHUNK
-#define ZK_FCHUNK 1024
-#endif
-static constexpr uint32_t FCHUNK = ZK_FCHUNK;  // scalars per workgroup (x nwin entries)
+// FCHUNK scalars per workgroup (x nwin entries): msm_plan.h
 
 __device__ __forceinline__ uint32_t msm_digits_of(const uint32_t* L, uint32_t c, uint32_t nwin, uint32_t i, uint32_t stride,
                                                   int16_t* __restrict__ digits, uint32_t* hist) {
@@ -168,11 +165,8 @@ __global__ __launch_bounds__(256) void msm_recode_hist_kernel(MsmBatch batch, ui
 // so that consecutive lanes store to consecutive addresses.  The 6-bit fine key rides in bits 24..29 of the entry between
 // the two levels (an entry is sign << 31 | window * n + i, which needs 24 bits up to 20 windows x 2^19).
 // ZK_SORT2, ZK_SORT2_MIN_N, CBINS_MAX and the rule that selects this sort (sort2_applies): msm_plan.h
-#ifndef ZK_SORT_SUB
-#define ZK_SORT_SUB 4096
-#endif
-static constexpr uint32_t SUB = ZK_SORT_SUB;  // entries sorted in LDS at a time
-static constexpr uint32_t COARSE_WORDS = 5 * (CBINS_MAX + 1);  // per column, CBINS_MAX + 1 words each: bin starts, chunk prefix, append cursors, (unused), wide path: the bins' part regions
+// SUB entries are sorted in LDS at a time: msm_plan.h
+// COARSE_WORDS (msm_plan.h): per column, CBINS_MAX + 1 words each: bin starts, chunk prefix, append cursors, (unused), wide path: the bins' part regions
 
 // digits + fine histogram: the global bucket totals (the workgroup's counts are added with one atomic per non-empty bucket)
 __global__ __launch_bounds__(256) void msm_recode_hist2_kernel(MsmBatch batch, uint32_t n, uint32_t stride, uint32_t c, uint32_t nwin,

@@ -27,20 +27,16 @@
 #ifndef ZK_WCAP_BATCH
 #define ZK_WCAP_BATCH 8
 #endif
-static constexpr uint32_t WCAP_MIN = 2, WCAP_BATCH = ZK_WCAP_BATCH;  // WCAP_MIN sizes the part lists
+static constexpr uint32_t WCAP_BATCH = ZK_WCAP_BATCH;  // (WCAP_MIN, which sizes the part lists: msm_plan.h)
 #ifndef ZK_WCAP_ONE
 #define ZK_WCAP_ONE 8
 #endif
 static inline uint32_t wcap_for(uint32_t batch) { return batch == 1 ? (uint32_t)ZK_WCAP_ONE : WCAP_BATCH; }
 static constexpr uint32_t WIDE_SUMS = 20; // bit sums per column handed to the host: 9 column bits, then up to 8 row bits (65 536 buckets)
-#ifndef ZK_WL
-#define ZK_WL 16
-#endif
-// entries per accumulation lane.  Measured with whole proofs, two pipelines in flight (tools/bench_ab.sh, proofs/s | single
+// WL (msm_plan.h): entries per accumulation lane.  Measured with whole proofs, two pipelines in flight (tools/bench_ab.sh, proofs/s | single
 // proof ms): 8: 90.0 | 12.9, 11: 91.4 | 12.9, 12: 92.8 | 12.5, 16: 95.0 | 12.2, 32: 91.4 | 12.8, 48: 85.8 | 13.7, 64: 84.4 | 13.9
 // — short runs mean more slots for the reduction tail to add up, long runs fewer, longer waves that share the chip badly
 // with the other kernels in flight (a 2^19 column is 8192 waves of 16 additions)
-static constexpr uint32_t WL = ZK_WL;
 // slots of a bucket whose cnt > 0 entries start at position s of the column's entry list: one per lane that holds some of them
 __device__ __forceinline__ uint32_t wide_slot_count(uint32_t s, uint32_t cnt) { return cnt ? (s + cnt - 1) / WL - s / WL + 1 : 0; }
 
@@ -55,16 +51,11 @@ __device__ __forceinline__ uint32_t wide_slot_count(uint32_t s, uint32_t cnt) { 
 //     the rest: fb = 31 - ib fine bits (128 / 64 / 32 buckets per coarse bin), 30 - ib distance bits;
 //   * the coarse scan is the prologue of the first scatter (every workgroup scans the <= 512 bin totals itself, workgroup
 //     0 publishes the header), the reset of the counters is the epilogue of the last tail kernel.
-static constexpr uint32_t WCB = 512;                  // coarse bins at most (65 536 buckets / 128, or 32 768 / 64)
+// (the constants of this layout, WCB .. WHDR: msm_plan.h)  WCB coarse bins at most (65 536 buckets / 128, or 32 768 / 64);
 // per column: bin starts, chunk prefix, (unused), (unused), part regions — WCB + 1 words each — then the append cursors, ONE
 // PER 128-BYTE LINE: every workgroup of H1 ends with a returning atomic per bin on them (131 K atomics on 256 words per 2^19
 // column); side by side they would all land on 8 cache lines
-#ifndef ZK_WCUR_STRIDE
-#define ZK_WCUR_STRIDE 32
-#endif
-static constexpr uint32_t WCUR = ZK_WCUR_STRIDE;      // words between two append cursors
-static constexpr uint32_t WCUR0 = 5 * (WCB + 1);      // first cursor
-static constexpr uint32_t WHDR = WCUR0 + WCB * WCUR;  // words of the header; the workgroups' reserved bases [blocks][WCB] follow
+// (WCUR words between two cursors, the first at WCUR0; WHDR words of header, then the workgroups' reserved bases [blocks][WCB])
 static constexpr uint32_t WSUB = 256 * 17;            // entries of a scatter sub-round: 256 scalars x all their windows (<= 17)
 
 struct WideGeo {

@@ -1,5 +1,10 @@
-// Host check of csrc/serde_host.h (tests/test_serde_host.py builds and drives it; no device is opened).  One answer per line of
-// standard input; <fmt> is a ZK_SERDE_* number, points travel as hex:
+// Host check of csrc/serde_host.h and the codec under it, csrc/g1_codec.hip.h (tests/test_serde_host.py builds and drives it, once
+// more under the sanitizers; no device is opened).  The functions are the ones the codec kernels call: this is a CPU run of what
+// they run.  One answer per line of standard input; <fmt> is a ZK_SERDE_* number, points travel as hex:
+//   sqrtexp                            ->  the compile-time (p + 1) / 4, 64 hex digits
+//   ptb <hex of 32 bytes>              ->  point <hex of x || y big-endian> | refuse     (a proof point of the Blake2b transcript)
+//   pte <hex of 64 bytes>              ->  point <hex of x || y big-endian> | refuse     (a proof point of the EVM transcript)
+//   frr <0 | 1: big-endian> <hex of 32 bytes>  ->  value <hex, big-endian> | refuse      (verifier::fr_read)
 //   g1r <fmt> <hex of 32 / 64 bytes>   ->  admit <hex of the 64-byte Montgomery image> | refuse       (host_g1_read)
 //   g2r <fmt> <hex of 64 / 128 bytes>  ->  admit <hex of the 128-byte Montgomery image> | refuse      (host_g2_read)
 //   g1w <fmt> <hex of the 64-byte image>   ->  bytes <hex>                                            (host_g1_write)
@@ -17,6 +22,7 @@
 #include <vector>
 
 #include "serde_host.h"
+#include "verifier.h"
 
 using namespace zk;
 
@@ -74,6 +80,35 @@ int main() {
                     host_g2_write(v.data(), fmt, out.data());
                 }
                 printf("bytes %s\n", hex(out.data(), out.size()).c_str());
+            }
+        } else if (op == "sqrtexp") {
+            for (int i = 7; i >= 0; i--) printf("%08x", FqSqrt::EXP[i]);
+            printf("\n");
+        } else if (op == "ptb" || op == "pte") {
+            in >> a;
+            const std::vector<uint8_t> v = unhex(a);  // (exactly sized, as above)
+            if (v.size() != (op == "ptb" ? 32u : 64u)) return 2;
+            G1Affine p;
+            uint8_t xy[64];
+            // as verify_decode_kernel: the codec's answer, and the verifier's own rule that a proof holds no identity
+            if (!(op == "ptb" ? g1_decompress(v.data(), &p) == G1_POINT : g1_read_evm(v.data(), &p))) {
+                printf("refuse\n");
+            } else {
+                g1_write_evm(p, xy);
+                printf("point %s\n", hex(xy, 64).c_str());
+            }
+        } else if (op == "frr") {
+            int be;
+            in >> be >> a;
+            const std::vector<uint8_t> v = unhex(a);
+            if (v.size() != 32u) return 2;
+            Fr s;
+            uint8_t out[32];
+            if (!verifier::fr_read(v.data(), be != 0, &s)) {
+                printf("refuse\n");
+            } else {
+                fe_to_bytes(fe_from_mont(s), true, out);
+                printf("value %s\n", hex(out, 32).c_str());
             }
         } else if (op == "in") {
             size_t len;

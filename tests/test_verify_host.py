@@ -1,8 +1,8 @@
 """csrc/pairing.h and csrc/verifier.h on the host (tests/verify_host_check.cpp, built here with hipcc; no GPU): the BN254 pairing's
 laws, the reference's golden EVM proof accepted by a real pairing — under the tau-free check, with the SRS's s_g2 — with the Yul
 verifier's challenges, and the same verdicts as the oracle verifier on oracle proofs of all four transcript x scheme combinations,
-intact and tampered.  The point decoding and the multi-scalar sums, which the product does on the device, are the test binary's own
-host restatement."""
+intact and tampered.  The point decoding is the product's own (csrc/g1_codec.hip.h, what verify_decode_kernel calls); the multi-scalar
+sums, which the product does on the device, are the test binary's own host restatement."""
 import json
 import os
 import shutil

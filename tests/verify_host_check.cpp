@@ -1,6 +1,6 @@
-// Host check of csrc/pairing.h and csrc/verifier.h (tests/test_verify_host.py builds and drives it).  The proof-point decoding and
-// the multi-scalar sums the product does on the device are restated here in their plainest host form — test code only: the
-// product has no CPU path.
+// Host check of csrc/pairing.h and csrc/verifier.h (tests/test_verify_host.py builds and drives it).  The proof-point decoding is
+// the product's own (csrc/g1_codec.hip.h): a CPU run of what verify_decode_kernel runs.  The multi-scalar sums the product does on
+// the device are restated here in their plainest host form — test code only: the product has no CPU path.
 //
 //   verify_host_check pairing <tau hex>     bilinearity / order / non-degeneracy, and e([tau]G1, G2) = e(G1, [tau]G2)
 //   verify_host_check verify < job          one verdict per proof line of the job (format: tests/test_verify_host.py)
@@ -71,48 +71,8 @@ static G1Affine g1_gen() {
     return g;
 }
 
-// the oracle's point readers (zkoracle plonk EvmTranscript / Blake2bTranscript .read_point)
-static bool decode_point(const uint8_t* b, bool evm, G1Affine* out) {
-    Fq x, y;
-    if (evm) {
-        for (int i = 0; i < 32; i++) ((uint8_t*)x.v)[i] = b[31 - i], ((uint8_t*)y.v)[i] = b[63 - i];
-        auto lt_p = [](const Fq& v) {
-            for (int i = 7; i >= 0; i--)
-                if (v.v[i] != FqParams::P[i]) return v.v[i] < FqParams::P[i];
-            return false;
-        };
-        if (!lt_p(x) || !lt_p(y) || (x.is_zero() && y.is_zero())) return false;
-        out->x = fe_to_mont(x);
-        out->y = fe_to_mont(y);
-        return fe_sqr(out->y) == fe_add(fe_mul(fe_sqr(out->x), out->x), fq_small(3));
-    }
-    memcpy(x.v, b, 32);
-    const uint32_t sign = x.v[7] >> 31;
-    x.v[7] &= 0x7fffffffu;
-    for (int i = 7; i >= 0; i--) {
-        if (x.v[i] != FqParams::P[i]) {
-            if (x.v[i] > FqParams::P[i]) return false;
-            break;
-        }
-        if (i == 0) return false;
-    }
-    const Fq xm = fe_to_mont(x), rhs = fe_add(fe_mul(fe_sqr(xm), xm), fq_small(3));
-    uint32_t e[8];  // (p + 1) / 4
-    uint64_t carry = 1;
-    uint32_t t[8];
-    for (int i = 0; i < 8; i++) {
-        const uint64_t s = (uint64_t)FqParams::P[i] + carry;
-        t[i] = (uint32_t)s;
-        carry = s >> 32;
-    }
-    for (int i = 0; i < 8; i++) e[i] = (t[i] >> 2) | (i + 1 < 8 ? t[i + 1] << 30 : 0);
-    Fq yy = fe_pow(rhs, e);
-    if (fe_sqr(yy) != rhs) return false;
-    if ((fe_from_mont(yy).v[0] & 1u) != sign) yy = fe_neg(yy);
-    out->x = xm;
-    out->y = yy;
-    return true;
-}
+// one proof point, exactly as verify_decode_kernel decodes it: the product's codec, and the caller's rule that a proof holds no identity
+static bool decode_point(const uint8_t* b, bool evm, G1Affine* out) { return evm ? g1_read_evm(b, out) : g1_decompress(b, out) == G1_POINT; }
 
 static std::vector<uint8_t> unhex(const std::string& s) {
     std::vector<uint8_t> v(s.size() / 2);

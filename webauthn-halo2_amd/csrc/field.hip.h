@@ -67,6 +67,12 @@ struct alignas(16) Fe {
         return o == 0;
     }
     __host__ __device__ __forceinline__ bool operator!=(const Fe& b) const { return !(*this == b); }
+    // the image, read as a 256-bit integer, is below the modulus: what every reader of outside bytes asks before it computes
+    __host__ __device__ __forceinline__ bool below_modulus() const {
+        for (int i = 7; i >= 0; i--)
+            if (v[i] != PRM::P[i]) return v[i] < PRM::P[i];
+        return false;
+    }
 };
 
 // r = a - p if a >= p (a < 2p assumed)

@@ -23,6 +23,7 @@
 
 #include "ec.hip.h"
 #include "field.hip.h"
+#include "g1_codec.hip.h"
 #include "hostutil.h"
 
 #ifndef ZK_PAIRING_VALID  // (include/zkmi355.h defines the same four: this header also stands alone)
@@ -49,16 +50,7 @@
 
 namespace zk {
 
-ZK_PAIR_FN Fq fq_small(uint32_t x) {
-    Fq t = Fq::zero();
-    t.v[0] = x;
-    return fe_to_mont(t);
-}
-ZK_PAIR_FN bool fq_is_canonical(const Fq& a) {  // the image is below p
-    for (int i = 7; i >= 0; i--)
-        if (a.v[i] != FqParams::P[i]) return a.v[i] < FqParams::P[i];
-    return false;
-}
+ZK_PAIR_FN bool fq_is_canonical(const Fq& a) { return a.below_modulus(); }  // (fq_small, the G1 curve test: g1_codec.hip.h)
 // the inverse; one value whichever way it is found (the host's binary Euclid, the device's Fermat power)
 ZK_PAIR_FN Fq fq_inv_any(const Fq& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -485,9 +477,8 @@ inline bool pairing_check(const G1Affine& a, const G1Affine& b, const G2A& g2, c
 // a and b are validated first (both coordinates below p, then on y^2 = x^3 + 3 or the identity (0, 0))
 ZK_PAIR_FN uint8_t pairing_check_lines(const G1Affine& a, const G1Affine& b, const PairingTable& t) {
     if (!fq_is_canonical(a.x) || !fq_is_canonical(a.y) || !fq_is_canonical(b.x) || !fq_is_canonical(b.y)) return ZK_PAIRING_RANGE;
-    const Fq three = fq_small(3);
-    if (!affine_is_identity(a) && fe_sqr(a.y) != fe_add(fe_mul(fe_sqr(a.x), a.x), three)) return ZK_PAIRING_OFF_CURVE;
-    if (!affine_is_identity(b) && fe_sqr(b.y) != fe_add(fe_mul(fe_sqr(b.x), b.x), three)) return ZK_PAIRING_OFF_CURVE;
+    if (!affine_is_identity(a) && !g1_on_curve(a.x, a.y)) return ZK_PAIRING_OFF_CURVE;
+    if (!affine_is_identity(b) && !g1_on_curve(b.x, b.y)) return ZK_PAIRING_OFF_CURVE;
     G1Affine nb = b;
     nb.y = fe_neg(b.y);  // (the identity stays (0, 0))
     const Fq12 f = final_exponentiation_chain(miller_loop_lines(a, nb, t), t.gamma);
@@ -497,7 +488,7 @@ ZK_PAIR_FN uint8_t pairing_check_lines(const G1Affine& a, const G1Affine& b, con
 // a point of G1 other than the identity: both coordinates reduced, y^2 = x^3 + 3 (G1 has cofactor 1)
 ZK_PAIR_FN bool g1_is_proper(const G1Affine& p) {
     if (!fq_is_canonical(p.x) || !fq_is_canonical(p.y) || affine_is_identity(p)) return false;
-    return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
+    return g1_on_curve(p.x, p.y);
 }
 
 // ---- G2 on a lane: a G2 point per check -------------------------------------------------------------------------------------

@@ -292,15 +292,8 @@ int pk_instance_values(const Layout& lay, const uint64_t* instance_mont, size_t 
     if ((n_instance && !instance_mont) || n_instance > (lay.n_inst ? lay.usable : 0u)) return ZK_EINVAL;
     out->resize(n_instance);
     if (n_instance) memcpy(out->data(), instance_mont, n_instance * sizeof(Fr));
-    for (const Fr& v : *out) {  // a Montgomery image is < r
-        bool lt = false;
-        for (int i = 7; i >= 0; i--)
-            if (v.v[i] != FrParams::P[i]) {
-                lt = v.v[i] < FrParams::P[i];
-                break;
-            }
-        if (!lt) return ZK_EINVAL;
-    }
+    for (const Fr& v : *out)
+        if (!v.below_modulus()) return ZK_EINVAL;  // a Montgomery image is < r
     return ZK_OK;
 }
 
@@ -817,14 +810,7 @@ ZK_API(zk_pk_set_transcript_repr, (zk_ctx* c, zk_pk h, const uint64_t transcript
     if (it == c->pks.end()) return ZK_EINVAL;
     Fr v;
     memcpy(&v, transcript_repr, 32);
-    // a Montgomery image is < r
-    for (int i = 7; i >= 0; i--) {
-        if (v.v[i] != FrParams::P[i]) {
-            if (v.v[i] > FrParams::P[i]) return ZK_EINVAL;
-            break;
-        }
-        if (i == 0) return ZK_EINVAL;
-    }
+    if (!v.below_modulus()) return ZK_EINVAL;  // a Montgomery image is < r
     it->second->transcript_repr = v;
     // the lock-step members are by-value copies of the record (pk_make_member): every key-half field that can change after
     // they were made has to be written through to them, or proofs j > 0 of the next batch would hash the stale value

@@ -39,89 +39,30 @@ namespace {
 
 // ------------------------------------------------------------ device side ---
 
-__device__ __forceinline__ bool words_lt_p(const uint32_t* v, const uint32_t* p) {
-    for (int i = 7; i >= 0; i--) {
-        if (v[i] != p[i]) return v[i] < p[i];
-    }
-    return false;
-}
-
-__device__ __forceinline__ Fq fq_three_mont() {
-    Fq t = Fq::zero();
-    t.v[0] = 3;
-    return fe_to_mont(t);
-}
-
-__device__ bool g1_on_curve(const Fq& x, const Fq& y) {
-    const Fq rhs = fe_add(fe_mul(fe_sqr(x), x), fq_three_mont());
-    return fe_sqr(y) == rhs;
-}
-
-// compressed (32 B: x canonical LE, bit 255 = y odd, all-zero = identity) -> affine Montgomery
-__global__ void g1_decompress_kernel(const uint8_t* __restrict__ in, G1Affine* __restrict__ out, uint32_t n, Words8 sqrt_exp,
-                                     uint32_t* __restrict__ err) {
+// The four codec kernels: one element per thread, the rule itself in g1_codec.hip.h / field.hip.h (the host readers run the same
+// functions).  A refused element sets *err; a file admits the identity
+__global__ void g1_decompress_kernel(const uint8_t* __restrict__ in, G1Affine* __restrict__ out, uint32_t n, uint32_t* __restrict__ err) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fq x;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(in + (size_t)i * 32);
-#pragma unroll
-    for (int k = 0; k < 8; k++) x.v[k] = src[k];
-    const uint32_t sign = x.v[7] >> 31;
-    x.v[7] &= 0x7fffffffu;
     G1Affine r;
-    r.x = Fq::zero();
-    r.y = Fq::zero();
-    if (!words_lt_p(x.v, FqParams::P)) {
-        atomicOr(err, 1u);
-    } else if (!(x.is_zero() && !sign)) {
-        const Fq xm = fe_to_mont(x);
-        const Fq rhs = fe_add(fe_mul(fe_sqr(xm), xm), fq_three_mont());
-        Fq y = fe_pow(rhs, sqrt_exp.w);  // p = 3 (mod 4): rhs^((p+1)/4)
-        if (fe_sqr(y) != rhs) {
-            atomicOr(err, 1u);
-        } else {
-            if ((fe_from_mont(y).v[0] & 1u) != sign) y = fe_neg(y);
-            r.x = xm;
-            r.y = y;
-        }
-    }
+    if (g1_decompress(in + (size_t)i * 32, &r) == G1_REFUSED) atomicOr(err, 1u);
     fe_store(&out[i].x, r.x);
     fe_store(&out[i].y, r.y);
 }
 
 __global__ void g1_compress_kernel(const G1Affine* __restrict__ in, uint8_t* __restrict__ out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const G1Affine p = affine_load(in + i);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(out + (size_t)i * 32);
-    if (affine_is_identity(p)) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) dst[k] = 0;
-        return;
-    }
-    Fq x = fe_from_mont(p.x);
-    x.v[7] |= (fe_from_mont(p.y).v[0] & 1u) << 31;
-#pragma unroll
-    for (int k = 0; k < 8; k++) dst[k] = x.v[k];
+    if (i < n) g1_compress(affine_load(in + i), out + (size_t)i * 32);
 }
 
-// RawBytes (checked): both coordinates reduced, point on the curve (or the identity (0,0))
 __global__ void g1_validate_kernel(const G1Affine* __restrict__ in, uint32_t n, uint32_t* __restrict__ err) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const G1Affine p = affine_load(in + i);
-    if (!words_lt_p(p.x.v, FqParams::P) || !words_lt_p(p.y.v, FqParams::P)) {
-        atomicOr(err, 1u);
-        return;
-    }
-    if (!affine_is_identity(p) && !g1_on_curve(p.x, p.y)) atomicOr(err, 1u);
+    if (i < n && !g1_raw_is_valid(affine_load(in + i))) atomicOr(err, 1u);
 }
 
 __global__ void fr_validate_kernel(const Fr* __restrict__ in, size_t n, uint32_t* __restrict__ err) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fr v = fe_load(in + i);
-    if (!words_lt_p(v.v, FrParams::P)) atomicOr(err, 1u);
+    if (i < n && !fe_load(in + i).below_modulus()) atomicOr(err, 1u);
 }
 
 __global__ void fr_from_mont_kernel(Fr* a, size_t n) {
@@ -138,6 +79,39 @@ __global__ void fr_to_mont_kernel(Fr* a, size_t n) {
 bool format_ok(int f) { return f == ZK_SERDE_PROCESSED || f == ZK_SERDE_RAW_BYTES || f == ZK_SERDE_RAW_BYTES_UNCHECKED; }
 
 uint32_t blocks_for(size_t n, uint32_t t = 256) { return (uint32_t)((n + t - 1) / t); }
+
+// The frame of a ParamsKZG image, read once for both SRS readers: K from the header, the length K and the format give, both
+// G2 points validated.  In this order: which fault refuses an image with several is behaviour
+struct SrsImage {
+    uint32_t K;
+    size_t N, gs;  // points per G1 section, bytes per point
+    uint8_t g2[128], s_g2[128];
+    const uint8_t* bytes;
+    const uint8_t* points(int section, size_t first) const { return bytes + 4 + ((size_t)section * N + first) * gs; }  // 0: g, 1: g_lagrange
+};
+bool srs_image_open(const uint8_t* bytes, size_t len, int format, SrsImage* im) {
+    if (len < 4) return false;
+    im->bytes = bytes;
+    im->K = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);
+    if (im->K < 1 || im->K > 24) return false;
+    im->N = (size_t)1 << im->K;
+    im->gs = g1_size(format);
+    if (len != 4 + 2 * im->N * im->gs + 2 * g2_size(format)) return false;
+    const uint8_t* g2 = bytes + 4 + 2 * im->N * im->gs;
+    return host_g2_read(g2, format, im->g2) && host_g2_read(g2 + g2_size(format), format, im->s_g2);
+}
+
+// `cnt` points of a G1 section at `src` into dst: uploaded and decompressed through `packed` (Processed), uploaded and validated in
+// place (RawBytes), or uploaded only (unchecked).  A refused point sets *d_err.  Stream-ordered; nothing is waited for, so the
+// caller's next run may reuse `packed`
+hipError_t srs_points_to_device(zk_ctx* c, const uint8_t* src, size_t cnt, int format, uint8_t* packed, G1Affine* dst, uint32_t* d_err) {
+    const bool processed = format == ZK_SERDE_PROCESSED;
+    const hipError_t e = hipMemcpyAsync(processed ? (void*)packed : (void*)dst, src, cnt * g1_size(format), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return e;
+    if (processed) hipLaunchKernelGGL(g1_decompress_kernel, dim3(blocks_for(cnt, 64)), dim3(64), 0, c->stream, packed, dst, (uint32_t)cnt, d_err);
+    else if (format == ZK_SERDE_RAW_BYTES) hipLaunchKernelGGL(g1_validate_kernel, dim3(blocks_for(cnt, 64)), dim3(64), 0, c->stream, dst, (uint32_t)cnt, d_err);
+    return hipGetLastError();
+}
 
 }  // namespace
 
@@ -214,15 +188,12 @@ ZK_API(zk_srs_write, (zk_ctx* c, int format, uint8_t* out, size_t cap, size_t* l
 }
 
 ZK_API(zk_srs_read, (zk_ctx* c, const uint8_t* bytes, size_t len, int format), (c, bytes, len, format)) {
-    if (!c || !bytes || len < 4 || !format_ok(format)) return ZK_EINVAL;
+    if (!c || !bytes || !format_ok(format)) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    const uint32_t k = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);
-    if (k < 1 || k > 24) return ZK_EINVAL;
-    const size_t n = (size_t)1 << k;
-    const size_t gs = g1_size(format);
-    if (len != 4 + 2 * n * gs + 2 * g2_size(format)) return ZK_EINVAL;
-    uint8_t g2[128], s_g2[128];
-    if (!host_g2_read(bytes + 4 + 2 * n * gs, format, g2) || !host_g2_read(bytes + 4 + 2 * n * gs + g2_size(format), format, s_g2)) return ZK_EINVAL;
+    SrsImage im;
+    if (!srs_image_open(bytes, len, format, &im)) return ZK_EINVAL;
+    const uint32_t k = im.K;
+    const size_t n = im.N;
     int rc = ctx_bind(c);
     if (rc) return rc;
     ctx_release_spares(c);  // the old SRS, its tables and the new bases are alive together below: parked vectors go first
@@ -230,7 +201,7 @@ ZK_API(zk_srs_read, (zk_ctx* c, const uint8_t* bytes, size_t len, int format), (
     // it as they were (they are replaced only once every point has been accepted)
     G1Affine* fresh[2] = {nullptr, nullptr};
     uint32_t* d_err = nullptr;
-    uint8_t* tmp = nullptr;
+    uint8_t* tmp = nullptr;  // one section's compressed points (Processed)
     auto drop = [&]() {
         hipFree(fresh[0]);
         hipFree(fresh[1]);
@@ -238,29 +209,12 @@ ZK_API(zk_srs_read, (zk_ctx* c, const uint8_t* bytes, size_t len, int format), (
         hipFree(tmp);
     };
     if (hipMalloc(&fresh[0], n * sizeof(G1Affine)) != hipSuccess || hipMalloc(&fresh[1], n * sizeof(G1Affine)) != hipSuccess ||
-        hipMalloc(&d_err, 4) != hipSuccess) {
+        hipMalloc(&d_err, 4) != hipSuccess || (format == ZK_SERDE_PROCESSED && hipMalloc(&tmp, n * 32) != hipSuccess)) {
         drop();
         return ZK_ENOMEM;
     }
-    hipMemsetAsync(d_err, 0, 4, c->stream);
-    hipError_t e = hipSuccess;
-    for (int b = 0; b < 2 && e == hipSuccess; b++) {
-        G1Affine* dst = fresh[b];
-        const uint8_t* src = bytes + 4 + (size_t)b * n * gs;
-        if (format == ZK_SERDE_PROCESSED) {
-            if (!tmp && hipMalloc(&tmp, n * 32) != hipSuccess) {
-                drop();
-                return ZK_ENOMEM;
-            }
-            e = hipMemcpyAsync(tmp, src, n * 32, hipMemcpyHostToDevice, c->stream);
-            hipLaunchKernelGGL(g1_decompress_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, c->stream, tmp, dst, (uint32_t)n, fq_sqrt_exp(), d_err);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // tmp is reused by the second basis
-        } else {
-            e = hipMemcpyAsync(dst, src, n * 64, hipMemcpyHostToDevice, c->stream);
-            if (format == ZK_SERDE_RAW_BYTES)
-                hipLaunchKernelGGL(g1_validate_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, c->stream, dst, (uint32_t)n, d_err);
-        }
-    }
+    hipError_t e = hipMemsetAsync(d_err, 0, 4, c->stream);
+    for (int b = 0; b < 2 && e == hipSuccess; b++) e = srs_points_to_device(c, im.points(b, 0), n, format, tmp, fresh[b], d_err);
     uint32_t herr = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -278,8 +232,8 @@ ZK_API(zk_srs_read, (zk_ctx* c, const uint8_t* bytes, size_t len, int format), (
     srs_adopt(c, k, fresh[0], fresh[1]);
     if ((rc = srs_build_tables(c, k)) != ZK_OK) return rc;
     c->srs_k = (int)k;
-    memcpy(c->g2_raw, g2, 128);
-    memcpy(c->s_g2_raw, s_g2, 128);
+    memcpy(c->g2_raw, im.g2, 128);
+    memcpy(c->s_g2_raw, im.s_g2, 128);
     c->g2_valid = true;
     return ZK_OK;
 }
@@ -288,16 +242,12 @@ ZK_API(zk_srs_read, (zk_ctx* c, const uint8_t* bytes, size_t len, int format), (
 // zk_srs_read checks it (length, both G2 points, every point of both G1 sections unless the format is unchecked), streamed
 // through a staging buffer of SRS_STAGE points; the first 2^k points of g are kept, g_lagrange is rebuilt from them.
 ZK_API(zk_srs_read_downsize, (zk_ctx* c, const uint8_t* bytes, size_t len, int format, uint32_t k), (c, bytes, len, format, k)) {
-    if (!c || !bytes || len < 4 || !format_ok(format)) return ZK_EINVAL;
+    if (!c || !bytes || !format_ok(format)) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    const uint32_t K = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);
-    if (K < 1 || K > 24) return ZK_EINVAL;
-    const size_t N = (size_t)1 << K;
-    const size_t gs = g1_size(format);
-    if (len != 4 + 2 * N * gs + 2 * g2_size(format)) return ZK_EINVAL;
-    uint8_t g2[128], s_g2[128];
-    if (!host_g2_read(bytes + 4 + 2 * N * gs, format, g2) || !host_g2_read(bytes + 4 + 2 * N * gs + g2_size(format), format, s_g2)) return ZK_EINVAL;
-    if (k < 1 || k > K) return ZK_EINVAL;  // halo2's downsize asserts k <= self.k
+    SrsImage im;
+    if (!srs_image_open(bytes, len, format, &im)) return ZK_EINVAL;
+    const size_t N = im.N;
+    if (k < 1 || k > im.K) return ZK_EINVAL;  // halo2's downsize asserts k <= self.k
     int rc = ctx_bind(c);
     if (rc) return rc;
     ctx_release_spares(c);
@@ -326,18 +276,7 @@ ZK_API(zk_srs_read_downsize, (zk_ctx* c, const uint8_t* bytes, size_t len, int f
         const size_t end = format == ZK_SERDE_RAW_BYTES_UNCHECKED ? (b ? 0 : n) : N;
         for (size_t off = 0; off < end && e == hipSuccess; off += chunk) {
             const size_t cnt = end - off < chunk ? end - off : chunk;
-            const uint8_t* src = bytes + 4 + (size_t)b * N * gs + off * gs;
-            if (format == ZK_SERDE_PROCESSED) {
-                e = hipMemcpyAsync(packed, src, cnt * 32, hipMemcpyHostToDevice, c->stream);
-                if (e == hipSuccess)
-                    hipLaunchKernelGGL(g1_decompress_kernel, dim3(blocks_for(cnt, 64)), dim3(64), 0, c->stream, packed, stage, (uint32_t)cnt,
-                                       fq_sqrt_exp(), d_err);
-            } else {
-                e = hipMemcpyAsync(stage, src, cnt * 64, hipMemcpyHostToDevice, c->stream);
-                if (e == hipSuccess && format == ZK_SERDE_RAW_BYTES)
-                    hipLaunchKernelGGL(g1_validate_kernel, dim3(blocks_for(cnt, 64)), dim3(64), 0, c->stream, stage, (uint32_t)cnt, d_err);
-            }
-            if (e == hipSuccess) e = hipGetLastError();
+            e = srs_points_to_device(c, im.points(b, off), cnt, format, packed, stage, d_err);
             if (e == hipSuccess && b == 0 && off < n) {
                 const size_t keep = n - off < cnt ? n - off : cnt;
                 e = hipMemcpyAsync(g + off, stage, keep * sizeof(G1Affine), hipMemcpyDeviceToDevice, c->stream);
@@ -366,8 +305,8 @@ ZK_API(zk_srs_read_downsize, (zk_ctx* c, const uint8_t* bytes, size_t len, int f
     }
     // the new SRS goes in whole or not at all: until srs_install succeeds the resident one, its G2 half and its keys stay
     if ((rc = srs_install(c, (uint32_t)k, g, gl)) != ZK_OK) return rc;
-    memcpy(c->g2_raw, g2, 128);
-    memcpy(c->s_g2_raw, s_g2, 128);
+    memcpy(c->g2_raw, im.g2, 128);
+    memcpy(c->s_g2_raw, im.s_g2, 128);
     c->g2_valid = true;
     return ZK_OK;
 }

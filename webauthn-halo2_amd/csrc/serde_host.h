@@ -9,79 +9,19 @@
 
 namespace zk {
 
-struct Words8 {
-    uint32_t w[8];
-};
-
-inline Words8 fq_sqrt_exp() {  // (p + 1) / 4
-    Words8 e;
-    uint64_t carry = 1;
-    uint32_t t[8];
-    for (int i = 0; i < 8; i++) {
-        const uint64_t s = (uint64_t)FqParams::P[i] + carry;
-        t[i] = (uint32_t)s;
-        carry = s >> 32;
-    }
-    for (int i = 0; i < 8; i++) e.w[i] = (t[i] >> 2) | (i + 1 < 8 ? t[i + 1] << 30 : 0);
-    return e;
-}
-
-inline bool host_lt_p(const uint32_t* v, const uint32_t* p) {
-    for (int i = 7; i >= 0; i--)
-        if (v[i] != p[i]) return v[i] < p[i];
-    return false;
-}
-
-inline bool host_g1_on_curve(const G1Affine& p) {
-    return fe_sqr(p.y) == fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3));
-}
-
-// one G1 point <-> bytes in `format`; returns bytes consumed / produced, 0 on a malformed point
+// one G1 point <-> bytes in `format` (the rules themselves: g1_codec.hip.h); false on a malformed point
 inline size_t g1_size(int format) { return format == ZK_SERDE_PROCESSED ? 32 : 64; }
 
 inline bool host_g1_read(const uint8_t* b, int format, G1Affine* out) {
-    if (format == ZK_SERDE_PROCESSED) {
-        Fq x;
-        memcpy(x.v, b, 32);
-        const uint32_t sign = x.v[7] >> 31;
-        x.v[7] &= 0x7fffffffu;
-        if (!host_lt_p(x.v, FqParams::P)) return false;
-        if (x.is_zero() && !sign) {
-            out->x = Fq::zero();
-            out->y = Fq::zero();
-            return true;
-        }
-        const Fq xm = fe_to_mont(x);
-        const Fq rhs = fe_add(fe_mul(fe_sqr(xm), xm), fq_small(3));
-        Fq y = fe_pow(rhs, fq_sqrt_exp().w);
-        if (fe_sqr(y) != rhs) return false;
-        if ((fe_from_mont(y).v[0] & 1u) != sign) y = fe_neg(y);
-        out->x = xm;
-        out->y = y;
-        return true;
-    }
+    if (format == ZK_SERDE_PROCESSED) return g1_decompress(b, out) != G1_REFUSED;  // a file may hold the identity
     memcpy(out, b, 64);
-    if (format == ZK_SERDE_RAW_BYTES) {
-        if (!host_lt_p(out->x.v, FqParams::P) || !host_lt_p(out->y.v, FqParams::P)) return false;
-        if (!affine_is_identity(*out) && !host_g1_on_curve(*out)) return false;
-    }
-    return true;
+    return format != ZK_SERDE_RAW_BYTES || g1_raw_is_valid(*out);  // RawBytesUnchecked: the bytes as they are
 }
 
 inline void host_g1_write(const G1Affine& p, int format, uint8_t* b) {
-    if (format == ZK_SERDE_PROCESSED) {
-        if (affine_is_identity(p)) {
-            memset(b, 0, 32);
-            return;
-        }
-        Fq x = fe_from_mont(p.x);
-        x.v[7] |= (fe_from_mont(p.y).v[0] & 1u) << 31;
-        memcpy(b, x.v, 32);
-        return;
-    }
-    memcpy(b, &p, 64);
+    if (format == ZK_SERDE_PROCESSED) g1_compress(p, b);
+    else memcpy(b, &p, 64);
 }
-
 
 // sqrt in Fq2 (complex method); false if `a` is not a square
 inline bool f2_sqrt(const Fq2& a, Fq2* out) {
@@ -89,11 +29,6 @@ inline bool f2_sqrt(const Fq2& a, Fq2* out) {
         *out = a;
         return true;
     }
-    const Words8 e = fq_sqrt_exp();
-    auto fq_sqrt = [&](const Fq& v, Fq* r) {
-        *r = fe_pow(v, e.w);
-        return fe_sqr(*r) == v;
-    };
     if (a.c1.is_zero()) {  // an element of Fq is always a square here: its root lies in Fq, or is sqrt(-c0) u for a non-residue c0
         Fq r;             // (the complex method below meets delta = 0 on a non-residue c0 and would refuse it)
         if (fq_sqrt(a.c0, &r)) {
@@ -139,21 +74,15 @@ inline bool host_g2_read(const uint8_t* b, int format, uint8_t raw[128]) {
         memcpy(raw, b, 128);
         if (format == ZK_SERDE_RAW_BYTES) {
             const G2A p = g2_from_raw(raw);
-            for (int q = 0; q < 4; q++) {
-                uint32_t w[8];
-                memcpy(w, raw + 32 * q, 32);
-                if (!host_lt_p(w, FqParams::P)) return false;
-            }
+            if (!p.x.c0.below_modulus() || !p.x.c1.below_modulus() || !p.y.c0.below_modulus() || !p.y.c1.below_modulus()) return false;
             if (!p.inf && !g2_on_curve(p)) return false;
         }
         return true;
     }
-    Fq x0, x1;
-    memcpy(x0.v, b, 32);
-    memcpy(x1.v, b + 32, 32);
+    Fq x0 = fe_from_bytes<FqParams>(b, false), x1 = fe_from_bytes<FqParams>(b + 32, false);
     const uint32_t sign = x1.v[7] >> 31;
     x1.v[7] &= 0x7fffffffu;
-    if (!host_lt_p(x0.v, FqParams::P) || !host_lt_p(x1.v, FqParams::P)) return false;
+    if (!x0.below_modulus() || !x1.below_modulus()) return false;
     G2A p;
     p.inf = false;
     if (x0.is_zero() && x1.is_zero() && !sign) {

@@ -13,6 +13,7 @@
 
 #include "ec.hip.h"
 #include "field.hip.h"
+#include "g1_codec.hip.h"
 #include "hostutil.h"
 
 namespace zk {
@@ -156,16 +157,7 @@ struct Blake2b {
 };
 
 // ------------------------------------------------------------ transcripts ---
-inline void fe_to_be32(const uint32_t v[8], uint8_t out[32]) {
-    for (int i = 0; i < 8; i++) {
-        uint32_t w = v[7 - i];
-        out[4 * i] = (uint8_t)(w >> 24);
-        out[4 * i + 1] = (uint8_t)(w >> 16);
-        out[4 * i + 2] = (uint8_t)(w >> 8);
-        out[4 * i + 3] = (uint8_t)w;
-    }
-}
-
+// (the byte forms of scalars and points: g1_codec.hip.h)
 struct Transcript {
     virtual ~Transcript() {}
     virtual void common_scalar(const Fr& s_mont) = 0;
@@ -180,28 +172,22 @@ struct EvmTranscript : Transcript {
     std::vector<uint8_t> buf;
     void common_scalar(const Fr& s) override {
         uint8_t b[32];
-        fe_to_be32(fe_from_mont(s).v, b);
+        fe_to_bytes(fe_from_mont(s), true, b);
         buf.insert(buf.end(), b, b + 32);
     }
     void write_scalar(const Fr& s) override {
-        uint8_t b[32];
-        fe_to_be32(fe_from_mont(s).v, b);
-        buf.insert(buf.end(), b, b + 32);
-        out.insert(out.end(), b, b + 32);
+        common_scalar(s);
+        out.insert(out.end(), buf.end() - 32, buf.end());
     }
     bool write_point(const G1Affine& p) override {
         if (affine_is_identity(p)) return false;
-        uint8_t b[64];
-        fe_to_be32(fe_from_mont(p.x).v, b);
-        fe_to_be32(fe_from_mont(p.y).v, b + 32);
-        buf.insert(buf.end(), b, b + 64);
-        out.insert(out.end(), b, b + 64);
+        common_point(p);
+        out.insert(out.end(), buf.end() - 64, buf.end());
         return true;
     }
     void common_point(const G1Affine& p) override {
         uint8_t b[64];
-        fe_to_be32(fe_from_mont(p.x).v, b);
-        fe_to_be32(fe_from_mont(p.y).v, b + 32);
+        g1_write_evm(p, b);
         buf.insert(buf.end(), b, b + 64);
     }
     Fr squeeze() override {
@@ -238,23 +224,17 @@ struct Blake2bTranscript : Transcript {
     }
     bool write_point(const G1Affine& p) override {
         if (affine_is_identity(p)) return false;
-        const Fq x = fe_from_mont(p.x), y = fe_from_mont(p.y);
-        const uint8_t pre = 1;
-        st.update(&pre, 1);
-        st.update((const uint8_t*)x.v, 32);
-        st.update((const uint8_t*)y.v, 32);
+        common_point(p);
         uint8_t c[32];
-        memcpy(c, x.v, 32);
-        c[31] |= (uint8_t)((y.v[0] & 1) << 7);
+        g1_compress(p, c);
         out.insert(out.end(), c, c + 32);
         return true;
     }
-    void common_point(const G1Affine& p) override {
-        const Fq x = fe_from_mont(p.x), y = fe_from_mont(p.y);
-        const uint8_t pre = 1;
-        st.update(&pre, 1);
-        st.update((const uint8_t*)x.v, 32);
-        st.update((const uint8_t*)y.v, 32);
+    void common_point(const G1Affine& p) override {  // absorbed as both coordinates, little-endian
+        uint8_t xy[65] = {1};
+        fe_to_bytes(fe_from_mont(p.x), false, xy + 1);
+        fe_to_bytes(fe_from_mont(p.y), false, xy + 33);
+        st.update(xy, 65);
     }
     Fr squeeze() override {
         const uint8_t pre = 0;

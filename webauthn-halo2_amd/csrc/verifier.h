@@ -200,15 +200,8 @@ inline ProofLayout proof_layout(const Layout& lay, bool evm, bool shplonk, uint3
 }
 
 inline bool fr_read(const uint8_t* b, bool big_endian, Fr* out_mont) {
-    Fr c;
-    for (int i = 0; i < 32; i++) ((uint8_t*)c.v)[i] = big_endian ? b[31 - i] : b[i];
-    for (int i = 7; i >= 0; i--) {
-        if (c.v[i] != FrParams::P[i]) {
-            if (c.v[i] > FrParams::P[i]) return false;
-            break;
-        }
-        if (i == 0) return false;  // == r
-    }
+    const Fr c = fe_from_bytes<FrParams>(b, big_endian);
+    if (!c.below_modulus()) return false;  // r itself is refused with everything above it
     *out_mont = fe_to_mont(c);
     return true;
 }

@@ -36,75 +36,18 @@ using zk::verifier::Term;
 
 namespace {
 
-struct Words8 {
-    uint32_t w[8];
-};
-
-__device__ __forceinline__ bool v_lt_p(const uint32_t* v) {
-    for (int i = 7; i >= 0; i--)
-        if (v[i] != FqParams::P[i]) return v[i] < FqParams::P[i];
-    return false;
-}
-__device__ __forceinline__ Fq v_three_mont() {
-    Fq t = Fq::zero();
-    t.v[0] = 3;
-    return fe_to_mont(t);
-}
-// 32 bytes at b as a 256-bit integer, little- or big-endian
-__device__ __forceinline__ Fq v_load_bytes(const uint8_t* b, bool big_endian) {
-    Fq r;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const uint32_t byte = big_endian ? b[31 - (4 * k + t)] : b[4 * k + t];
-            w |= byte << (8 * t);
-        }
-        r.v[k] = w;
-    }
-    return r;
-}
-
-// point i of the batch: bytes at off[i]; out = affine Montgomery, flag[i] = 1 if the point is one the verifier accepts
-__global__ void verify_decode_kernel(const uint8_t* __restrict__ bytes, const uint32_t* __restrict__ off, uint32_t n, int evm, Words8 sqrt_exp,
+// point i of the batch: bytes at off[i]; out = affine Montgomery ((0, 0) when refused), flag[i] = 1 if the point is one the
+// verifier accepts.  The encodings are g1_codec.hip.h's; the rule that is this caller's own: a proof holds no identity
+__global__ void verify_decode_kernel(const uint8_t* __restrict__ bytes, const uint32_t* __restrict__ off, uint32_t n, int evm,
                                      G1Affine* __restrict__ out, uint8_t* __restrict__ flag) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint8_t* b = bytes + off[i];
     G1Affine r;
-    r.x = Fq::zero();
-    r.y = Fq::zero();
-    uint8_t ok = 0;
-    if (evm) {
-        const Fq x = v_load_bytes(b, true), y = v_load_bytes(b + 32, true);
-        if (v_lt_p(x.v) && v_lt_p(y.v) && !(x.is_zero() && y.is_zero())) {
-            const Fq xm = fe_to_mont(x), ym = fe_to_mont(y);
-            if (fe_sqr(ym) == fe_add(fe_mul(fe_sqr(xm), xm), v_three_mont())) {
-                r.x = xm;
-                r.y = ym;
-                ok = 1;
-            }
-        }
-    } else {
-        Fq x = v_load_bytes(b, false);
-        const uint32_t sign = x.v[7] >> 31;
-        x.v[7] &= 0x7fffffffu;
-        if (v_lt_p(x.v)) {  // (x = 0 has no point: 3 is not a square mod p)
-            const Fq xm = fe_to_mont(x);
-            const Fq rhs = fe_add(fe_mul(fe_sqr(xm), xm), v_three_mont());
-            Fq y = fe_pow(rhs, sqrt_exp.w);  // p = 3 (mod 4)
-            if (fe_sqr(y) == rhs) {
-                if ((fe_from_mont(y).v[0] & 1u) != sign) y = fe_neg(y);
-                r.x = xm;
-                r.y = y;
-                ok = 1;
-            }
-        }
-    }
+    const bool ok = evm ? g1_read_evm(b, &r) : g1_decompress(b, &r) == G1_POINT;
     fe_store(&out[i].x, r.x);
     fe_store(&out[i].y, r.y);
-    flag[i] = ok;
+    flag[i] = ok ? 1 : 0;
 }
 
 struct VSeg {
@@ -276,19 +219,6 @@ __global__ __launch_bounds__(64) void instance_eval_finish_kernel(const IePair* 
     }
 }
 
-Words8 fq_sqrt_exp_words() {  // (p + 1) / 4
-    Words8 e;
-    uint64_t carry = 1;
-    uint32_t t[8];
-    for (int i = 0; i < 8; i++) {
-        const uint64_t s = (uint64_t)FqParams::P[i] + carry;
-        t[i] = (uint32_t)s;
-        carry = s >> 32;
-    }
-    for (int i = 0; i < 8; i++) e.w[i] = (t[i] >> 2) | (i + 1 < 8 ? t[i + 1] << 30 : 0);
-    return e;
-}
-
 // grow-only device buffer
 int ws_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
     if (*cap >= bytes) return ZK_OK;
@@ -381,13 +311,7 @@ int pk_make_verify_only(zk_ctx* c, const Layout& lay, const std::vector<G1Affine
     Fr repr;
     if (transcript_repr) {
         memcpy(&repr, transcript_repr, 32);
-        bool lt = false;
-        for (int i = 7; i >= 0; i--)
-            if (repr.v[i] != FrParams::P[i]) {
-                lt = repr.v[i] < FrParams::P[i];
-                break;
-            }
-        if (!lt) return ZK_EINVAL;
+        if (!repr.below_modulus()) return ZK_EINVAL;  // a Montgomery image is < r
     } else {
         repr = vkrepr::transcript_repr(lay, fixed, perm);
     }
@@ -431,11 +355,8 @@ ZK_API(zk_vk_from_parts, (zk_ctx* c, const zk_circuit_params* params, const uint
     memcpy(fixed.data(), fixed_commitments, fixed.size() * sizeof(G1Affine));
     memcpy(perm.data(), perm_commitments, perm.size() * sizeof(G1Affine));
     for (const std::vector<G1Affine>* v : {&fixed, &perm})
-        for (const G1Affine& p : *v) {
-            const Fq x = fe_from_mont(p.x), y = fe_from_mont(p.y);  // (a Montgomery image >= p would not round-trip)
-            if (fe_to_mont(x) != p.x || fe_to_mont(y) != p.y) return ZK_EINVAL;
-            if (!affine_is_identity(p) && fe_sqr(p.y) != fe_add(fe_mul(fe_sqr(p.x), p.x), fq_small(3))) return ZK_EINVAL;
-        }
+        for (const G1Affine& p : *v)
+            if (!g1_raw_is_valid(p)) return ZK_EINVAL;  // the caller's Montgomery images: the checked RawBytes rule
     return pk_make_verify_only(c, lay, fixed, perm, transcript_repr, out);
 }
 
@@ -704,8 +625,7 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
         HIPCHK(c, hipMemcpyAsync(w->off, off.data(), npts * 4, hipMemcpyHostToDevice, c->stream));
         if (c->audit.on) c->audit.op(c->stream, {w->bytes, w->off}, {w->pts, w->flag}, "verify: point decoding (verify_decode_kernel)");
         hipLaunchKernelGGL(verify_decode_kernel, dim3((uint32_t)((npts + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)w->bytes,
-                           (const uint32_t*)w->off, (uint32_t)npts, transcript == ZK_TRANSCRIPT_EVM ? 1 : 0, fq_sqrt_exp_words(),
-                           (G1Affine*)w->pts, (uint8_t*)w->flag);
+                           (const uint32_t*)w->off, (uint32_t)npts, transcript == ZK_TRANSCRIPT_EVM ? 1 : 0, (G1Affine*)w->pts, (uint8_t*)w->flag);
         HIPCHK(c, hipGetLastError());
         std::vector<G1Affine> pts(npts);
         std::vector<uint8_t> flag(npts);
@@ -905,11 +825,6 @@ ZK_API(zk_verify_pairing_stats, (zk_ctx* c, uint64_t out[2]), (c, out)) {
 ZK_API(zk_instance_eval, (zk_ctx* c, uint32_t k, size_t count, const uint64_t* const* instances_mont, const size_t* n_instances, const uint64_t* x_mont, uint64_t* out_mont, uint8_t* on_domain), (c, k, count, instances_mont, n_instances, x_mont, out_mont, on_domain)) {
     if (!c || k > 26 || (count && (!n_instances || !x_mont || !out_mont || !on_domain))) return ZK_EINVAL;
     if (!count) return ZK_OK;
-    auto below_modulus = [](const Fr& v) {
-        for (int i = 7; i >= 0; i--)
-            if (v.v[i] != FrParams::P[i]) return v.v[i] < FrParams::P[i];
-        return false;
-    };
     std::vector<verifier::InstanceList> lists(count);
     std::vector<Fr> xs(count);
     memcpy(xs.data(), x_mont, count * sizeof(Fr));
@@ -917,7 +832,7 @@ ZK_API(zk_instance_eval, (zk_ctx* c, uint32_t k, size_t count, const uint64_t* c
         const size_t m = n_instances[j];
         if (m > ((size_t)1 << k) || (m && (!instances_mont || !instances_mont[j]))) return ZK_EINVAL;
         lists[j] = verifier::InstanceList{m ? reinterpret_cast<const Fr*>(instances_mont[j]) : nullptr, m};
-        if (!below_modulus(xs[j])) return ZK_EINVAL;
+        if (!xs[j].below_modulus()) return ZK_EINVAL;
     }
     // every value a Montgomery image below the modulus; a list that several pairs share is looked at once
     for (size_t j = 0; j < count; j++) {
@@ -925,7 +840,7 @@ ZK_API(zk_instance_eval, (zk_ctx* c, uint32_t k, size_t count, const uint64_t* c
         for (size_t i = 0; i < j && !seen; i++) seen = lists[i].vals == lists[j].vals && lists[i].n >= lists[j].n;
         if (seen) continue;
         for (size_t i = 0; i < lists[j].n; i++)
-            if (!below_modulus(lists[j].vals[i])) return ZK_EINVAL;
+            if (!lists[j].vals[i].below_modulus()) return ZK_EINVAL;
     }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = ctx_bind(c);

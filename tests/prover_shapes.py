@@ -13,11 +13,14 @@ SHAPES = {
     # batched transforms / grand products / divisions) that the full-size proofs use
     "k10batched": (3, 2, 1, 10, 8),
     "k10single": (1, 1, 1, 10, 9),
-    # more than 32 terms in every group of the quotient's y-combination (gate terms, l_0 terms, active-row terms): the
-    # lazy sums of quotient.hip are folded back below 2p (the k <= 13 bench rows do that at full size)
+    # more than 32 terms in every group of the quotient's y-combination (36 gate terms, 49 l_0 terms, 49 active-row terms) — but
+    # quotient_log_slices(9, 36) = 4: quotient_sliced_kernel with 16 lanes per row, and no lane holds more than 3 gate terms, 4 l_0
+    # terms, 2 l_last terms and 4 active-row terms.  The 32-term fold of quotient.hip's lazy sums is NOT reached here (nor by any
+    # other shape of this file: tests/test_quotient_cases.py counts them); tests/test_gpu_quotient_device.py reaches it
     "manycols": (36, 12, 2, 7, 5),
     # more than 40 polynomials in one rotation set over >= 256 rows: the multi-open's linear combinations go through the
-    # argument-list kernel (lincomb_terms), the quotient through the lanes-per-row kernel
+    # argument-list kernel (lincomb_terms), the quotient through the lanes-per-row kernel (16 lanes per row: at most 3 gate
+    # terms, 4 l_0 terms, 2 l_last terms and 4 active-row terms per lane)
     "manycols_k8": (44, 6, 2, 8, 6),
 }
 

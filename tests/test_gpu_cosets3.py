@@ -14,8 +14,11 @@ import test_gpu_prover as t
 
 pytestmark = pytest.mark.gpu
 
-# A, L, F, k, lookup_bits, idle: k below / at / above one NTT tile and one pass, plain and sliced quotient kernels, several
-# chunks and lookups, combined selectors
+# A, L, F, k, lookup_bits, idle: k below / at / above one NTT tile and one pass, several chunks and lookups, combined selectors.
+# Quotient kernels on three cosets (3 * 2^k rows; lanes per row from quotient_log_slices(k + 2, A)): k = 5 has 96 rows and runs
+# quotient_kernel<C3>, one lane per row with 2 gate terms, 4 l_0 terms and 4 active-row terms; every other shape runs
+# quotient_sliced_kernel<C3> with 2, 4, 4, 16, 2 and 16 lanes per row, at most 3 gate terms, 4 l_0 terms and 4 active-row terms per
+# lane (2 l_last terms everywhere).  No sum reaches the 32-term fold: tests/test_gpu_quotient_device.py covers that
 SHAPES = [(2, 1, 1, 5, 3, 0), (2, 1, 1, 8, 5, 0), (4, 1, 1, 10, 7, 0), (4, 2, 2, 9, 6, 1), (17, 3, 1, 8, 5, 0), (3, 1, 1, 13, 10, 0),
           (44, 6, 2, 8, 6, 0)]
 

@@ -3,8 +3,8 @@
 With one circuit the call is zk_prove, byte for byte, at every prover shape and all four transcript x scheme pairs.  With more it is
 compared byte for byte with tests/halo2_ref.py, the plain-Python statement of the rule (tied to the pinned oracle at N = 1 by
 tests/test_multi_ref.py): a wrong chain weight of the accumulating quotient passes, a wrong RNG order or a wrong query order each
-change the bytes.  The accumulating quotient kernel is driven through its branches (lazy sums folded past 32 terms, lanes per row,
-whole domain and three cosets), the merged MSM passes through widths that fill, overflow and split unevenly; refusals leave the
+change the bytes.  The accumulating quotient kernel is driven through the forms a key selects (4 and 16 lanes per row, whole domain,
+and one lane per row on three cosets; the 32-term folds of its lazy sums are reached by tests/test_gpu_quotient_device.py only), the merged MSM passes through widths that fill, overflow and split unevenly; refusals leave the
 outputs untouched; zk_prove and zk_prove_batch on the same key return the bytes they returned before."""
 import ctypes
 
@@ -62,8 +62,10 @@ def test_bytes_of_the_reference(name, N):
 
 @pytest.mark.parametrize("name,kind,scheme", [("manycols", "evm", "gwc"), ("manycols_k8", "blake2b", "shplonk")])
 def test_accumulating_quotient_many_columns(name, kind, scheme):
-    """manycols: more than 32 terms in every group of the y-combination — the lazy sums are folded within each pass;
-    manycols_k8: several lanes share a row and add their shares through LDS before the pass adds to the running quotient."""
+    """Both shapes run quotient_sliced_kernel with 16 lanes per row (quotient_log_slices(9, 36) = quotient_log_slices(10, 44) = 4),
+    plain for circuit 0 and accumulating for circuit 1: the lanes add their shares through LDS before the pass adds to the running
+    quotient.  Per lane at most 3 gate terms, 4 l_0 terms, 2 l_last terms and 4 active-row terms: the row's 36 / 49 / 49 (manycols)
+    terms never meet in one sum, so the 32-term fold of the lazy sums is not reached (tests/test_gpu_quotient_device.py does that)."""
     eng = zk.Engine(0)
     asgs = witnesses(name, 2)
     opk = oracle_key(name, asgs[0])
@@ -74,6 +76,10 @@ def test_accumulating_quotient_many_columns(name, kind, scheme):
 
 
 def test_accumulating_quotient_whole_domain_and_three_cosets():
+    """k17like (4 gate columns, k = 7).  Whole domain: 512 rows, quotient_sliced_kernel with 4 lanes per row, per lane 1 gate term,
+    3 l_0 terms, 2 l_last terms and 3 active-row terms.  Three cosets: 384 rows are no multiple of 256, so the launcher falls back
+    to quotient_kernel, one lane per row with 4 gate terms, 5 l_0 terms, 2 l_last terms and 5 active-row terms.  Each route runs
+    its plain form for circuit 0 and its accumulating form for circuit 1; no sum comes near a fold."""
     eng = zk.Engine(0)
     asgs = witnesses("k17like", 2)
     opk = oracle_key("k17like", asgs[0])

@@ -419,15 +419,20 @@ def test_quotient_entry_point_matches_oracle_h(engine, name):
     engine.pk_free(pk)
 
 
-@pytest.mark.parametrize("name", ["k17like", "manycols"])
+@pytest.mark.parametrize("name", ["k17like", "manycols", "k19like", "idle"])
 def test_quotient_rows_on_adversarial_cosets(engine, name):
     """The quotient kernel computes lazily on 29-bit limbs (value bounds tracked per expression, quotient.hip): its rows must
     equal the oracle's for ANY operand values, not only those of a satisfied circuit — cosets made of the largest stored
-    words (p - 1), zeros, ones, alternations and random elements, with and without the division by X^n - 1."""
+    words (p - 1), zeros, ones, alternations and random elements, with and without the division by X^n - 1.
+    Through the ABI the key decides the kernel (quotient_log_slices; tests/quotient_cases.py has the counts): k17like 4 lanes per
+    row, manycols 16, idle 4 with the selector forms q (2 - q) and q (1 - q), k19like one lane per row with the single-column
+    lookup input q_lookup * a_0.  The key-side vectors are honest here and no sum reaches a fold; tests/test_gpu_quotient_device.py
+    drives the kernels themselves past both."""
     from zkoracle import fastprover as fp, field as F
     A, L, Fx, k, lb = SHAPES[name][:5]
-    p, asg, pk, polys = setup(engine, A, L, Fx, k, lb)
-    sh = plonk.Shape(k, A, L, Fx, lb, 0)
+    idle = SHAPES[name][5] if len(SHAPES[name]) > 5 else 0
+    p, asg, pk, polys = setup(engine, A, L, Fx, k, lb, idle=idle)
+    sh = plonk.Shape(k, A, L, Fx, lb, idle)
     opk = fp.keygen(sh, asg.fixed, asg.copies)
     N = 4 * sh.n
     rng = np.random.default_rng(7)

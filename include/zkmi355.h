@@ -763,6 +763,67 @@ int zk_instance_eval(zk_ctx* ctx, uint32_t k, size_t count, const uint64_t* cons
 int zk_es256_verify(zk_ctx* ctx, size_t count, const uint8_t* sigs /* count x 160 */, uint8_t* verdicts /* count: 1 = valid */,
                     uint8_t* reasons /* count, may be NULL */);
 
+/* ---- WebAuthn assertion check: the relying party's work on the device, ending in the ES256 check above ------------------------
+ * `count` assertions (navigator.credentials.get with an ES256 credential) in two launches, one assertion per lane.  The call makes
+ * msghash from the assertion itself - SHA-256(authenticatorData || SHA-256(clientDataJSON)) -, checks what a relying party must
+ * check of both, parses the DER signature, assembles zk_es256_verify's 160-byte record and verifies it.  verdicts[i] = 1 for an
+ * accepted assertion, else 0; reasons (may be NULL) names the FIRST failing test, in this order:
+ *   ZK_WEBAUTHN_SIZE           authenticator_data_len > ZK_WEBAUTHN_AUTHDATA_MAX, client_data_json_len > ZK_WEBAUTHN_CLIENTDATA_MAX,
+ *                              signature_len outside 8 .. 72, challenge_len outside 1 .. ZK_WEBAUTHN_CHALLENGE_MAX, origin_len >
+ *                              ZK_WEBAUTHN_ORIGIN_MAX (decided on the host: such a request is not uploaded)
+ *   ZK_WEBAUTHN_AUTHDATA       authenticatorData shorter than 37 bytes
+ *   ZK_WEBAUTHN_RPID           its bytes 0 .. 31 are not rp_id_hash
+ *   ZK_WEBAUTHN_FLAGS          (byte 32 & flags_required) != flags_required (UP = 0x01, UV = 0x04).  Bytes 33 .. 36, big-endian, are
+ *                              the signature counter: returned in sign_counts, not judged
+ *   ZK_WEBAUTHN_CLIENTDATA     the limited verification algorithm of WebAuthn Level 2: with
+ *                                E = {"type":"webauthn.get","challenge":"<base64url of challenge, no padding>","origin":"<origin>","crossOrigin":
+ *                              clientDataJSON must start with E, go on with `true` or `false`, then `,` or `}`, and end in `}`;
+ *                              `true` passes only with allow_cross_origin.  No JSON is parsed: the same members in another order
+ *                              are refused with this reason
+ *   ZK_WEBAUTHN_SIGNATURE_DER  the signature is not the strict DER of ECDSA-Sig-Value (30 len 02 lr r 02 ls s: short-form lengths,
+ *                              len exact, INTEGERs of 1 .. 33 bytes, non-negative, minimal, below 2^256, nothing after s)
+ *   ZK_WEBAUTHN_RANGE, _OFF_CURVE, _MISMATCH   zk_es256_verify's, with the same values, over the assembled record
+ * records (may be NULL): the 160-byte record of each assertion - pubkey_x, pubkey_y, r, s, msghash as 32 LITTLE-endian bytes each,
+ * what the provers and zk_es256_verify take -, all zero for one refused before the curve (SIZE .. SIGNATURE_DER).  sign_counts (may
+ * be NULL): the counter, 0 for SIZE and AUTHDATA.  A bad assertion is a verdict, never an error.  Needs no SRS and no key; shares
+ * zk_es256_verify's table of G (built by the first call of either on a context).  Public data only: NOT constant time.
+ * ZK_EINVAL: ctx, a or verdicts NULL, count == 0 or > ZK_WEBAUTHN_BATCH_MAX, a NULL pointer with a non-zero length.  Outputs are
+ * untouched on every error. */
+#define ZK_WEBAUTHN_VALID 0
+#define ZK_WEBAUTHN_RANGE 1
+#define ZK_WEBAUTHN_OFF_CURVE 2
+#define ZK_WEBAUTHN_MISMATCH 3
+#define ZK_WEBAUTHN_SIZE 4
+#define ZK_WEBAUTHN_AUTHDATA 5
+#define ZK_WEBAUTHN_RPID 6
+#define ZK_WEBAUTHN_FLAGS 7
+#define ZK_WEBAUTHN_CLIENTDATA 8
+#define ZK_WEBAUTHN_SIGNATURE_DER 9
+#define ZK_WEBAUTHN_BATCH_MAX ZK_ES256_BATCH_MAX
+#define ZK_WEBAUTHN_AUTHDATA_MAX 1024
+#define ZK_WEBAUTHN_CLIENTDATA_MAX 4096
+#define ZK_WEBAUTHN_CHALLENGE_MAX 64
+#define ZK_WEBAUTHN_ORIGIN_MAX 255
+typedef struct zk_webauthn_assertion {
+    const uint8_t* authenticator_data;
+    size_t authenticator_data_len;
+    const uint8_t* client_data_json;
+    size_t client_data_json_len;
+    const uint8_t* signature; /* DER */
+    size_t signature_len;
+    uint8_t pubkey_x[32], pubkey_y[32]; /* BIG-endian: COSE's -2 / -3 as they are */
+    const uint8_t* challenge;           /* the raw bytes the server issued */
+    size_t challenge_len;
+    const char* origin;
+    size_t origin_len;
+    uint8_t rp_id_hash[32];
+    uint8_t flags_required; /* e.g. 0x01, or 0x05 with user verification */
+    uint8_t allow_cross_origin;
+} zk_webauthn_assertion;
+int zk_webauthn_verify(zk_ctx* ctx, size_t count, const zk_webauthn_assertion* a, uint8_t* verdicts /* count */,
+                       uint8_t* reasons /* count, may be NULL */, uint8_t* records /* count x 160, may be NULL */,
+                       uint32_t* sign_counts /* count, may be NULL */);
+
 /* ---- KZG pairing checks on the device ----------------------------------------------------------------------------------
  * `count` checks e(a_i, s_g2) = e(b_i, g2) in one launch, one per lane, against ONE (g2, s_g2) pair: the caller's (16-word
  * Montgomery images as zk_srs_set_g2 takes them), or with both NULL the resident SRS's.  a_i, b_i are affine Montgomery points of

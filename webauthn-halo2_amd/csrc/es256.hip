@@ -11,15 +11,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ctx.h"
-#include "p256.hip.h"
-
-// the context's ES256 state: the comb of G and the grow-only staging buffers
-struct Es256Ws {
-    P256Affine* table = nullptr;
-    void *in = nullptr, *out = nullptr;
-    size_t c_in = 0, c_out = 0;
-};
+#include "es256.h"
 
 void es256_ws_destroy(Es256Ws* w) {
     if (!w) return;
@@ -40,13 +32,19 @@ __global__ __launch_bounds__(ES256_WG) void es256_comb_kernel(P256Affine* table)
     p256_comb_window((int)w, st, table + (size_t)w * P256_COMB_ENTRIES);
 }
 
-__global__ __launch_bounds__(ES256_WG) void es256_verify_kernel(const uint8_t* sigs, uint32_t count, const P256Affine* table, uint8_t* reasons) {
+// `settled` (null for zk_es256_verify): reasons an earlier launch already decided, one per record; a lane whose byte is set
+// returns at once and leaves its reason as it is (zk_webauthn_verify: `settled` and `reasons` are one array)
+__global__ __launch_bounds__(ES256_WG) void es256_verify_kernel(const uint8_t* sigs, uint32_t count, const P256Affine* table, const uint8_t* settled,
+                                                                uint8_t* reasons) {
     const uint32_t i = blockIdx.x * ES256_WG + threadIdx.x;
     if (i >= count) return;  // the tail lanes of the last wave touch no memory
+    if (settled && settled[i] != ZK_ES256_VALID) return;
     reasons[i] = p256_verify_one(sigs + (size_t)i * 160, table);
 }
 
-int es_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
+}  // namespace
+
+int es256_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
     if (*cap >= bytes) return ZK_OK;
     if (*p) {
         hipStreamSynchronize(c->stream);
@@ -61,7 +59,9 @@ int es_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
 }
 
 // made once per context on its main stream and waited for, like the twiddle tables (ctx.hip ctx_cached_table)
-int es256_table(zk_ctx* c, Es256Ws* w) {
+int es256_table(zk_ctx* c) {
+    if (!c->es256 && !(c->es256 = new (std::nothrow) Es256Ws())) return ZK_ENOMEM;
+    Es256Ws* w = c->es256;
     if (w->table) return ZK_OK;
     P256Affine* t = nullptr;
     if (hipMalloc(&t, (size_t)P256_COMB_POINTS * sizeof(P256Affine)) != hipSuccess) return ZK_ENOMEM;
@@ -78,7 +78,11 @@ int es256_table(zk_ctx* c, Es256Ws* w) {
     return ZK_OK;
 }
 
-}  // namespace
+hipError_t es256_enqueue(zk_ctx* c, const uint8_t* d_sigs, uint32_t count, const uint8_t* d_settled, uint8_t* d_reasons) {
+    hipLaunchKernelGGL(es256_verify_kernel, dim3((count + ES256_WG - 1) / ES256_WG), dim3(ES256_WG), 0, c->stream, d_sigs, count,
+                       (const P256Affine*)c->es256->table, d_settled, d_reasons);
+    return hipGetLastError();
+}
 
 ZK_API(zk_es256_verify, (zk_ctx* c, size_t count, const uint8_t* sigs, uint8_t* verdicts, uint8_t* reasons), (c, count, sigs, verdicts, reasons)) {
     if (!c || !sigs || !verdicts || count == 0 || count > ZK_ES256_BATCH_MAX) return ZK_EINVAL;
@@ -87,16 +91,14 @@ ZK_API(zk_es256_verify, (zk_ctx* c, size_t count, const uint8_t* sigs, uint8_t* 
     if (rc) return rc;
     const uint64_t aud0 = c->audit.violations;
     c->audit.base_of.clear();
-    if (!c->es256 && !(c->es256 = new (std::nothrow) Es256Ws())) return ZK_ENOMEM;
+    if ((rc = es256_table(c))) return rc;
     Es256Ws* w = c->es256;
-    if ((rc = es256_table(c, w)) || (rc = es_grow(c, &w->in, &w->c_in, count * 160)) || (rc = es_grow(c, &w->out, &w->c_out, count))) return rc;
+    if ((rc = es256_grow(c, &w->in, &w->c_in, count * 160)) || (rc = es256_grow(c, &w->out, &w->c_out, count))) return rc;
     std::vector<uint8_t> res(count);
     if (c->audit.on) c->audit.op(c->stream, {}, {w->in}, "es256: signatures upload");
     HIPCHK(c, hipMemcpyAsync(w->in, sigs, count * 160, hipMemcpyHostToDevice, c->stream));
     if (c->audit.on) c->audit.op(c->stream, {w->in, w->table}, {w->out}, "es256: verification (es256_verify_kernel)");
-    hipLaunchKernelGGL(es256_verify_kernel, dim3((uint32_t)((count + ES256_WG - 1) / ES256_WG)), dim3(ES256_WG), 0, c->stream, (const uint8_t*)w->in,
-                       (uint32_t)count, (const P256Affine*)w->table, (uint8_t*)w->out);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, es256_enqueue(c, (const uint8_t*)w->in, (uint32_t)count, nullptr, (uint8_t*)w->out));
     if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "es256: reasons download");
     HIPCHK(c, hipMemcpyAsync(res.data(), w->out, count, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, aud_sync(c, c->stream));  // (the caller's records and `res` are pageable)

@@ -35,6 +35,7 @@ What the scope of this repository imposes, stated where a caller
     and `encode_calldata` lays instances and proof out as snark-verifier's verifier contracts read them.  The rule is
     [RECALLED] (include/zkmi355.h "public inputs").
 """
+import base64
 import dataclasses
 import hashlib
 import os
@@ -49,6 +50,9 @@ from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEM
                      ZK_SRS_CONTRIB_BATCH_MAX, ZK_SRS_CONTRIB_CHAINED, ZK_SRS_CONTRIB_NONTRIVIAL, ZK_SRS_CONTRIB_RESIDENT,
                      ZK_SRS_CONTRIB_SAME_SECRET, ZK_TRANSCRIPT_BLAKE2B,
                      ZK_ES256_BATCH_MAX, ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
+from .engine import (WEBAUTHN_REASON_NAMES, ZK_WEBAUTHN_AUTHDATA, ZK_WEBAUTHN_AUTHDATA_MAX, ZK_WEBAUTHN_BATCH_MAX, ZK_WEBAUTHN_CHALLENGE_MAX,
+                     ZK_WEBAUTHN_CLIENTDATA, ZK_WEBAUTHN_CLIENTDATA_MAX, ZK_WEBAUTHN_FLAGS, ZK_WEBAUTHN_MISMATCH, ZK_WEBAUTHN_OFF_CURVE,
+                     ZK_WEBAUTHN_ORIGIN_MAX, ZK_WEBAUTHN_RANGE, ZK_WEBAUTHN_RPID, ZK_WEBAUTHN_SIGNATURE_DER, ZK_WEBAUTHN_SIZE, ZK_WEBAUTHN_VALID)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -794,6 +798,112 @@ def _signature_ok(pubkey_x, pubkey_y, r, s, msg_hash, device):
     if _SIGNATURE_CHECK == "device":
         return es256_verify_many([(pubkey_x, pubkey_y, r, s, msg_hash)], device)[0]
     return es256_verify(pubkey_x, pubkey_y, r, s, msg_hash)
+
+
+# ---- the WebAuthn assertion check: msghash made HERE from the assertion, not taken from the client ---------------------------
+# What the web client does before it posts a ProveRequestBody (web-demo/src/pages/index.tsx:172-197, 237-250, 285-293: both hashes,
+# the ASN.1 parse, the reversal to little-endian) and what a relying party must check of clientDataJSON and authenticatorData, as
+# one rule with one reason code per request (include/zkmi355.h, zk_webauthn_verify; csrc/webauthn.hip.h states it in full).
+# webauthn_verify is the host route in Python, webauthn_verify_many the device route; set_signature_check chooses, as for ES256.
+def _der_integer(sig, pos):
+    if pos + 2 > len(sig) or sig[pos] != 0x02:
+        return None
+    n = sig[pos + 1]
+    if not 1 <= n <= 33 or pos + 2 + n > len(sig):
+        return None
+    body = sig[pos + 2:pos + 2 + n]
+    if body[0] & 0x80 or (n > 1 and body[0] == 0 and not body[1] & 0x80) or (n == 33 and body[0] != 0):
+        return None
+    return int.from_bytes(body, "big"), pos + 2 + n
+
+
+def webauthn_der_signature(sig: bytes):
+    """(r, s) of the strict DER of ECDSA-Sig-Value (short-form lengths, exact, non-negative minimal INTEGERs below 2^256), or None."""
+    if not 8 <= len(sig) <= 72 or sig[0] != 0x30 or sig[1] != len(sig) - 2:
+        return None
+    a = _der_integer(sig, 2)
+    b = a and _der_integer(sig, a[1])
+    if not b or b[1] != len(sig):
+        return None
+    return a[0], b[0]
+
+
+def webauthn_expected_prefix(challenge: bytes, origin) -> bytes:
+    """E of the client-data rule: what a conforming client's clientDataJSON for this challenge and origin starts with."""
+    origin = origin.encode() if isinstance(origin, str) else bytes(origin)
+    return (b'{"type":"webauthn.get","challenge":"' + base64.urlsafe_b64encode(bytes(challenge)).rstrip(b"=") + b'","origin":"' + origin
+            + b'","crossOrigin":')
+
+
+def _client_data_ok(cd, challenge, origin, allow_cross_origin):
+    e = webauthn_expected_prefix(challenge, origin)
+    if not cd.startswith(e):
+        return False
+    rest = cd[len(e):]
+    word = b"true" if rest.startswith(b"true") else b"false" if rest.startswith(b"false") else None
+    if word is None or rest[len(word):len(word) + 1] not in (b",", b"}") or not cd.endswith(b"}"):
+        return False
+    return word == b"false" or bool(allow_cross_origin)
+
+
+def webauthn_verify(authenticator_data, client_data_json, signature, pubkey_x, pubkey_y, challenge, origin, rp_id_hash, flags_required=0x01,
+                    allow_cross_origin=False):
+    """The relying party's check of one assertion on the host: zk_webauthn_verify's rule in Python (hashlib, the DER and prefix
+    rules, es256_verify).  pubkey_x, pubkey_y: 32 BIG-endian bytes (COSE's -2 / -3).  -> (ok, reason, record, sign_count): reason an
+    engine.ZK_WEBAUTHN_* code, the FIRST failing test; record the 160 bytes pubkey_x || pubkey_y || r || s || msghash, little-endian
+    fields (what the provers take), all zero for a request refused before the curve."""
+    ad, cd, sig = bytes(authenticator_data), bytes(client_data_json), bytes(signature)
+    origin_b = origin.encode() if isinstance(origin, str) else bytes(origin)
+    zero = bytes(160)
+    if (len(ad) > ZK_WEBAUTHN_AUTHDATA_MAX or len(cd) > ZK_WEBAUTHN_CLIENTDATA_MAX or not 8 <= len(sig) <= 72
+            or not 1 <= len(challenge) <= ZK_WEBAUTHN_CHALLENGE_MAX or len(origin_b) > ZK_WEBAUTHN_ORIGIN_MAX):
+        return False, ZK_WEBAUTHN_SIZE, zero, 0
+    if len(ad) < 37:
+        return False, ZK_WEBAUTHN_AUTHDATA, zero, 0
+    count = int.from_bytes(ad[33:37], "big")
+    if ad[:32] != bytes(rp_id_hash):
+        return False, ZK_WEBAUTHN_RPID, zero, count
+    if ad[32] & flags_required != flags_required:
+        return False, ZK_WEBAUTHN_FLAGS, zero, count
+    if not _client_data_ok(cd, challenge, origin_b, allow_cross_origin):
+        return False, ZK_WEBAUTHN_CLIENTDATA, zero, count
+    rs = webauthn_der_signature(sig)
+    if rs is None:
+        return False, ZK_WEBAUTHN_SIGNATURE_DER, zero, count
+    z = hashlib.sha256(ad + hashlib.sha256(cd).digest()).digest()
+    x, y = int.from_bytes(pubkey_x, "big"), int.from_bytes(pubkey_y, "big")
+    fields = (bytes(pubkey_x)[::-1], bytes(pubkey_y)[::-1], rs[0].to_bytes(32, "little"), rs[1].to_bytes(32, "little"), z[::-1])
+    record = b"".join(fields)
+    if x >= _P or y >= _P or int.from_bytes(z, "big") >= _N or not 0 < rs[0] < _N or not 0 < rs[1] < _N:
+        return False, ZK_WEBAUTHN_RANGE, record, count
+    if (y * y - (x * x * x - 3 * x + _B)) % _P:
+        return False, ZK_WEBAUTHN_OFF_CURVE, record, count
+    ok = es256_verify(*fields)
+    return ok, ZK_WEBAUTHN_VALID if ok else ZK_WEBAUTHN_MISMATCH, record, count
+
+
+def webauthn_verify_many(assertions, device: int = 0):
+    """webauthn_verify of every assertion on the device, in one zk_webauthn_verify call per ZK_WEBAUTHN_BATCH_MAX of them ->
+    [(ok, reason, record, sign_count)], in order.  assertions: dicts as Engine.webauthn_verify takes them."""
+    assertions = list(assertions)
+    out = []
+    with _ES256_LOCK:
+        eng = _ES256_ENGINES.get(device)
+        if eng is None:
+            eng = _ES256_ENGINES[device] = Engine(device)
+        for lo in range(0, len(assertions), ZK_WEBAUTHN_BATCH_MAX):
+            out += zip(*eng.webauthn_verify(assertions[lo:lo + ZK_WEBAUTHN_BATCH_MAX]))
+    return out
+
+
+def webauthn_check(assertions, device: int = 0):
+    """[(ok, reason, record, sign_count)] of the assertions by the route set_signature_check names: one webauthn_verify each on the
+    host, or all of them in one launch on the device."""
+    assertions = list(assertions)
+    if _SIGNATURE_CHECK == "device":
+        return webauthn_verify_many(assertions, device)
+    return [webauthn_verify(q["authenticator_data"], q["client_data_json"], q["signature"], q["pubkey_x"], q["pubkey_y"], q["challenge"],
+                            q["origin"], q["rp_id_hash"], q.get("flags_required", 0x01), q.get("allow_cross_origin", False)) for q in assertions]
 
 
 def _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash) -> int:

@@ -29,6 +29,11 @@ ZK_VERIFY_BATCH_MAX = 1024
 ZK_PROVE_MULTI_MAX = 16
 ZK_ES256_VALID, ZK_ES256_RANGE, ZK_ES256_OFF_CURVE, ZK_ES256_MISMATCH = 0, 1, 2, 3
 ZK_ES256_BATCH_MAX = 16384
+(ZK_WEBAUTHN_VALID, ZK_WEBAUTHN_RANGE, ZK_WEBAUTHN_OFF_CURVE, ZK_WEBAUTHN_MISMATCH, ZK_WEBAUTHN_SIZE, ZK_WEBAUTHN_AUTHDATA, ZK_WEBAUTHN_RPID,
+ ZK_WEBAUTHN_FLAGS, ZK_WEBAUTHN_CLIENTDATA, ZK_WEBAUTHN_SIGNATURE_DER) = range(10)
+ZK_WEBAUTHN_BATCH_MAX = ZK_ES256_BATCH_MAX
+ZK_WEBAUTHN_AUTHDATA_MAX, ZK_WEBAUTHN_CLIENTDATA_MAX, ZK_WEBAUTHN_CHALLENGE_MAX, ZK_WEBAUTHN_ORIGIN_MAX = 1024, 4096, 64, 255
+WEBAUTHN_REASON_NAMES = ("VALID", "RANGE", "OFF_CURVE", "MISMATCH", "SIZE", "AUTHDATA", "RPID", "FLAGS", "CLIENTDATA", "SIGNATURE_DER")
 ZK_PAIRING_VALID, ZK_PAIRING_RANGE, ZK_PAIRING_OFF_CURVE, ZK_PAIRING_MISMATCH = 0, 1, 2, 3
 ZK_PAIRING_G2 = 4
 ZK_PAIRING_BATCH_MAX = 4096
@@ -127,6 +132,14 @@ class PkFindingC(ctypes.Structure):
 class SrsContributionC(ctypes.Structure):
     _fields_ = [("before_g1", ctypes.c_uint64 * 8), ("after_g1", ctypes.c_uint64 * 8), ("s_g1", ctypes.c_uint64 * 8),
                 ("s_g2", ctypes.c_uint64 * 16)]
+
+
+class WebauthnAssertionC(ctypes.Structure):
+    _fields_ = [("authenticator_data", ctypes.c_char_p), ("authenticator_data_len", ctypes.c_size_t), ("client_data_json", ctypes.c_char_p),
+                ("client_data_json_len", ctypes.c_size_t), ("signature", ctypes.c_char_p), ("signature_len", ctypes.c_size_t),
+                ("pubkey_x", ctypes.c_uint8 * 32), ("pubkey_y", ctypes.c_uint8 * 32), ("challenge", ctypes.c_char_p),
+                ("challenge_len", ctypes.c_size_t), ("origin", ctypes.c_char_p), ("origin_len", ctypes.c_size_t),
+                ("rp_id_hash", ctypes.c_uint8 * 32), ("flags_required", ctypes.c_uint8), ("allow_cross_origin", ctypes.c_uint8)]
 
 
 class PlacementC(ctypes.Structure):
@@ -245,6 +258,8 @@ def load_library():
         "zk_verify_instance_eval_mode": ([vp, ctypes.c_int], ctypes.c_int),
         "zk_instance_eval": ([vp, u32, sz, ctypes.POINTER(u64p), ctypes.POINTER(sz), u64p, u64p, ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "zk_es256_verify": ([vp, sz, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
+        "zk_webauthn_verify": ([vp, sz, ctypes.POINTER(WebauthnAssertionC), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
+                                ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(u32)], ctypes.c_int),
         "zk_srs_write": ([vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_srs_read": ([vp, vp, sz, ctypes.c_int], ctypes.c_int),
         "zk_srs_set_g2": ([vp, u64p, u64p], ctypes.c_int),
@@ -305,7 +320,7 @@ def load_library():
                         "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
                         "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify",
                         "zk_pairing_check_batch", "zk_verify_pairing_mode", "zk_verify_pairing_stats", "zk_evm_verifier",
-                        "zk_evm_verifier_cost", "zk_pairing_check_each", "zk_srs_contribution_check_batch") and os.environ.get("ZKMI355_LIB"):
+                        "zk_evm_verifier_cost", "zk_pairing_check_each", "zk_srs_contribution_check_batch", "zk_webauthn_verify") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -973,6 +988,48 @@ class Engine:
         reasons = (ctypes.c_uint8 * max(count, 1))()
         self._chk(self.L.zk_es256_verify(self.ctx, count, sigs, verdicts, reasons), "zk_es256_verify")
         return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+
+    def webauthn_verify(self, assertions):
+        """zk_webauthn_verify: the relying party's check of WebAuthn assertions in two launches, one assertion per lane - both hashes,
+        the rules for authenticatorData and clientDataJSON, the DER parse, then zk_es256_verify's rule over the record it assembled.
+        assertions: a sequence of dicts with authenticator_data, client_data_json, signature (DER), pubkey_x, pubkey_y (32 BIG-endian
+        bytes each), challenge (the raw bytes issued), origin (str or bytes), rp_id_hash (32 bytes) and, optionally, flags_required
+        (default 0x01, UP) and allow_cross_origin (default False).  -> ([bool verdicts], [ZK_WEBAUTHN_* reasons], [160-byte records],
+        [signature counters]); a bad assertion is a verdict, not an error.  A caller that makes the same call again (a measurement)
+        passes webauthn_pack's result instead and skips the marshalling."""
+        arr = assertions if isinstance(assertions, ctypes.Array) else self.webauthn_pack(assertions)
+        count = len(arr) if getattr(arr, "zk_count", 1) else 0
+        verdicts = (ctypes.c_uint8 * max(count, 1))()
+        reasons = (ctypes.c_uint8 * max(count, 1))()
+        records = (ctypes.c_uint8 * (160 * max(count, 1)))()
+        counts = (ctypes.c_uint32 * max(count, 1))()
+        self._chk(self.L.zk_webauthn_verify(self.ctx, count, arr, verdicts, reasons, records, counts), "zk_webauthn_verify")
+        raw = bytes(records)
+        return ([bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)],
+                [raw[160 * j:160 * j + 160] for j in range(count)], [int(counts[j]) for j in range(count)])
+
+    @staticmethod
+    def webauthn_pack(assertions):
+        """The zk_webauthn_assertion array of webauthn_verify's dicts (it keeps their byte strings alive)."""
+        assertions = list(assertions)
+        count = len(assertions)
+        arr = (WebauthnAssertionC * max(count, 1))()
+        for c, q in zip(arr, assertions):
+            origin = q["origin"].encode() if isinstance(q["origin"], str) else bytes(q["origin"])
+            for name, v in (("authenticator_data", q["authenticator_data"]), ("client_data_json", q["client_data_json"]),
+                            ("signature", q["signature"]), ("challenge", q["challenge"]), ("origin", origin)):
+                v = bytes(v)
+                setattr(c, name, v)  # (the structure keeps the bytes object alive)
+                setattr(c, name + "_len", len(v))
+            for name in ("pubkey_x", "pubkey_y", "rp_id_hash"):
+                v = bytes(q[name])
+                if len(v) != 32:
+                    raise ValueError(name + ": 32 bytes")
+                getattr(c, name)[:] = v
+            c.flags_required = int(q.get("flags_required", 0x01))
+            c.allow_cross_origin = 1 if q.get("allow_cross_origin", False) else 0
+        arr.zk_count = count  # (an empty list still makes an array of one: the call then refuses count = 0)
+        return arr
 
     def pairing_check_batch(self, a, b, g2=None, s_g2=None):
         """zk_pairing_check_batch: e(a_i, s_g2) = e(b_i, g2) for every pair in one launch, one check per lane.  a, b: (count, 8)

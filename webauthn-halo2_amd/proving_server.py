@@ -24,6 +24,8 @@ integers in 0..=255; so does `parse_request`.
 The proofs are those of `ecdsa_p256.generate_proof*_synthetic` (the same-shape synthetic circuit, ES256
 signature checked on the host — see that module's docstring for what that does and does not mean).
 """
+import base64
+import hashlib
 import json
 import re
 import threading
@@ -122,11 +124,19 @@ def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE, public=False):
         if parsed:
             for (i, _), ok in zip(parsed, ecdsa_p256.es256_verify_many([q for _, q in parsed], devices[0])):
                 checked[i] = ok
+    _prove_slots(bodies, checked, out, evm, devices, degree, public)
+    return out
+
+
+def _prove_slots(bodies, checked, out, evm, devices, degree, public):
+    """prove_batch's threads: out[i] = the hex proof of bodies[i] or its exception; a slot that already holds something is left."""
     per = max(1, ecdsa_p256.PIPELINES_PER_DEVICE)
     workers = len(devices) * per
 
     def work(q):
         for i in range(q, len(bodies), workers):
+            if out[i] is not None:
+                continue
             try:
                 out[i] = _prove(bodies[i], evm, devices[q % len(devices)], degree, None, False, public, checked[i])
             except Exception as e:  # the reference answers 500 for that request and keeps serving
@@ -137,6 +147,110 @@ def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE, public=False):
         t.start()
     for t in ths:
         t.join()
+
+
+# ---- an extension the reference server does not have: the assertion itself in, msghash made here ---------------------------------
+# The reference's web client hashes clientDataJSON and authenticatorData, parses the ASN.1 signature, reverses everything and posts
+# the five arrays (web-demo/src/pages/index.tsx:172-197, 237-250, 285-293); the server then has to trust the client for the hash and
+# for the challenge, origin and relying party inside it.  These entry points take what the authenticator returned, check it against
+# what THIS server issued and expects (ecdsa_p256.webauthn_verify / zk_webauthn_verify), and build the classic request from the
+# record that check assembled - so the answer is byte for byte what prove / prove_evm / prove_batch give for the body an honest web
+# client would have posted.
+
+_B64URL = re.compile(r"[A-Za-z0-9_-]*")
+ASSERTION_FIELDS = ("authenticator_data", "client_data_json", "signature")
+
+
+def parse_assertion(body):
+    """An assertion body from a JSON string / dict: authenticator_data, client_data_json, signature as base64url strings without
+    padding (as @simplewebauthn/browser delivers response.authenticatorData, .clientDataJSON, .signature), pubkey_x, pubkey_y as
+    [u8; 32] LITTLE-endian arrays (ProveRequestBody's), proving_key_path."""
+    if isinstance(body, (str, bytes, bytearray)):
+        body = json.loads(body)
+    if not isinstance(body, dict):
+        raise ValueError("request body must be a JSON object")
+    out = {}
+    for f in ASSERTION_FIELDS:
+        v = body.get(f)
+        if not isinstance(v, str) or not _B64URL.fullmatch(v) or len(v) % 4 == 1:
+            raise ValueError(f"{f}: expected a base64url string without padding")
+        out[f] = base64.urlsafe_b64decode(v + "=" * (-len(v) % 4))
+    for f in ("pubkey_x", "pubkey_y"):
+        v = body.get(f)
+        if not isinstance(v, list) or len(v) != 32 or not all(isinstance(b, int) and not isinstance(b, bool) and 0 <= b <= 255 for b in v):
+            raise ValueError(f"{f}: expected an array of 32 integers in 0..=255")
+        out[f] = bytes(v)
+    path = body.get("proving_key_path")
+    if not isinstance(path, str):
+        raise ValueError("proving_key_path: expected a string")
+    out["proving_key_path"] = path
+    return out
+
+
+def _expectation(q, expected_challenge, origin, rp_id, require_uv, allow_cross_origin):
+    """The assertion of a parsed body with what this server expects of it, as ecdsa_p256.webauthn_check takes it."""
+    rp_id = rp_id.encode() if isinstance(rp_id, str) else bytes(rp_id)
+    return {"authenticator_data": q["authenticator_data"], "client_data_json": q["client_data_json"], "signature": q["signature"],
+            "pubkey_x": q["pubkey_x"][::-1], "pubkey_y": q["pubkey_y"][::-1], "challenge": bytes(expected_challenge), "origin": origin,
+            "rp_id_hash": hashlib.sha256(rp_id).digest(), "flags_required": 0x05 if require_uv else 0x01,
+            "allow_cross_origin": bool(allow_cross_origin)}
+
+
+def _classic_body(q, verdict):
+    """The ProveRequestBody an honest web client would have posted for an accepted assertion, from the record the check assembled;
+    ValueError naming the reason for a refused one."""
+    ok, reason, record, _ = verdict
+    if not ok:
+        raise ValueError("WebAuthn assertion refused: %s" % ecdsa_p256.WEBAUTHN_REASON_NAMES[reason])
+    f = [list(record[32 * i:32 * i + 32]) for i in range(5)]
+    return {"pubkey_x": f[0], "pubkey_y": f[1], "r": f[2], "s": f[3], "msghash": f[4], "proving_key_path": q["proving_key_path"]}
+
+
+def _prove_assertion(body, evm, expected_challenge, origin, rp_id, require_uv, allow_cross_origin, device, degree, rng_seed, check, public):
+    q = parse_assertion(body)
+    verdict = ecdsa_p256.webauthn_check([_expectation(q, expected_challenge, origin, rp_id, require_uv, allow_cross_origin)], device)[0]
+    return _prove(_classic_body(q, verdict), evm, device, degree, rng_seed, check, public, signature_ok=True)
+
+
+def prove_assertion(body, expected_challenge, origin, rp_id, require_uv=False, allow_cross_origin=False, device=0, degree=DEGREE, rng_seed=None,
+                    check=False, public=False) -> str:
+    """prove for an assertion body (parse_assertion): the assertion is checked against expected_challenge (the raw bytes this server
+    issued), origin and rp_id (rpIdHash = SHA-256(rp_id) is made here; UP is required, UV too with require_uv), msghash comes out of
+    that check, and the answer is prove's for the classic body.  A refused assertion is a ValueError naming the first failing test."""
+    return _prove_assertion(body, False, expected_challenge, origin, rp_id, require_uv, allow_cross_origin, device, degree, rng_seed, check, public)
+
+
+def prove_assertion_evm(body, expected_challenge, origin, rp_id, require_uv=False, allow_cross_origin=False, device=0, degree=DEGREE,
+                        rng_seed=None, check=False, public=False) -> str:
+    """prove_evm for an assertion body: prove_assertion's with the Keccak EvmTranscript + GWC."""
+    return _prove_assertion(body, True, expected_challenge, origin, rp_id, require_uv, allow_cross_origin, device, degree, rng_seed, check, public)
+
+
+def prove_assertions_batch(bodies, expected_challenges, origin, rp_id, require_uv=False, allow_cross_origin=False, evm=True, devices=(0,),
+                           degree=DEGREE, public=False):
+    """prove_batch for assertion bodies; expected_challenges: one per body.  All assertions are checked before any proof starts -
+    under ecdsa_p256.set_signature_check("device") in ONE launch on devices[0].  Returns the hex proofs in request order; a body that
+    does not parse, or an assertion that is refused, yields its exception in its own slot and leaves the others alone."""
+    bodies, expected_challenges = list(bodies), list(expected_challenges)
+    if len(expected_challenges) != len(bodies):
+        raise ValueError("one expected challenge per body")
+    out = [None] * len(bodies)
+    parsed = []
+    for i, b in enumerate(bodies):
+        try:
+            parsed.append((i, parse_assertion(b)))
+        except Exception as e:
+            out[i] = e
+    classic = [None] * len(bodies)
+    if parsed:
+        verdicts = ecdsa_p256.webauthn_check([_expectation(q, expected_challenges[i], origin, rp_id, require_uv, allow_cross_origin)
+                                              for i, q in parsed], devices[0])
+        for (i, q), verdict in zip(parsed, verdicts):
+            try:
+                classic[i] = _classic_body(q, verdict)
+            except ValueError as e:
+                out[i] = e
+    _prove_slots(classic, [True] * len(bodies), out, evm, devices, degree, public)
     return out
 
 

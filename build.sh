@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")/webauthn-halo2_amd"
 OUT=libzkmi355.so
-SRCS="csrc/ctx.hip csrc/streams.hip csrc/msm_lanes.hip csrc/srs.hip csrc/poly_abi.hip csrc/ntt.hip csrc/msm.hip csrc/poly.hip csrc/prover_kernels.hip csrc/quotient.hip csrc/prover.hip csrc/prover_key.hip csrc/prover_phases.hip csrc/serde.hip csrc/verify.hip csrc/g1_ntt.hip csrc/witness_check.hip csrc/pk_check.hip csrc/placement.hip csrc/es256.hip csrc/webauthn.hip csrc/pairing.hip csrc/pairing_each.hip"
+SRCS="csrc/ctx.hip csrc/streams.hip csrc/msm_lanes.hip csrc/srs.hip csrc/poly_abi.hip csrc/ntt.hip csrc/msm.hip csrc/poly.hip csrc/prover_kernels.hip csrc/quotient.hip csrc/prover.hip csrc/prover_key.hip csrc/prover_phases.hip csrc/serde.hip csrc/verify.hip csrc/g1_ntt.hip csrc/witness_check.hip csrc/pk_check.hip csrc/placement.hip csrc/es256.hip csrc/webauthn.hip csrc/webauthn_register.hip csrc/pairing.hip csrc/pairing_each.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result"
 mkdir -p build
 objs=""

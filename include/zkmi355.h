@@ -824,6 +824,77 @@ int zk_webauthn_verify(zk_ctx* ctx, size_t count, const zk_webauthn_assertion* a
                        uint8_t* reasons /* count, may be NULL */, uint8_t* records /* count x 160, may be NULL */,
                        uint32_t* sign_counts /* count, may be NULL */);
 
+/* ---- WebAuthn registration check: where the key zk_webauthn_verify takes came from ------------------------------------------------
+ * `count` registrations (navigator.credentials.create with an ES256 credential) in two launches, one per lane.  The call walks the
+ * attestationObject (CBOR), checks authData and the attested credential data in it, takes the COSE key out, checks clientDataJSON
+ * and, where the policy asks for it, the attestation statement; a packed self attestation is verified with the credential's own
+ * key through zk_es256_verify's rule.  verdicts[i] = 1 for an accepted registration, else 0; reasons (may be NULL) names the FIRST
+ * failing test, in this order (0 .. 9 are zk_webauthn_verify's values and meanings):
+ *   ZK_WEBAUTHN_SIZE           attestation_object_len outside 1 .. ZK_WEBAUTHN_ATTOBJ_MAX, client_data_json_len >
+ *                              ZK_WEBAUTHN_CLIENTDATA_MAX, challenge_len outside 1 .. ZK_WEBAUTHN_CHALLENGE_MAX, origin_len >
+ *                              ZK_WEBAUTHN_ORIGIN_MAX (decided on the host: such a request is not uploaded)
+ *   ZK_WEBAUTHN_CBOR           the object is not a definite-length map of exactly  "fmt" -> text, "attStmt" -> map, "authData" ->
+ *                              byte string  in this order (CTAP2's canonical one) with nothing after it, or holds a data item that
+ *                              is not well-formed under the strict rule: definite lengths only (additional information 28 .. 31
+ *                              refused, `break` included), every head in its shortest form, a one-byte simple value >= 32, no
+ *                              declared count of bytes, items or pairs above the bytes left.  Floats are taken as they are, text is
+ *                              not checked for UTF-8
+ *   ZK_WEBAUTHN_AUTHDATA, _RPID, _FLAGS   zk_webauthn_verify's rules over the authData bytes
+ *   ZK_WEBAUTHN_CREDENTIAL     AT (0x40) clear; or aaguid (16 bytes), credentialIdLength (big-endian, 1 .. 1023), the id or the key
+ *                              (one well-formed data item) run past the end of authData; or, behind the key, ED (0x80) clear and
+ *                              authData goes on, ED set and what follows is not exactly one well-formed map
+ *   ZK_WEBAUTHN_COSE_KEY       the key is not the 77 bytes  a5 01 02 03 26 20 01 21 58 20 <x> 22 58 20 <y>  (EC2, ES256, P-256 in
+ *                              canonical form; compared as bytes: other algorithms, curves, member orders, extra members and
+ *                              coordinates not of 32 bytes are refused)
+ *   ZK_WEBAUTHN_CLIENTDATA     zk_webauthn_verify's rule with "type":"webauthn.create" in E
+ *   ZK_WEBAUTHN_RANGE, _OFF_CURVE   the credential key: x, y below p and on the curve, whatever the statement
+ *   ZK_WEBAUTHN_ATTESTATION    only under ZK_WEBAUTHN_ATT_NONE_OR_SELF: the statement is neither fmt "none" with an empty map nor
+ *                              fmt "packed" with exactly {"alg": -7, "sig": bytes} in that order (self attestation, no x5c)
+ *   ZK_WEBAUTHN_SIGNATURE_DER, then _RANGE / _MISMATCH   for a packed self statement under that policy: sig through the strict DER
+ *                              parse, then zk_es256_verify's rule over  x, y, r, s, SHA-256(authData || SHA-256(clientDataJSON))
+ * Under ZK_WEBAUTHN_ATT_IGNORE the statement only has to be well-formed and is not judged (attestation = _NOT_JUDGED for every
+ * fmt): what a relying party that asked for conveyance "none" does.  Certificate chains (x5c) and every other format's own
+ * verification are not done here.  out (may be NULL): the credential of each accepted registration, ALL ZERO for a refused one - a
+ * refused registration never hands out a key.  A bad registration is a verdict, never an error.  Needs no SRS and no key; shares
+ * zk_es256_verify's table of G.  Public data only: NOT constant time.
+ * ZK_EINVAL: ctx, r or verdicts NULL, count == 0 or > ZK_WEBAUTHN_BATCH_MAX, a NULL pointer with a non-zero length, an
+ * attestation_policy above 1.  Outputs are untouched on every error. */
+#define ZK_WEBAUTHN_CBOR 10
+#define ZK_WEBAUTHN_CREDENTIAL 11
+#define ZK_WEBAUTHN_COSE_KEY 12
+#define ZK_WEBAUTHN_ATTESTATION 13
+#define ZK_WEBAUTHN_ATTOBJ_MAX 8192
+#define ZK_WEBAUTHN_ATT_IGNORE 0
+#define ZK_WEBAUTHN_ATT_NONE_OR_SELF 1
+#define ZK_WEBAUTHN_ATTESTED_NONE 0
+#define ZK_WEBAUTHN_ATTESTED_SELF 1 /* the signature was verified with the credential's key */
+#define ZK_WEBAUTHN_ATTESTED_NOT_JUDGED 2
+typedef struct zk_webauthn_registration {
+    const uint8_t* attestation_object; /* CBOR, as the authenticator returned it */
+    size_t attestation_object_len;
+    const uint8_t* client_data_json;
+    size_t client_data_json_len;
+    const uint8_t* challenge; /* the raw bytes the server issued */
+    size_t challenge_len;
+    const char* origin;
+    size_t origin_len;
+    uint8_t rp_id_hash[32];
+    uint8_t flags_required; /* e.g. 0x01, or 0x05 with user verification */
+    uint8_t allow_cross_origin;
+    uint8_t attestation_policy; /* ZK_WEBAUTHN_ATT_* */
+} zk_webauthn_registration;
+typedef struct zk_webauthn_credential {
+    uint8_t pubkey_x[32], pubkey_y[32]; /* BIG-endian, what zk_webauthn_assertion takes */
+    uint8_t aaguid[16];
+    uint32_t auth_data_off, auth_data_len; /* within the caller's attestation_object */
+    uint32_t credential_id_off, credential_id_len;
+    uint32_t sign_count;
+    uint8_t flags;       /* authData byte 32 */
+    uint8_t attestation; /* ZK_WEBAUTHN_ATTESTED_* */
+} zk_webauthn_credential;
+int zk_webauthn_register(zk_ctx* ctx, size_t count, const zk_webauthn_registration* r, uint8_t* verdicts /* count */,
+                         uint8_t* reasons /* count, may be NULL */, zk_webauthn_credential* out /* count, may be NULL */);
+
 /* ---- KZG pairing checks on the device ----------------------------------------------------------------------------------
  * `count` checks e(a_i, s_g2) = e(b_i, g2) in one launch, one per lane, against ONE (g2, s_g2) pair: the caller's (16-word
  * Montgomery images as zk_srs_set_g2 takes them), or with both NULL the resident SRS's.  a_i, b_i are affine Montgomery points of

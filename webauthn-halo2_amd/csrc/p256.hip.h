@@ -418,6 +418,20 @@ P256_FN uint32_t p256_take_digit(uint32_t (&k)[8]) {
 }
 
 // ---- the rule --------------------------------------------------------------------------------------------------------------------
+// The key's part of the rule alone, for a caller that has a key and no signature yet (webauthn_register.hip.h): x, y as eight
+// little-endian words each.  ZK_ES256_RANGE unless both are below p, ZK_ES256_OFF_CURVE unless (x, y) is on the curve: the two
+// tests p256_verify_with applies to a record's key, from the same primitives
+P256_FN uint8_t p256_key_check(const uint32_t (&x)[8], const uint32_t (&y)[8]) {
+    if (!p256_words_lt(x, P256FpPrm::P) || !p256_words_lt(y, P256FpPrm::P)) return ZK_ES256_RANGE;
+    P256Affine Q;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        Q.x.v[i] = x[i];
+        Q.y.v[i] = y[i];
+    }
+    return p256_on_curve(p256_to_mont(Q.x), p256_to_mont(Q.y)) ? ZK_ES256_VALID : ZK_ES256_OFF_CURVE;
+}
+
 // One request: sig = pubkey_x || pubkey_y || r || s || msghash, each 32 little-endian bytes.  Returns the FIRST failing test
 // (ZK_ES256_RANGE, ZK_ES256_OFF_CURVE, ZK_ES256_MISMATCH) or ZK_ES256_VALID.  g_table: the comb of G (P256_COMB_POINTS entries).
 // `st`: working space for the multiples of Q.  u2 Q: 4-bit windows over st, 4 doublings per window; u1 G: mixed additions from

@@ -183,12 +183,16 @@ P256_FN bool webauthn_client_data_ok(const uint8_t* cd, uint32_t cd_len, const u
 }
 
 // E of the rule above into out (WEBAUTHN_PREFIX_MAX bytes at least); returns its length.  Host side: the library and the tests
-// build it per request.  challenge_len in 1 .. 64, origin_len <= 255 (webauthn_size_ok)
-inline uint32_t webauthn_expected_prefix(const uint8_t* challenge, size_t challenge_len, const char* origin, size_t origin_len, uint8_t* out) {
+// build it per request.  challenge_len in 1 .. 64, origin_len <= 255 (webauthn_size_ok).  create: the type is webauthn.create
+// (a registration, webauthn_register.hip.h), E is three bytes longer and out has WEBAUTHN_CREATE_PREFIX_MAX bytes at least
+constexpr uint32_t WEBAUTHN_CREATE_PREFIX_MAX = WEBAUTHN_PREFIX_MAX + 3;
+inline uint32_t webauthn_expected_prefix(const uint8_t* challenge, size_t challenge_len, const char* origin, size_t origin_len, uint8_t* out,
+                                         bool create = false) {
     static const char B64[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
-    static const char P0[] = "{\"type\":\"webauthn.get\",\"challenge\":\"", P1[] = "\",\"origin\":\"", P2[] = "\",\"crossOrigin\":";
+    static const char GET[] = "{\"type\":\"webauthn.get\",\"challenge\":\"", CREATE[] = "{\"type\":\"webauthn.create\",\"challenge\":\"";
+    static const char P1[] = "\",\"origin\":\"", P2[] = "\",\"crossOrigin\":";
     uint32_t n = 0;
-    for (const char* p = P0; *p; p++) out[n++] = (uint8_t)*p;
+    for (const char* p = create ? CREATE : GET; *p; p++) out[n++] = (uint8_t)*p;
     for (size_t i = 0; i < challenge_len; i += 3) {
         const size_t left = challenge_len - i;
         const uint32_t v = ((uint32_t)challenge[i] << 16) | (left > 1 ? (uint32_t)challenge[i + 1] << 8 : 0) | (left > 2 ? (uint32_t)challenge[i + 2] : 0);
@@ -203,10 +207,30 @@ inline uint32_t webauthn_expected_prefix(const uint8_t* challenge, size_t challe
     return n;
 }
 
+// The 160-byte record of (key, r, s, SHA-256(ad || SHA-256(cd))) for p256_verify_one, from a signature webauthn_der_parse took
+// apart.  Bytes 128 .. 159 hold the first digest in between: the second hash reads it from there, so that no lane keeps a byte
+// array of its own.  x_be, y_be: the key, big-endian (COSE's -2 / -3)
+P256_FN void webauthn_record(const uint8_t* ad, uint32_t ad_len, const uint8_t* cd, uint32_t cd_len, const uint8_t* sig, uint32_t r_off, uint32_t r_n,
+                             uint32_t s_off, uint32_t s_n, const uint8_t* x_be, const uint8_t* y_be, uint8_t* record) {
+    uint32_t h[8];
+    sha256_two(cd, cd_len, nullptr, 0, h);
+    sha256_put(h, record + 128);
+    sha256_two(ad, ad_len, record + 128, 32, h);
+    for (uint32_t k = 0; k < 32; k++) {
+        record[k] = x_be[31 - k];
+        record[32 + k] = y_be[31 - k];
+        record[64 + k] = k < r_n ? sig[r_off + r_n - 1 - k] : 0;
+        record[96 + k] = k < s_n ? sig[s_off + s_n - 1 - k] : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) record[128 + 4 * i + j] = (uint8_t)(h[7 - i] >> (8 * j));
+}
+
 // Everything before the curve: AUTHDATA .. SIGNATURE_DER over lengths that passed webauthn_size_ok, both hashes, and the record.
 // Returns the first failing test, or ZK_WEBAUTHN_VALID where the record is ready for p256_verify_one.  record: 160 bytes, all
-// zero on a failure (bytes 128 .. 159 hold the first digest in between: the second hash reads it from there, so that no lane keeps
-// a byte array of its own).  sign_count: 0 on AUTHDATA, else the counter.  x_be, y_be: the key, big-endian (COSE's -2 / -3)
+// zero on a failure, else webauthn_record's.  sign_count: 0 on AUTHDATA, else the counter.  x_be, y_be: the key, big-endian
 P256_FN uint8_t webauthn_digest_one(const uint8_t* ad, uint32_t ad_len, const uint8_t* cd, uint32_t cd_len, const uint8_t* sig, uint32_t sig_len,
                                     const uint8_t* e, uint32_t e_len, const uint8_t* x_be, const uint8_t* y_be, const uint8_t* rp_id_hash,
                                     uint8_t flags_required, bool allow_cross_origin, uint8_t* record, uint32_t* sign_count) {
@@ -232,20 +256,7 @@ P256_FN uint8_t webauthn_digest_one(const uint8_t* ad, uint32_t ad_len, const ui
         for (int i = 0; i < 160; i++) record[i] = 0;
         return reason;
     }
-    uint32_t h[8];
-    sha256_two(cd, cd_len, nullptr, 0, h);
-    sha256_put(h, record + 128);
-    sha256_two(ad, ad_len, record + 128, 32, h);
-    for (uint32_t k = 0; k < 32; k++) {
-        record[k] = x_be[31 - k];
-        record[32 + k] = y_be[31 - k];
-        record[64 + k] = k < r_n ? sig[r_off + r_n - 1 - k] : 0;
-        record[96 + k] = k < s_n ? sig[s_off + s_n - 1 - k] : 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) record[128 + 4 * i + j] = (uint8_t)(h[7 - i] >> (8 * j));
+    webauthn_record(ad, ad_len, cd, cd_len, sig, r_off, r_n, s_off, s_n, x_be, y_be, record);
     return ZK_WEBAUTHN_VALID;
 }
 

@@ -52,7 +52,10 @@ from .engine import (ZK_PK_CHECK_ALL, ZK_SCHEME_DEFAULT, ZK_SCHEME_GWC, ZK_SCHEM
                      ZK_ES256_BATCH_MAX, ZK_TRANSCRIPT_EVM, Engine, ZkError, stream_placement)
 from .engine import (WEBAUTHN_REASON_NAMES, ZK_WEBAUTHN_AUTHDATA, ZK_WEBAUTHN_AUTHDATA_MAX, ZK_WEBAUTHN_BATCH_MAX, ZK_WEBAUTHN_CHALLENGE_MAX,
                      ZK_WEBAUTHN_CLIENTDATA, ZK_WEBAUTHN_CLIENTDATA_MAX, ZK_WEBAUTHN_FLAGS, ZK_WEBAUTHN_MISMATCH, ZK_WEBAUTHN_OFF_CURVE,
-                     ZK_WEBAUTHN_ORIGIN_MAX, ZK_WEBAUTHN_RANGE, ZK_WEBAUTHN_RPID, ZK_WEBAUTHN_SIGNATURE_DER, ZK_WEBAUTHN_SIZE, ZK_WEBAUTHN_VALID)
+                     ZK_WEBAUTHN_ORIGIN_MAX, ZK_WEBAUTHN_RANGE, ZK_WEBAUTHN_RPID, ZK_WEBAUTHN_SIGNATURE_DER, ZK_WEBAUTHN_SIZE, ZK_WEBAUTHN_VALID,
+                     ZK_WEBAUTHN_ATT_IGNORE, ZK_WEBAUTHN_ATT_NONE_OR_SELF, ZK_WEBAUTHN_ATTESTATION, ZK_WEBAUTHN_ATTESTED_NONE,
+                     ZK_WEBAUTHN_ATTESTED_NOT_JUDGED, ZK_WEBAUTHN_ATTESTED_SELF, ZK_WEBAUTHN_ATTOBJ_MAX, ZK_WEBAUTHN_CBOR, ZK_WEBAUTHN_COSE_KEY,
+                     ZK_WEBAUTHN_CREDENTIAL)
 
 # (device) -> {"eng": Engine, "k": int, "keys": {path: (params, pk_handle)}, "slots": {columns: [[Poly]]},
 #              "extra": [{"eng": Engine sharing the first one's SRS, "keys": {path: pk_handle}, "slots": {..}}], "free": Queue of pipeline indices}
@@ -828,15 +831,16 @@ def webauthn_der_signature(sig: bytes):
     return a[0], b[0]
 
 
-def webauthn_expected_prefix(challenge: bytes, origin) -> bytes:
-    """E of the client-data rule: what a conforming client's clientDataJSON for this challenge and origin starts with."""
+def webauthn_expected_prefix(challenge: bytes, origin, typ: bytes = b"webauthn.get") -> bytes:
+    """E of the client-data rule: what a conforming client's clientDataJSON for this challenge and origin starts with.  typ:
+    b"webauthn.get" for an assertion, b"webauthn.create" for a registration."""
     origin = origin.encode() if isinstance(origin, str) else bytes(origin)
-    return (b'{"type":"webauthn.get","challenge":"' + base64.urlsafe_b64encode(bytes(challenge)).rstrip(b"=") + b'","origin":"' + origin
+    return (b'{"type":"' + typ + b'","challenge":"' + base64.urlsafe_b64encode(bytes(challenge)).rstrip(b"=") + b'","origin":"' + origin
             + b'","crossOrigin":')
 
 
-def _client_data_ok(cd, challenge, origin, allow_cross_origin):
-    e = webauthn_expected_prefix(challenge, origin)
+def _client_data_ok(cd, challenge, origin, allow_cross_origin, typ=b"webauthn.get"):
+    e = webauthn_expected_prefix(challenge, origin, typ)
     if not cd.startswith(e):
         return False
     rest = cd[len(e):]
@@ -904,6 +908,173 @@ def webauthn_check(assertions, device: int = 0):
         return webauthn_verify_many(assertions, device)
     return [webauthn_verify(q["authenticator_data"], q["client_data_json"], q["signature"], q["pubkey_x"], q["pubkey_y"], q["challenge"],
                             q["origin"], q["rp_id_hash"], q.get("flags_required", 0x01), q.get("allow_cross_origin", False)) for q in assertions]
+
+
+# ---- the WebAuthn registration check: where the key of an assertion came from --------------------------------------------------
+# The other ceremony (navigator.credentials.create): the attestationObject's CBOR, authData's attested credential data, the COSE key
+# in it, clientDataJSON of type webauthn.create and, if asked for, the statement - one rule with one reason code per request
+# (include/zkmi355.h, zk_webauthn_register; csrc/webauthn_register.hip.h states it in full).  webauthn_register is the host route in
+# Python, webauthn_register_many the device route; set_signature_check chooses.  The CBOR below is the header's: heads are read, items
+# are skipped with one counter of items still owed, nothing is decoded.
+def _cbor_head(b, pos):
+    """(major, argument, position behind the head) of the head at b[pos:], or None where it is not well-formed and in shortest form."""
+    if pos >= len(b):
+        return None
+    major, ai = b[pos] >> 5, b[pos] & 31
+    pos += 1
+    if ai < 24:
+        return major, ai, pos
+    if ai > 27:
+        return None  # 28 .. 30 reserved; 31 indefinite lengths and `break`
+    width = 1 << (ai - 24)
+    if len(b) - pos < width:
+        return None
+    val = int.from_bytes(b[pos:pos + width], "big")
+    pos += width
+    if major == 7:
+        return (major, val, pos) if ai != 24 or val >= 32 else None  # (25 .. 27: a float, any bits)
+    return (major, val, pos) if val >= (24, 1 << 8, 1 << 16, 1 << 32)[ai - 24] else None
+
+
+def _cbor_skip(b, pos):
+    """The position behind the data item at b[pos:], or None where it is not well-formed."""
+    owed = 1
+    while owed:
+        head = _cbor_head(b, pos)
+        if head is None:
+            return None
+        major, val, pos = head
+        owed -= 1
+        if 2 <= major <= 5 and val > len(b) - pos:
+            return None  # more bytes, items or pairs than bytes left
+        if major in (2, 3):
+            pos += val
+        else:
+            owed += {4: val, 5: 2 * val, 6: 1}.get(major, 0)
+    return pos
+
+
+def _attestation_object(o):
+    """(fmt, attStmt item, offset of authData, authData) of the accepted encoding, or None."""
+    head = _cbor_head(o, 0)
+    if head is None or head[:2] != (5, 3) or o[head[2]:head[2] + 4] != b"\x63fmt":
+        return None
+    head = _cbor_head(o, head[2] + 4)
+    if head is None or head[0] != 3 or head[1] > len(o) - head[2]:
+        return None
+    fmt, pos = o[head[2]:head[2] + head[1]], head[2] + head[1]
+    if o[pos:pos + 8] != b"\x67attStmt" or o[pos + 8:pos + 9] == b"" or o[pos + 8] >> 5 != 5:
+        return None
+    end = _cbor_skip(o, pos + 8)
+    if end is None or o[end:end + 9] != b"\x68authData":
+        return None
+    stmt = o[pos + 8:end]
+    head = _cbor_head(o, end + 9)
+    if head is None or head[0] != 2 or head[2] + head[1] != len(o):
+        return None
+    return fmt, stmt, head[2], o[head[2]:]
+
+
+_COSE_HEAD, _COSE_Y = bytes.fromhex("a5010203262001215820"), bytes.fromhex("225820")
+
+
+def webauthn_register(attestation_object, client_data_json, challenge, origin, rp_id_hash, flags_required=0x01, allow_cross_origin=False,
+                      attestation_policy=ZK_WEBAUTHN_ATT_IGNORE):
+    """The relying party's check of one registration on the host: zk_webauthn_register's rule in Python.  -> (ok, reason, credential):
+    reason an engine.ZK_WEBAUTHN_* code, the FIRST failing test; credential None unless ok, else what Engine.webauthn_register
+    gives (pubkey_x, pubkey_y: 32 BIG-endian bytes, what webauthn_verify takes)."""
+    o, cd = bytes(attestation_object), bytes(client_data_json)
+    origin_b = origin.encode() if isinstance(origin, str) else bytes(origin)
+    if attestation_policy not in (ZK_WEBAUTHN_ATT_IGNORE, ZK_WEBAUTHN_ATT_NONE_OR_SELF):
+        raise ValueError("attestation policy: ZK_WEBAUTHN_ATT_IGNORE or ZK_WEBAUTHN_ATT_NONE_OR_SELF")
+
+    def refused(reason):
+        return False, reason, None
+
+    if (not 1 <= len(o) <= ZK_WEBAUTHN_ATTOBJ_MAX or len(cd) > ZK_WEBAUTHN_CLIENTDATA_MAX or not 1 <= len(challenge) <= ZK_WEBAUTHN_CHALLENGE_MAX
+            or len(origin_b) > ZK_WEBAUTHN_ORIGIN_MAX):
+        return refused(ZK_WEBAUTHN_SIZE)
+    parts = _attestation_object(o)
+    if parts is None:
+        return refused(ZK_WEBAUTHN_CBOR)
+    fmt, stmt, ad_off, ad = parts
+    if len(ad) < 37:
+        return refused(ZK_WEBAUTHN_AUTHDATA)
+    if ad[:32] != bytes(rp_id_hash):
+        return refused(ZK_WEBAUTHN_RPID)
+    flags = ad[32]
+    if flags & flags_required != flags_required:
+        return refused(ZK_WEBAUTHN_FLAGS)
+    id_len = int.from_bytes(ad[53:55], "big")
+    if not flags & 0x40 or len(ad) < 55 or not 1 <= id_len <= 1023 or len(ad) - 55 < id_len:
+        return refused(ZK_WEBAUTHN_CREDENTIAL)
+    key_off = 55 + id_len
+    pos = _cbor_skip(ad, key_off)
+    if pos is None:
+        return refused(ZK_WEBAUTHN_CREDENTIAL)
+    key = ad[key_off:pos]
+    if flags & 0x80:  # ED: exactly one map of extensions
+        pos = _cbor_skip(ad, pos) if pos < len(ad) and ad[pos] >> 5 == 5 else None
+    if pos != len(ad):
+        return refused(ZK_WEBAUTHN_CREDENTIAL)
+    if len(key) != 77 or key[:10] != _COSE_HEAD or key[42:45] != _COSE_Y:
+        return refused(ZK_WEBAUTHN_COSE_KEY)
+    if not _client_data_ok(cd, challenge, origin_b, allow_cross_origin, b"webauthn.create"):
+        return refused(ZK_WEBAUTHN_CLIENTDATA)
+    xb, yb = key[10:42], key[45:77]
+    x, y = int.from_bytes(xb, "big"), int.from_bytes(yb, "big")
+    if x >= _P or y >= _P:
+        return refused(ZK_WEBAUTHN_RANGE)
+    if (y * y - (x * x * x - 3 * x + _B)) % _P:
+        return refused(ZK_WEBAUTHN_OFF_CURVE)
+    attestation = ZK_WEBAUTHN_ATTESTED_NOT_JUDGED
+    if attestation_policy == ZK_WEBAUTHN_ATT_NONE_OR_SELF:
+        if fmt == b"none" and stmt == b"\xa0":
+            attestation = ZK_WEBAUTHN_ATTESTED_NONE
+        elif fmt == b"packed" and stmt[:10] == b"\xa2\x63alg\x26\x63sig":
+            head = _cbor_head(stmt, 10)
+            if head is None or head[0] != 2 or head[2] + head[1] != len(stmt):
+                return refused(ZK_WEBAUTHN_ATTESTATION)
+            attestation = ZK_WEBAUTHN_ATTESTED_SELF
+            rs = webauthn_der_signature(stmt[head[2]:])
+            if rs is None:
+                return refused(ZK_WEBAUTHN_SIGNATURE_DER)
+            z = hashlib.sha256(ad + hashlib.sha256(cd).digest()).digest()
+            if int.from_bytes(z, "big") >= _N or not 0 < rs[0] < _N or not 0 < rs[1] < _N:
+                return refused(ZK_WEBAUTHN_RANGE)
+            if not es256_verify(xb[::-1], yb[::-1], rs[0].to_bytes(32, "little"), rs[1].to_bytes(32, "little"), z[::-1]):
+                return refused(ZK_WEBAUTHN_MISMATCH)
+        else:
+            return refused(ZK_WEBAUTHN_ATTESTATION)
+    return True, ZK_WEBAUTHN_VALID, {
+        "pubkey_x": xb, "pubkey_y": yb, "aaguid": ad[37:53], "credential_id": ad[55:key_off], "auth_data": ad, "auth_data_off": ad_off,
+        "auth_data_len": len(ad), "credential_id_off": ad_off + 55, "credential_id_len": id_len, "sign_count": int.from_bytes(ad[33:37], "big"),
+        "flags": flags, "attestation": attestation}
+
+
+def webauthn_register_many(registrations, device: int = 0):
+    """webauthn_register of every registration on the device, in one zk_webauthn_register call per ZK_WEBAUTHN_BATCH_MAX of them ->
+    [(ok, reason, credential or None)], in order.  registrations: dicts as Engine.webauthn_register takes them."""
+    registrations = list(registrations)
+    out = []
+    with _ES256_LOCK:
+        eng = _ES256_ENGINES.get(device)
+        if eng is None:
+            eng = _ES256_ENGINES[device] = Engine(device)
+        for lo in range(0, len(registrations), ZK_WEBAUTHN_BATCH_MAX):
+            out += eng.webauthn_register(registrations[lo:lo + ZK_WEBAUTHN_BATCH_MAX])
+    return out
+
+
+def webauthn_register_check(registrations, device: int = 0):
+    """[(ok, reason, credential or None)] of the registrations by the route set_signature_check names: one webauthn_register each on
+    the host, or all of them in one launch on the device."""
+    registrations = list(registrations)
+    if _SIGNATURE_CHECK == "device":
+        return webauthn_register_many(registrations, device)
+    return [webauthn_register(q["attestation_object"], q["client_data_json"], q["challenge"], q["origin"], q["rp_id_hash"],
+                              q.get("flags_required", 0x01), q.get("allow_cross_origin", False),
+                              q.get("attestation_policy", ZK_WEBAUTHN_ATT_IGNORE)) for q in registrations]
 
 
 def _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash) -> int:

@@ -33,7 +33,12 @@ ZK_ES256_BATCH_MAX = 16384
  ZK_WEBAUTHN_FLAGS, ZK_WEBAUTHN_CLIENTDATA, ZK_WEBAUTHN_SIGNATURE_DER) = range(10)
 ZK_WEBAUTHN_BATCH_MAX = ZK_ES256_BATCH_MAX
 ZK_WEBAUTHN_AUTHDATA_MAX, ZK_WEBAUTHN_CLIENTDATA_MAX, ZK_WEBAUTHN_CHALLENGE_MAX, ZK_WEBAUTHN_ORIGIN_MAX = 1024, 4096, 64, 255
-WEBAUTHN_REASON_NAMES = ("VALID", "RANGE", "OFF_CURVE", "MISMATCH", "SIZE", "AUTHDATA", "RPID", "FLAGS", "CLIENTDATA", "SIGNATURE_DER")
+ZK_WEBAUTHN_CBOR, ZK_WEBAUTHN_CREDENTIAL, ZK_WEBAUTHN_COSE_KEY, ZK_WEBAUTHN_ATTESTATION = 10, 11, 12, 13  # zk_webauthn_register's own
+ZK_WEBAUTHN_ATTOBJ_MAX = 8192
+ZK_WEBAUTHN_ATT_IGNORE, ZK_WEBAUTHN_ATT_NONE_OR_SELF = 0, 1
+ZK_WEBAUTHN_ATTESTED_NONE, ZK_WEBAUTHN_ATTESTED_SELF, ZK_WEBAUTHN_ATTESTED_NOT_JUDGED = 0, 1, 2
+WEBAUTHN_REASON_NAMES = ("VALID", "RANGE", "OFF_CURVE", "MISMATCH", "SIZE", "AUTHDATA", "RPID", "FLAGS", "CLIENTDATA", "SIGNATURE_DER", "CBOR",
+                         "CREDENTIAL", "COSE_KEY", "ATTESTATION")
 ZK_PAIRING_VALID, ZK_PAIRING_RANGE, ZK_PAIRING_OFF_CURVE, ZK_PAIRING_MISMATCH = 0, 1, 2, 3
 ZK_PAIRING_G2 = 4
 ZK_PAIRING_BATCH_MAX = 4096
@@ -140,6 +145,20 @@ class WebauthnAssertionC(ctypes.Structure):
                 ("pubkey_x", ctypes.c_uint8 * 32), ("pubkey_y", ctypes.c_uint8 * 32), ("challenge", ctypes.c_char_p),
                 ("challenge_len", ctypes.c_size_t), ("origin", ctypes.c_char_p), ("origin_len", ctypes.c_size_t),
                 ("rp_id_hash", ctypes.c_uint8 * 32), ("flags_required", ctypes.c_uint8), ("allow_cross_origin", ctypes.c_uint8)]
+
+
+class WebauthnRegistrationC(ctypes.Structure):
+    _fields_ = [("attestation_object", ctypes.c_char_p), ("attestation_object_len", ctypes.c_size_t), ("client_data_json", ctypes.c_char_p),
+                ("client_data_json_len", ctypes.c_size_t), ("challenge", ctypes.c_char_p), ("challenge_len", ctypes.c_size_t),
+                ("origin", ctypes.c_char_p), ("origin_len", ctypes.c_size_t), ("rp_id_hash", ctypes.c_uint8 * 32),
+                ("flags_required", ctypes.c_uint8), ("allow_cross_origin", ctypes.c_uint8), ("attestation_policy", ctypes.c_uint8)]
+
+
+class WebauthnCredentialC(ctypes.Structure):
+    _fields_ = [("pubkey_x", ctypes.c_uint8 * 32), ("pubkey_y", ctypes.c_uint8 * 32), ("aaguid", ctypes.c_uint8 * 16),
+                ("auth_data_off", ctypes.c_uint32), ("auth_data_len", ctypes.c_uint32), ("credential_id_off", ctypes.c_uint32),
+                ("credential_id_len", ctypes.c_uint32), ("sign_count", ctypes.c_uint32), ("flags", ctypes.c_uint8),
+                ("attestation", ctypes.c_uint8)]
 
 
 class PlacementC(ctypes.Structure):
@@ -260,6 +279,8 @@ def load_library():
         "zk_es256_verify": ([vp, sz, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)], ctypes.c_int),
         "zk_webauthn_verify": ([vp, sz, ctypes.POINTER(WebauthnAssertionC), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
                                 ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(u32)], ctypes.c_int),
+        "zk_webauthn_register": ([vp, sz, ctypes.POINTER(WebauthnRegistrationC), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
+                                  ctypes.POINTER(WebauthnCredentialC)], ctypes.c_int),
         "zk_srs_write": ([vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)], ctypes.c_int),
         "zk_srs_read": ([vp, vp, sz, ctypes.c_int], ctypes.c_int),
         "zk_srs_set_g2": ([vp, u64p, u64p], ctypes.c_int),
@@ -320,7 +341,8 @@ def load_library():
                         "zk_pk_num_instance_columns", "zk_prove_batch_public", "zk_prove_multi_public", "zk_verify_batch_public",
                         "zk_verify_multi_public", "zk_instance_eval", "zk_verify_instance_eval_mode", "zk_es256_verify",
                         "zk_pairing_check_batch", "zk_verify_pairing_mode", "zk_verify_pairing_stats", "zk_evm_verifier",
-                        "zk_evm_verifier_cost", "zk_pairing_check_each", "zk_srs_contribution_check_batch", "zk_webauthn_verify") and os.environ.get("ZKMI355_LIB"):
+                        "zk_evm_verifier_cost", "zk_pairing_check_each", "zk_srs_contribution_check_batch", "zk_webauthn_verify",
+                        "zk_webauthn_register") and os.environ.get("ZKMI355_LIB"):
                 continue  # an earlier build of the library under A/B (tools/witness_check_time.py --ab-lib): calling it raises AttributeError
             raise ZkError(-4, f"{p} does not export {name} — rebuild it (./build.sh)")
         fn.argtypes = args
@@ -1028,6 +1050,61 @@ class Engine:
                 getattr(c, name)[:] = v
             c.flags_required = int(q.get("flags_required", 0x01))
             c.allow_cross_origin = 1 if q.get("allow_cross_origin", False) else 0
+        arr.zk_count = count  # (an empty list still makes an array of one: the call then refuses count = 0)
+        return arr
+
+    def webauthn_register(self, registrations):
+        """zk_webauthn_register: the relying party's check of WebAuthn registrations in two launches, one per lane - the CBOR walk of
+        the attestationObject, the authData and attested-credential-data rules, the COSE key template, the client-data rule with
+        webauthn.create, the key's curve test and, under policy ZK_WEBAUTHN_ATT_NONE_OR_SELF, the statement (a packed self
+        attestation is verified with the credential's own key).  registrations: a sequence of dicts with attestation_object,
+        client_data_json, challenge (the raw bytes issued), origin (str or bytes), rp_id_hash (32 bytes) and, optionally,
+        flags_required (default 0x01, UP), allow_cross_origin (default False) and attestation_policy (default
+        ZK_WEBAUTHN_ATT_IGNORE).  -> [(ok, ZK_WEBAUTHN_* reason, credential dict or None)]: pubkey_x, pubkey_y (32 BIG-endian bytes,
+        what webauthn_verify takes), aaguid, credential_id, auth_data (both cut out of the object), sign_count, flags, attestation
+        (ZK_WEBAUTHN_ATTESTED_*).  A bad registration is a verdict, not an error.  A caller that makes the same call again (a
+        measurement) passes webauthn_register_pack's result instead and skips the marshalling."""
+        arr = registrations if isinstance(registrations, ctypes.Array) else self.webauthn_register_pack(registrations)
+        count = len(arr) if getattr(arr, "zk_count", 1) else 0
+        verdicts = (ctypes.c_uint8 * max(count, 1))()
+        reasons = (ctypes.c_uint8 * max(count, 1))()
+        creds = (WebauthnCredentialC * max(count, 1))()
+        self._chk(self.L.zk_webauthn_register(self.ctx, count, arr, verdicts, reasons, creds), "zk_webauthn_register")
+        out = []
+        for j in range(count):
+            cred = None
+            if verdicts[j]:
+                c, obj = creds[j], arr.zk_objects[j]  # (reading the c_char_p field back would stop at the first zero byte)
+                cred = {"pubkey_x": bytes(c.pubkey_x), "pubkey_y": bytes(c.pubkey_y), "aaguid": bytes(c.aaguid),
+                        "credential_id": obj[c.credential_id_off:c.credential_id_off + c.credential_id_len],
+                        "auth_data": obj[c.auth_data_off:c.auth_data_off + c.auth_data_len], "auth_data_off": int(c.auth_data_off),
+                        "auth_data_len": int(c.auth_data_len), "credential_id_off": int(c.credential_id_off),
+                        "credential_id_len": int(c.credential_id_len), "sign_count": int(c.sign_count), "flags": int(c.flags),
+                        "attestation": int(c.attestation)}
+            out.append((bool(verdicts[j]), int(reasons[j]), cred))
+        return out
+
+    @staticmethod
+    def webauthn_register_pack(registrations):
+        """The zk_webauthn_registration array of webauthn_register's dicts (it keeps their byte strings alive)."""
+        registrations = list(registrations)
+        count = len(registrations)
+        arr = (WebauthnRegistrationC * max(count, 1))()
+        for c, q in zip(arr, registrations):
+            origin = q["origin"].encode() if isinstance(q["origin"], str) else bytes(q["origin"])
+            for name, v in (("attestation_object", q["attestation_object"]), ("client_data_json", q["client_data_json"]),
+                            ("challenge", q["challenge"]), ("origin", origin)):
+                v = bytes(v)
+                setattr(c, name, v)  # (the structure keeps the bytes object alive)
+                setattr(c, name + "_len", len(v))
+            v = bytes(q["rp_id_hash"])
+            if len(v) != 32:
+                raise ValueError("rp_id_hash: 32 bytes")
+            c.rp_id_hash[:] = v
+            c.flags_required = int(q.get("flags_required", 0x01))
+            c.allow_cross_origin = 1 if q.get("allow_cross_origin", False) else 0
+            c.attestation_policy = int(q.get("attestation_policy", ZK_WEBAUTHN_ATT_IGNORE))
+        arr.zk_objects = [bytes(q["attestation_object"]) for q in registrations]  # the offsets of a credential count within these
         arr.zk_count = count  # (an empty list still makes an array of one: the call then refuses count = 0)
         return arr
 

@@ -254,6 +254,87 @@ def prove_assertions_batch(bodies, expected_challenges, origin, rp_id, require_u
     return out
 
 
+# ---- the other ceremony: a registration in, the credential to store out ----------------------------------------------------------
+# Where the pubkey_x / pubkey_y of every body above come from: navigator.credentials.create returns an attestationObject whose
+# authData holds the credential id and the COSE key.  register_credential checks it against what THIS server issued and expects
+# (ecdsa_p256.webauthn_register / zk_webauthn_register) and answers with what to store; the key arrays are the LITTLE-endian ones
+# parse_request / parse_assertion take, so a stored credential drops into a prove body.  No proof is made here.
+REGISTRATION_FIELDS = ("attestation_object", "client_data_json")
+_ATTESTATION_POLICY = {"ignore": ecdsa_p256.ZK_WEBAUTHN_ATT_IGNORE, "none-or-self": ecdsa_p256.ZK_WEBAUTHN_ATT_NONE_OR_SELF}
+_ATTESTATION_NAME = {ecdsa_p256.ZK_WEBAUTHN_ATTESTED_NONE: "none", ecdsa_p256.ZK_WEBAUTHN_ATTESTED_SELF: "self",
+                     ecdsa_p256.ZK_WEBAUTHN_ATTESTED_NOT_JUDGED: "not-judged"}
+
+
+def parse_registration(body):
+    """A registration body from a JSON string / dict: attestation_object and client_data_json as base64url strings without padding
+    (AuthenticatorAttestationResponse's attestationObject and clientDataJSON after toJSON())."""
+    if isinstance(body, (str, bytes, bytearray)):
+        body = json.loads(body)
+    if not isinstance(body, dict):
+        raise ValueError("request body must be a JSON object")
+    out = {}
+    for f in REGISTRATION_FIELDS:
+        v = body.get(f)
+        if not isinstance(v, str) or not _B64URL.fullmatch(v) or len(v) % 4 == 1:
+            raise ValueError(f"{f}: expected a base64url string without padding")
+        out[f] = base64.urlsafe_b64decode(v + "=" * (-len(v) % 4))
+    return out
+
+
+def _registration(q, expected_challenge, origin, rp_id, require_uv, allow_cross_origin, attestation):
+    """The registration of a parsed body with what this server expects of it, as ecdsa_p256.webauthn_register_check takes it."""
+    if attestation not in _ATTESTATION_POLICY:
+        raise ValueError('attestation: "ignore" or "none-or-self"')
+    rp_id = rp_id.encode() if isinstance(rp_id, str) else bytes(rp_id)
+    return {"attestation_object": q["attestation_object"], "client_data_json": q["client_data_json"], "challenge": bytes(expected_challenge),
+            "origin": origin, "rp_id_hash": hashlib.sha256(rp_id).digest(), "flags_required": 0x05 if require_uv else 0x01,
+            "allow_cross_origin": bool(allow_cross_origin), "attestation_policy": _ATTESTATION_POLICY[attestation]}
+
+
+def _stored_credential(verdict):
+    """What to store for an accepted registration; ValueError naming the reason for a refused one."""
+    ok, reason, cred = verdict
+    if not ok:
+        raise ValueError("WebAuthn registration refused: %s" % ecdsa_p256.WEBAUTHN_REASON_NAMES[reason])
+    return {"credential_id": cred["credential_id"].hex(), "pubkey_x": list(cred["pubkey_x"][::-1]), "pubkey_y": list(cred["pubkey_y"][::-1]),
+            "aaguid": cred["aaguid"].hex(), "sign_count": cred["sign_count"], "flags": cred["flags"],
+            "attestation": _ATTESTATION_NAME[cred["attestation"]]}
+
+
+def register_credential(body, expected_challenge, origin, rp_id, require_uv=False, allow_cross_origin=False, attestation="ignore", device=0):
+    """The credential of a registration body (parse_registration), checked against expected_challenge (the raw bytes this server
+    issued), origin and rp_id (rpIdHash = SHA-256(rp_id) is made here; UP is required, UV too with require_uv).  attestation:
+    "ignore" (the statement only has to be well-formed) or "none-or-self".  -> {"credential_id": hex, "pubkey_x", "pubkey_y": 32
+    integers each, LITTLE-endian as parse_request / parse_assertion take them, "aaguid": hex, "sign_count", "flags", "attestation":
+    "none" | "self" | "not-judged"}.  A refused registration is a ValueError naming the first failing test."""
+    q = _registration(parse_registration(body), expected_challenge, origin, rp_id, require_uv, allow_cross_origin, attestation)
+    return _stored_credential(ecdsa_p256.webauthn_register_check([q], device)[0])
+
+
+def register_credentials_batch(bodies, expected_challenges, origin, rp_id, require_uv=False, allow_cross_origin=False, attestation="ignore",
+                               device=0):
+    """register_credential for many bodies (an enrolment wave, an imported credential store); expected_challenges: one per body.
+    Under ecdsa_p256.set_signature_check("device") all of them are checked in ONE launch.  Returns one slot per body: the credential,
+    or the exception of a body that does not parse or a registration that is refused, which leaves the others alone."""
+    bodies, expected_challenges = list(bodies), list(expected_challenges)
+    if len(expected_challenges) != len(bodies):
+        raise ValueError("one expected challenge per body")
+    out = [None] * len(bodies)
+    parsed = []
+    for i, b in enumerate(bodies):
+        try:
+            parsed.append((i, _registration(parse_registration(b), expected_challenges[i], origin, rp_id, require_uv, allow_cross_origin, attestation)))
+        except Exception as e:
+            out[i] = e
+    if parsed:
+        for (i, _), verdict in zip(parsed, ecdsa_p256.webauthn_register_check([q for _, q in parsed], device)):
+            try:
+                out[i] = _stored_credential(verdict)
+            except ValueError as e:
+                out[i] = e
+    return out
+
+
 _HEX = re.compile(r"[0-9a-fA-F]*")
 
 

@@ -6,19 +6,14 @@
 // that lane's own digit, so it lives in LDS (15 Jacobian points x 64 lanes = 90 KiB of the CU's 160), never in a register array.
 // u1 G comes from a comb of G (64 windows x 15 affine multiples, 60 KiB) that es256_comb_kernel builds on the first call of a
 // context — one window per lane, each lane normalising its 15 points with one inversion — and that stays with the context.
+// The host side of a call - grow, upload, launch, download, wait - is lane_call.h's round trip.
 #include <string.h>
 
-#include <algorithm>
 #include <vector>
 
 #include "es256.h"
 
-void es256_ws_destroy(Es256Ws* w) {
-    if (!w) return;
-    for (void* p : {(void*)w->table, w->in, w->out})
-        if (p) hipFree(p);
-    delete w;
-}
+void es256_ws_destroy(Es256Ws* w) { delete w; }
 
 namespace {
 
@@ -44,20 +39,6 @@ __global__ __launch_bounds__(ES256_WG) void es256_verify_kernel(const uint8_t* s
 
 }  // namespace
 
-int es256_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return ZK_OK;
-    if (*p) {
-        hipStreamSynchronize(c->stream);
-        hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t want = std::max<size_t>(bytes, 4096);
-    if (hipMalloc(p, want) != hipSuccess) return ZK_ENOMEM;
-    *cap = want;
-    return ZK_OK;
-}
-
 // made once per context on its main stream and waited for, like the twiddle tables (ctx.hip ctx_cached_table)
 int es256_table(zk_ctx* c) {
     if (!c->es256 && !(c->es256 = new (std::nothrow) Es256Ws())) return ZK_ENOMEM;
@@ -79,7 +60,7 @@ int es256_table(zk_ctx* c) {
 }
 
 hipError_t es256_enqueue(zk_ctx* c, const uint8_t* d_sigs, uint32_t count, const uint8_t* d_settled, uint8_t* d_reasons) {
-    hipLaunchKernelGGL(es256_verify_kernel, dim3((count + ES256_WG - 1) / ES256_WG), dim3(ES256_WG), 0, c->stream, d_sigs, count,
+    hipLaunchKernelGGL(es256_verify_kernel, lane_grid(count, ES256_WG), dim3(ES256_WG), 0, c->stream, d_sigs, count,
                        (const P256Affine*)c->es256->table, d_settled, d_reasons);
     return hipGetLastError();
 }
@@ -87,21 +68,15 @@ hipError_t es256_enqueue(zk_ctx* c, const uint8_t* d_sigs, uint32_t count, const
 ZK_API(zk_es256_verify, (zk_ctx* c, size_t count, const uint8_t* sigs, uint8_t* verdicts, uint8_t* reasons), (c, count, sigs, verdicts, reasons)) {
     if (!c || !sigs || !verdicts || count == 0 || count > ZK_ES256_BATCH_MAX) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
-    if ((rc = es256_table(c))) return rc;
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
+    if (rc || (rc = es256_table(c))) return rc;
     Es256Ws* w = c->es256;
-    if ((rc = es256_grow(c, &w->in, &w->c_in, count * 160)) || (rc = es256_grow(c, &w->out, &w->c_out, count))) return rc;
     std::vector<uint8_t> res(count);
-    if (c->audit.on) c->audit.op(c->stream, {}, {w->in}, "es256: signatures upload");
-    HIPCHK(c, hipMemcpyAsync(w->in, sigs, count * 160, hipMemcpyHostToDevice, c->stream));
-    if (c->audit.on) c->audit.op(c->stream, {w->in, w->table}, {w->out}, "es256: verification (es256_verify_kernel)");
-    HIPCHK(c, es256_enqueue(c, (const uint8_t*)w->in, (uint32_t)count, nullptr, (uint8_t*)w->out));
-    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "es256: reasons download");
-    HIPCHK(c, hipMemcpyAsync(res.data(), w->out, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, aud_sync(c, c->stream));  // (the caller's records and `res` are pageable)
+    auto enqueue = [&] { return es256_enqueue(c, (const uint8_t*)w->in.p, (uint32_t)count, nullptr, (uint8_t*)w->out.p); };
+    if ((rc = lane_round_trip(c, {{&w->in, sigs, count * 160}}, w->table, &w->out, count, res.data(), count,
+                              {"es256: signatures upload", "es256: verification (es256_verify_kernel)", "es256: reasons download"}, enqueue)))
+        return rc;
     if ((rc = aud_verdict(c, aud0, ZK_OK))) return rc;
     for (size_t i = 0; i < count; i++) verdicts[i] = res[i] == ZK_ES256_VALID ? 1 : 0;
     if (reasons) memcpy(reasons, res.data(), count);

@@ -14,22 +14,16 @@
 // The resident SRS's table is kept with the SRS view (ctx.h PairLinesDev) and dropped with the block or the pair; a caller's own
 // pair gets a table per call.
 // The checks with a G2 point per lane (zk_pairing_check_each, zk_srs_contribution_check_batch) are pairing_each.hip's; they share
-// the staging buffers and the two table helpers below (pairing_ws.h).
+// the staging buffers and the two table helpers below (pairing_ws.h).  The host side of a call - grow, upload, launch, download,
+// wait - is lane_call.h's round trip.
 #include <string.h>
 
-#include <algorithm>
 #include <vector>
 
-#include "ctx.h"
 #include "pairing_ws.h"
 #include "srs_update.h"
 
-void pairing_ws_destroy(PairingWs* w) {
-    if (!w) return;
-    for (void* p : {w->a, w->b, w->out, w->own, w->q, w->gen})
-        if (p) hipFree(p);
-    delete w;
-}
+void pairing_ws_destroy(PairingWs* w) { delete w; }
 
 namespace {
 
@@ -43,20 +37,6 @@ __global__ __launch_bounds__(PAIRING_WG) void pairing_check_kernel(const G1Affin
 }
 
 }  // namespace
-
-int pw_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return ZK_OK;
-    if (*p) {
-        hipStreamSynchronize(c->stream);
-        hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t want = std::max<size_t>(bytes, 4096);
-    if (hipMalloc(p, want) != hipSuccess) return ZK_ENOMEM;
-    *cap = want;
-    return ZK_OK;
-}
 
 int pairing_ws(zk_ctx* c, PairingWs** out) {
     if (!c->pairing && !(c->pairing = new (std::nothrow) PairingWs())) return ZK_ENOMEM;
@@ -78,21 +58,14 @@ namespace {
 
 // `count` host pairs against the table at d_table, one launch; reasons: a host array of `count`
 int pairing_launch(zk_ctx* c, PairingWs* w, size_t count, const G1Affine* a, const G1Affine* b, const void* d_table, uint8_t* reasons) {
-    int rc;
-    if ((rc = pw_grow(c, &w->a, &w->c_a, count * sizeof(G1Affine))) || (rc = pw_grow(c, &w->b, &w->c_b, count * sizeof(G1Affine))) ||
-        (rc = pw_grow(c, &w->out, &w->c_out, count)))
-        return rc;
-    if (c->audit.on) c->audit.op(c->stream, {}, {w->a, w->b}, "pairing: pairs upload");
-    HIPCHK(c, hipMemcpyAsync(w->a, a, count * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->b, b, count * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-    if (c->audit.on) c->audit.op(c->stream, {w->a, w->b, d_table}, {w->out}, "pairing: checks (pairing_check_kernel)");
-    hipLaunchKernelGGL(pairing_check_kernel, dim3((uint32_t)((count + PAIRING_WG - 1) / PAIRING_WG)), dim3(PAIRING_WG), 0, c->stream,
-                       (const G1Affine*)w->a, (const G1Affine*)w->b, (uint32_t)count, (const PairingTable*)d_table, (uint8_t*)w->out);
-    HIPCHK(c, hipGetLastError());
-    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "pairing: reasons download");
-    HIPCHK(c, hipMemcpyAsync(reasons, w->out, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, aud_sync(c, c->stream));  // (the caller's arrays are pageable)
-    return ZK_OK;
+    const size_t pts = count * sizeof(G1Affine);
+    auto enqueue = [&] {
+        hipLaunchKernelGGL(pairing_check_kernel, lane_grid(count, PAIRING_WG), dim3(PAIRING_WG), 0, c->stream, (const G1Affine*)w->a.p,
+                           (const G1Affine*)w->b.p, (uint32_t)count, (const PairingTable*)d_table, (uint8_t*)w->out.p);
+        return hipGetLastError();
+    };
+    return lane_round_trip(c, {{&w->a, a, pts}, {&w->b, b, pts}}, d_table, &w->out, count, reasons, count,
+                           {"pairing: pairs upload", "pairing: checks (pairing_check_kernel)", "pairing: reasons download"}, enqueue);
 }
 
 }  // namespace
@@ -134,17 +107,15 @@ ZK_API(zk_pairing_check_batch, (zk_ctx* c, size_t count, const uint64_t* a, cons
     }
     std::lock_guard<std::mutex> lk(c->mu);
     if (!g2 && (c->srs_k < 0 || !c->g2_valid)) return ZK_ESTATE;
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     PairingWs* w;
-    if ((rc = pairing_ws(c, &w))) return rc;
+    if (rc || (rc = pairing_ws(c, &w))) return rc;
     std::vector<uint8_t> res(count);
     const G1Affine *pa = reinterpret_cast<const G1Affine*>(a), *pb = reinterpret_cast<const G1Affine*>(b);
     if (g2) {
-        if ((rc = pw_grow(c, &w->own, &w->c_own, sizeof(PairingTable))) || (rc = pairing_table_upload(c, own[0], own[1], w->own)) ||
-            (rc = pairing_launch(c, w, count, pa, pb, w->own, res.data())))
+        if ((rc = w->own.grow(c, sizeof(PairingTable))) || (rc = pairing_table_upload(c, own[0], own[1], w->own.p)) ||
+            (rc = pairing_launch(c, w, count, pa, pb, w->own.p, res.data())))
             return rc;
     } else if ((rc = pairing_check_resident(c, count, pa, pb, res.data()))) {
         return rc;

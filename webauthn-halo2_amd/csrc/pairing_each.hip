@@ -6,12 +6,11 @@
 // table.  A receipt's two equations share s_g2, so its lane walks once into two accumulators.  A lane whose point is improper
 // returns before it walks; its neighbours go on alone.  Shape, calls and trip counts are pairing.hip's: workgroups of one wave, the
 // tower's products as calls, every loop of constant length.  This is a unit of its own so that pairing_check_kernel's code object
-// stays what it was.
+// stays what it was.  The host side of a call is lane_call.h's round trip, over pairing.hip's staging buffers.
 #include <string.h>
 
 #include <vector>
 
-#include "ctx.h"
 #include "pairing_ws.h"
 #include "srs_update.h"
 
@@ -52,22 +51,14 @@ __global__ __launch_bounds__(PAIRING_WG) void contribution_check_kernel(const Fq
 
 // `count` host triples (a_i, b_i, q_i) against the table at d_table (its line[1]: g2's walk), one launch
 int pairing_each_launch(zk_ctx* c, PairingWs* w, size_t count, const G1Affine* a, const G1Affine* b, const uint64_t* q, const void* d_table, uint8_t* reasons) {
-    int rc;
-    if ((rc = pw_grow(c, &w->a, &w->c_a, count * sizeof(G1Affine))) || (rc = pw_grow(c, &w->b, &w->c_b, count * sizeof(G1Affine))) ||
-        (rc = pw_grow(c, &w->q, &w->c_q, count * 128)) || (rc = pw_grow(c, &w->out, &w->c_out, count)))
-        return rc;
-    if (c->audit.on) c->audit.op(c->stream, {}, {w->a, w->b, w->q}, "pairing: triples upload");
-    HIPCHK(c, hipMemcpyAsync(w->a, a, count * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->b, b, count * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->q, q, count * 128, hipMemcpyHostToDevice, c->stream));
-    if (c->audit.on) c->audit.op(c->stream, {w->a, w->b, w->q, d_table}, {w->out}, "pairing: checks (pairing_check_each_kernel)");
-    hipLaunchKernelGGL(pairing_check_each_kernel, dim3((uint32_t)((count + PAIRING_WG - 1) / PAIRING_WG)), dim3(PAIRING_WG), 0, c->stream,
-                       (const G1Affine*)w->a, (const G1Affine*)w->b, (const Fq*)w->q, (uint32_t)count, (const PairingTable*)d_table, (uint8_t*)w->out);
-    HIPCHK(c, hipGetLastError());
-    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "pairing: reasons download");
-    HIPCHK(c, hipMemcpyAsync(reasons, w->out, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, aud_sync(c, c->stream));  // (the caller's arrays are pageable)
-    return ZK_OK;
+    const size_t pts = count * sizeof(G1Affine);
+    auto enqueue = [&] {
+        hipLaunchKernelGGL(pairing_check_each_kernel, lane_grid(count, PAIRING_WG), dim3(PAIRING_WG), 0, c->stream, (const G1Affine*)w->a.p,
+                           (const G1Affine*)w->b.p, (const Fq*)w->q.p, (uint32_t)count, (const PairingTable*)d_table, (uint8_t*)w->out.p);
+        return hipGetLastError();
+    };
+    return lane_round_trip(c, {{&w->a, a, pts}, {&w->b, b, pts}, {&w->q, q, count * 128}}, d_table, &w->out, count, reasons, count,
+                           {"pairing: triples upload", "pairing: checks (pairing_check_each_kernel)", "pairing: reasons download"}, enqueue);
 }
 
 // the table whose line[1] is the G2 generator's walk: what every receipt's fixed side reads.  Made once per context
@@ -88,18 +79,13 @@ int generator_table(zk_ctx* c, PairingWs* w, const void** out) {
 
 // the flag bytes of `count` receipts, one launch; flags: a host array of `count`
 int contribution_launch(zk_ctx* c, PairingWs* w, size_t count, const zk_srs_contribution* r, const void* d_table, uint8_t* flags) {
-    int rc;
-    if ((rc = pw_grow(c, &w->q, &w->c_q, count * sizeof(zk_srs_contribution))) || (rc = pw_grow(c, &w->out, &w->c_out, count))) return rc;
-    if (c->audit.on) c->audit.op(c->stream, {}, {w->q}, "pairing: receipts upload");
-    HIPCHK(c, hipMemcpyAsync(w->q, r, count * sizeof(zk_srs_contribution), hipMemcpyHostToDevice, c->stream));
-    if (c->audit.on) c->audit.op(c->stream, {w->q, d_table}, {w->out}, "pairing: receipts (contribution_check_kernel)");
-    hipLaunchKernelGGL(contribution_check_kernel, dim3((uint32_t)((count + PAIRING_WG - 1) / PAIRING_WG)), dim3(PAIRING_WG), 0, c->stream,
-                       (const Fq*)w->q, (uint32_t)count, (const PairingTable*)d_table, (uint8_t*)w->out);
-    HIPCHK(c, hipGetLastError());
-    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "pairing: flags download");
-    HIPCHK(c, hipMemcpyAsync(flags, w->out, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, aud_sync(c, c->stream));
-    return ZK_OK;
+    auto enqueue = [&] {
+        hipLaunchKernelGGL(contribution_check_kernel, lane_grid(count, PAIRING_WG), dim3(PAIRING_WG), 0, c->stream, (const Fq*)w->q.p, (uint32_t)count,
+                           (const PairingTable*)d_table, (uint8_t*)w->out.p);
+        return hipGetLastError();
+    };
+    return lane_round_trip(c, {{&w->q, r, count * sizeof(zk_srs_contribution)}}, d_table, &w->out, count, flags, count,
+                           {"pairing: receipts upload", "pairing: receipts (contribution_check_kernel)", "pairing: flags download"}, enqueue);
 }
 
 }  // namespace
@@ -113,17 +99,15 @@ ZK_API(zk_pairing_check_each, (zk_ctx* c, size_t count, const uint64_t* a, const
     }
     std::lock_guard<std::mutex> lk(c->mu);
     if (!g2 && (c->srs_k < 0 || !c->g2_valid)) return ZK_ESTATE;
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     PairingWs* w;
-    if ((rc = pairing_ws(c, &w))) return rc;
+    if (rc || (rc = pairing_ws(c, &w))) return rc;
     const void* table;
     if (g2) {  // the lanes read g2's walk alone: the table's other half stays empty
         const G2A none{f2_zero(), f2_zero(), true};
-        if ((rc = pw_grow(c, &w->own, &w->c_own, sizeof(PairingTable))) || (rc = pairing_table_upload(c, own, none, w->own))) return rc;
-        table = w->own;
+        if ((rc = w->own.grow(c, sizeof(PairingTable))) || (rc = pairing_table_upload(c, own, none, w->own.p))) return rc;
+        table = w->own.p;
     } else if ((rc = pairing_resident_table(c, &table))) {
         return rc;
     }
@@ -138,13 +122,11 @@ ZK_API(zk_pairing_check_each, (zk_ctx* c, size_t count, const uint64_t* a, const
 ZK_API(zk_srs_contribution_check_batch, (zk_ctx* c, size_t count, const zk_srs_contribution* r, uint32_t* flags), (c, count, r, flags)) {
     if (!c || !r || !flags || count == 0 || count > ZK_SRS_CONTRIB_BATCH_MAX) return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     PairingWs* w;
     const void* table;
-    if ((rc = pairing_ws(c, &w)) || (rc = generator_table(c, w, &table))) return rc;
+    if (rc || (rc = pairing_ws(c, &w)) || (rc = generator_table(c, w, &table))) return rc;
     std::vector<uint8_t> res(count);
     if ((rc = contribution_launch(c, w, count, r, table, res.data()))) return rc;
     G1Affine g1;

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "lane_call.h"
 #include "pk.h"
 #include "sigma_decode.hip.h"
 
@@ -222,10 +223,9 @@ ZK_API(zk_pk_check, (zk_ctx* c, zk_pk h, uint32_t* flags, zk_pk_finding* out, si
     zk_pk_rec* pk = it->second;
     const Layout& lay = pk->lay;
     if (pk->srs_gen != c->srs_gen || pk->verify_only) return ZK_ESTATE;  // (a verifying-only key holds no column to audit)
-    int rc = ctx_bind(c);
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();  // (allocations may have changed hands since the last call)
     if ((rc = pc_ensure_state(c, pk))) return rc;
     PkCheckState* s = pk->pc;
     hipStream_t st = c->stream;

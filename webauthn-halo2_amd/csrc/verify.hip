@@ -27,6 +27,7 @@
 #include <thread>
 
 #include "evm_codegen.h"
+#include "lane_call.h"
 #include "pairing.h"
 #include "pk.h"
 #include "verifier.h"
@@ -219,21 +220,6 @@ __global__ __launch_bounds__(64) void instance_eval_finish_kernel(const IePair* 
     }
 }
 
-// grow-only device buffer
-int ws_grow(zk_ctx* c, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return ZK_OK;
-    if (*p) {
-        hipStreamSynchronize(c->stream);
-        hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t want = std::max<size_t>(bytes, 4096);
-    if (hipMalloc(p, want) != hipSuccess) return ZK_ENOMEM;
-    *cap = want;
-    return ZK_OK;
-}
-
 // affine forms of XYZZ sums (one inversion for all of them)
 std::vector<G1Affine> to_affine_batch(const std::vector<G1X>& v) {
     std::vector<Fq> den, pre;
@@ -286,23 +272,14 @@ void parallel_for(size_t n, Fn fn) {
 
 }  // namespace
 
-// the context's verify workspace (grow-only, sized by the largest batch seen)
+// the context's verify workspace (grow-only buffers, sized by the largest batch seen)
 struct VerifyWs {
-    void *bytes = nullptr, *off = nullptr, *pts = nullptr, *flag = nullptr, *scal = nullptr, *idx = nullptr, *seg = nullptr, *out = nullptr,
-         *fold = nullptr;
-    size_t c_bytes = 0, c_off = 0, c_pts = 0, c_flag = 0, c_scal = 0, c_idx = 0, c_seg = 0, c_out = 0, c_fold = 0;
+    DevBuf bytes, off, pts, flag, scal, idx, seg, out, fold;
     // instance_eval_device: the call's distinct lists, the pairs, their points, the slices' sums and flags, the results
-    void *ie_vals = nullptr, *ie_pairs = nullptr, *ie_x = nullptr, *ie_part = nullptr, *ie_pflag = nullptr, *ie_out = nullptr, *ie_flag = nullptr;
-    size_t c_ie_vals = 0, c_ie_pairs = 0, c_ie_x = 0, c_ie_part = 0, c_ie_pflag = 0, c_ie_out = 0, c_ie_flag = 0;
+    DevBuf ie_vals, ie_pairs, ie_x, ie_part, ie_pflag, ie_out, ie_flag;
 };
 
-void verify_ws_destroy(VerifyWs* w) {
-    if (!w) return;
-    for (void* p : {w->bytes, w->off, w->pts, w->flag, w->scal, w->idx, w->seg, w->out, w->fold, w->ie_vals, w->ie_pairs, w->ie_x, w->ie_part,
-                    w->ie_pflag, w->ie_out, w->ie_flag})
-        if (p) hipFree(p);
-    delete w;
-}
+void verify_ws_destroy(VerifyWs* w) { delete w; }
 
 // a key record holding the verifying key only: commitments (host and device), transcript_repr; no SRS-sized memory
 int pk_make_verify_only(zk_ctx* c, const Layout& lay, const std::vector<G1Affine>& fixed, const std::vector<G1Affine>& perm,
@@ -441,21 +418,21 @@ int fold(Job& J, const std::vector<uint32_t>& S, G1Affine* A, G1Affine* B) {
             }
         }
     int rc;
-    if ((rc = ws_grow(c, &w->scal, &w->c_scal, sc.size() * sizeof(Fr))) || (rc = ws_grow(c, &w->idx, &w->c_idx, ix.size() * 4)) ||
-        (rc = ws_grow(c, &w->seg, &w->c_seg, sg.size() * sizeof(VSeg))) || (rc = ws_grow(c, &w->out, &w->c_out, sg.size() * sizeof(G1X))))
+    if ((rc = w->scal.grow(c, sc.size() * sizeof(Fr))) || (rc = w->idx.grow(c, ix.size() * 4)) ||
+        (rc = w->seg.grow(c, sg.size() * sizeof(VSeg))) || (rc = w->out.grow(c, sg.size() * sizeof(G1X))))
         return rc;
-    if (c->audit.on) c->audit.op(c->stream, {}, {w->scal, w->idx, w->seg}, "verify: fold arguments upload");
-    HIPCHK(c, hipMemcpyAsync(w->scal, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->idx, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->seg, sg.data(), sg.size() * sizeof(VSeg), hipMemcpyHostToDevice, c->stream));
-    if (c->audit.on) c->audit.op(c->stream, {w->scal, w->idx, w->seg, w->fold}, {w->out}, "verify: fold (verify_msm_kernel)");
-    hipLaunchKernelGGL(verify_msm_kernel, dim3((uint32_t)sg.size()), dim3(64), 0, c->stream, (const Fr*)w->scal, (const uint32_t*)w->idx,
-                       (const VSeg*)w->seg, (const G1Affine*)w->fold, (uint32_t)J.acc.size(), (const G1Affine*)nullptr, 0u,
-                       (const G1Affine*)w->fold, 128u, (G1X*)w->out);
+    if (c->audit.on) c->audit.op(c->stream, {}, {w->scal.p, w->idx.p, w->seg.p}, "verify: fold arguments upload");
+    HIPCHK(c, hipMemcpyAsync(w->scal.p, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->idx.p, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->seg.p, sg.data(), sg.size() * sizeof(VSeg), hipMemcpyHostToDevice, c->stream));
+    if (c->audit.on) c->audit.op(c->stream, {w->scal.p, w->idx.p, w->seg.p, w->fold.p}, {w->out.p}, "verify: fold (verify_msm_kernel)");
+    hipLaunchKernelGGL(verify_msm_kernel, dim3((uint32_t)sg.size()), dim3(64), 0, c->stream, (const Fr*)w->scal.p, (const uint32_t*)w->idx.p,
+                       (const VSeg*)w->seg.p, (const G1Affine*)w->fold.p, (uint32_t)J.acc.size(), (const G1Affine*)nullptr, 0u,
+                       (const G1Affine*)w->fold.p, 128u, (G1X*)w->out.p);
     HIPCHK(c, hipGetLastError());
     std::vector<G1X> res(sg.size());
-    if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "verify: fold results download");
-    HIPCHK(c, hipMemcpyAsync(res.data(), w->out, res.size() * sizeof(G1X), hipMemcpyDeviceToHost, c->stream));
+    if (c->audit.on) c->audit.op(c->stream, {w->out.p}, {}, "verify: fold results download");
+    HIPCHK(c, hipMemcpyAsync(res.data(), w->out.p, res.size() * sizeof(G1X), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, aud_sync(c, c->stream));
     G1X sum[2] = {G1X::identity(), G1X::identity()};
     const size_t per_side = sg.size() / 2;
@@ -535,28 +512,28 @@ int instance_eval_device(zk_ctx* c, uint32_t k, size_t count, const verifier::In
     const uint32_t slices_max = (uint32_t)std::max<size_t>(1, (longest + IE_SLICE - 1) / IE_SLICE);  // <= 2^26 / IE_SLICE: a grid's y extent
     const size_t np = count * (size_t)slices_max;
     int rc;
-    if ((rc = ws_grow(c, &w->ie_vals, &w->c_ie_vals, std::max<size_t>(vals.size(), 1) * sizeof(Fr))) ||
-        (rc = ws_grow(c, &w->ie_pairs, &w->c_ie_pairs, count * sizeof(IePair))) || (rc = ws_grow(c, &w->ie_x, &w->c_ie_x, count * sizeof(Fr))) ||
-        (rc = ws_grow(c, &w->ie_part, &w->c_ie_part, np * sizeof(Fr))) || (rc = ws_grow(c, &w->ie_pflag, &w->c_ie_pflag, np)) ||
-        (rc = ws_grow(c, &w->ie_out, &w->c_ie_out, count * sizeof(Fr))) || (rc = ws_grow(c, &w->ie_flag, &w->c_ie_flag, count)))
+    if ((rc = w->ie_vals.grow(c, std::max<size_t>(vals.size(), 1) * sizeof(Fr))) ||
+        (rc = w->ie_pairs.grow(c, count * sizeof(IePair))) || (rc = w->ie_x.grow(c, count * sizeof(Fr))) ||
+        (rc = w->ie_part.grow(c, np * sizeof(Fr))) || (rc = w->ie_pflag.grow(c, np)) ||
+        (rc = w->ie_out.grow(c, count * sizeof(Fr))) || (rc = w->ie_flag.grow(c, count)))
         return rc;
-    if (c->audit.on) c->audit.op(c->stream, {}, {w->ie_vals, w->ie_pairs, w->ie_x}, "instance evaluation: lists, pairs and points upload");
-    if (!vals.empty()) HIPCHK(c, hipMemcpyAsync(w->ie_vals, vals.data(), vals.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->ie_pairs, pairs.data(), count * sizeof(IePair), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w->ie_x, xs, count * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    if (c->audit.on) c->audit.op(c->stream, {}, {w->ie_vals.p, w->ie_pairs.p, w->ie_x.p}, "instance evaluation: lists, pairs and points upload");
+    if (!vals.empty()) HIPCHK(c, hipMemcpyAsync(w->ie_vals.p, vals.data(), vals.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->ie_pairs.p, pairs.data(), count * sizeof(IePair), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w->ie_x.p, xs, count * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
     const Fr omega = fr_omega(k), omega_inv = fe_inv_fast(omega), n_inv = fe_inv_fast(fr_from_u64((uint64_t)1 << k));
-    if (c->audit.on) c->audit.op(c->stream, {w->ie_vals, w->ie_pairs, w->ie_x}, {w->ie_part, w->ie_pflag}, "instance evaluation (instance_eval_kernel)");
-    hipLaunchKernelGGL(instance_eval_kernel, dim3((uint32_t)count, slices_max), dim3(IE_WG), 0, c->stream, (const Fr*)w->ie_vals, (const IePair*)w->ie_pairs,
-                       (const Fr*)w->ie_x, omega, omega_inv, slices_max, (Fr*)w->ie_part, (uint8_t*)w->ie_pflag);
+    if (c->audit.on) c->audit.op(c->stream, {w->ie_vals.p, w->ie_pairs.p, w->ie_x.p}, {w->ie_part.p, w->ie_pflag.p}, "instance evaluation (instance_eval_kernel)");
+    hipLaunchKernelGGL(instance_eval_kernel, dim3((uint32_t)count, slices_max), dim3(IE_WG), 0, c->stream, (const Fr*)w->ie_vals.p, (const IePair*)w->ie_pairs.p,
+                       (const Fr*)w->ie_x.p, omega, omega_inv, slices_max, (Fr*)w->ie_part.p, (uint8_t*)w->ie_pflag.p);
     HIPCHK(c, hipGetLastError());
     if (c->audit.on)
-        c->audit.op(c->stream, {w->ie_pairs, w->ie_x, w->ie_part, w->ie_pflag}, {w->ie_out, w->ie_flag}, "instance evaluation: second stage");
-    hipLaunchKernelGGL(instance_eval_finish_kernel, dim3((uint32_t)count), dim3(IE_WG), 0, c->stream, (const IePair*)w->ie_pairs, (const Fr*)w->ie_x,
-                       (const Fr*)w->ie_part, (const uint8_t*)w->ie_pflag, slices_max, k, n_inv, (Fr*)w->ie_out, (uint8_t*)w->ie_flag);
+        c->audit.op(c->stream, {w->ie_pairs.p, w->ie_x.p, w->ie_part.p, w->ie_pflag.p}, {w->ie_out.p, w->ie_flag.p}, "instance evaluation: second stage");
+    hipLaunchKernelGGL(instance_eval_finish_kernel, dim3((uint32_t)count), dim3(IE_WG), 0, c->stream, (const IePair*)w->ie_pairs.p, (const Fr*)w->ie_x.p,
+                       (const Fr*)w->ie_part.p, (const uint8_t*)w->ie_pflag.p, slices_max, k, n_inv, (Fr*)w->ie_out.p, (uint8_t*)w->ie_flag.p);
     HIPCHK(c, hipGetLastError());
-    if (c->audit.on) c->audit.op(c->stream, {w->ie_out, w->ie_flag}, {}, "instance evaluation: results download");
-    HIPCHK(c, hipMemcpyAsync(out, w->ie_out, count * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(on_domain, w->ie_flag, count, hipMemcpyDeviceToHost, c->stream));
+    if (c->audit.on) c->audit.op(c->stream, {w->ie_out.p, w->ie_flag.p}, {}, "instance evaluation: results download");
+    HIPCHK(c, hipMemcpyAsync(out, w->ie_out.p, count * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(on_domain, w->ie_flag.p, count, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, aud_sync(c, c->stream));  // (the host vectors above are pageable and go out of scope)
     return ZK_OK;
 }
@@ -593,10 +570,9 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
     const bool on_device = may_device && per_proof && c->opt_verify_inst_eval == 2;
     if (!pk->verify_only && pk->srs_gen != c->srs_gen) return ZK_ESTATE;  // a full key under a replaced SRS: its vk is stale
     if (c->srs_k < 0 || !c->g2_valid) return ZK_ESTATE;  // g[0], g2 and s_g2 come from the resident SRS
-    int rc = ctx_bind(c);
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
     if (!c->vws && !(c->vws = new (std::nothrow) VerifyWs())) return ZK_ENOMEM;
     VerifyWs* w = c->vws;
     if ((rc = pk_vk_bases(c, pk))) return rc;
@@ -617,21 +593,21 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
             memcpy(bytes.data() + t * pl.len, proofs[cand[t]], pl.len);
             for (size_t i = 0; i < np; i++) off[t * np + i] = (uint32_t)(t * pl.len + pl.point_off[i]);
         }
-        if ((rc = ws_grow(c, &w->bytes, &w->c_bytes, nb)) || (rc = ws_grow(c, &w->off, &w->c_off, npts * 4)) ||
-            (rc = ws_grow(c, &w->pts, &w->c_pts, npts * sizeof(G1Affine))) || (rc = ws_grow(c, &w->flag, &w->c_flag, npts)))
+        if ((rc = w->bytes.grow(c, nb)) || (rc = w->off.grow(c, npts * 4)) ||
+            (rc = w->pts.grow(c, npts * sizeof(G1Affine))) || (rc = w->flag.grow(c, npts)))
             return rc;
-        if (c->audit.on) c->audit.op(c->stream, {}, {w->bytes, w->off}, "verify: proof bytes upload");
-        HIPCHK(c, hipMemcpyAsync(w->bytes, bytes.data(), nb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(w->off, off.data(), npts * 4, hipMemcpyHostToDevice, c->stream));
-        if (c->audit.on) c->audit.op(c->stream, {w->bytes, w->off}, {w->pts, w->flag}, "verify: point decoding (verify_decode_kernel)");
-        hipLaunchKernelGGL(verify_decode_kernel, dim3((uint32_t)((npts + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)w->bytes,
-                           (const uint32_t*)w->off, (uint32_t)npts, transcript == ZK_TRANSCRIPT_EVM ? 1 : 0, (G1Affine*)w->pts, (uint8_t*)w->flag);
+        if (c->audit.on) c->audit.op(c->stream, {}, {w->bytes.p, w->off.p}, "verify: proof bytes upload");
+        HIPCHK(c, hipMemcpyAsync(w->bytes.p, bytes.data(), nb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(w->off.p, off.data(), npts * 4, hipMemcpyHostToDevice, c->stream));
+        if (c->audit.on) c->audit.op(c->stream, {w->bytes.p, w->off.p}, {w->pts.p, w->flag.p}, "verify: point decoding (verify_decode_kernel)");
+        hipLaunchKernelGGL(verify_decode_kernel, dim3((uint32_t)((npts + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t*)w->bytes.p,
+                           (const uint32_t*)w->off.p, (uint32_t)npts, transcript == ZK_TRANSCRIPT_EVM ? 1 : 0, (G1Affine*)w->pts.p, (uint8_t*)w->flag.p);
         HIPCHK(c, hipGetLastError());
         std::vector<G1Affine> pts(npts);
         std::vector<uint8_t> flag(npts);
-        if (c->audit.on) c->audit.op(c->stream, {w->pts, w->flag}, {}, "verify: decoded points download");
-        HIPCHK(c, hipMemcpyAsync(pts.data(), w->pts, npts * sizeof(G1Affine), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(flag.data(), w->flag, npts, hipMemcpyDeviceToHost, c->stream));
+        if (c->audit.on) c->audit.op(c->stream, {w->pts.p, w->flag.p}, {}, "verify: decoded points download");
+        HIPCHK(c, hipMemcpyAsync(pts.data(), w->pts.p, npts * sizeof(G1Affine), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(flag.data(), w->flag.p, npts, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, aud_sync(c, c->stream));
 
         // 2. transcripts and term lists, per proof on the host.  With inst(x) on the device: every proof's transcript runs to x
@@ -693,22 +669,22 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
             }
         }
         if (!J.live.empty()) {
-            if ((rc = ws_grow(c, &w->scal, &w->c_scal, sc.size() * sizeof(Fr))) || (rc = ws_grow(c, &w->idx, &w->c_idx, ix.size() * 4)) ||
-                (rc = ws_grow(c, &w->seg, &w->c_seg, sg.size() * sizeof(VSeg))) || (rc = ws_grow(c, &w->out, &w->c_out, sg.size() * sizeof(G1X))))
+            if ((rc = w->scal.grow(c, sc.size() * sizeof(Fr))) || (rc = w->idx.grow(c, ix.size() * 4)) ||
+                (rc = w->seg.grow(c, sg.size() * sizeof(VSeg))) || (rc = w->out.grow(c, sg.size() * sizeof(G1X))))
                 return rc;
-            if (c->audit.on) c->audit.op(c->stream, {}, {w->scal, w->idx, w->seg}, "verify: term lists upload");
-            HIPCHK(c, hipMemcpyAsync(w->scal, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(w->idx, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(w->seg, sg.data(), sg.size() * sizeof(VSeg), hipMemcpyHostToDevice, c->stream));
+            if (c->audit.on) c->audit.op(c->stream, {}, {w->scal.p, w->idx.p, w->seg.p}, "verify: term lists upload");
+            HIPCHK(c, hipMemcpyAsync(w->scal.p, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(w->idx.p, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(w->seg.p, sg.data(), sg.size() * sizeof(VSeg), hipMemcpyHostToDevice, c->stream));
             if (c->audit.on)
-                c->audit.op(c->stream, {w->scal, w->idx, w->seg, w->pts, pk->d_vk_bases, c->g}, {w->out}, "verify: accumulators (verify_msm_kernel)");
-            hipLaunchKernelGGL(verify_msm_kernel, dim3((uint32_t)sg.size()), dim3(64), 0, c->stream, (const Fr*)w->scal, (const uint32_t*)w->idx,
-                               (const VSeg*)w->seg, (const G1Affine*)w->pts, (uint32_t)npts, (const G1Affine*)pk->d_vk_bases, n_key,
-                               (const G1Affine*)c->g, 256u, (G1X*)w->out);
+                c->audit.op(c->stream, {w->scal.p, w->idx.p, w->seg.p, w->pts.p, pk->d_vk_bases, c->g}, {w->out.p}, "verify: accumulators (verify_msm_kernel)");
+            hipLaunchKernelGGL(verify_msm_kernel, dim3((uint32_t)sg.size()), dim3(64), 0, c->stream, (const Fr*)w->scal.p, (const uint32_t*)w->idx.p,
+                               (const VSeg*)w->seg.p, (const G1Affine*)w->pts.p, (uint32_t)npts, (const G1Affine*)pk->d_vk_bases, n_key,
+                               (const G1Affine*)c->g, 256u, (G1X*)w->out.p);
             HIPCHK(c, hipGetLastError());
             std::vector<G1X> res(sg.size());
-            if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "verify: accumulators download");
-            HIPCHK(c, hipMemcpyAsync(res.data(), w->out, res.size() * sizeof(G1X), hipMemcpyDeviceToHost, c->stream));
+            if (c->audit.on) c->audit.op(c->stream, {w->out.p}, {}, "verify: accumulators download");
+            HIPCHK(c, hipMemcpyAsync(res.data(), w->out.p, res.size() * sizeof(G1X), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, aud_sync(c, c->stream));
             J.acc = to_affine_batch(res);
 
@@ -746,9 +722,9 @@ static int verify_proofs(zk_ctx* c, zk_pk h, size_t batch, uint32_t n_circuits, 
                     if (r.is_zero()) r.v[0] = 1;
                     J.rho[s] = fe_to_mont(r);
                 }
-                if ((rc = ws_grow(c, &w->fold, &w->c_fold, J.acc.size() * sizeof(G1Affine)))) return rc;
-                if (c->audit.on) c->audit.op(c->stream, {}, {w->fold}, "verify: accumulators upload for the fold");
-                HIPCHK(c, hipMemcpyAsync(w->fold, J.acc.data(), J.acc.size() * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
+                if ((rc = w->fold.grow(c, J.acc.size() * sizeof(G1Affine)))) return rc;
+                if (c->audit.on) c->audit.op(c->stream, {}, {w->fold.p}, "verify: accumulators upload for the fold");
+                HIPCHK(c, hipMemcpyAsync(w->fold.p, J.acc.data(), J.acc.size() * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
             }
             std::vector<uint32_t> S(J.live.size());
             for (uint32_t s = 0; s < S.size(); s++) S[s] = s;
@@ -843,10 +819,9 @@ ZK_API(zk_instance_eval, (zk_ctx* c, uint32_t k, size_t count, const uint64_t* c
             if (!lists[j].vals[i].below_modulus()) return ZK_EINVAL;
     }
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_bind(c);
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
     std::vector<Fr> out(count);
     std::vector<uint8_t> flags(count);
     if ((rc = instance_eval_device(c, k, count, lists.data(), xs.data(), out.data(), flags.data()))) return rc;

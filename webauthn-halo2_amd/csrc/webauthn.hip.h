@@ -4,7 +4,8 @@
 // Like p256.hip.h, every function is __host__ __device__ in ONE portable form, no inline assembly: the kernel (webauthn.hip) is a
 // wrapper around webauthn_digest_one, and a CPU program runs the same code (tests/webauthn_host_check.cpp does, under the
 // sanitizers).  NOT constant time, on purpose: everything an assertion carries is public request data; nothing here may be used
-// with a secret.
+// with a secret.  At the end stands the host-only packing of a batch into its upload image ("the upload image of a batch"),
+// which that program calls too.
 //
 // The rule.  An assertion is (authenticatorData, clientDataJSON, a DER signature, the credential's public key) and the relying
 // party's expectations (the challenge it issued, its origin, SHA-256 of its RP ID, the flags it requires, whether it accepts a
@@ -38,6 +39,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <vector>
 
 #include "p256.hip.h"
 
@@ -274,6 +278,92 @@ P256_FN uint8_t webauthn_check_one(const uint8_t* ad, size_t ad_len, const uint8
     const uint8_t reason = webauthn_digest_one(ad, (uint32_t)ad_len, cd, (uint32_t)cd_len, sig, (uint32_t)sig_len, e, e_len, x_be, y_be, rp_id_hash,
                                                flags_required, allow_cross_origin, record, sign_count);
     return reason != ZK_WEBAUTHN_VALID ? reason : p256_verify_one(record, g_table);
+}
+
+// ---- the upload image of a batch -------------------------------------------------------------------------------------------------
+// Host only, and nothing of HIP is called: the library packs with these (webauthn.hip, webauthn_register.hip), and the CPU programs
+// of the tests call the same functions under the sanitizers.  An image is one fixed-size descriptor per LIVE request (one inside
+// the caps; the others are never uploaded and get no lane), then ONE blob with every live request's strings and its E back to
+// back; a descriptor's offsets count from the start of the blob.
+
+// one assertion as the lane sees it
+struct WebauthnDesc {
+    uint32_t ad_off, ad_len, cd_off, cd_len, sig_off, sig_len, e_off, e_len;
+    uint8_t x[32], y[32], rp_id_hash[32];
+    uint8_t flags_required, allow_cross_origin, pad[2];
+};
+static_assert(sizeof(WebauthnDesc) == 132, "the descriptor is packed words and bytes");
+
+struct WebauthnImage {
+    std::vector<uint32_t> live;  // the indices of the live requests in the caller's array, ascending: descriptor j is request live[j]
+    std::vector<uint8_t> bytes;  // live.size() descriptors, then the blob; its size is the upload's length
+};
+
+// the end of a blob being filled: appends a string and says where it lies
+struct WebauthnCursor {
+    uint8_t* blob;
+    uint32_t pos = 0;  // (16 384 requests of 8192 + 4096 + 362 bytes stay below 2^28)
+    uint32_t put(const uint8_t* p, size_t len) {
+        const uint32_t at = pos;
+        if (len) memcpy(blob + pos, p, len);
+        pos += (uint32_t)len;
+        return at;
+    }
+};
+
+// The image of r[0 .. count).  room(q): 0 for a request outside the caps (not live), else an upper bound of its bytes in the blob;
+// fill(q, cur, d): puts a live request's strings through the cursor and fills what is the ceremony's own in its descriptor d,
+// which comes zeroed.  What both ceremonies have is done here: E (built in place behind the strings; create: its type) and the
+// relying party's expectations
+template <class Desc, class Req, class Room, class Fill>
+WebauthnImage webauthn_pack_image(const Req* r, size_t count, bool create, Room room, Fill fill) {
+    WebauthnImage im;
+    im.live.reserve(count);
+    size_t blob_room = 0;
+    for (size_t i = 0; i < count; i++)
+        if (const size_t bytes = room(r[i])) {
+            im.live.push_back((uint32_t)i);
+            blob_room += bytes;
+        }
+    const size_t n = im.live.size(), desc_bytes = n * sizeof(Desc);
+    im.bytes.resize(desc_bytes + blob_room);
+    WebauthnCursor cur{im.bytes.data() + desc_bytes};
+    for (size_t j = 0; j < n; j++) {
+        const Req& q = r[im.live[j]];
+        Desc d;
+        memset(&d, 0, sizeof d);
+        fill(q, cur, d);
+        d.e_off = cur.pos;
+        d.e_len = webauthn_expected_prefix(q.challenge, q.challenge_len, q.origin, q.origin_len, cur.blob + cur.pos, create);
+        cur.pos += d.e_len;
+        memcpy(d.rp_id_hash, q.rp_id_hash, 32);
+        d.flags_required = q.flags_required;
+        d.allow_cross_origin = q.allow_cross_origin;
+        memcpy(im.bytes.data() + j * sizeof(Desc), &d, sizeof d);
+    }
+    im.bytes.resize(desc_bytes + cur.pos);
+    return im;
+}
+
+// n reason bytes padded to whole words: what follows them in a download (counters, credentials) stays aligned
+inline size_t webauthn_padded(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// the image of `count` assertions; Req: zk_webauthn_assertion (include/zkmi355.h), which this header does not need otherwise
+template <class Req>
+WebauthnImage webauthn_pack(const Req* a, size_t count) {
+    return webauthn_pack_image<WebauthnDesc>(
+        a, count, false,
+        [](const Req& q) -> size_t {
+            if (!webauthn_size_ok(q.authenticator_data_len, q.client_data_json_len, q.signature_len, q.challenge_len, q.origin_len)) return 0;
+            return q.authenticator_data_len + q.client_data_json_len + q.signature_len + WEBAUTHN_PREFIX_MAX;
+        },
+        [](const Req& q, WebauthnCursor& cur, WebauthnDesc& d) {
+            d.ad_len = (uint32_t)q.authenticator_data_len, d.ad_off = cur.put(q.authenticator_data, q.authenticator_data_len);
+            d.cd_len = (uint32_t)q.client_data_json_len, d.cd_off = cur.put(q.client_data_json, q.client_data_json_len);
+            d.sig_len = (uint32_t)q.signature_len, d.sig_off = cur.put(q.signature, q.signature_len);
+            memcpy(d.x, q.pubkey_x, 32);
+            memcpy(d.y, q.pubkey_y, 32);
+        });
 }
 
 }  // namespace zk

@@ -3,7 +3,9 @@
 //
 // The rule is webauthn_register.hip.h's (host and device in one form).  What stays on the host, as in webauthn.hip: the argument
 // checks, the SIZE verdict (a request outside the caps is never uploaded and gets no lane) and the expected clientDataJSON prefix E
-// of every request.  Everything of variable length goes into ONE blob behind one fixed-size descriptor per request: one upload.
+// of every request.  Everything of variable length goes into ONE blob behind one fixed-size descriptor per request: one upload
+// (webauthn_register.hip.h webauthn_register_pack: host only, so that the tests run it under the sanitizers).  The round trip is
+// lane_call.h's.
 //   launch 1  webauthn_register_kernel, workgroups of 256, one registration per lane: the CBOR walk, the authData and credential
 //             rules, the COSE template, E, the key's curve test, the statement under the policy; for a packed self statement the
 //             DER parse, both SHA-256 passes and the 160-byte record.  It writes a provisional reason, the credential, and one
@@ -29,14 +31,6 @@ namespace {
 
 constexpr uint32_t WEBAUTHN_REGISTER_WG = 256;
 
-// one request as the lane sees it; the offsets count from the start of the blob
-struct WebauthnRegisterDesc {
-    uint32_t obj_off, obj_len, cd_off, cd_len, e_off, e_len;
-    uint8_t rp_id_hash[32];
-    uint8_t flags_required, allow_cross_origin, policy, pad;
-};
-static_assert(sizeof(WebauthnRegisterDesc) == 60, "the descriptor is packed words and bytes");
-
 __global__ __launch_bounds__(WEBAUTHN_REGISTER_WG) void webauthn_register_kernel(const WebauthnRegisterDesc* descs, const uint8_t* blob, uint32_t count,
                                                                                  uint8_t* reasons, uint8_t* settled, WebauthnCredential* creds,
                                                                                  uint8_t* records) {
@@ -61,69 +55,35 @@ ZK_API(zk_webauthn_register,
             (!r[i].challenge && r[i].challenge_len) || (!r[i].origin && r[i].origin_len) || r[i].attestation_policy > ZK_WEBAUTHN_ATT_NONE_OR_SELF)
             return ZK_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = ctx_bind(c);
-    if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();
-    if ((rc = es256_table(c))) return rc;
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
+    if (rc || (rc = es256_table(c))) return rc;
     Es256Ws* w = c->es256;
 
-    // the live requests (those inside the caps), their descriptors and the blob
-    std::vector<uint32_t> live;
-    live.reserve(count);
-    size_t blob_bytes = 0;
-    for (size_t i = 0; i < count; i++)
-        if (webauthn_register_size_ok(r[i].attestation_object_len, r[i].client_data_json_len, r[i].challenge_len, r[i].origin_len)) {
-            live.push_back((uint32_t)i);
-            blob_bytes += r[i].attestation_object_len + r[i].client_data_json_len + WEBAUTHN_CREATE_PREFIX_MAX;
-        }
+    const WebauthnImage im = webauthn_register_pack(r, count);
     // the output buffer: reasons (padded to words) and credentials, which come back; settled bytes and records, which stay there
-    const size_t n = live.size(), desc_bytes = n * sizeof(WebauthnRegisterDesc);
-    const size_t bytes_n = (n + 3) & ~(size_t)3, down_bytes = bytes_n + n * sizeof(WebauthnCredential), out_bytes = down_bytes + bytes_n + n * 160;
+    const size_t n = im.live.size(), desc_bytes = n * sizeof(WebauthnRegisterDesc);
+    const size_t bytes_n = webauthn_padded(n), down_bytes = bytes_n + n * sizeof(WebauthnCredential), out_bytes = down_bytes + bytes_n + n * 160;
     std::vector<uint8_t> out(down_bytes);
     if (n) {
-        std::vector<uint8_t> in(desc_bytes + blob_bytes);
-        uint8_t* blob = in.data() + desc_bytes;
-        uint32_t pos = 0;  // (16 384 requests of 8192 + 4096 + 362 bytes stay below 2^28)
-        auto put = [&](const uint8_t* p, size_t len) {
-            const uint32_t at = pos;
-            if (len) memcpy(blob + pos, p, len);
-            pos += (uint32_t)len;
-            return at;
+        auto enqueue = [&] {
+            const uint8_t* d_in = (const uint8_t*)w->in.p;
+            uint8_t* d_out = (uint8_t*)w->out.p;
+            uint8_t* d_settled = d_out + down_bytes;
+            uint8_t* d_records = d_settled + bytes_n;
+            hipLaunchKernelGGL(webauthn_register_kernel, lane_grid(n, WEBAUTHN_REGISTER_WG), dim3(WEBAUTHN_REGISTER_WG), 0, c->stream,
+                               (const WebauthnRegisterDesc*)d_in, d_in + desc_bytes, (uint32_t)n, d_out, d_settled, (WebauthnCredential*)(d_out + bytes_n),
+                               d_records);
+            if (hipError_t e = hipGetLastError()) return e;
+            if (c->audit.on)
+                c->audit.op(c->stream, {w->out.p, w->table}, {w->out.p}, "webauthn register: verification of the records (es256_verify_kernel)");
+            return es256_enqueue(c, d_records, (uint32_t)n, d_settled, d_out);
         };
-        for (size_t j = 0; j < n; j++) {
-            const zk_webauthn_registration& q = r[live[j]];
-            WebauthnRegisterDesc d;
-            memset(&d, 0, sizeof d);
-            d.obj_len = (uint32_t)q.attestation_object_len, d.obj_off = put(q.attestation_object, q.attestation_object_len);
-            d.cd_len = (uint32_t)q.client_data_json_len, d.cd_off = put(q.client_data_json, q.client_data_json_len);
-            d.e_off = pos;
-            d.e_len = webauthn_expected_prefix(q.challenge, q.challenge_len, q.origin, q.origin_len, blob + pos, true);
-            pos += d.e_len;
-            memcpy(d.rp_id_hash, q.rp_id_hash, 32);
-            d.flags_required = q.flags_required;
-            d.allow_cross_origin = q.allow_cross_origin;
-            d.policy = q.attestation_policy;
-            memcpy(in.data() + j * sizeof(WebauthnRegisterDesc), &d, sizeof d);
-        }
-        const size_t in_bytes = desc_bytes + pos;
-        if ((rc = es256_grow(c, &w->in, &w->c_in, in_bytes)) || (rc = es256_grow(c, &w->out, &w->c_out, out_bytes))) return rc;
-        uint8_t* d_in = (uint8_t*)w->in;
-        uint8_t* d_out = (uint8_t*)w->out;
-        uint8_t* d_settled = d_out + down_bytes;
-        uint8_t* d_records = d_settled + bytes_n;
-        if (c->audit.on) c->audit.op(c->stream, {}, {w->in}, "webauthn register: descriptors and blob upload");
-        HIPCHK(c, hipMemcpyAsync(d_in, in.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-        if (c->audit.on) c->audit.op(c->stream, {w->in}, {w->out}, "webauthn register: walk, rules, records (webauthn_register_kernel)");
-        hipLaunchKernelGGL(webauthn_register_kernel, dim3((uint32_t)((n + WEBAUTHN_REGISTER_WG - 1) / WEBAUTHN_REGISTER_WG)), dim3(WEBAUTHN_REGISTER_WG), 0,
-                           c->stream, (const WebauthnRegisterDesc*)d_in, (const uint8_t*)(d_in + desc_bytes), (uint32_t)n, d_out, d_settled,
-                           (WebauthnCredential*)(d_out + bytes_n), d_records);
-        HIPCHK(c, hipGetLastError());
-        if (c->audit.on) c->audit.op(c->stream, {w->out, w->table}, {w->out}, "webauthn register: verification of the records (es256_verify_kernel)");
-        HIPCHK(c, es256_enqueue(c, d_records, (uint32_t)n, d_settled, d_out));
-        if (c->audit.on) c->audit.op(c->stream, {w->out}, {}, "webauthn register: reasons and credentials download");
-        HIPCHK(c, hipMemcpyAsync(out.data(), d_out, down_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, aud_sync(c, c->stream));  // (the staging vectors are pageable)
+        if ((rc = lane_round_trip(c, {{&w->in, im.bytes.data(), im.bytes.size()}}, nullptr, &w->out, out_bytes, out.data(), down_bytes,
+                                  {"webauthn register: descriptors and blob upload", "webauthn register: walk, rules, records (webauthn_register_kernel)",
+                                   "webauthn register: reasons and credentials download"},
+                                  enqueue)))
+            return rc;
         if ((rc = aud_verdict(c, aud0, ZK_OK))) return rc;
     }
 
@@ -131,7 +91,7 @@ ZK_API(zk_webauthn_register,
     if (reasons) memset(reasons, ZK_WEBAUTHN_SIZE, count);
     if (creds) memset(creds, 0, count * sizeof(zk_webauthn_credential));
     for (size_t j = 0; j < n; j++) {
-        const size_t i = live[j];
+        const size_t i = im.live[j];
         verdicts[i] = out[j] == ZK_WEBAUTHN_VALID ? 1 : 0;
         if (reasons) reasons[i] = out[j];
         if (creds && verdicts[i]) memcpy(creds + i, out.data() + bytes_n + j * sizeof(WebauthnCredential), sizeof(WebauthnCredential));

@@ -306,4 +306,29 @@ P256_FN uint8_t webauthn_register_check_one(const uint8_t* o, size_t o_len, cons
     return reason;
 }
 
+// ---- the upload image of a batch (webauthn.hip.h: host only) ----------------------------------------------------------------------
+// one registration as the lane sees it; the offsets count from the start of the blob
+struct WebauthnRegisterDesc {
+    uint32_t obj_off, obj_len, cd_off, cd_len, e_off, e_len;
+    uint8_t rp_id_hash[32];
+    uint8_t flags_required, allow_cross_origin, policy, pad;
+};
+static_assert(sizeof(WebauthnRegisterDesc) == 60, "the descriptor is packed words and bytes");
+
+// the image of `count` registrations; Req: zk_webauthn_registration (include/zkmi355.h)
+template <class Req>
+WebauthnImage webauthn_register_pack(const Req* r, size_t count) {
+    return webauthn_pack_image<WebauthnRegisterDesc>(
+        r, count, true,
+        [](const Req& q) -> size_t {
+            if (!webauthn_register_size_ok(q.attestation_object_len, q.client_data_json_len, q.challenge_len, q.origin_len)) return 0;
+            return q.attestation_object_len + q.client_data_json_len + WEBAUTHN_CREATE_PREFIX_MAX;
+        },
+        [](const Req& q, WebauthnCursor& cur, WebauthnRegisterDesc& d) {
+            d.obj_len = (uint32_t)q.attestation_object_len, d.obj_off = cur.put(q.attestation_object, q.attestation_object_len);
+            d.cd_len = (uint32_t)q.client_data_json_len, d.cd_off = cur.put(q.client_data_json, q.client_data_json_len);
+            d.policy = q.attestation_policy;
+        });
+}
+
 }  // namespace zk

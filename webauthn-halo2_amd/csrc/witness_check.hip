@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "lane_call.h"
 #include "pk.h"
 #include "sigma_decode.hip.h"
 
@@ -353,10 +354,9 @@ static int witness_check_run(zk_ctx* c, zk_pk h, const zk_poly* advice, size_t n
         if (!r || r->n != lay.n) return ZK_EINVAL;
         adv[j] = r->ptr;
     }
-    int rc = ctx_bind(c);
+    uint64_t aud0;
+    int rc = call_enter(c, &aud0);
     if (rc) return rc;
-    const uint64_t aud0 = c->audit.violations;
-    c->audit.base_of.clear();  // (allocations may have changed hands since the last call)
     if ((rc = wc_ensure_state(c, pk))) return rc;
     WitnessCheckState* s = pk->wc;
     if ((rc = wc_upload_args(c, pk, adv))) return rc;

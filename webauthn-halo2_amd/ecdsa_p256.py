@@ -733,16 +733,22 @@ def _p256_mul(k, pt):
     return acc
 
 
+def _p256_key_reason(x, y):
+    """The key's own tests, what ZK_ES256_ / ZK_WEBAUTHN_RANGE and _OFF_CURVE mean for it: x, y below p, then on the curve
+    (Secp256r1Affine::from_xy is None off it).  -> the failing one's code, or 0 (_VALID)."""
+    if x >= _P or y >= _P:
+        return ZK_WEBAUTHN_RANGE
+    return ZK_WEBAUTHN_OFF_CURVE if (y * y - (x * x * x - 3 * x + _B)) % _P else ZK_WEBAUTHN_VALID
+
+
 def es256_verify(pubkey_x: bytes, pubkey_y: bytes, r: bytes, s: bytes, msg_hash: bytes) -> bool:
     """Plain secp256r1 ECDSA verification of the request, all five fields 32 little-endian bytes as the web
     client posts them (web-demo/src/pages/index.tsx:285-293; `Fp::from_bytes` / `Fq::from_bytes` at
     ecdsa_p256.rs:345-352 reject non-canonical encodings — so does this)."""
     x, y = int.from_bytes(pubkey_x, "little"), int.from_bytes(pubkey_y, "little")
     ri, si, z = int.from_bytes(r, "little"), int.from_bytes(s, "little"), int.from_bytes(msg_hash, "little")
-    if x >= _P or y >= _P or z >= _N or not (0 < ri < _N) or not (0 < si < _N):
+    if _p256_key_reason(x, y) or z >= _N or not (0 < ri < _N) or not (0 < si < _N):
         return False
-    if (y * y - (x * x * x - 3 * x + _B)) % _P:
-        return False  # Secp256r1Affine::from_xy is None off the curve
     w = pow(si, -1, _N)
     pt = _p256_add(_p256_mul(z * w % _N, _G), _p256_mul(ri * w % _N, (x, y)))
     return pt is not None and pt[0] % _N == ri
@@ -783,18 +789,31 @@ def _es256_record(q):
     return b"".join(bytes(v) for v in q)
 
 
-def es256_verify_many(requests, device: int = 0):
-    """es256_verify of every request on the device, in one zk_es256_verify call per ZK_ES256_BATCH_MAX requests -> [bool], in order.
-    requests: (pubkey_x, pubkey_y, r, s, msg_hash) tuples, or parsed request bodies."""
-    recs = [_es256_record(q) for q in requests]
+def _on_check_engine(device, items, cap, call):
+    """The results of call(engine, chunk) over the chunks of at most `cap` items, joined in order: the device's check engine is made
+    on first use, and the lock is held for the whole walk."""
     out = []
     with _ES256_LOCK:
         eng = _ES256_ENGINES.get(device)
         if eng is None:
             eng = _ES256_ENGINES[device] = Engine(device)
-        for lo in range(0, len(recs), ZK_ES256_BATCH_MAX):
-            out += eng.es256_verify(b"".join(recs[lo:lo + ZK_ES256_BATCH_MAX]))[0]
+        for lo in range(0, len(items), cap):
+            out += call(eng, items[lo:lo + cap])
     return out
+
+
+def es256_verify_many(requests, device: int = 0):
+    """es256_verify of every request on the device, in one zk_es256_verify call per ZK_ES256_BATCH_MAX requests -> [bool], in order.
+    requests: (pubkey_x, pubkey_y, r, s, msg_hash) tuples, or parsed request bodies."""
+    return _on_check_engine(device, [_es256_record(q) for q in requests], ZK_ES256_BATCH_MAX, lambda eng, recs: eng.es256_verify(b"".join(recs))[0])
+
+
+def _check_route(items, device, many, one):
+    """The items' results by the route set_signature_check names: one(item) each on the host, or many(items, device)."""
+    items = list(items)
+    if _SIGNATURE_CHECK == "device":
+        return many(items, device)
+    return [one(q) for q in items]
 
 
 def _signature_ok(pubkey_x, pubkey_y, r, s, msg_hash, device):
@@ -850,6 +869,15 @@ def _client_data_ok(cd, challenge, origin, allow_cross_origin, typ=b"webauthn.ge
     return word == b"false" or bool(allow_cross_origin)
 
 
+def _auth_data_reason(ad, rp_id_hash, flags_required):
+    """The AUTHDATA, RPID and FLAGS steps of both ceremonies over authData -> the first failing one's code, or 0 (_VALID)."""
+    if len(ad) < 37:
+        return ZK_WEBAUTHN_AUTHDATA
+    if ad[:32] != bytes(rp_id_hash):
+        return ZK_WEBAUTHN_RPID
+    return ZK_WEBAUTHN_FLAGS if ad[32] & flags_required != flags_required else ZK_WEBAUTHN_VALID
+
+
 def webauthn_verify(authenticator_data, client_data_json, signature, pubkey_x, pubkey_y, challenge, origin, rp_id_hash, flags_required=0x01,
                     allow_cross_origin=False):
     """The relying party's check of one assertion on the host: zk_webauthn_verify's rule in Python (hashlib, the DER and prefix
@@ -862,13 +890,10 @@ def webauthn_verify(authenticator_data, client_data_json, signature, pubkey_x, p
     if (len(ad) > ZK_WEBAUTHN_AUTHDATA_MAX or len(cd) > ZK_WEBAUTHN_CLIENTDATA_MAX or not 8 <= len(sig) <= 72
             or not 1 <= len(challenge) <= ZK_WEBAUTHN_CHALLENGE_MAX or len(origin_b) > ZK_WEBAUTHN_ORIGIN_MAX):
         return False, ZK_WEBAUTHN_SIZE, zero, 0
-    if len(ad) < 37:
-        return False, ZK_WEBAUTHN_AUTHDATA, zero, 0
-    count = int.from_bytes(ad[33:37], "big")
-    if ad[:32] != bytes(rp_id_hash):
-        return False, ZK_WEBAUTHN_RPID, zero, count
-    if ad[32] & flags_required != flags_required:
-        return False, ZK_WEBAUTHN_FLAGS, zero, count
+    reason = _auth_data_reason(ad, rp_id_hash, flags_required)
+    count = 0 if reason == ZK_WEBAUTHN_AUTHDATA else int.from_bytes(ad[33:37], "big")
+    if reason:
+        return False, reason, zero, count
     if not _client_data_ok(cd, challenge, origin_b, allow_cross_origin):
         return False, ZK_WEBAUTHN_CLIENTDATA, zero, count
     rs = webauthn_der_signature(sig)
@@ -878,10 +903,11 @@ def webauthn_verify(authenticator_data, client_data_json, signature, pubkey_x, p
     x, y = int.from_bytes(pubkey_x, "big"), int.from_bytes(pubkey_y, "big")
     fields = (bytes(pubkey_x)[::-1], bytes(pubkey_y)[::-1], rs[0].to_bytes(32, "little"), rs[1].to_bytes(32, "little"), z[::-1])
     record = b"".join(fields)
-    if x >= _P or y >= _P or int.from_bytes(z, "big") >= _N or not 0 < rs[0] < _N or not 0 < rs[1] < _N:
+    key = _p256_key_reason(x, y)  # (RANGE covers the key, the digest and the signature together, before the curve)
+    if key == ZK_WEBAUTHN_RANGE or int.from_bytes(z, "big") >= _N or not 0 < rs[0] < _N or not 0 < rs[1] < _N:
         return False, ZK_WEBAUTHN_RANGE, record, count
-    if (y * y - (x * x * x - 3 * x + _B)) % _P:
-        return False, ZK_WEBAUTHN_OFF_CURVE, record, count
+    if key:
+        return False, key, record, count
     ok = es256_verify(*fields)
     return ok, ZK_WEBAUTHN_VALID if ok else ZK_WEBAUTHN_MISMATCH, record, count
 
@@ -889,25 +915,15 @@ def webauthn_verify(authenticator_data, client_data_json, signature, pubkey_x, p
 def webauthn_verify_many(assertions, device: int = 0):
     """webauthn_verify of every assertion on the device, in one zk_webauthn_verify call per ZK_WEBAUTHN_BATCH_MAX of them ->
     [(ok, reason, record, sign_count)], in order.  assertions: dicts as Engine.webauthn_verify takes them."""
-    assertions = list(assertions)
-    out = []
-    with _ES256_LOCK:
-        eng = _ES256_ENGINES.get(device)
-        if eng is None:
-            eng = _ES256_ENGINES[device] = Engine(device)
-        for lo in range(0, len(assertions), ZK_WEBAUTHN_BATCH_MAX):
-            out += zip(*eng.webauthn_verify(assertions[lo:lo + ZK_WEBAUTHN_BATCH_MAX]))
-    return out
+    return _on_check_engine(device, list(assertions), ZK_WEBAUTHN_BATCH_MAX, lambda eng, chunk: zip(*eng.webauthn_verify(chunk)))
 
 
 def webauthn_check(assertions, device: int = 0):
     """[(ok, reason, record, sign_count)] of the assertions by the route set_signature_check names: one webauthn_verify each on the
     host, or all of them in one launch on the device."""
-    assertions = list(assertions)
-    if _SIGNATURE_CHECK == "device":
-        return webauthn_verify_many(assertions, device)
-    return [webauthn_verify(q["authenticator_data"], q["client_data_json"], q["signature"], q["pubkey_x"], q["pubkey_y"], q["challenge"],
-                            q["origin"], q["rp_id_hash"], q.get("flags_required", 0x01), q.get("allow_cross_origin", False)) for q in assertions]
+    return _check_route(assertions, device, webauthn_verify_many, lambda q: webauthn_verify(
+        q["authenticator_data"], q["client_data_json"], q["signature"], q["pubkey_x"], q["pubkey_y"], q["challenge"], q["origin"], q["rp_id_hash"],
+        q.get("flags_required", 0x01), q.get("allow_cross_origin", False)))
 
 
 # ---- the WebAuthn registration check: where the key of an assertion came from --------------------------------------------------
@@ -998,13 +1014,10 @@ def webauthn_register(attestation_object, client_data_json, challenge, origin, r
     if parts is None:
         return refused(ZK_WEBAUTHN_CBOR)
     fmt, stmt, ad_off, ad = parts
-    if len(ad) < 37:
-        return refused(ZK_WEBAUTHN_AUTHDATA)
-    if ad[:32] != bytes(rp_id_hash):
-        return refused(ZK_WEBAUTHN_RPID)
+    reason = _auth_data_reason(ad, rp_id_hash, flags_required)
+    if reason:
+        return refused(reason)
     flags = ad[32]
-    if flags & flags_required != flags_required:
-        return refused(ZK_WEBAUTHN_FLAGS)
     id_len = int.from_bytes(ad[53:55], "big")
     if not flags & 0x40 or len(ad) < 55 or not 1 <= id_len <= 1023 or len(ad) - 55 < id_len:
         return refused(ZK_WEBAUTHN_CREDENTIAL)
@@ -1022,11 +1035,9 @@ def webauthn_register(attestation_object, client_data_json, challenge, origin, r
     if not _client_data_ok(cd, challenge, origin_b, allow_cross_origin, b"webauthn.create"):
         return refused(ZK_WEBAUTHN_CLIENTDATA)
     xb, yb = key[10:42], key[45:77]
-    x, y = int.from_bytes(xb, "big"), int.from_bytes(yb, "big")
-    if x >= _P or y >= _P:
-        return refused(ZK_WEBAUTHN_RANGE)
-    if (y * y - (x * x * x - 3 * x + _B)) % _P:
-        return refused(ZK_WEBAUTHN_OFF_CURVE)
+    reason = _p256_key_reason(int.from_bytes(xb, "big"), int.from_bytes(yb, "big"))
+    if reason:
+        return refused(reason)
     attestation = ZK_WEBAUTHN_ATTESTED_NOT_JUDGED
     if attestation_policy == ZK_WEBAUTHN_ATT_NONE_OR_SELF:
         if fmt == b"none" and stmt == b"\xa0":
@@ -1055,26 +1066,15 @@ def webauthn_register(attestation_object, client_data_json, challenge, origin, r
 def webauthn_register_many(registrations, device: int = 0):
     """webauthn_register of every registration on the device, in one zk_webauthn_register call per ZK_WEBAUTHN_BATCH_MAX of them ->
     [(ok, reason, credential or None)], in order.  registrations: dicts as Engine.webauthn_register takes them."""
-    registrations = list(registrations)
-    out = []
-    with _ES256_LOCK:
-        eng = _ES256_ENGINES.get(device)
-        if eng is None:
-            eng = _ES256_ENGINES[device] = Engine(device)
-        for lo in range(0, len(registrations), ZK_WEBAUTHN_BATCH_MAX):
-            out += eng.webauthn_register(registrations[lo:lo + ZK_WEBAUTHN_BATCH_MAX])
-    return out
+    return _on_check_engine(device, list(registrations), ZK_WEBAUTHN_BATCH_MAX, lambda eng, chunk: eng.webauthn_register(chunk))
 
 
 def webauthn_register_check(registrations, device: int = 0):
     """[(ok, reason, credential or None)] of the registrations by the route set_signature_check names: one webauthn_register each on
     the host, or all of them in one launch on the device."""
-    registrations = list(registrations)
-    if _SIGNATURE_CHECK == "device":
-        return webauthn_register_many(registrations, device)
-    return [webauthn_register(q["attestation_object"], q["client_data_json"], q["challenge"], q["origin"], q["rp_id_hash"],
-                              q.get("flags_required", 0x01), q.get("allow_cross_origin", False),
-                              q.get("attestation_policy", ZK_WEBAUTHN_ATT_IGNORE)) for q in registrations]
+    return _check_route(registrations, device, webauthn_register_many, lambda q: webauthn_register(
+        q["attestation_object"], q["client_data_json"], q["challenge"], q["origin"], q["rp_id_hash"], q.get("flags_required", 0x01),
+        q.get("allow_cross_origin", False), q.get("attestation_policy", ZK_WEBAUTHN_ATT_IGNORE)))
 
 
 def _witness_seed(pubkey_x, pubkey_y, r, s, msg_hash) -> int:

@@ -362,6 +362,35 @@ def _arr(a, cols):
     return a.reshape(-1, cols)
 
 
+def _lane_results(count):
+    """The verdicts / reasons arrays of a call with one item per lane (an array of one where count is 0: the call then refuses
+    it), and what turns them into ([bool verdicts], [int reasons]) after the call."""
+    verdicts = (ctypes.c_uint8 * max(count, 1))()
+    reasons = (ctypes.c_uint8 * max(count, 1))()
+    return verdicts, reasons, lambda: ([bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)])
+
+
+def _pack_requests(ctype, dicts, strings, fixed32, scalars):
+    """The `ctype` array of a sequence of dicts (it keeps their byte strings alive).  strings: the fields of variable length (a
+    pointer and NAME_len; origin may be a str), fixed32: the fields of exactly 32 bytes, scalars: (name, default, int or bool)."""
+    dicts = list(dicts)
+    arr = (ctype * max(len(dicts), 1))()
+    for c, q in zip(arr, dicts):
+        for name in strings:
+            v = q[name].encode() if name == "origin" and isinstance(q[name], str) else bytes(q[name])
+            setattr(c, name, v)  # (the structure keeps the bytes object alive)
+            setattr(c, name + "_len", len(v))
+        for name in fixed32:
+            v = bytes(q[name])
+            if len(v) != 32:
+                raise ValueError(name + ": 32 bytes")
+            getattr(c, name)[:] = v
+        for name, default, kind in scalars:
+            setattr(c, name, int(kind(q.get(name, default))))
+    arr.zk_count = len(dicts)  # (an empty list still makes an array of one: the call then refuses count = 0)
+    return arr
+
+
 class Poly:
     """Handle of a device-resident vector of Fr."""
 
@@ -1006,10 +1035,9 @@ class Engine:
         if len(sigs) % 160:
             raise ValueError("a record is 160 bytes")
         count = len(sigs) // 160
-        verdicts = (ctypes.c_uint8 * max(count, 1))()
-        reasons = (ctypes.c_uint8 * max(count, 1))()
+        verdicts, reasons, unpack = _lane_results(count)
         self._chk(self.L.zk_es256_verify(self.ctx, count, sigs, verdicts, reasons), "zk_es256_verify")
-        return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+        return unpack()
 
     def webauthn_verify(self, assertions):
         """zk_webauthn_verify: the relying party's check of WebAuthn assertions in two launches, one assertion per lane - both hashes,
@@ -1021,37 +1049,18 @@ class Engine:
         passes webauthn_pack's result instead and skips the marshalling."""
         arr = assertions if isinstance(assertions, ctypes.Array) else self.webauthn_pack(assertions)
         count = len(arr) if getattr(arr, "zk_count", 1) else 0
-        verdicts = (ctypes.c_uint8 * max(count, 1))()
-        reasons = (ctypes.c_uint8 * max(count, 1))()
+        verdicts, reasons, unpack = _lane_results(count)
         records = (ctypes.c_uint8 * (160 * max(count, 1)))()
         counts = (ctypes.c_uint32 * max(count, 1))()
         self._chk(self.L.zk_webauthn_verify(self.ctx, count, arr, verdicts, reasons, records, counts), "zk_webauthn_verify")
         raw = bytes(records)
-        return ([bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)],
-                [raw[160 * j:160 * j + 160] for j in range(count)], [int(counts[j]) for j in range(count)])
+        return unpack() + ([raw[160 * j:160 * j + 160] for j in range(count)], [int(counts[j]) for j in range(count)])
 
     @staticmethod
     def webauthn_pack(assertions):
         """The zk_webauthn_assertion array of webauthn_verify's dicts (it keeps their byte strings alive)."""
-        assertions = list(assertions)
-        count = len(assertions)
-        arr = (WebauthnAssertionC * max(count, 1))()
-        for c, q in zip(arr, assertions):
-            origin = q["origin"].encode() if isinstance(q["origin"], str) else bytes(q["origin"])
-            for name, v in (("authenticator_data", q["authenticator_data"]), ("client_data_json", q["client_data_json"]),
-                            ("signature", q["signature"]), ("challenge", q["challenge"]), ("origin", origin)):
-                v = bytes(v)
-                setattr(c, name, v)  # (the structure keeps the bytes object alive)
-                setattr(c, name + "_len", len(v))
-            for name in ("pubkey_x", "pubkey_y", "rp_id_hash"):
-                v = bytes(q[name])
-                if len(v) != 32:
-                    raise ValueError(name + ": 32 bytes")
-                getattr(c, name)[:] = v
-            c.flags_required = int(q.get("flags_required", 0x01))
-            c.allow_cross_origin = 1 if q.get("allow_cross_origin", False) else 0
-        arr.zk_count = count  # (an empty list still makes an array of one: the call then refuses count = 0)
-        return arr
+        return _pack_requests(WebauthnAssertionC, assertions, ("authenticator_data", "client_data_json", "signature", "challenge", "origin"),
+                              ("pubkey_x", "pubkey_y", "rp_id_hash"), (("flags_required", 0x01, int), ("allow_cross_origin", False, bool)))
 
     def webauthn_register(self, registrations):
         """zk_webauthn_register: the relying party's check of WebAuthn registrations in two launches, one per lane - the CBOR walk of
@@ -1066,14 +1075,13 @@ class Engine:
         measurement) passes webauthn_register_pack's result instead and skips the marshalling."""
         arr = registrations if isinstance(registrations, ctypes.Array) else self.webauthn_register_pack(registrations)
         count = len(arr) if getattr(arr, "zk_count", 1) else 0
-        verdicts = (ctypes.c_uint8 * max(count, 1))()
-        reasons = (ctypes.c_uint8 * max(count, 1))()
+        verdicts, reasons, unpack = _lane_results(count)
         creds = (WebauthnCredentialC * max(count, 1))()
         self._chk(self.L.zk_webauthn_register(self.ctx, count, arr, verdicts, reasons, creds), "zk_webauthn_register")
         out = []
-        for j in range(count):
+        for j, (ok, reason) in enumerate(zip(*unpack())):
             cred = None
-            if verdicts[j]:
+            if ok:
                 c, obj = creds[j], arr.zk_objects[j]  # (reading the c_char_p field back would stop at the first zero byte)
                 cred = {"pubkey_x": bytes(c.pubkey_x), "pubkey_y": bytes(c.pubkey_y), "aaguid": bytes(c.aaguid),
                         "credential_id": obj[c.credential_id_off:c.credential_id_off + c.credential_id_len],
@@ -1081,31 +1089,16 @@ class Engine:
                         "auth_data_len": int(c.auth_data_len), "credential_id_off": int(c.credential_id_off),
                         "credential_id_len": int(c.credential_id_len), "sign_count": int(c.sign_count), "flags": int(c.flags),
                         "attestation": int(c.attestation)}
-            out.append((bool(verdicts[j]), int(reasons[j]), cred))
+            out.append((ok, reason, cred))
         return out
 
     @staticmethod
     def webauthn_register_pack(registrations):
         """The zk_webauthn_registration array of webauthn_register's dicts (it keeps their byte strings alive)."""
         registrations = list(registrations)
-        count = len(registrations)
-        arr = (WebauthnRegistrationC * max(count, 1))()
-        for c, q in zip(arr, registrations):
-            origin = q["origin"].encode() if isinstance(q["origin"], str) else bytes(q["origin"])
-            for name, v in (("attestation_object", q["attestation_object"]), ("client_data_json", q["client_data_json"]),
-                            ("challenge", q["challenge"]), ("origin", origin)):
-                v = bytes(v)
-                setattr(c, name, v)  # (the structure keeps the bytes object alive)
-                setattr(c, name + "_len", len(v))
-            v = bytes(q["rp_id_hash"])
-            if len(v) != 32:
-                raise ValueError("rp_id_hash: 32 bytes")
-            c.rp_id_hash[:] = v
-            c.flags_required = int(q.get("flags_required", 0x01))
-            c.allow_cross_origin = 1 if q.get("allow_cross_origin", False) else 0
-            c.attestation_policy = int(q.get("attestation_policy", ZK_WEBAUTHN_ATT_IGNORE))
+        arr = _pack_requests(WebauthnRegistrationC, registrations, ("attestation_object", "client_data_json", "challenge", "origin"), ("rp_id_hash",),
+                             (("flags_required", 0x01, int), ("allow_cross_origin", False, bool), ("attestation_policy", ZK_WEBAUTHN_ATT_IGNORE, int)))
         arr.zk_objects = [bytes(q["attestation_object"]) for q in registrations]  # the offsets of a credential count within these
-        arr.zk_count = count  # (an empty list still makes an array of one: the call then refuses count = 0)
         return arr
 
     def pairing_check_batch(self, a, b, g2=None, s_g2=None):
@@ -1118,10 +1111,9 @@ class Engine:
         count = a.shape[0]
         u64p = ctypes.POINTER(ctypes.c_uint64)
         gp = [ctypes.cast(None, u64p) if g is None else _p(np.ascontiguousarray(g, dtype=np.uint64).reshape(16)) for g in (g2, s_g2)]
-        verdicts = (ctypes.c_uint8 * max(count, 1))()
-        reasons = (ctypes.c_uint8 * max(count, 1))()
+        verdicts, reasons, unpack = _lane_results(count)
         self._chk(self.L.zk_pairing_check_batch(self.ctx, count, _p(a), _p(b), gp[0], gp[1], verdicts, reasons), "zk_pairing_check_batch")
-        return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+        return unpack()
 
     def pairing_check_each(self, a, b, q, g2=None):
         """zk_pairing_check_each: e(a_i, q_i) = e(b_i, g2) with a G2 point per item, one check per lane; every lane tests and walks
@@ -1133,10 +1125,9 @@ class Engine:
             raise ValueError("one b and one q per a")
         count = a.shape[0]
         gp = ctypes.cast(None, ctypes.POINTER(ctypes.c_uint64)) if g2 is None else _p(np.ascontiguousarray(g2, dtype=np.uint64).reshape(16))
-        verdicts = (ctypes.c_uint8 * max(count, 1))()
-        reasons = (ctypes.c_uint8 * max(count, 1))()
+        verdicts, reasons, unpack = _lane_results(count)
         self._chk(self.L.zk_pairing_check_each(self.ctx, count, _p(a), _p(b), _p(q), gp, verdicts, reasons), "zk_pairing_check_each")
-        return [bool(verdicts[j]) for j in range(count)], [int(reasons[j]) for j in range(count)]
+        return unpack()
 
     def verify_pairing_mode(self, mode):
         """zk_verify_pairing_mode: how verify_batch / verify_batch_public settle a failing fold of two or more proofs - 0 auto (the

@@ -115,17 +115,30 @@ def prove_batch(bodies, evm=True, devices=(0,), degree=DEGREE, public=False):
     out = [None] * len(bodies)
     checked = [None] * len(bodies)
     if ecdsa_p256.signature_check() == "device":
-        parsed = []
-        for i, b in enumerate(bodies):
-            try:
-                parsed.append((i, parse_request(b)))
-            except Exception:
-                pass
-        if parsed:
-            for (i, _), ok in zip(parsed, ecdsa_p256.es256_verify_many([q for _, q in parsed], devices[0])):
-                checked[i] = ok
+        checked, _ = _each_body(bodies, lambda i, b: parse_request(b), lambda parsed: ecdsa_p256.es256_verify_many([q for _, q in parsed], devices[0]),
+                                lambda q, ok: ok)
     _prove_slots(bodies, checked, out, evm, devices, degree, public)
     return out
+
+
+def _each_body(bodies, parse, check_all, finish):
+    """The walk of the batch entry points: parse(i, body) each, check_all([(i, parsed)]) - ONE call over all that parsed, which
+    gives a verdict each -, finish(parsed, verdict) each.  -> (results, errors), a slot per body in both: a body whose parse raised,
+    or whose finish raised a ValueError, has its exception in errors and None in results, and leaves the others alone."""
+    results, errors = [None] * len(bodies), [None] * len(bodies)
+    parsed = []
+    for i, b in enumerate(bodies):
+        try:
+            parsed.append((i, parse(i, b)))
+        except Exception as e:
+            errors[i] = e
+    if parsed:
+        for (i, q), verdict in zip(parsed, check_all(parsed)):
+            try:
+                results[i] = finish(q, verdict)
+            except ValueError as e:
+                errors[i] = e
+    return results, errors
 
 
 def _prove_slots(bodies, checked, out, evm, devices, degree, public):
@@ -161,20 +174,26 @@ _B64URL = re.compile(r"[A-Za-z0-9_-]*")
 ASSERTION_FIELDS = ("authenticator_data", "client_data_json", "signature")
 
 
-def parse_assertion(body):
-    """An assertion body from a JSON string / dict: authenticator_data, client_data_json, signature as base64url strings without
-    padding (as @simplewebauthn/browser delivers response.authenticatorData, .clientDataJSON, .signature), pubkey_x, pubkey_y as
-    [u8; 32] LITTLE-endian arrays (ProveRequestBody's), proving_key_path."""
+def _b64url_fields(body, names):
+    """(the body as a dict, {name: bytes}) of a JSON string / dict whose members `names` are base64url strings without padding."""
     if isinstance(body, (str, bytes, bytearray)):
         body = json.loads(body)
     if not isinstance(body, dict):
         raise ValueError("request body must be a JSON object")
     out = {}
-    for f in ASSERTION_FIELDS:
+    for f in names:
         v = body.get(f)
         if not isinstance(v, str) or not _B64URL.fullmatch(v) or len(v) % 4 == 1:
             raise ValueError(f"{f}: expected a base64url string without padding")
         out[f] = base64.urlsafe_b64decode(v + "=" * (-len(v) % 4))
+    return body, out
+
+
+def parse_assertion(body):
+    """An assertion body from a JSON string / dict: authenticator_data, client_data_json, signature as base64url strings without
+    padding (as @simplewebauthn/browser delivers response.authenticatorData, .clientDataJSON, .signature), pubkey_x, pubkey_y as
+    [u8; 32] LITTLE-endian arrays (ProveRequestBody's), proving_key_path."""
+    body, out = _b64url_fields(body, ASSERTION_FIELDS)
     for f in ("pubkey_x", "pubkey_y"):
         v = body.get(f)
         if not isinstance(v, list) or len(v) != 32 or not all(isinstance(b, int) and not isinstance(b, bool) and 0 <= b <= 255 for b in v):
@@ -187,13 +206,18 @@ def parse_assertion(body):
     return out
 
 
+def _expected(expected_challenge, origin, rp_id, require_uv, allow_cross_origin):
+    """What this server expects of either ceremony, as the fields ecdsa_p256.webauthn_check / webauthn_register_check take."""
+    rp_id = rp_id.encode() if isinstance(rp_id, str) else bytes(rp_id)
+    return {"challenge": bytes(expected_challenge), "origin": origin, "rp_id_hash": hashlib.sha256(rp_id).digest(),
+            "flags_required": 0x05 if require_uv else 0x01, "allow_cross_origin": bool(allow_cross_origin)}
+
+
 def _expectation(q, expected_challenge, origin, rp_id, require_uv, allow_cross_origin):
     """The assertion of a parsed body with what this server expects of it, as ecdsa_p256.webauthn_check takes it."""
-    rp_id = rp_id.encode() if isinstance(rp_id, str) else bytes(rp_id)
     return {"authenticator_data": q["authenticator_data"], "client_data_json": q["client_data_json"], "signature": q["signature"],
-            "pubkey_x": q["pubkey_x"][::-1], "pubkey_y": q["pubkey_y"][::-1], "challenge": bytes(expected_challenge), "origin": origin,
-            "rp_id_hash": hashlib.sha256(rp_id).digest(), "flags_required": 0x05 if require_uv else 0x01,
-            "allow_cross_origin": bool(allow_cross_origin)}
+            "pubkey_x": q["pubkey_x"][::-1], "pubkey_y": q["pubkey_y"][::-1],
+            **_expected(expected_challenge, origin, rp_id, require_uv, allow_cross_origin)}
 
 
 def _classic_body(q, verdict):
@@ -234,22 +258,11 @@ def prove_assertions_batch(bodies, expected_challenges, origin, rp_id, require_u
     bodies, expected_challenges = list(bodies), list(expected_challenges)
     if len(expected_challenges) != len(bodies):
         raise ValueError("one expected challenge per body")
-    out = [None] * len(bodies)
-    parsed = []
-    for i, b in enumerate(bodies):
-        try:
-            parsed.append((i, parse_assertion(b)))
-        except Exception as e:
-            out[i] = e
-    classic = [None] * len(bodies)
-    if parsed:
-        verdicts = ecdsa_p256.webauthn_check([_expectation(q, expected_challenges[i], origin, rp_id, require_uv, allow_cross_origin)
-                                              for i, q in parsed], devices[0])
-        for (i, q), verdict in zip(parsed, verdicts):
-            try:
-                classic[i] = _classic_body(q, verdict)
-            except ValueError as e:
-                out[i] = e
+    classic, out = _each_body(
+        bodies, lambda i, b: parse_assertion(b),
+        lambda parsed: ecdsa_p256.webauthn_check([_expectation(q, expected_challenges[i], origin, rp_id, require_uv, allow_cross_origin)
+                                                  for i, q in parsed], devices[0]),
+        _classic_body)
     _prove_slots(classic, [True] * len(bodies), out, evm, devices, degree, public)
     return out
 
@@ -268,27 +281,15 @@ _ATTESTATION_NAME = {ecdsa_p256.ZK_WEBAUTHN_ATTESTED_NONE: "none", ecdsa_p256.ZK
 def parse_registration(body):
     """A registration body from a JSON string / dict: attestation_object and client_data_json as base64url strings without padding
     (AuthenticatorAttestationResponse's attestationObject and clientDataJSON after toJSON())."""
-    if isinstance(body, (str, bytes, bytearray)):
-        body = json.loads(body)
-    if not isinstance(body, dict):
-        raise ValueError("request body must be a JSON object")
-    out = {}
-    for f in REGISTRATION_FIELDS:
-        v = body.get(f)
-        if not isinstance(v, str) or not _B64URL.fullmatch(v) or len(v) % 4 == 1:
-            raise ValueError(f"{f}: expected a base64url string without padding")
-        out[f] = base64.urlsafe_b64decode(v + "=" * (-len(v) % 4))
-    return out
+    return _b64url_fields(body, REGISTRATION_FIELDS)[1]
 
 
 def _registration(q, expected_challenge, origin, rp_id, require_uv, allow_cross_origin, attestation):
     """The registration of a parsed body with what this server expects of it, as ecdsa_p256.webauthn_register_check takes it."""
     if attestation not in _ATTESTATION_POLICY:
         raise ValueError('attestation: "ignore" or "none-or-self"')
-    rp_id = rp_id.encode() if isinstance(rp_id, str) else bytes(rp_id)
-    return {"attestation_object": q["attestation_object"], "client_data_json": q["client_data_json"], "challenge": bytes(expected_challenge),
-            "origin": origin, "rp_id_hash": hashlib.sha256(rp_id).digest(), "flags_required": 0x05 if require_uv else 0x01,
-            "allow_cross_origin": bool(allow_cross_origin), "attestation_policy": _ATTESTATION_POLICY[attestation]}
+    return {"attestation_object": q["attestation_object"], "client_data_json": q["client_data_json"],
+            "attestation_policy": _ATTESTATION_POLICY[attestation], **_expected(expected_challenge, origin, rp_id, require_uv, allow_cross_origin)}
 
 
 def _stored_credential(verdict):
@@ -319,20 +320,10 @@ def register_credentials_batch(bodies, expected_challenges, origin, rp_id, requi
     bodies, expected_challenges = list(bodies), list(expected_challenges)
     if len(expected_challenges) != len(bodies):
         raise ValueError("one expected challenge per body")
-    out = [None] * len(bodies)
-    parsed = []
-    for i, b in enumerate(bodies):
-        try:
-            parsed.append((i, _registration(parse_registration(b), expected_challenges[i], origin, rp_id, require_uv, allow_cross_origin, attestation)))
-        except Exception as e:
-            out[i] = e
-    if parsed:
-        for (i, _), verdict in zip(parsed, ecdsa_p256.webauthn_register_check([q for _, q in parsed], device)):
-            try:
-                out[i] = _stored_credential(verdict)
-            except ValueError as e:
-                out[i] = e
-    return out
+    stored, errors = _each_body(
+        bodies, lambda i, b: _registration(parse_registration(b), expected_challenges[i], origin, rp_id, require_uv, allow_cross_origin, attestation),
+        lambda parsed: ecdsa_p256.webauthn_register_check([q for _, q in parsed], device), lambda q, verdict: _stored_credential(verdict))
+    return [cred if e is None else e for cred, e in zip(stored, errors)]
 
 
 _HEX = re.compile(r"[0-9a-fA-F]*")

@@ -47,6 +47,13 @@ if [ ! -f $x ] || [ ../tests/quotient_device_check.hip -nt $x ] || [ csrc/quotie
   hipcc $FLAGS -Icsrc ../tests/quotient_device_check.hip -o $x &
   pids="$pids $!"
 fi
+# the device harness of the wide MSM path (tests/msm_wide_device_check.hip, run by tests/test_gpu_msm_wide_device.py): the source
+# includes msm.hip itself; -DZK_MSM_POISON makes a slot, part or row / column sum that a pass reads without writing it a wrong value
+x=../tests/msm_wide_device_check
+if [ ! -f $x ] || [ ../tests/msm_wide_device_check.hip -nt $x ] || [ csrc/msm.hip -nt $x ] || [ -n "$(find csrc ../include -name '*.h' -newer $x)" ]; then
+  hipcc $FLAGS -DZK_MSM_POISON -Icsrc ../tests/msm_wide_device_check.hip -o $x &
+  pids="$pids $!"
+fi
 for p in $pids; do wait $p; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs
 echo "built $(pwd)/$OUT"
@@ -54,6 +61,7 @@ echo "built $(cd ../tests && pwd)/field_device_check_{a0,a1,a2,a2m,a2p}"
 echo "built $(cd ../tests && pwd)/p256_device_check"
 echo "built $(cd ../tests && pwd)/pairing_device_check"
 echo "built $(cd ../tests && pwd)/quotient_device_check"
+echo "built $(cd ../tests && pwd)/msm_wide_device_check"
 # the C++ host example of the same ABI (examples/prove_host.cpp): plain g++, linked against the library above
 cd ..
 g++ -O2 -std=c++17 -Wall -Iinclude examples/prove_host.cpp -Lwebauthn-halo2_amd -lzkmi355 -Wl,-rpath,'$ORIGIN/../webauthn-halo2_amd' -o examples/prove_host
